@@ -271,6 +271,62 @@ def offline_counters(nx, ny, kernel):
     return None
 
 
+# --dump-outputs DIR: what the timed path computed in its last step, one DIR/<name>.npy per array a caller of that path receives, in
+# float64 (the precision the kernels compute in).  An array of at most DUMP_SAMPLE positions (elements or nodes) is written whole in
+# its global shape; a larger one at a fixed, seeded sample of DUMP_SAMPLE positions -- [coefficients, DUMP_SAMPLE] or [DUMP_SAMPLE],
+# positions in increasing order of the flat index -- so that the files stay under DUMP_BUDGET_BYTES and two runs with the same
+# arguments write the same positions.
+DUMP_SAMPLE = 1 << 17
+DUMP_SEED = 2718
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_positions(n):
+    """sorted flat indices of the sampled positions of an array of n positions (all of them when n <= DUMP_SAMPLE)"""
+    if n <= DUMP_SAMPLE:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+
+
+def dump_part(a, first, shape):
+    """the values of the sampled positions held by `a` -- a numpy array [C, rows, cols] (len(shape) == 3) or [rows, cols] / [n] of
+    consecutive positions starting at the global flat position `first` of an array of global shape `shape` -> (part, shape)"""
+    lead = len(shape) == 3
+    flat = a.reshape(a.shape[0], -1) if lead else a.reshape(-1)
+    idx = dump_positions(int(np.prod(shape[1:] if lead else shape)))
+    sel = idx[(idx >= first) & (idx < first + flat.shape[-1])] - first
+    return flat[..., sel], tuple(shape)
+
+
+def dynamics_outputs(core, coupled):
+    """this rank's parts of what a caller of core.step() receives -- its state_dict(): the DG2 fields H and A, the velocity u, v, the
+    stress s11, s12, s22; and the column state hsnow, tice0 of the coupled model -- at the sampled positions of the global grid"""
+    st = core.state_dict()
+    r0, nx, ny = st["rows"][0], st["nx"], st["ny_global"]
+    out = {k: dump_part(st[k], r0 * nx, (st[k].shape[0], ny, nx)) for k in ("H", "A", "s11", "s12", "s22")}
+    out.update({k: dump_part(st[k], 2 * r0 * (2 * nx + 1), (2 * ny + 1, 2 * nx + 1)) for k in ("u", "v")})
+    if coupled:
+        b = core.blk
+        for k in rowblock.CoupledCore.COLUMN_STATE:
+            out[k] = dump_part(core.col[k][b.j0:b.j1].cpu().numpy(), r0 * nx, (ny, nx))
+    return out
+
+
+def write_outputs(path, parts):
+    """parts: one {name: (part, global shape)} per rank in the order of their rows -> path/<name>.npy"""
+    arrays = {}
+    for name, (_, shape) in parts[0].items():
+        a = np.concatenate([p[name][0] for p in parts], axis=-1)
+        n = int(np.prod(shape[1:] if len(shape) == 3 else shape))
+        arrays[name] = a.reshape(shape) if n <= DUMP_SAMPLE else a
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the budget of %d" % (total, DUMP_BUDGET_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def column_bench(args, device):
     """Secondary workload: the reference's column-physics step (the only per-element path the snapshot
     contains) on nx*ny seeded elements; 160 B / element-step algorithmic traffic."""
@@ -291,6 +347,10 @@ def column_bench(args, device):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     ms = e0.elapsed_time(e1) / args.steps
+    if args.dump_outputs:
+        out = {k: dump_part(v.cpu().numpy(), 0, (n,)) for k, v in ds.items()}
+        out["newice"] = dump_part(dn.cpu().numpy(), 0, (n,))
+        write_outputs(args.dump_outputs, [out])
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import oracle_lib as O
 
@@ -367,22 +427,23 @@ def transport_bench(args, device):
             ctx.transport_step(order, dt, [d], adv, scratch)
 
     nwarm = max(args.warmup, 1) + (max(args.warmup, 1) % 2)  # an even number of steps: the field is back in d
-    nsteps = args.steps + (args.steps % 2 if fused else 0)
     for k in range(nwarm):
         step(k)
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
     e0.record(ctx.stream)
-    for k in range(nsteps):
+    for k in range(args.steps):
         step(k)
     e1.record(ctx.stream)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    ms = e0.elapsed_time(e1) / nsteps
-    if abs(float(d[0].sum()) - m0) > 1e-11 * abs(m0):
+    ms = e0.elapsed_time(e1) / args.steps
+    res = d2 if (fused and args.steps % 2) else d  # the fused step of an odd count leaves the field in d2
+    if abs(float(res[0].sum()) - m0) > 1e-11 * abs(m0):
         raise SystemExit("transport bench lost mass: invalid run")
-    args.steps = nsteps
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, [{"phi": dump_part(res.cpu().numpy(), 0, (nc, n, n))}])
     stages = order + 1
     per_stage = 8 * nc * 2 + 2 * 8 * nc + 2 * ng * 8
     alg = n * n * stages * per_stage
@@ -468,6 +529,9 @@ def main():
                          "bound for Delta_min = 2e-9")
     ap.add_argument("--delta-min", type=float, default=None, help="regularisation of Delta [1/s] instead of 2e-9 (adaptive, keep_delta_min) / as a floor (keep_alpha)")
     ap.add_argument("--dry-run", action="store_true", help="plumbing check without a GPU (gloo): launch, rendezvous, planning; no metric")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float64; arrays larger "
+                         "than %d positions at a fixed, seeded sample of them, at most %d MB in all)" % (DUMP_SAMPLE, DUMP_BUDGET_BYTES >> 20))
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or os.environ.get("NSDG_BENCH_SELF_LAUNCH")):
@@ -527,6 +591,8 @@ def main():
     loop_world = int(os.environ.get("NSDG_BENCH_LOOPBACK_WORLD", "0"))
     if loop_world and (world != 1 or loop_world < 3):
         raise SystemExit("NSDG_BENCH_LOOPBACK_WORLD needs a single process and a world of at least 3 (an interior block)")
+    if loop_world and args.dump_outputs:
+        raise SystemExit("--dump-outputs needs a real run: the values of the loopback rehearsal wrap around")
     eff_world, eff_rank = (loop_world, loop_world // 2) if loop_world else (world, rank)
     H, A = bt.dg_fields()
     uo, vo = bt.ocean()
@@ -653,6 +719,15 @@ def main():
         if use_dist:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t[0])
+        if args.dump_outputs:
+            where = "output dump"
+            parts = [dynamics_outputs(core, coupled)]
+            if use_dist:
+                parts = [None] * world
+                dist.all_gather_object(parts, dynamics_outputs(core, coupled))
+            if rank == 0:
+                write_outputs(args.dump_outputs, parts)  # ranks own consecutive rows in rank order
+            where = "reduction over the ranks"
         cycle_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in ev]))  # one sub-cycle (nsub sub-iterations), this rank
         rank_report = {"rank": eff_rank, "rows_owned": blk.r1 - blk.r0, "rows_local": blk.ny, "ghost_rows_below": blk.gb, "ghost_rows_above": blk.gt,
                        "cycle_ms": cycle_ms, "prepare_ms": float(np.mean([e[0].elapsed_time(e[1]) for e in ev])),

@@ -1,11 +1,13 @@
 """`python bench.py --gpus N` must work as typed (the driver runs exactly that form): without WORLD_SIZE in the
 environment bench.py starts one worker per rank through torch.distributed.run itself.  Checked here without a
 GPU through the --dry-run plumbing path (gloo): launch, rendezvous on 127.0.0.1, row-block planning, max-over-ranks
-reduction, ONE JSON line from rank 0, exit status of the workers."""
+reduction, ONE JSON line from rank 0, exit status of the workers.  On the GPU: --steps and --dump-outputs of a real run."""
 import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -138,3 +140,66 @@ def test_roofline_labels_say_what_was_measured():
                 assert c["flops"] == bench.FP64_FLOPS_PER_ELEMENT_SUBITER[adaptive], c
                 assert c["fma"] == bench.FP64_FMA_PER_ELEMENT_SUBITER[adaptive], c
                 assert c["fma"] + c["addmul"] + 4 * c["trans"] + c["other_f64"] == bench.FP64_ISSUE_SLOTS_PER_ELEMENT_SUBITER[adaptive], c
+
+
+def test_dump_samples_merge_over_row_blocks(tmp_path):
+    """--dump-outputs: the parts of the ranks (consecutive rows each) assemble into what one rank writes; an array that fits is written
+    whole in its global shape, a larger one at the fixed, seeded positions"""
+    import numpy as np
+
+    import bench
+
+    rng = np.random.default_rng(1)
+    for nx, ny in ((40, 30), (512, 300)):
+        H = rng.random((6, ny, nx))
+        u = rng.random((2 * ny + 1, 2 * nx + 1))
+        got = []
+        for world in (1, 3):
+            parts = []
+            for r in np.array_split(np.arange(ny), world):
+                r0, r1 = int(r[0]), int(r[-1]) + 1
+                top = 2 * r1 + (1 if r1 == ny else 0)  # the last block owns the closing node row
+                parts.append({"H": bench.dump_part(H[:, r0:r1], r0 * nx, (6, ny, nx)),
+                              "u": bench.dump_part(u[2 * r0:top], 2 * r0 * (2 * nx + 1), (2 * ny + 1, 2 * nx + 1))})
+            d = str(tmp_path / ("%d_%d_%d" % (nx, ny, world)))
+            bench.write_outputs(d, parts)
+            got.append({k: np.load(os.path.join(d, k + ".npy")) for k in ("H", "u")})
+        for k in ("H", "u"):
+            assert got[0][k].dtype == np.float64 and np.array_equal(got[0][k], got[1][k])
+        if nx * ny <= bench.DUMP_SAMPLE:
+            assert np.array_equal(got[0]["H"], H)
+        else:
+            idx = bench.dump_positions(nx * ny)
+            assert got[0]["H"].shape == (6, bench.DUMP_SAMPLE) and np.array_equal(got[0]["H"], H.reshape(6, -1)[:, idx])
+        idx = bench.dump_positions(u.size)
+        assert np.array_equal(got[0]["u"].reshape(-1), u.reshape(-1)[idx])
+    assert np.array_equal(bench.dump_positions(10 ** 6), bench.dump_positions(10 ** 6))
+
+
+@pytest.mark.gpu
+def test_bench_steps_and_dumped_outputs(gpu, tmp_path):
+    """the real bench on a small grid: the line holds the --steps it was given and ms_per_step; --dump-outputs writes what a caller of
+    the step receives, finite, float64, and the same in two runs with the same arguments (the inputs are seeded); the transport workload
+    keeps an odd step count"""
+    import numpy as np
+
+    small = ["--gpus", "1", "--nx", "64", "--ny", "48", "--nsub", "8", "--warmup", "1", "--no-cpu-baseline"]
+    dumps = []
+    for k in range(2):
+        d = str(tmp_path / ("run%d" % k))
+        p = run_bench(*small, "--steps", "3", "--dump-outputs", d)
+        assert p.returncode == 0, p.stderr.decode()[-2000:]
+        (line,) = json_lines(p.stdout)
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    assert sorted(dumps[0]) == ["A", "H", "s11", "s12", "s22", "u", "v"]
+    for name, a in dumps[0].items():
+        assert a.dtype == np.float64 and bool(np.isfinite(a).all()) and np.array_equal(a, dumps[1][name]), name
+    assert dumps[0]["H"].shape == (6, 48, 64) and dumps[0]["u"].shape == (97, 129) and float(np.abs(dumps[0]["u"]).max()) > 0
+    d = str(tmp_path / "transport")
+    p = run_bench("--workload", "transport", "--nx", "64", "--order", "2", "--steps", "3", "--warmup", "1", "--dump-outputs", d)
+    assert p.returncode == 0, p.stderr.decode()[-2000:]
+    (line,) = json_lines(p.stdout)
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    phi = np.load(os.path.join(d, "phi.npy"))
+    assert phi.shape == (6, 64, 64) and bool(np.isfinite(phi).all())

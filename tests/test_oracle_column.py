@@ -1,6 +1,6 @@
 """Pins the column-physics oracle (oracle/column_oracle.c) against every known-answer value the
-reference's own tests hold for this path, the survey's 17-digit probe table, and -- where it could be
-built -- the reference's own header-only leaf functions (oracle/_ref)."""
+reference's own tests hold for this path, the survey's 17-digit probe table, and the recorded outputs of
+the reference's own header-only leaf functions (tests/golden/ref_leaf_v1.json; live as well where oracle/_ref is built)."""
 import json
 import os
 
@@ -60,20 +60,27 @@ def test_no_ice_branch():
 
 
 def test_against_reference_leaf_build():
-    """oracle/_ref = LinearFreezing.hpp / UnescoFreezing.hpp / constants.hpp compiled in place from
-    /root/reference.  Bit-exact agreement is required (same expressions, same libm)."""
-    R = O.ref_leaf()
-    if R is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
+    """LinearFreezing.hpp / UnescoFreezing.hpp / constants.hpp of the reference, compiled by oracle/ref_leaf_driver.cpp:
+    their outputs are recorded in tests/golden/ref_leaf_v1.json (tools/gen_ref_leaf_golden.py), and where oracle/_ref is
+    built the live library must still produce the recording.  Bit-exact agreement is required (same expressions, same libm)."""
+    gold = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "ref_leaf_v1.json")))
+    h = lambda xs: [float.fromhex(x) for x in xs]
+    sss, linear, unesco = h(gold["sss"]), h(gold["freezing_linear"]), h(gold["freezing_unesco"])
+    consts = h(c["value"] for c in gold["constants"])
+    assert sss == [float(s) for s in np.random.default_rng(7).uniform(0, 45, 200)] + [0.0, 32.0, 35.0]
     L = O.lib()
-    rng = np.random.default_rng(7)
-    for s in list(rng.uniform(0, 45, 200)) + [0.0, 32.0, 35.0]:
-        assert L.oracle_freezing_point(0, s) == R.ref_freezing_linear(s)
-        assert L.oracle_freezing_point(1, s) == R.ref_freezing_unesco(s)
+    for s, fl, fu in zip(sss, linear, unesco):
+        assert L.oracle_freezing_point(0, s) == fl, s
+        assert L.oracle_freezing_point(1, s) == fu, s
     want = [5.670374419e-8, 2100., 0.996, 2.0334, 333.55e3, 917., 330., 5., 273.15, 1004.64, 287.058,
             1860., 2500.79e3, 461.5, 4186.84, 333.55e3, 0.055, 1025., 273.15, 273.15]
-    for k, w in enumerate(want):
-        assert R.ref_constant(k) == w, k
+    assert consts == want
+    R = O.ref_leaf()
+    if R is not None:
+        for s, fl, fu in zip(sss, linear, unesco):
+            assert R.ref_freezing_linear(s) == fl and R.ref_freezing_unesco(s) == fu, s
+        for k, w in enumerate(want):
+            assert R.ref_constant(k) == w, k
 
 
 def test_newice_carry_over_quirk():

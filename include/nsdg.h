@@ -52,6 +52,8 @@
 extern "C" {
 #endif
 
+/* 6: a pipeline wait that gives up is an error status.  Since then the ABI has only grown, without a new number: nsdg_concentration_max,
+ * nsdg_substep_count and nsdg_comm_max_f64 (sub-stepping of the model time step) are additions; nothing that existed changed. */
 #define NSDG_ABI_VERSION 6
 
 typedef enum {
@@ -205,7 +207,8 @@ int nsdg_mevp_params_set(nsdg_ctx* ctx, const nsdg_mevp_params* p);
  *                                2 % of the maximum speed left after 120 sub-iterations at 1024^2 / 2048^2).  A converged plastic
  *                                solution exposes the time-step limit of the explicit strength / transport splitting (Lipscomb et al.
  *                                2007): dt = 120 s is too long for it at 250 m and below (2048^2 leaves the physical range after 11 model
- *                                hours, with dt = 60 s or 30 s it does not: profiles/r06_adaptive_noise.md) -- choose dt with the mesh.
+ *                                hours, with dt = 60 s or 30 s it does not: profiles/r06_adaptive_noise.md) -- split the model step with
+ *                                nsdg_substep_count below (the hosts' dynamics.substeps = auto / DynamicsCore.advance(substeps="auto")).
  *   NSDG_SUBCYCLE_KEEP_ALPHA     uniform alpha = beta = p->alpha; delta_min is raised to the smallest value for which that is stable
  *                                (never lowered): the viscosity is capped -- below a strain rate of delta_min the ice creeps
  *                                (nsdg_mevp_creep_percent_per_day).  The hosts' default of round 5.
@@ -215,6 +218,34 @@ enum { NSDG_SUBCYCLE_ADAPTIVE = 0, NSDG_SUBCYCLE_KEEP_ALPHA = 1, NSDG_SUBCYCLE_K
 int nsdg_mevp_stable_params(nsdg_mevp_params* p, int32_t mode, double h, double dt);
 /* strain rate below which the ice creeps instead of staying rigid (= delta_min), in percent per day */
 double nsdg_mevp_creep_percent_per_day(const nsdg_mevp_params* p);
+
+/* ---- sub-stepping: the model time step split by the ice's own strength wave speed (csrc/substep.hip) ----------------------------------
+ * The explicit coupling of ice strength and transport (Lipscomb et al. 2007) is stable while the plastic wave of the current state crosses
+ * at most about 1.5 cells per step: with the converging sub-cycle at 250 m, dt = 120 s leaves the physical range after 11 model hours and
+ * dt = 60 s or 30 s does not, and at 125 m dt = 30 s completes -- the same c dt / h = 1.5 at a = 0.9 (profiles/r06_adaptive_noise.md).
+ * The wave speed depends on the local concentration a only and grows with it,
+ *     c^2 = (1 + C a) P* exp(-C (1 - a)) / (2 rho_ice)        (C = compaction; P* = 27 500, C = 20, rho_ice = 900: 6.27 m/s at a = 0.9,
+ *                                                           17.91 m/s at a = 1),
+ * so the fastest wave of a state is c(max a).  A host that opts in measures max a at the start of a model step (nsdg_concentration_max, then
+ * nsdg_comm_max_f64 over the row blocks: every block must take the same n or the ghost exchanges stop matching) and runs the step as n
+ * sub-steps of dt / n:
+ *     n = max(1, ceil(c dt / (courant h))),   h = min(hx, hy),   courant = 1.5 by default (NSDG_SUBSTEP_COURANT)
+ * 1.5 is the largest ratio shown to work, read off the record at a = 0.9; the rule takes c at max a, which may reach 1 (the ridging cap
+ * allows it), so it can be conservative there: at a = 1 the runs that completed sit at c dt / h = 4.3 (profiles/r07_substeps.md).
+ * A step of n = 1 is the unsplit step, bit for bit.
+ *
+ * nsdg_concentration_max: the largest clamped concentration clamp(A, 0, 1) at the 3x3 Gauss points of the elements of rows [j0, j1) (the
+ * points and the clamp of nsdg_ice_strength), over the points where the clamped mean thickness max(H, 0) is > 0; 0 where there are none.
+ * Rows outside [j0, j1) (ghost rows) do not count.  H and A are DG2 fields (6 coefficient planes).  Every raw coefficient and every
+ * unclamped point value is checked: a non-finite one returns NSDG_ERR_ARG with the element in nsdg_last_error(), never a number.  One
+ * launch; the maximum of the bit patterns (exact, independent of the launch order) travels in one 8-byte copy; the call waits for it (on a
+ * context with a communicator within the communicator's deadline: NSDG_ERR_COMM on expiry).
+ * nsdg_substep_count: n by the rule above for the mEVP parameters' pstar, compaction and rho_ice, and c (may be NULL).  amax in [0, 1], h,
+ * dt, courant finite and positive, max_substeps >= 1, else NSDG_ERR_ARG.  If n would exceed max_substeps it returns NSDG_ERR_ARG with the
+ * needed n in the message: n is never capped.  Host only: usable without a device. */
+#define NSDG_SUBSTEP_COURANT 1.5
+int nsdg_concentration_max(nsdg_ctx* ctx, int32_t j0, int32_t j1, const double* H, const double* A, double* amax_host);
+int nsdg_substep_count(const nsdg_mevp_params* p, double amax, double h, double dt, double courant, int32_t max_substeps, int32_t* n, double* c);
 
 /* number of doubles of a tiled array (see "Data layout") */
 int64_t nsdg_tiled_len(int32_t nx, int32_t ny, int32_t nc);
@@ -437,6 +468,11 @@ int nsdg_comm_rank(nsdg_ctx* ctx, int32_t* rank, int32_t* world);
  * nsdg_ctx_synchronize (RCCL: a dead peer never answers).  0 = wait for ever.  Default: the environment variable
  * NSDG_COMM_TIMEOUT_S, else 300.  May be called before or after nsdg_comm_init*. */
 int nsdg_comm_deadline_set(nsdg_ctx* ctx, double seconds);
+/* Replaces *value in place with its maximum over the ranks of the context's communicator (a NaN on any rank gives NaN); without a
+ * communicator, or with a world of one, it is left as it is.  Collective: every rank calls it, in the same order relative to its other
+ * collective calls.  RCCL: ncclAllReduce(ncclMax) on a device scalar on the communication stream, the wait bounded by the deadline; local
+ * transport: on the host, under the same deadline.  NSDG_ERR_COMM when a rank does not arrive in time. */
+int nsdg_comm_max_f64(nsdg_ctx* ctx, double* value);
 
 /* Rehearsal aid for a box with ONE GPU (tools/rank_share_timing.py, bench.py's loopback rehearsal): a loopback exchange
  * has no wire time, so a kernel that spins for delay_us + bytes of the larger direction / gbs (GB/s per direction) is put on

@@ -99,6 +99,8 @@ SYMBOLS = {
     "nsdg_mevp_params_set": (C.c_int, [VP, C.POINTER(MevpParams)]),
     "nsdg_mevp_stable_params": (C.c_int, [C.POINTER(MevpParams), I32, D, D]),
     "nsdg_mevp_creep_percent_per_day": (C.c_double, [C.POINTER(MevpParams)]),
+    "nsdg_concentration_max": (C.c_int, [VP, I32, I32, VP, VP, C.POINTER(D)]),
+    "nsdg_substep_count": (C.c_int, [C.POINTER(MevpParams), D, D, D, D, I32, C.POINTER(I32), C.POINTER(D)]),
     "nsdg_tiled_len": (C.c_int64, [I32, I32, I32]),
     "nsdg_grid_set": (C.c_int, [VP, I32, I32, D, D]),
     "nsdg_mevp_variant_set": (C.c_int, [VP, I32]),
@@ -137,6 +139,7 @@ SYMBOLS = {
     "nsdg_comm_finalize": (C.c_int, [VP]),
     "nsdg_comm_rank": (C.c_int, [VP, C.POINTER(I32), C.POINTER(I32)]),
     "nsdg_comm_deadline_set": (C.c_int, [VP, D]),
+    "nsdg_comm_max_f64": (C.c_int, [VP, C.POINTER(D)]),
     "nsdg_comm_simulate_wire": (C.c_int, [VP, D, D]),
     "nsdg_halo_plan_create": (C.c_int, [VP, I32, I32, I32, C.POINTER(HaloSeg), I32, C.POINTER(HaloSeg), I32, C.POINTER(HaloSeg), I32,
                                         C.POINTER(HaloSeg), C.POINTER(VP)]),
@@ -191,6 +194,20 @@ def stable_mevp_params(p, mode, h, dt):
     if rc != 0:
         raise NsdgError("nsdg error %d: %s" % (rc, load_library().nsdg_last_error().decode()))
     return p
+
+
+SUBSTEP_COURANT = 1.5  # NSDG_SUBSTEP_COURANT: the default of the sub-stepping rule (include/nsdg.h "sub-stepping")
+
+
+def substep_count(p, amax, h, dt, courant=SUBSTEP_COURANT, max_substeps=16):
+    """nsdg_substep_count: (n, c) -- the number of sub-steps of dt that keeps the strength wave of a state with largest concentration amax
+    within `courant` cells of size h per sub-step, and that wave speed c [m/s]; NsdgError (with the needed n) if n > max_substeps"""
+    lib = load_library()
+    n, c = I32(0), D(0.0)
+    rc = lib.nsdg_substep_count(C.byref(p), float(amax), float(h), float(dt), float(courant), int(max_substeps), C.byref(n), C.byref(c))
+    if rc != 0:
+        raise NsdgError("nsdg error %d: %s" % (rc, lib.nsdg_last_error().decode()))
+    return int(n.value), float(c.value)
 
 
 def creep_percent_per_day(p):
@@ -627,6 +644,20 @@ class Context:
     def ice_strength(self, H, A, pg, j0=0, j1=None):
         _check_f64(H, A, pg)
         self._call(self.lib.nsdg_ice_strength(self.h, j0, self.ny if j1 is None else j1, _ptr(H), _ptr(A), _ptr(pg)))
+
+    def concentration_max(self, H, A, j0=0, j1=None):
+        """nsdg_concentration_max: largest clamped concentration at the Gauss points of rows [j0, j1) where there is ice (waits for the
+        result; NsdgError on a non-finite H or A)"""
+        _check_f64(H, A)
+        out = D(0.0)
+        self._call(self.lib.nsdg_concentration_max(self.h, j0, self.ny if j1 is None else j1, _ptr(H), _ptr(A), C.byref(out)))
+        return float(out.value)
+
+    def comm_max_f64(self, value):
+        """nsdg_comm_max_f64: the maximum of `value` over the ranks of the context's communicator (collective)"""
+        v = D(float(value))
+        self._call(self.lib.nsdg_comm_max_f64(self.h, C.byref(v)))
+        return float(v.value)
 
     def boxtest_forcing(self, domain_size, t, wind=None, ocean=None):
         ts = list(wind or (None, None)) + list(ocean or (None, None))

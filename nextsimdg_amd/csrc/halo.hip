@@ -25,6 +25,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <cmath>
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
@@ -51,6 +52,7 @@ struct RcclApi {
     ncclResult_t (*GroupEnd)() = nullptr;
     ncclResult_t (*Send)(const void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
     ncclResult_t (*Recv)(void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
+    ncclResult_t (*AllReduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
     const char* (*GetErrorString)(ncclResult_t) = nullptr;
 };
 
@@ -88,6 +90,7 @@ int rccl_load()
     NSDG_RCCL_SYM(GroupEnd, "ncclGroupEnd")
     NSDG_RCCL_SYM(Send, "ncclSend")
     NSDG_RCCL_SYM(Recv, "ncclRecv")
+    NSDG_RCCL_SYM(AllReduce, "ncclAllReduce")
     NSDG_RCCL_SYM(GetErrorString, "ncclGetErrorString")
 #undef NSDG_RCCL_SYM
     g_rccl = a;
@@ -123,6 +126,12 @@ struct LocalGroup {
     bool failed = false;
     std::map<std::tuple<int, int, int>, std::deque<LocalMsg>> box; // (src, dst, plan)
     std::map<std::tuple<int, int, int>, std::deque<hipEvent_t>> ack; // (src, dst, plan): dst has consumed src's buffer
+    // nsdg_comm_max_f64: the ranks that have arrived at the current reduction, its running maximum, and the result of the last
+    // completed one (a generation counter tells a waiter that its reduction is complete; the next one cannot complete -- and
+    // overwrite the result -- before every rank, the waiter included, has arrived at it)
+    int red_arrived = 0;
+    long red_generation = 0;
+    double red_acc = 0., red_result = 0.;
 };
 
 std::mutex g_groups_mutex;
@@ -711,6 +720,64 @@ int nsdg_comm_simulate_wire(nsdg_ctx* ctx, double delay_us, double gbs)
     }
     ctx->comm->sim_delay_us = delay_us;
     ctx->comm->sim_gbs = gbs;
+    return NSDG_OK;
+}
+
+int nsdg_comm_max_f64(nsdg_ctx* ctx, double* value)
+{
+    NSDG_CHECK_ARG(ctx && value, "null argument");
+    nsdg_comm* c = ctx->comm;
+    if (!c || c->world == 1)
+        return NSDG_OK;
+    if (c->broken) {
+        nsdg_set_error("nsdg_comm_max_f64: the communicator is broken (an earlier wait ran into the deadline)");
+        return NSDG_ERR_COMM;
+    }
+    if (c->nccl) {
+        // on the communication stream behind everything exchanged so far; the wait for the answer is bounded by the deadline
+        NSDG_CHECK_HIP(hipSetDevice(ctx->device));
+        double* d = ctx->scalar_dev + 1;
+        double* h = ctx->scalar_host + 1;
+        *h = *value;
+        NSDG_CHECK_HIP(hipMemcpyAsync(d, h, sizeof(double), hipMemcpyHostToDevice, c->stream));
+        NSDG_CHECK_RCCL(g_rccl.AllReduce(d, d, 1, ncclDouble, ncclMax, c->nccl, c->stream));
+        NSDG_CHECK_HIP(hipMemcpyAsync(h, d, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        const int rc = nsdg_comm_bounded_drain(ctx);
+        if (rc != NSDG_OK)
+            return rc;
+        *value = *h;
+        return NSDG_OK;
+    }
+    // local transport: the ranks are threads of this process -- the maximum is taken on the host, under the group's mutex
+    LocalGroup* g = c->local;
+    std::unique_lock<std::mutex> lock(g->m);
+    if (g->failed) {
+        nsdg_set_error("nsdg_comm_max_f64: a rank of the local group failed");
+        return NSDG_ERR_COMM;
+    }
+    const long generation = g->red_generation;
+    const double v = *value;
+    g->red_acc = g->red_arrived == 0 ? v : (std::isnan(v) || std::isnan(g->red_acc) ? NAN : std::max(g->red_acc, v));
+    if (++g->red_arrived == g->world) {
+        g->red_result = g->red_acc;
+        g->red_arrived = 0;
+        ++g->red_generation;
+        g->cv.notify_all();
+    } else {
+        const auto done = [&] { return g->failed || g->red_generation != generation; };
+        bool ok = true;
+        if (ctx->comm_deadline_s > 0.)
+            ok = g->cv.wait_for(lock, std::chrono::duration<double>(ctx->comm_deadline_s), done);
+        else
+            g->cv.wait(lock, done);
+        if (!ok || g->failed) {
+            g->failed = true;
+            g->cv.notify_all();
+            nsdg_set_error("nsdg_comm_max_f64: a rank of the local group failed or did not arrive within %g s", ctx->comm_deadline_s);
+            return NSDG_ERR_COMM;
+        }
+    }
+    *value = g->red_result;
     return NSDG_OK;
 }
 

@@ -173,8 +173,13 @@ int nsdg_ctx_create(int device_id, void* stream, nsdg_ctx** out)
         *c->p2p_flag_host = 0;
         e = hipHostGetDevicePointer((void**)&c->p2p_flag_dev, c->p2p_flag_host, 0);
     }
+    c->scalar_dev = nullptr, c->scalar_host = nullptr;
+    if (e == hipSuccess)
+        e = hipMalloc((void**)&c->scalar_dev, 2 * sizeof(double));
+    if (e == hipSuccess)
+        e = hipHostMalloc((void**)&c->scalar_host, 2 * sizeof(double), hipHostMallocDefault);
     if (e != hipSuccess) {
-        nsdg_set_error("nsdg_ctx_create: allocating the pipeline report channel failed: %s", hipGetErrorString(e));
+        nsdg_set_error("nsdg_ctx_create: allocating the pipeline report channel or the reduction scalars failed: %s", hipGetErrorString(e));
         nsdg_ctx_destroy(c);
         return NSDG_ERR_HIP;
     }
@@ -194,6 +199,10 @@ int nsdg_ctx_destroy(nsdg_ctx* ctx)
             (void)hipFree(ctx->p2p_count_dev);
         if (ctx->p2p_flag_host)
             (void)hipHostFree(ctx->p2p_flag_host);
+        if (ctx->scalar_dev)
+            (void)hipFree(ctx->scalar_dev);
+        if (ctx->scalar_host)
+            (void)hipHostFree(ctx->scalar_host);
     }
     delete ctx;
     return NSDG_OK;

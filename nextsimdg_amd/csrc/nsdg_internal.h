@@ -35,6 +35,10 @@ struct nsdg_ctx {
     unsigned* p2p_flag_host; // hipHostMalloc'ed; p2p_flag_dev is its device address
     unsigned* p2p_flag_dev;
     unsigned p2p_given_up; // sticky: events seen so far and not yet taken by nsdg_mevp_pipeline_health
+    // two device scalars and their pinned host mirrors: [0] the result of nsdg_concentration_max (substep.hip), [1] the value of
+    // nsdg_comm_max_f64 (halo.hip)
+    double* scalar_dev;
+    double* scalar_host; // hipHostMalloc'ed
 };
 
 void nsdg_set_error(const char* fmt, ...);

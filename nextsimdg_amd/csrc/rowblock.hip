@@ -124,7 +124,7 @@ int make_plan(nsdg_ctx* ctx, const Geometry& g, const SegList& L, nsdg_halo** ou
 // Delta_min^2, the cell size, the strip height, the kernel variant): the cache remembers the values its graphs were
 // recorded with and is dropped when any of them has changed, so a replay never mixes two parameter sets.
 struct GraphStamp {
-    double v[8];
+    double v[10];
     int k[6];
     bool operator==(const GraphStamp& o) const { return std::memcmp(this, &o, sizeof *this) == 0; }
 };
@@ -134,7 +134,9 @@ GraphStamp graph_stamp(const nsdg_ctx* c)
     GraphStamp s;
     std::memset(&s, 0, sizeof s);
     const nsdg_mevp_params& P = c->mevp;
-    const double v[8] = { c->pack_dt, P.alpha, P.beta, P.rho_ice, P.fc, P.delta_min, c->hx, c->hy };
+    // aevp_c and aevp_alpha_min: the adaptive form's constants (alpha_min follows dt under NSDG_SUBCYCLE_ADAPTIVE_CONVERGED, so a host that
+    // sub-steps changes it between model steps)
+    const double v[10] = { c->pack_dt, P.alpha, P.beta, P.rho_ice, P.fc, P.delta_min, c->hx, c->hy, P.aevp_c, P.aevp_alpha_min };
     const int k[6] = { c->strip_rows, c->mevp_variant, c->fused_min_waves, c->nx, c->ny, c->num_cus };
     std::memcpy(s.v, v, sizeof v);
     std::memcpy(s.k, k, sizeof k);

@@ -33,6 +33,12 @@
 //     dynamics.thermodynamics  run the column physics first       (false)
 //     dynamics.forcing       thermodynamic forcing: host (the structure's planes, constant in time) | dummy | winter
 //                            (generated on the device at every step's model time, wind speed from the dynamics' wind)
+//     dynamics.substeps      sub-steps per model step: an integer >= 1 (default 1: the unsplit step, bit for bit) or auto -- n decided at
+//                            the start of every model step from the state's strength wave speed, the same on every block
+//                            (nsdg_concentration_max, nsdg_comm_max_f64, nsdg_substep_count: include/nsdg.h "sub-stepping"); the whole
+//                            step (forcing, column, strength, sub-cycle, transport) runs n times with dt / n
+//     dynamics.substep_courant  cells the strength wave may cross per sub-step under auto (1.5)
+//     dynamics.max_substeps  the largest n auto may choose (16); a state that needs more stops the run with the needed n
 //     dynamics.row_blocks, dynamics.devices, dynamics.passes_per_exchange (2), dynamics.overlap (true),
 //     dynamics.graph (false), dynamics.loopback_world (0: off; N: rehearse an interior block of N on one GPU with
 //     real RCCL send/recv to the rank itself -- values wrap around, for timing and call-path checks only)
@@ -95,6 +101,7 @@ public:
 
 private:
     void release();
+    void subStep(double dt); //!< forcing at m_time, column step, ice strength, prepare, sub-cycle and transport with dt
     template <class F> void forEachBlock(F&& f); //!< one thread per block when there are several
     IStructure* pStructure = nullptr;
     std::vector<std::unique_ptr<DynamicsBlock>> m_blocks;
@@ -107,6 +114,11 @@ private:
     std::string subcycle = "adaptive"; // dynamics.subcycle
     double minConc = 1e-12, minThick = 0.01; // ice-free-node rule (dynamics.min_conc / min_thick; the column model's cut-off values)
     std::string forcing = "host", devices;
+    int substeps = 1; // dynamics.substeps; 0 = auto
+    double substepCourant = 1.5; // dynamics.substep_courant (NSDG_SUBSTEP_COURANT)
+    int maxSubsteps = 16; // dynamics.max_substeps
+    bool timing = false; // model.timing: one line whenever auto changes n
+    int m_lastSubsteps = 0; // n of the previous model step (auto)
     int m_world = 1, m_rank = 0; // multi-process run (one block per process)
     long m_steps = 0;
     double m_time = 0; // model time of the next step [s]

@@ -86,6 +86,7 @@ public:
     nsdg_rb_mevp* mevp = nullptr;
     nsdg_rb_transport* transport = nullptr;
     int par = 0, tpar = 0; // which buffers hold the velocity/stress iterate and the advected state
+    double amax = 0.; // largest concentration of the owned rows at the start of the model step (dynamics.substeps = auto)
 
     ~DynamicsBlock() { release(); }
     void release()
@@ -114,7 +115,8 @@ const std::map<int, std::string> Configured<DynamicsStep>::keyMap = { { 0, "dyna
     { 2, "dynamics.alpha" }, { 3, "dynamics.beta" }, { 4, "dynamics.thermodynamics" }, { 5, "dynamics.row_blocks" },
     { 6, "dynamics.passes_per_exchange" }, { 7, "dynamics.overlap" }, { 8, "dynamics.graph" }, { 9, "dynamics.forcing" },
     { 10, "dynamics.devices" }, { 11, "dynamics.loopback_world" }, { 12, "dynamics.closure" }, { 13, "dynamics.min_conc" },
-    { 14, "dynamics.min_thick" }, { 15, "dynamics.delta_min" }, { 16, "dynamics.subcycle" } };
+    { 14, "dynamics.min_thick" }, { 15, "dynamics.delta_min" }, { 16, "dynamics.subcycle" }, { 17, "dynamics.substeps" },
+    { 18, "dynamics.substep_courant" }, { 19, "dynamics.max_substeps" } };
 
 DynamicsStep::DynamicsStep() = default;
 DynamicsStep::~DynamicsStep() { release(); }
@@ -172,6 +174,27 @@ void DynamicsStep::configure()
     subcycle = getConfiguration(keyMap.at(16), std::string(alpha > 0 ? "keep_alpha" : "adaptive"));
     if (subcycle != "adaptive" && subcycle != "adaptive_converged" && subcycle != "keep_alpha" && subcycle != "keep_delta_min")
         throw std::invalid_argument("dynamics.subcycle must be adaptive, adaptive_converged, keep_alpha or keep_delta_min");
+    // sub-stepping of the model step (include/nsdg.h "sub-stepping"); off by default
+    {
+        const std::string v = getConfiguration(keyMap.at(17), std::string("1"));
+        std::size_t used = 0;
+        long k = 0;
+        try {
+            k = v == "auto" ? 0 : std::stol(v, &used);
+        } catch (const std::exception&) {
+            used = 0;
+        }
+        if (v != "auto" && (used != v.size() || k < 1 || k > 1000000))
+            throw std::invalid_argument("dynamics.substeps must be an integer >= 1 or auto");
+        substeps = (int)k;
+    }
+    substepCourant = getConfiguration(keyMap.at(18), (double)NSDG_SUBSTEP_COURANT);
+    maxSubsteps = getConfiguration(keyMap.at(19), 16);
+    if (!(std::isfinite(substepCourant) && substepCourant > 0))
+        throw std::invalid_argument("dynamics.substep_courant must be positive");
+    if (maxSubsteps < 1)
+        throw std::invalid_argument("dynamics.max_substeps must be >= 1");
+    timing = getConfiguration(std::string("model.timing"), false);
     if (rowBlocks < 1 || passesPerExchange < 1 || nsub < 0)
         throw std::invalid_argument("dynamics.row_blocks and dynamics.passes_per_exchange must be >= 1, dynamics.nsub >= 0");
     if (forcing != "host" && forcing != "dummy" && forcing != "winter")
@@ -406,6 +429,37 @@ void DynamicsStep::iterate(const Iterator::Duration& dtSeconds)
     if (m_blocks.empty())
         start(0);
     const double dt = dtSeconds;
+    int n = substeps;
+    if (n == 0) { // auto: from the state at the start of the model step, the same n on every block
+        nsdg_mevp_params p;
+        nsdg_mevp_default_params(&p);
+        forEachBlock([&](DynamicsBlock& b) {
+            checkHip(hipSetDevice(b.device), "hipSetDevice");
+            check(nsdg_concentration_max(b.ctx, b.j0, b.j1, b.curH(), b.curA(), &b.amax), "nsdg_concentration_max");
+        });
+        double amax = 0.; // the blocks of this process are its threads: their maximum is taken here ...
+        for (auto& b : m_blocks)
+            amax = std::max(amax, b->amax);
+        if (m_world > 1) // ... and the processes' through the communicator
+            check(nsdg_comm_max_f64(m_blocks[0]->ctx, &amax), "nsdg_comm_max_f64");
+        double c = 0.;
+        int32_t k = 0;
+        check(nsdg_substep_count(&p, amax, std::min(L / nxf, L / nyf), dt, substepCourant, maxSubsteps, &k, &c), "dynamics.substeps = auto");
+        n = k;
+        if (timing && n != m_lastSubsteps && m_rank == 0)
+            std::printf("dynamics substeps: t=%.17g s n=%d amax=%.17g c=%.17g m/s\n", m_time, n, amax, c);
+        m_lastSubsteps = n;
+    }
+    const double sub = dt / n;
+    for (int k = 0; k < n; ++k) {
+        subStep(sub);
+        m_time += sub;
+    }
+    ++m_steps;
+}
+
+void DynamicsStep::subStep(double dt)
+{
     nsdg_mevp_params p;
     nsdg_mevp_default_params(&p);
     const SubcycleChoice sc = subcycleChoice(std::min(L / nxf, L / nyf), dt);
@@ -441,8 +495,6 @@ void DynamicsStep::iterate(const Iterator::Duration& dtSeconds)
         check(nsdg_rb_transport_run(ctx, b.transport, dt, b.tpar, &out), "nsdg_rb_transport_run");
         b.tpar = out;
     });
-    ++m_steps;
-    m_time += dt;
 }
 
 void DynamicsStep::stop(const Iterator::TimePoint&)

@@ -543,6 +543,48 @@ class DynamicsCore:
         self.momentum()
         self.transport()
 
+    # ---- sub-stepping (include/nsdg.h "sub-stepping"): a model step of model_dt run as n steps of model_dt / n
+    def substep_count(self, model_dt, courant=None, max_substeps=16, params=None):
+        """(n, amax, c): the number of sub-steps the state asks for (nsdg_substep_count) from the largest concentration of the owned rows
+        (ops.concentration_max), the same on every rank: the maximum over the ranks goes through nsdg_comm_max_f64 on a
+        NativeHaloExchanger's communicator and through torch.distributed (MAX on a CPU scalar) otherwise.  params: the MevpParams whose
+        pstar, compaction and rho_ice give the wave speed (default: nsdg_mevp_default_params)"""
+        from nextsimdg_amd import abi
+
+        b = self.blk
+        self._set_grid()
+        amax = self.ops.concentration_max(self.H, self.A, b.j0, b.j1)
+        if isinstance(self.halo, NativeHaloExchanger):
+            amax = self.halo.ctx.comm_max_f64(amax)
+        elif b.world > 1:
+            t = torch.tensor([amax], dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.halo.group)
+            amax = float(t.item())
+        if params is None:
+            params = abi.MevpParams()
+            abi.load_library().nsdg_mevp_default_params(abi.C.byref(params))
+        n, c = abi.substep_count(params, amax, min(self.hx, self.hy), model_dt, abi.SUBSTEP_COURANT if courant is None else courant,
+                                 max_substeps)
+        return n, amax, c
+
+    def advance(self, model_dt, substeps=1, courant=None, max_substeps=16, params=None):
+        """one model step of model_dt as n calls of step() with self.dt = model_dt / n (restored afterwards); substeps: an int >= 1, or
+        "auto" (n from the state at the start of the step, substep_count).  Returns n; substeps = 1 is step() at model_dt, bit for bit"""
+        if substeps == "auto":
+            n = self.substep_count(model_dt, courant, max_substeps, params)[0]
+        elif isinstance(substeps, int) and not isinstance(substeps, bool) and substeps >= 1:
+            n = substeps
+        else:
+            raise ValueError("substeps must be an integer >= 1 or 'auto', got %r" % (substeps,))
+        dt = self.dt
+        self.dt = model_dt / n
+        try:
+            for _ in range(n):
+                self.step()
+        finally:
+            self.dt = dt
+        return n
+
     def owned(self, f):
         """owned element rows of a DG array / owned node rows of a nodal array (for gathering)"""
         b = self.blk

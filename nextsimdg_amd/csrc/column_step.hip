@@ -75,6 +75,12 @@ __device__ __forceinline__ double rdiv(double a, double b, double rb)
 }
 #define CDIV(a, c) rdiv((a), (c), 1.0 / (c)) /* c is a compile-time constant: 1/c is folded */
 
+// std::min / std::max as ThermoIce0.cpp:67-79 calls them: (b < a) ? b : a and (a < b) ? b : a.  Not fmin / fmax, which
+// return the other operand for a NaN: with a NaN thickness or ice temperature in, the reference's snow melt rate and
+// snow depth are NaN, fmin / fmax made them 0 (tests/golden/ref_column_v1.npz, the two NaN rows of each edge group).
+__device__ __forceinline__ double std_min(double a, double b) { return (b < a) ? b : a; }
+__device__ __forceinline__ double std_max(double a, double b) { return (a < b) ? b : a; }
+
 // NextsimPhysics::SpecificHumidity parameter sets, NextsimPhysics.cpp:310,346,324-325
 struct SpHum {
     double a, b, c, d, A, B, C;
@@ -212,12 +218,12 @@ __device__ __forceinline__ ColumnOut column_element(const nsdg_column_params& P,
             const double QIceConduction = k_lSlab * (tf - tice); // :60
             const double remainingFlux = QIceConduction - Qia; // :61
             Tnew = tice + remainingFlux / (k_lSlab + dQ_dT); // :62-63 (IEEE)
-            Tnew = fmin((hs_true > 0.) ? 0. : freezingPointIce, Tnew); // :66-68
-            const double snowMeltRate = CDIV(fmin(-remainingFlux, 0.), bulkLHFusionSnow); // :71
+            Tnew = std_min((hs_true > 0.) ? 0. : freezingPointIce, Tnew); // :66-68
+            const double snowMeltRate = CDIV(std_min(-remainingFlux, 0.), bulkLHFusionSnow); // :71
             const double snowSublRate = CDIV(subl, ICE_RHOSNOW); // :72
             hs += (snowMeltRate - snowSublRate) * dt; // :74
-            const double excessIceMelt = CDIV(fmin(hs, 0.) * bulkLHFusionSnow, bulkLHFusionIce); // :76-77
-            hs = fmax(hs, 0.); // :79
+            const double excessIceMelt = CDIV(std_min(hs, 0.) * bulkLHFusionSnow, bulkLHFusionIce); // :76-77
+            hs = std_max(hs, 0.); // :79
             hs += CDIV(snowfall * dt, ICE_RHOSNOW); // :81
             const double iceBottomChange = CDIV((QIceConduction - Qio) * dt, bulkLHFusionIce); // :84-85
             hi += excessIceMelt + iceBottomChange; // :87-88

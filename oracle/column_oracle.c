@@ -7,11 +7,11 @@
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this file's
  * shared object; the product path (nextsimdg_amd/) never does.
  *
- * Pinning: checked by tests/test_oracle_column.py against every known-answer value the
+ * Pinning: checked by tests/test_oracle_column.py bit for bit against the reference's own column
+ * step (tests/golden/ref_column_v1.npz, recorded from oracle/_ref/libref_column.so: the reference's
+ * sources compiled in place, oracle/ref_column_driver.cpp), and against every known-answer value the
  * reference's own tests hold for this path (physics/test/NextsimPhysics_test.cpp:73-77,123,
- * 160-172,229-240,298-309; core/test/ElementData_test.cpp:76-86) and against the 17-digit
- * probe values recorded in SURVEY.md Appendix C.  The reference itself is NOT buildable in this
- * image (needs Boost.program_options + generated .ipp files), see DESIGN.md section 4.
+ * 160-172,229-240,298-309; core/test/ElementData_test.cpp:76-86).  See DESIGN.md section 4.
  *
  * Every function cites the reference file:line it follows (paths relative to /root/reference).
  * Operation order is kept as written in the reference so that a CPU run is as close to the
@@ -47,6 +47,11 @@ static const double WATER_RHOOCEAN = 1025.; /* :117 */
 static const double WATER_TF = 273.15; /* :120 (= Ice::Tm :69) */
 
 static double kelvin(double c) { return c + WATER_TF; } /* constants.hpp:128 */
+
+/* std::min / std::max as ThermoIce0.cpp:67-79 calls them, not fmin / fmax: a NaN first operand is returned, where
+ * fmin / fmax would return the other one (the NaN rows of tests/golden/ref_column_v1.npz) */
+static double std_min(double a, double b) { return (b < a) ? b : a; }
+static double std_max(double a, double b) { return (a < b) ? b : a; }
 
 void oracle_column_default_params(oracle_column_params* p)
 {
@@ -217,12 +222,12 @@ void oracle_column_element(const oracle_column_params* P, double dt, double* H, 
             const double remainingFlux = QIceConduction - Qia; /* :61 */
             Tnew = tice + remainingFlux / (k_lSlab + dQ_dT); /* :62-63 */
             const double meltingLimit = (hs_true > 0.) ? 0 : freezingPointIce; /* :66 */
-            Tnew = fmin(meltingLimit, Tnew); /* :67-68 */
-            const double snowMeltRate = fmin(-remainingFlux, 0.) / bulkLHFusionSnow; /* :71 */
+            Tnew = std_min(meltingLimit, Tnew); /* :67-68 */
+            const double snowMeltRate = std_min(-remainingFlux, 0.) / bulkLHFusionSnow; /* :71 */
             const double snowSublRate = subl / ICE_RHOSNOW; /* :72 */
             hs += (snowMeltRate - snowSublRate) * dt; /* :74 */
-            const double excessIceMelt = fmin(hs, 0.) * bulkLHFusionSnow / bulkLHFusionIce; /* :76-77 */
-            hs = fmax(hs, 0.); /* :79 */
+            const double excessIceMelt = std_min(hs, 0.) * bulkLHFusionSnow / bulkLHFusionIce; /* :76-77 */
+            hs = std_max(hs, 0.); /* :79 */
             hs += snowfall * dt / ICE_RHOSNOW; /* :81 */
             const double iceBottomChange = (QIceConduction - Qio) * dt / bulkLHFusionIce; /* :84-85 */
             const double iceThicknessChange = excessIceMelt + iceBottomChange; /* :87 */

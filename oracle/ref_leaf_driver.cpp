@@ -1,15 +1,14 @@
 // ref_leaf_driver.cpp -- TEST INFRASTRUCTURE.
 //
-// Thin extern "C" driver around the only pieces of the reference that compile from their own
+// Thin extern "C" driver around the pieces of the reference that compile from their own
 // sources with g++ alone (no Boost, no generated .ipp): the two header-only freezing-point models
 // and the constants header.  The reference headers are #included BY PATH from /root/reference at
 // build time (oracle/Makefile passes -I/root/reference/core/src ...); nothing from the reference is
 // copied into this repository, and the resulting library goes to oracle/_ref/ (git-ignored).
 //
-// Everything else on the column-physics path (NextsimPhysics.cpp, ThermoIce0.cpp, the albedo and
-// concentration modules) includes Configured.hpp -> <boost/program_options.hpp> and
-// ModuleLoader.cpp -> generated moduleLoader*.ipp, neither of which exists in this image, so it is
-// treated as unbuildable here.
+// The rest of the column-physics path needs <boost/program_options.hpp> and the generated
+// moduleLoader*.ipp files; it is built by oracle/ref_column_driver.cpp with the stand-in of
+// oracle/refshim/ (DESIGN.md section 4).
 #include "modules/include/LinearFreezing.hpp" // core/src/modules/include/LinearFreezing.hpp:30-34
 #include "modules/include/UnescoFreezing.hpp" // core/src/modules/include/UnescoFreezing.hpp:28-38
 #include "include/constants.hpp" // core/src/include/constants.hpp:11-144

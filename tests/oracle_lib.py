@@ -4,6 +4,7 @@ Imported by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg -- n
 product package nextsimdg_amd/.
 """
 import ctypes as C
+import json
 import os
 import subprocess
 
@@ -200,3 +201,63 @@ def ref_leaf():
     L.ref_constant.restype = C.c_double
     L.ref_constant.argtypes = [C.c_int]
     return L
+
+
+def ref_column():
+    """oracle/_ref/libref_column.so: the reference's own column physics (oracle/ref_column_driver.cpp), or None if not built.
+    Configure it once per process (ref_column_configure): HiblerConcentration latches 1/h0 on its first use."""
+    path = os.path.join(ORACLE_DIR, "_ref", "libref_column.so")
+    if not os.path.exists(path):
+        return None
+    L = C.CDLL(path)
+    L.ref_column_configure.argtypes = [C.c_char_p]
+    L.ref_column_run.argtypes = [C.c_long, C.c_int, C.c_double, C.c_long] + [c_double_p] * 17
+    return L
+
+
+def ref_column_ini(params):
+    """The reference's configuration text for a ColumnParams: every key the column path reads
+    (NextsimPhysics.cpp:49-57, ThermoIce0.cpp:22-25, HiblerConcentration.cpp:20-23, CCSMIceAlbedo.cpp:38-41) and the
+    [Modules] choices (physics/src/modules/modules.json, core/src/modules/modules.json).  Values as C99 hex floats, which
+    strtod reads exactly."""
+    albedo = {v: k for k, v in ALBEDO.items()}[params.albedo_kind]
+    impl = {"smu": "SMUIceAlbedo", "smu2": "SMU2IceAlbedo", "ccsm": "CCSMIceAlbedo"}[albedo]
+    freezing = {0: "LinearFreezing", 1: "UnescoFreezing"}[params.freezing_kind]
+    h = lambda x: float(x).hex()
+    return "\n".join([
+        "[Modules]",
+        "Nextsim::IIceAlbedo = Nextsim::%s" % impl,
+        "Nextsim::IFreezingPoint = Nextsim::%s" % freezing,
+        "[nextsim_thermo]",
+        "drag_ocean_q = %s" % h(params.drag_ocean_q),
+        "drag_ocean_t = %s" % h(params.drag_ocean_t),
+        "drag_ice_t = %s" % h(params.drag_ice_t),
+        "albedoW = %s" % h(params.ocean_albedo),
+        "I_0 = %s" % h(params.i0),
+        "min_conc = %s" % h(params.min_conc),
+        "min_thick = %s" % h(params.min_thick),
+        "[thermoice0]",
+        "ks = %s" % h(params.ks),
+        "flooding = %s" % ("true" if params.flooding else "false"),
+        "[Hibler]",
+        "h0 = %s" % h(params.h0),
+        "phiM = %s" % h(params.phi_m),
+        "[CCSMIceAlbedo]",
+        "iceAlbedo = %s" % h(params.ccsm_ice_albedo),
+        "snowAlbedo = %s" % h(params.ccsm_snow_albedo),
+        ""])
+
+
+def ref_column_fixture():
+    """tests/golden/ref_column_v1.npz (tools/gen_ref_column_golden.py): (meta, arrays) -- meta lists the module sets with
+    their parameters and the recorded groups; a group's inputs are "<its 'inputs' prefix>in/<field>" (the random draw and the
+    chain are shared by every set), its outputs "<set>/<group>/out/<field>", ".../out/diag" [15, n] (last step) and, for
+    chains, ".../out/record" [nsteps, 5, n] (hice, cice, hsnow, tice0, newice)."""
+    with np.load(os.path.join(ROOT, "tests", "golden", "ref_column_v1.npz")) as z:
+        arrays = {k: z[k] for k in z.files}
+    return json.loads(str(arrays.pop("meta"))), arrays
+
+
+def ref_column_set_params(meta, name):
+    """keyword arguments of column_params() (and of abi.Context.column_default_params()) for a recorded module set"""
+    return {k: (float.fromhex(v) if isinstance(v, str) else v) for k, v in meta["sets"][name].items()}

@@ -119,6 +119,62 @@ def test_column_step_matches_oracle(ctx, pk):
     ctx.set_column_params(ctx.column_default_params())
 
 
+RC_META, RC = O.ref_column_fixture()
+RC_SETS = list(RC_META["sets"])
+
+
+def assert_same_class(got, want, what):
+    """NaN where the reference has NaN, +-Inf where it has the same Inf; nothing else is special"""
+    for name, f in (("NaN", np.isnan), ("+Inf", np.isposinf), ("-Inf", np.isneginf)):
+        bad = f(got) != f(want)
+        assert not bad.any(), "%s: %s differs at %d entries (first %d)" % (what, name, bad.sum(), np.argmax(bad))
+
+
+def assert_close_ref(got, want, rtol, atol, what):
+    assert_same_class(got, want, what)
+    fin = np.isfinite(want)
+    assert_close(got[fin], want[fin], rtol, atol, what)
+
+
+@pytest.mark.parametrize("name", RC_SETS)
+def test_column_step_matches_reference_build(ctx, name):
+    """nsdg_column_step against the reference's own column physics, recorded case by case (tests/golden/ref_column_v1.npz:
+    random draw, the edge grid at each recorded dt, and 10 chained steps with forcing that changes per step), per module set.
+    Chains are re-synchronised from the recording before every step.  1e-11 relative (device exp / sqrt / pow and FMA
+    contraction against glibc) plus the tiny absolute floors of test_column_step_matches_oracle; NaN and Inf class for class."""
+    ctx.set_column_params(ctx.column_default_params(**O.ref_column_set_params(RC_META, name)))
+    for g in (x for x in RC_META["groups"] if x["set"] == name):
+        key, ikey = "%s/%s/" % (name, g["group"]), g["inputs"] + "in/"
+        nsteps = g["nsteps"]
+        rec = RC.get(key + "out/record")
+        for step in range(nsteps):
+            if step == 0:
+                state = {k: RC[ikey + k] for k in abi.STATE}
+                newice = np.zeros(state["hice"].size)
+            else:
+                state = {k: rec[step - 1][i] for i, k in enumerate(abi.STATE)}
+                newice = rec[step - 1][4]
+            forcing = {k: RC[ikey + k][step] if nsteps > 1 else RC[ikey + k] for k in abi.FORCING}
+            ds, df, dn = {k: dev(v) for k, v in state.items()}, {k: dev(v) for k, v in forcing.items()}, dev(newice)
+            diag = torch.zeros(abi.NDIAG, newice.size, dtype=torch.float64, device="cuda")
+            ctx.column_step(g["dt"], ds, df, dn, diag)
+            if rec is not None:
+                want = {k: rec[step][i] for i, k in enumerate(abi.STATE + ["newice"])}
+            else:
+                want = {k: RC[key + "out/" + k] for k in abi.STATE + ["newice"]}
+            what = "%s step %d" % (key, step)
+            for k in abi.STATE:
+                assert_close_ref(host(ds[k]), want[k], 1e-11, 1e-13, "%s %s" % (what, k))
+            assert_close_ref(host(dn), want["newice"], 1e-11, 1e-16, what + " newice")
+            if step == nsteps - 1:
+                d, wd = host(diag), RC[key + "out/diag"]
+                for i, k in enumerate(abi.DIAG):
+                    fin = np.isfinite(wd[i])
+                    scale = (np.max(np.abs(wd[i][fin])) if fin.any() else 0.0) + 1e-300
+                    assert_close_ref(d[i], wd[i], 1e-11, 1e-13 * scale, "%s diag %s" % (what, k))
+    ctx.set_column_params(ctx.column_default_params())
+
+
 def test_column_edge_cases(ctx):
     # empty input is a no-op
     e = torch.zeros(0, dtype=torch.float64, device="cuda")

@@ -53,7 +53,8 @@ extern "C" {
 #endif
 
 /* 6: a pipeline wait that gives up is an error status.  Since then the ABI has only grown, without a new number: nsdg_concentration_max,
- * nsdg_substep_count and nsdg_comm_max_f64 (sub-stepping of the model time step) are additions; nothing that existed changed. */
+ * nsdg_substep_count and nsdg_comm_max_f64 (sub-stepping of the model time step) and nsdg_forcing_sample (forcing from a file) are
+ * additions; nothing that existed changed. */
 #define NSDG_ABI_VERSION 6
 
 typedef enum {
@@ -350,6 +351,29 @@ int nsdg_column_forcing(nsdg_ctx* ctx, int32_t kind, double t, double* tair, dou
 
 /* wind speed of the column step = |u_a| at the element centre (CG2 node (2 ix + 1, 2 iy + 1)) */
 int nsdg_column_wind(nsdg_ctx* ctx, const double* ua, const double* va, double* wind);
+
+/* Forcing from a file (csrc/forcing_file.hip): two records rec0, rec1 already on the device, each of nfields planes of nyr x nxr
+ * doubles (row-major, x fastest) on one lattice, sampled onto the local array and interpolated in time with weight w:
+ *     out[k] = lerp(S(rec0[k]), S(rec1[k]), w),   lerp(a, b, f) = a + f (b - a)   (the device may contract it to an FMA)
+ * Target (where): NSDG_AT_NODES = the CG2 node lattice, (2 nx + 1) x (2 ny + 1) values per plane (wind and ocean components);
+ * NSDG_AT_ELEMENTS = the element centres, nx x ny (column forcing planes).
+ * Lattice: cell-centred over the model's square domain, point i at x / L = (i + 1/2) / nxr, the same in y with nyr.
+ * S, the bilinear sample: the index-space coordinate of a target point is num / den, computed in integers and divided once --
+ *     node gx:    num = gx nxr - nx,            den = 2 nx;     element ix:  num = (2 ix + 1) nxr - nx,  den = 2 nx
+ * and in y the same with the GLOBAL row (node row gy + 2 row0, element row iy + row0) and ny_global of nsdg_block_set in place of nx.
+ * num <= 0 takes index 0 with weight 0; num >= (nxr - 1) den takes index nxr - 1 with weight 0; otherwise i0 = num / den (integer
+ * division), i1 = i0 + 1, f = (double)(num - i0 den) / den.  The sample interpolates along x on rows j0 and j1, then along y:
+ *     S = lerp(lerp(r[j0][i0], r[j0][i1], fx), lerp(r[j1][i0], r[j1][i1], fx), fy)
+ * Consequences, bit for bit: a constant field comes out constant; w = 0 gives rec0's sample; nxr = 1 (nyr = 1) is constant along x
+ * (y); nxr = nx and nyr = ny_global at the element centres is the identity; a row block computes what the whole domain computes for
+ * its rows, ghost rows included.
+ * Null pointers, nxr or nyr < 1 or > NSDG_FORCING_MAX_LATTICE, nfields outside [1, NSDG_FORCING_MAX_FIELDS], an unknown `where`, or
+ * a w that is not finite or outside [0, 1] return NSDG_ERR_ARG.  One launch; asynchronous on the context's stream. */
+enum { NSDG_AT_NODES = 0, NSDG_AT_ELEMENTS = 1 };
+#define NSDG_FORCING_MAX_FIELDS 8
+#define NSDG_FORCING_MAX_LATTICE 65536
+int nsdg_forcing_sample(nsdg_ctx* ctx, int32_t where, int32_t nxr, int32_t nyr, int32_t nfields, const double* const* rec0,
+    const double* const* rec1, double w, double* const* out);
 
 /* tau_a = c_atm * rho_atm * |u_a| u_a at nnodes nodes */
 int nsdg_wind_stress(nsdg_ctx* ctx, int64_t nnodes, const double* ua, const double* va, double* tax, double* tay);

@@ -118,6 +118,7 @@ SYMBOLS = {
     "nsdg_block_set": (C.c_int, [VP, I32, I32]),
     "nsdg_column_forcing": (C.c_int, [VP, I32, D] + [VP] * 7),
     "nsdg_column_wind": (C.c_int, [VP, VP, VP, VP]),
+    "nsdg_forcing_sample": (C.c_int, [VP, I32, I32, I32, I32, C.POINTER(VP), C.POINTER(VP), D, C.POINTER(VP)]),
     "nsdg_wind_stress": (C.c_int, [VP, I64, VP, VP, VP, VP]),
     "nsdg_mevp_stress": (C.c_int, [VP, I32, I32] + [VP] * 6),
     "nsdg_mevp_pack_nodal": (C.c_int, [VP, D] + [VP] * 9),
@@ -195,6 +196,9 @@ def stable_mevp_params(p, mode, h, dt):
         raise NsdgError("nsdg error %d: %s" % (rc, load_library().nsdg_last_error().decode()))
     return p
 
+
+AT_NODES, AT_ELEMENTS = 0, 1  # NSDG_AT_NODES / NSDG_AT_ELEMENTS: the targets of nsdg_forcing_sample
+FORCING_MAX_FIELDS = 8  # NSDG_FORCING_MAX_FIELDS
 
 SUBSTEP_COURANT = 1.5  # NSDG_SUBSTEP_COURANT: the default of the sub-stepping rule (include/nsdg.h "sub-stepping")
 
@@ -677,6 +681,25 @@ class Context:
     def column_wind(self, ua, va, wind):
         _check_f64(ua, va, wind)
         self._call(self.lib.nsdg_column_wind(self.h, _ptr(ua), _ptr(va), _ptr(wind)))
+
+    def forcing_sample(self, where, rec0, rec1, w, out):
+        """nsdg_forcing_sample: out[k] = the records rec0[k], rec1[k] ([nyr, nxr] tensors on one lattice) sampled bilinearly onto the
+        local array's CG2 nodes (where = "nodes") or element centres (where = "elements") and interpolated in time with weight w in
+        [0, 1] (include/nsdg.h "forcing from a file")"""
+        rec0, rec1, out = list(rec0), list(rec1), list(out)
+        if not (len(rec0) == len(rec1) == len(out)) or not rec0:
+            raise NsdgError("forcing_sample: rec0, rec1 and out need the same number (>= 1) of fields")
+        _check_f64(*(rec0 + rec1 + out))
+        nyr, nxr = rec0[0].shape
+        for r in rec0 + rec1:
+            if tuple(r.shape) != (nyr, nxr):
+                raise NsdgError("forcing_sample: every record plane must be [nyr, nxr] = [%d, %d]" % (nyr, nxr))
+        n = (2 * self.nx + 1) * (2 * self.ny + 1) if where == "nodes" else self.nx * self.ny
+        for o in out:  # the kernel writes n values into every output plane
+            if o.numel() != n:
+                raise NsdgError("forcing_sample: an output plane of %d values, the %s of the grid need %d" % (o.numel(), where, n))
+        self._call(self.lib.nsdg_forcing_sample(self.h, {"nodes": AT_NODES, "elements": AT_ELEMENTS}[where], nxr, nyr, len(out),
+                                                _ptr_array(rec0), _ptr_array(rec1), float(w), _ptr_array(out)))
 
     def wind_stress(self, ua, va, tax, tay):
         _check_f64(ua, va, tax, tay)

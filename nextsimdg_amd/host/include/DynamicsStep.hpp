@@ -32,7 +32,11 @@
 //     dynamics.min_conc/.min_thick   the ice-free-node rule's thresholds (defaults 1e-12, 0.01: the column model's cut-off)
 //     dynamics.thermodynamics  run the column physics first       (false)
 //     dynamics.forcing       thermodynamic forcing: host (the structure's planes, constant in time) | dummy | winter
-//                            (generated on the device at every step's model time, wind speed from the dynamics' wind)
+//                            (generated on the device at every step's model time, wind speed from the dynamics' wind) | file
+//                            (records of dynamics.forcing_file, sampled on the device at every (sub-)step's model time: bilinear in
+//                            space, linear in time -- nsdg_forcing_sample; the file's wind_u / wind_v and ocean_u / ocean_v pairs, where
+//                            present, replace the box test's cyclone and gyre; host/include/ForcingFile.hpp has the file layout)
+//     dynamics.forcing_file  the forcing file of forcing = file; read and checked when the step is configured
 //     dynamics.substeps      sub-steps per model step: an integer >= 1 (default 1: the unsplit step, bit for bit) or auto -- n decided at
 //                            the start of every model step from the state's strength wave speed, the same on every block
 //                            (nsdg_concentration_max, nsdg_comm_max_f64, nsdg_substep_count: include/nsdg.h "sub-stepping"); the whole
@@ -44,7 +48,7 @@
 //     real RCCL send/recv to the rank itself -- values wrap around, for timing and call-path checks only)
 // The structure's cell means initialise the DG fields: H <- hice, A <- cice (coefficient 0; higher coefficients
 // start at zero) and receive them back at stop().  Ocean current and wind come from the device-side forcing
-// provider nsdg_boxtest_forcing (the wind is re-evaluated at every step's model time).
+// provider nsdg_boxtest_forcing (the wind is re-evaluated at every step's model time), or from a forcing file's pairs.
 #pragma once
 #include <memory>
 #include <string>
@@ -57,6 +61,8 @@
 struct nsdg_ctx;
 
 namespace Nextsim {
+
+class ForcingFile;
 
 class DynamicsBlock; // one row block: context, device arrays, driver plans (DynamicsStep.cpp)
 
@@ -102,6 +108,9 @@ public:
 private:
     void release();
     void subStep(double dt); //!< forcing at m_time, column step, ice strength, prepare, sub-cycle and transport with dt
+    //! dynamics.forcing = file: records k0, k1 resident on the block's device, sampled with time weight w into the block's wind / ocean
+    //! (the pairs the file holds) and, with thermodynamics, its column forcing planes
+    void sampleForcingFile(DynamicsBlock& b, std::size_t k0, std::size_t k1, double w);
     template <class F> void forEachBlock(F&& f); //!< one thread per block when there are several
     IStructure* pStructure = nullptr;
     std::vector<std::unique_ptr<DynamicsBlock>> m_blocks;
@@ -114,6 +123,7 @@ private:
     std::string subcycle = "adaptive"; // dynamics.subcycle
     double minConc = 1e-12, minThick = 0.01; // ice-free-node rule (dynamics.min_conc / min_thick; the column model's cut-off values)
     std::string forcing = "host", devices;
+    std::shared_ptr<const ForcingFile> m_forcingFile; // dynamics.forcing = file: the records, read and checked in configure()
     int substeps = 1; // dynamics.substeps; 0 = auto
     double substepCourant = 1.5; // dynamics.substep_courant (NSDG_SUBSTEP_COURANT)
     int maxSubsteps = 16; // dynamics.max_substeps

@@ -14,6 +14,7 @@
 #include <thread>
 
 #include "../../../include/nsdg.h"
+#include "ForcingFile.hpp"
 #include "ModuleLoader.hpp"
 #include "PhysicsModules.hpp"
 #include "Rendezvous.hpp"
@@ -87,6 +88,10 @@ public:
     nsdg_rb_transport* transport = nullptr;
     int par = 0, tpar = 0; // which buffers hold the velocity/stress iterate and the advected state
     double amax = 0.; // largest concentration of the owned rows at the start of the model step (dynamics.substeps = auto)
+    // dynamics.forcing = file: two records of every variable of the file on the device (slot s: variables one after the other, in the
+    // order of ForcingFile::variables()), and which record each slot holds (-1: none)
+    double* records = nullptr;
+    long recordOf[2] = { -1, -1 };
 
     ~DynamicsBlock() { release(); }
     void release()
@@ -99,6 +104,9 @@ public:
         if (block)
             (void)hipFree(block);
         block = nullptr;
+        if (records)
+            (void)hipFree(records);
+        records = nullptr;
         if (ctx)
             nsdg_ctx_destroy(ctx); // finalises the communicator too
         ctx = nullptr;
@@ -116,7 +124,7 @@ const std::map<int, std::string> Configured<DynamicsStep>::keyMap = { { 0, "dyna
     { 6, "dynamics.passes_per_exchange" }, { 7, "dynamics.overlap" }, { 8, "dynamics.graph" }, { 9, "dynamics.forcing" },
     { 10, "dynamics.devices" }, { 11, "dynamics.loopback_world" }, { 12, "dynamics.closure" }, { 13, "dynamics.min_conc" },
     { 14, "dynamics.min_thick" }, { 15, "dynamics.delta_min" }, { 16, "dynamics.subcycle" }, { 17, "dynamics.substeps" },
-    { 18, "dynamics.substep_courant" }, { 19, "dynamics.max_substeps" } };
+    { 18, "dynamics.substep_courant" }, { 19, "dynamics.max_substeps" }, { 20, "dynamics.forcing_file" } };
 
 DynamicsStep::DynamicsStep() = default;
 DynamicsStep::~DynamicsStep() { release(); }
@@ -197,8 +205,19 @@ void DynamicsStep::configure()
     timing = getConfiguration(std::string("model.timing"), false);
     if (rowBlocks < 1 || passesPerExchange < 1 || nsub < 0)
         throw std::invalid_argument("dynamics.row_blocks and dynamics.passes_per_exchange must be >= 1, dynamics.nsub >= 0");
-    if (forcing != "host" && forcing != "dummy" && forcing != "winter")
-        throw std::invalid_argument("dynamics.forcing must be host, dummy or winter");
+    if (forcing != "host" && forcing != "dummy" && forcing != "winter" && forcing != "file")
+        throw std::invalid_argument("dynamics.forcing must be host, dummy, winter or file");
+    // forcing records from a file: read and checked here, before any device is touched
+    m_forcingFile.reset();
+    if (forcing == "file") {
+        const std::string path = getConfiguration(keyMap.at(20), std::string(""));
+        if (path.empty())
+            throw std::invalid_argument("dynamics.forcing = file needs dynamics.forcing_file");
+        m_forcingFile = std::make_shared<const ForcingFile>(path, thermo);
+        if (!thermo && !m_forcingFile->hasWind() && !m_forcingFile->hasOcean())
+            throw std::invalid_argument("dynamics.forcing_file " + path + ": without dynamics.thermodynamics the run uses only wind_u / wind_v "
+                                        "and ocean_u / ocean_v, and the file holds neither pair");
+    }
     if (loopbackWorld != 0 && loopbackWorld < 3)
         throw std::invalid_argument("dynamics.loopback_world needs an interior block: at least 3");
 }
@@ -389,8 +408,14 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
                 checkHip(hipMemcpy(b.d[dst[k]], t.data(), (std::size_t)TS * sizeof(double), hipMemcpyHostToDevice), "upload stress");
             }
         }
-        // analytic box-test forcing, evaluated on the device (ocean once, wind at the current model time every step)
+        // analytic box-test forcing, evaluated on the device (ocean once, wind at the current model time every step); a forcing file's
+        // wind and ocean pairs replace it at every step
         check(nsdg_boxtest_forcing(b.ctx, L, m_time, b.d[UA], b.d[VA], b.d[UO], b.d[VO]), "nsdg_boxtest_forcing");
+        if (m_forcingFile) {
+            const std::size_t n = 2 * m_forcingFile->variables().size() * (std::size_t)m_forcingFile->nxr() * m_forcingFile->nyr();
+            checkHip(hipMalloc(reinterpret_cast<void**>(&b.records), n * sizeof(double)), "DynamicsStep: hipMalloc (forcing records)");
+            b.recordOf[0] = b.recordOf[1] = -1;
+        }
         if (thermo) {
             const std::vector<double>* planes[NCOL] = { &f.hsnow, &f.tice, &f.sst, &f.sss, &f.tair, &f.tdew, &f.slp, &f.qsw, &f.qlw, &f.mld,
                 &f.snowfall, &f.wind, &f.newice };
@@ -468,16 +493,25 @@ void DynamicsStep::subStep(double dt)
     p.min_thick = closure ? minThick : 0.;
     const double t = m_time;
     const int kind = forcing == "winter" ? NSDG_FORCING_WINTER : NSDG_FORCING_DUMMY;
+    const ForcingFile* ff = m_forcingFile.get();
+    std::size_t k0 = 0, k1 = 0;
+    double w = 0.;
+    if (ff)
+        ff->bracket(t, k0, k1, w); // the records around the model time (throws outside the file's time range)
     forEachBlock([&](DynamicsBlock& b) {
         checkHip(hipSetDevice(b.device), "hipSetDevice");
         nsdg_ctx* ctx = b.ctx;
         check(nsdg_mevp_params_set(ctx, &p), "nsdg_mevp_params_set");
-        check(nsdg_boxtest_forcing(ctx, L, t, b.d[UA], b.d[VA], nullptr, nullptr), "nsdg_boxtest_forcing"); // the cyclone moves
+        if (!ff || !ff->hasWind())
+            check(nsdg_boxtest_forcing(ctx, L, t, b.d[UA], b.d[VA], nullptr, nullptr), "nsdg_boxtest_forcing"); // the cyclone moves
+        if (ff)
+            sampleForcingFile(b, k0, k1, w);
         if (thermo) {
             if (forcing != "host") { // DummyExternalData's replacement, and the wind speed the reference never sets
-                check(nsdg_column_forcing(ctx, kind, t, b.col(C_TAIR), b.col(C_TDEW), b.col(C_SLP), b.col(C_QSW), b.col(C_QLW), b.col(C_MLD),
-                          b.col(C_SNOWFALL)),
-                    "nsdg_column_forcing");
+                if (!ff)
+                    check(nsdg_column_forcing(ctx, kind, t, b.col(C_TAIR), b.col(C_TDEW), b.col(C_SLP), b.col(C_QSW), b.col(C_QLW), b.col(C_MLD),
+                              b.col(C_SNOWFALL)),
+                        "nsdg_column_forcing");
                 check(nsdg_column_wind(ctx, b.d[UA], b.d[VA], b.col(C_WIND)), "nsdg_column_wind");
             }
             // the column physics needs no exchange: it runs on the ghost rows too, redundantly
@@ -495,6 +529,63 @@ void DynamicsStep::subStep(double dt)
         check(nsdg_rb_transport_run(ctx, b.transport, dt, b.tpar, &out), "nsdg_rb_transport_run");
         b.tpar = out;
     });
+}
+
+void DynamicsStep::sampleForcingFile(DynamicsBlock& b, std::size_t k0, std::size_t k1, double w)
+{
+    const ForcingFile& ff = *m_forcingFile;
+    const std::vector<std::string> vars = ff.variables();
+    const std::size_t plane = (std::size_t)ff.nxr() * ff.nyr(), slot = vars.size() * plane;
+    // the two records around the model time stay resident: a record is uploaded when the model time crosses into it, into a slot
+    // whose record is no longer needed (after the work queued on the context, which may still read that slot)
+    int at[2] = { -1, -1 };
+    for (int i = 0; i < 2; ++i) {
+        const long k = (long)(i == 0 ? k0 : k1);
+        for (int s = 0; s < 2; ++s)
+            if (b.recordOf[s] == k)
+                at[i] = s;
+    }
+    for (int i = 0; i < 2; ++i) {
+        if (at[i] >= 0)
+            continue;
+        const long k = (long)(i == 0 ? k0 : k1), other = (long)(i == 0 ? k1 : k0);
+        const int s = b.recordOf[0] == other ? 1 : 0; // never the slot of the other record of the pair
+        std::vector<double> host(slot);
+        for (std::size_t v = 0; v < vars.size(); ++v)
+            std::copy(ff.record(vars[v], (std::size_t)k), ff.record(vars[v], (std::size_t)k) + plane, host.begin() + v * plane);
+        check(nsdg_ctx_synchronize(b.ctx), "DynamicsStep: forcing record upload");
+        checkHip(hipMemcpy(b.records + s * slot, host.data(), slot * sizeof(double), hipMemcpyHostToDevice), "upload forcing record");
+        b.recordOf[s] = k;
+        at[i] = s;
+        if (k0 == k1)
+            at[1] = s;
+    }
+    auto rec = [&](int i, const std::string& var) -> const double* {
+        std::size_t v = 0;
+        while (vars[v] != var)
+            ++v;
+        return b.records + at[i] * slot + v * plane;
+    };
+    // one launch per lattice: the wind and ocean pairs at the CG2 nodes, the column planes at the element centres
+    std::vector<const double*> r0, r1;
+    std::vector<double*> out;
+    for (const auto& pr : { std::make_pair("wind_u", UA), std::make_pair("wind_v", VA), std::make_pair("ocean_u", UO), std::make_pair("ocean_v", VO) })
+        if (ff.has(pr.first)) {
+            r0.push_back(rec(0, pr.first)), r1.push_back(rec(1, pr.first)), out.push_back(b.d[pr.second]);
+        }
+    if (!out.empty())
+        check(nsdg_forcing_sample(b.ctx, NSDG_AT_NODES, ff.nxr(), ff.nyr(), (int32_t)out.size(), r0.data(), r1.data(), w, out.data()),
+            "nsdg_forcing_sample (nodes)");
+    if (thermo) {
+        r0.clear(), r1.clear(), out.clear();
+        const int planes[7] = { C_TAIR, C_TDEW, C_SLP, C_QSW, C_QLW, C_MLD, C_SNOWFALL };
+        for (int c = 0; c < 7; ++c) {
+            const std::string& var = ForcingFile::columnVariables()[c];
+            r0.push_back(rec(0, var)), r1.push_back(rec(1, var)), out.push_back(b.col(planes[c]));
+        }
+        check(nsdg_forcing_sample(b.ctx, NSDG_AT_ELEMENTS, ff.nxr(), ff.nyr(), 7, r0.data(), r1.data(), w, out.data()),
+            "nsdg_forcing_sample (elements)");
+    }
 }
 
 void DynamicsStep::stop(const Iterator::TimePoint&)

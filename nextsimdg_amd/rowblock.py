@@ -643,6 +643,62 @@ class DynamicsCore:
         return out
 
 
+class ForcingSeries:
+    """Forcing records on one lattice at model times (include/nsdg.h "forcing from a file"; the C++ host reads the same records from a
+    file, host/include/ForcingFile.hpp).  times: strictly increasing model times [s] (the clock of CoupledCore.time); fields: name ->
+    float64 array [nt, nyr, nxr] on a cell-centred lattice over the square domain.  Names: the column planes tair tdew slp qsw qlw mld
+    snowfall, and the pairs wind_u / wind_v and ocean_u / ocean_v (each pair complete or absent).  A time outside [times[0], times[-1]]
+    is an error: there is no extrapolation."""
+
+    COLUMN = ("tair", "tdew", "slp", "qsw", "qlw", "mld", "snowfall")
+    WIND = ("wind_u", "wind_v")
+    OCEAN = ("ocean_u", "ocean_v")
+
+    def __init__(self, times, fields):
+        import numpy as np
+
+        t = np.array(times, dtype=np.float64)
+        if t.ndim != 1 or t.size < 1:
+            raise ValueError("times must be a 1-d array of at least one record time")
+        if not np.all(np.isfinite(t)) or np.any(np.diff(t) <= 0):
+            raise ValueError("times must be finite and strictly increasing")
+        if not fields:
+            raise ValueError("a forcing series needs at least one field")
+        known = self.COLUMN + self.WIND + self.OCEAN
+        out = {}
+        for name, a in fields.items():
+            if name not in known:
+                raise ValueError("unknown forcing field %r (known: %s)" % (name, " ".join(known)))
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.ndim != 3 or a.shape[0] != t.size or min(a.shape) < 1:
+                raise ValueError("forcing field %r has shape %s, expected (%d, nyr, nxr)" % (name, a.shape, t.size))
+            if not np.all(np.isfinite(a)):
+                k = int(np.argwhere(~np.isfinite(a))[0][0])
+                raise ValueError("forcing field %r has a non-finite value in record %d" % (name, k))
+            out[name] = a
+        shapes = {a.shape for a in out.values()}
+        if len(shapes) != 1:
+            raise ValueError("all forcing fields must be on one lattice, got shapes %s" % sorted(shapes))
+        for pair in (self.WIND, self.OCEAN):
+            if (pair[0] in out) != (pair[1] in out):
+                raise ValueError("forcing fields %s and %s come as a pair" % pair)
+        self.times, self.fields = t, out
+        _, self.nyr, self.nxr = shapes.pop()
+
+    def bracket(self, t):
+        """(k0, k1, w): the records around model time t and the weight of k1 -- k0 is the last record with times[k0] <= t, k1 = k0 + 1,
+        w = (t - times[k0]) / (times[k1] - times[k0]); at the last record itself k1 = k0 and w = 0"""
+        import numpy as np
+
+        t0, t1 = float(self.times[0]), float(self.times[-1])
+        if not (t0 <= t <= t1):
+            raise ValueError("model time %r s is outside the forcing records [%r, %r] s" % (t, t0, t1))
+        k0 = int(np.searchsorted(self.times, t, side="right")) - 1
+        if k0 == self.times.size - 1:
+            return k0, k0, 0.0
+        return k0, k0 + 1, (t - float(self.times[k0])) / (float(self.times[k0 + 1]) - float(self.times[k0]))
+
+
 class CoupledCore(DynamicsCore):
     """BASELINE config 5: dynamics + column thermodynamics.  Each model step first advances the column
     physics of every owned element (the reference's DevStep::iterate, core/src/DevStep.cpp:14-23) and then
@@ -660,12 +716,27 @@ class CoupledCore(DynamicsCore):
         """forcing: None = the forcing planes are whatever load_column() put there (constant in time);
         "dummy" / "winter" = regenerated on the device at every step's model time (nsdg_column_forcing) and the
         column wind speed is |u_a| of the dynamics' wind (nsdg_column_wind) -- the replacement of the reference's
-        DummyExternalData (core/src/include/DummyExternalData.hpp:22-34) and of its never-set windSpeed"""
+        DummyExternalData (core/src/include/DummyExternalData.hpp:22-34) and of its never-set windSpeed;
+        a ForcingSeries = records of a file sampled on the device at every step's model time (ops.forcing_sample): the column planes,
+        and the wind (ua, va) and the ocean current (uo, vo) where the series holds them; the column wind speed as above"""
         super().__init__(ops, blk, hx, hy, dt, nsub, device, **kw)
         z = lambda: torch.zeros(blk.ny, blk.nx, dtype=torch.float64, device=device)
         self.col = {k: z() for k in self.COLUMN_STATE + self.COLUMN_FORCING}
         self.newice = z()
         self.forcing, self.time = forcing, 0.0
+        if isinstance(forcing, ForcingSeries):
+            missing = [k for k in ForcingSeries.COLUMN if k not in forcing.fields]
+            if missing:
+                raise ValueError("the column step needs the forcing series to hold %s" % ", ".join(missing))
+            # one launch per lattice and step: the column planes at the element centres, the wind and ocean pairs at the nodes
+            self._series_groups = [("elements", ForcingSeries.COLUMN, [self.col[k] for k in ForcingSeries.COLUMN])]
+            nodal = [(names, outs) for names, outs in ((ForcingSeries.WIND, (self.ua, self.va)), (ForcingSeries.OCEAN, (self.uo, self.vo)))
+                     if names[0] in forcing.fields]
+            if nodal:
+                self._series_groups.append(("nodes", sum((n for n, _ in nodal), ()), [o for _, outs in nodal for o in outs]))
+            self._records, self._device = {}, device
+        elif forcing not in (None, "dummy", "winter"):
+            raise ValueError("forcing must be None, 'dummy', 'winter' or a ForcingSeries, got %r" % (forcing,))
 
     def load_column(self, fields):
         """fields: dict name -> global [ny, nx] numpy array for hsnow, tice0 and the 10 forcing fields"""
@@ -680,8 +751,23 @@ class CoupledCore(DynamicsCore):
         forcing = {k: self.col[k] for k in self.COLUMN_FORCING}
         self.ops.column_step(self.dt, state, forcing, self.newice)
 
+    def _record(self, k):
+        """record k of the forcing series on the device: {name: [nyr, nxr] tensor}"""
+        if k not in self._records:
+            self._records[k] = {name: torch.from_numpy(a[k]).to(self._device) for name, a in self.forcing.fields.items()}
+        return self._records[k]
+
     def external_forcing(self):
-        if self.forcing is not None:
+        if isinstance(self.forcing, ForcingSeries):
+            # the two records around the model time stay resident; a record is uploaded when the model time crosses into it
+            k0, k1, w = self.forcing.bracket(self.time)
+            for k in [k for k in self._records if k not in (k0, k1)]:
+                del self._records[k]
+            r0, r1 = self._record(k0), self._record(k1)
+            for where, names, outs in self._series_groups:
+                self.ops.forcing_sample(where, [r0[n] for n in names], [r1[n] for n in names], w, outs)
+            self.ops.column_wind(self.ua, self.va, self.col["wind"])
+        elif self.forcing is not None:
             self.ops.column_forcing(self.forcing, self.time, self.col)
             self.ops.column_wind(self.ua, self.va, self.col["wind"])
 

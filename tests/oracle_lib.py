@@ -119,13 +119,13 @@ def ncoef(order):
     return {0: 1, 1: 3, 2: 6}[order]
 
 
-def prepare_advection(nx, ny, order, u, v):
+def prepare_advection(nx, ny, order, u, v, omp=False):
     nc, ng = ncoef(order), order + 1
     vx = np.zeros((nc, ny, nx))
     vy = np.zeros((nc, ny, nx))
     unx = np.zeros((ng, ny, nx + 1))
     uny = np.zeros((ng, ny + 1, nx))
-    lib().oracle_prepare_advection(nx, ny, order, dp(u), dp(v), dp(vx), dp(vy), dp(unx), dp(uny))
+    lib(omp).oracle_prepare_advection(nx, ny, order, dp(u), dp(v), dp(vx), dp(vy), dp(unx), dp(uny))
     return vx, vy, unx, uny
 
 
@@ -141,20 +141,20 @@ def transport_step(nx, ny, hx, hy, order, dt, phi, adv, omp=False):
     lib(omp).oracle_transport_step(nx, ny, hx, hy, order, dt, dp(phi), dp(vx), dp(vy), dp(unx), dp(uny), dp(scratch))
 
 
-def transport_limit(nx, ny, order, phi, lo, hi, cap, j0=0, j1=None):
+def transport_limit(nx, ny, order, phi, lo, hi, cap, j0=0, j1=None, omp=False):
     """closure of the transport on rows [j0, j1), in place: cell-mean cap (cap) + scaling limiter to [lo, hi]"""
-    lib().oracle_transport_limit(nx, ny, j0, ny if j1 is None else j1, order, dp(phi), float(lo), float(hi), int(bool(cap)))
+    lib(omp).oracle_transport_limit(nx, ny, j0, ny if j1 is None else j1, order, dp(phi), float(lo), float(hi), int(bool(cap)))
 
 
-def dg_to_cg(nx, ny, f_dg):
+def dg_to_cg(nx, ny, f_dg, omp=False):
     out = np.zeros((2 * ny + 1, 2 * nx + 1))
-    lib().oracle_dg_to_cg(nx, ny, f_dg.shape[0], dp(f_dg), dp(out))
+    lib(omp).oracle_dg_to_cg(nx, ny, f_dg.shape[0], dp(f_dg), dp(out))
     return out
 
 
-def ice_strength(nx, ny, params, H, A, j0=0, j1=None):
+def ice_strength(nx, ny, params, H, A, j0=0, j1=None, omp=False):
     pg = np.zeros((9, ny, nx))
-    lib().oracle_ice_strength(nx, ny, j0, ny if j1 is None else j1, C.byref(params), dp(H), dp(A), dp(pg))
+    lib(omp).oracle_ice_strength(nx, ny, j0, ny if j1 is None else j1, C.byref(params), dp(H), dp(A), dp(pg))
     return pg
 
 
@@ -182,10 +182,10 @@ def mevp_subcycle(nx, ny, hx, hy, dt, nsub, params, s, u, v, u0, v0, tax, tay, u
                                   dp(u0), dp(v0), dp(tax), dp(tay), dp(uo), dp(vo), dp(cgh), dp(cga), dp(pg), dp(scratch))
 
 
-def wind_stress(params, ua, va):
+def wind_stress(params, ua, va, omp=False):
     tax = np.zeros_like(ua)
     tay = np.zeros_like(va)
-    lib().oracle_wind_stress(ua.size, C.byref(params), dp(ua), dp(va), dp(tax), dp(tay))
+    lib(omp).oracle_wind_stress(ua.size, C.byref(params), dp(ua), dp(va), dp(tax), dp(tay))
     return tax, tay
 
 

@@ -97,7 +97,7 @@ def test_config4_2048_dynamics_step_properties(ctx):
     box, finite fields, agreement of the fused and the two-kernel mEVP variants at full size"""
     n = 2048
     results = {}
-    for variant in (3, 2, 1, 0):
+    for variant in (4, 3, 2, 1, 0):
         ctx.set_mevp_variant(variant)
         core = box_core(ctx, n, nsub=12)
         mH, mA = float(core.H[0].sum()), float(core.A[0].sum())
@@ -118,7 +118,7 @@ def test_config4_2048_dynamics_step_properties(ctx):
     for a, b in zip(results[0], results[1]):
         scale = float(a.abs().max())
         assert float((a - b).abs().max()) <= 1e-10 * scale
-    for other in (2, 3):  # one, two and three sub-iterations per pass: bit-identical velocities and thickness
+    for other in (2, 3, 4):  # one, two, three and four sub-iterations per pass: bit-identical velocities and thickness
         for a, b in zip(results[1][:2] + results[1][3:], results[other][:2] + results[other][3:]):
             assert torch.equal(a, b), other
 

@@ -610,3 +610,51 @@ def test_oracle_limiter_properties(order):
     out3 = f.copy()
     O.transport_limit(nx, ny, order, out3, 0.0, 1.0, True, 4, 9)
     assert np.array_equal(out3[:, 4:9], out[:, 4:9]) and np.array_equal(out3[:, :4], f[:, :4]) and np.array_equal(out3[:, 9:], f[:, 9:])
+
+
+def test_openmp_oracle_is_bitwise_the_serial_oracle():
+    """oracle/liboracle_omp.so is the reference of the full-size device tests (tests/test_gpu_fullsize_parity.py): it must be the serial
+    oracle bit for bit -- each parallel loop writes only its own rows -- on a ragged case (301 x 97): a DG0 / DG1 / DG2 transport step of H
+    and A with the closure's limiter, 8 adaptive and 8 uniform sub-iterations"""
+    nx, ny = 301, 97
+    bt = synthetic.BoxTest(nx, ny)
+    rng = np.random.default_rng(17)
+    X, Y = basis.node_coords(nx, ny, bt.L, bt.L)
+    u = np.ascontiguousarray(0.1 * np.sin(3e-5 * X) * np.cos(2e-5 * Y) + 0.02)
+    v = np.ascontiguousarray(0.1 * np.cos(2e-5 * X + 1) * np.sin(4e-5 * Y) - 0.03)
+    for order in (0, 1, 2):
+        nc = O.ncoef(order)
+        H = rng.uniform(-0.2, 2.0, (nc, ny, nx))  # slopes and means that leave [0, inf) and [0, 1]: the limiter and the cap act
+        A = rng.uniform(0.3, 1.2, (nc, ny, nx))
+        H[1:] *= 0.3
+        A[1:] *= 0.3
+        dt = 0.2 * bt.hx / 0.15 / (2 * order + 1)
+        out = []
+        for omp in (False, True):
+            adv = O.prepare_advection(nx, ny, order, u, v, omp=omp)
+            fields = [H.copy(), A.copy()]
+            for f, (lo, hi, cap) in zip(fields, ((0.0, np.inf, False), (0.0, 1.0, True))):
+                O.transport_step(nx, ny, bt.hx, bt.hy, order, dt, f, adv, omp=omp)
+                O.transport_limit(nx, ny, order, f, lo, hi, cap, omp=omp)
+            out.append(fields)
+        for a, b in zip(*out):
+            assert np.array_equal(a, b), order
+        assert not np.array_equal(out[0][0], H) and float(out[0][1][0].max()) <= 1.0
+    H, A = bt.dg_fields()
+    A[0] -= 0.2 * rng.random((ny, nx))
+    H[1:] += 0.01 * rng.standard_normal(H[1:].shape)
+    uo, vo = [np.ascontiguousarray(a) for a in bt.ocean()]
+    for mode in ("adaptive", "keep_delta_min"):
+        po = O.mevp_params(**bt.subcycle_parameters(120.0, mode))
+        out = []
+        for omp in (False, True):
+            pg = O.ice_strength(nx, ny, po, H, A, omp=omp)
+            cgh, cga = O.dg_to_cg(nx, ny, H, omp=omp), O.dg_to_cg(nx, ny, A, omp=omp)
+            tax, tay = O.wind_stress(po, *[np.ascontiguousarray(a) for a in bt.wind(0.0)], omp=omp)
+            uu, vv = u.copy(), v.copy()
+            s = [np.zeros((8, ny, nx)) for _ in range(3)]
+            O.mevp_subcycle(nx, ny, bt.hx, bt.hy, 120.0, 8, po, s, uu, vv, u, v, tax, tay, uo, vo, cgh, cga, pg, omp=omp)
+            out.append([uu, vv] + s)
+        for a, b in zip(*out):
+            assert np.array_equal(a, b), mode
+        assert np.max(np.abs(out[0][0] - u)) > 1e-4

@@ -53,8 +53,8 @@ extern "C" {
 #endif
 
 /* 6: a pipeline wait that gives up is an error status.  Since then the ABI has only grown, without a new number: nsdg_concentration_max,
- * nsdg_substep_count and nsdg_comm_max_f64 (sub-stepping of the model time step) and nsdg_forcing_sample (forcing from a file) are
- * additions; nothing that existed changed. */
+ * nsdg_substep_count and nsdg_comm_max_f64 (sub-stepping of the model time step), nsdg_forcing_sample (forcing from a file) and
+ * nsdg_tracer_weight / nsdg_tracer_recover (column state transport) are additions; nothing that existed changed. */
 #define NSDG_ABI_VERSION 6
 
 typedef enum {
@@ -326,6 +326,26 @@ int nsdg_dg_to_cg(nsdg_ctx* ctx, int32_t ncoef, const double* f_dg, double* f_cg
 
 /* P = pstar * max(H,0) * exp(-C (1 - clamp(A,0,1))) at the 3x3 Gauss points of rows [j0, j1) */
 int nsdg_ice_strength(nsdg_ctx* ctx, int32_t j0, int32_t j1, const double* H, const double* A, double* pg);
+
+/* ---- column state transport: the snow and the ice surface temperature ride on the moving ice (csrc/tracer.hip) ----------------------
+ * In the coupled model the column step's other prognostic state moves with the ice (opt-in in both hosts; off by default).  The snow
+ * volume per unit area hsnow is a DG2 field S of its own whose plane 0 IS the column's hsnow (as plane 0 of H is hice), advected with H
+ * and A and bounded below by 0.  The surface temperature tice0 is intensive: it travels as the conserved product Q = H T, weighted by
+ * the ice VOLUME H (not A: the ridging cap changes the mean of A but never the mean of H, and the scaling limiter changes no cell mean),
+ * so sum_e mean(H)_e T_e is conserved by the transport up to rounding.  Q is unbounded (-HUGE_VAL, HUGE_VAL, no cap) and is rebuilt
+ * every step.  A coupled transport step is: nsdg_tracer_weight, one transport step of the four fields H, A, S, Q, nsdg_tracer_recover.
+ *
+ * nsdg_tracer_weight: Q[c*nx*ny + e] = T[e] * H[c*nx*ny + e] for every coefficient c < nc(order) of the elements of rows [j0, j1); T is
+ * one plane (tice0 is DG0).  The product of a constant and a DG field is exact: the result is that multiplication, bit for bit.
+ * nsdg_tracer_recover: where an element holds ice after the step -- mean(H) > 0, mean(A) >= min_conc and mean(H) >= min_thick * mean(A),
+ * the test of the ice-free-node rule (nsdg_mevp_params.min_conc / min_thick), false for a NaN -- T[e] = mean(Q) / mean(H) (plane 0 of
+ * each, one IEEE division); everywhere else T[e] keeps its value (the column step ignores tice0 where there is no ice).
+ * Both are element-local: a row block runs them on its ghost rows too, which then stay bit-identical to their owners without an
+ * exchange.  Stream-ordered, one launch each; Q must not alias H or T.  A null pointer, an order outside 0..2 or a row range outside
+ * the local array: NSDG_ERR_ARG. */
+int nsdg_tracer_weight(nsdg_ctx* ctx, int32_t order, int32_t j0, int32_t j1, const double* H, const double* T, double* Q);
+int nsdg_tracer_recover(nsdg_ctx* ctx, int32_t order, int32_t j0, int32_t j1, const double* H, const double* A, const double* Q,
+    double min_conc, double min_thick, double* T);
 
 /* ---- external forcing providers, evaluated on the device at the model time of each step (csrc/forcing.hip) ----
  * They replace DummyExternalData::setAll (core/src/include/DummyExternalData.hpp:22-34: the same eight constants in

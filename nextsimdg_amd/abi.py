@@ -114,6 +114,8 @@ SYMBOLS = {
     "nsdg_transport_limit": (C.c_int, [VP, I32, I32, I32, I32, C.POINTER(VP)]),
     "nsdg_dg_to_cg": (C.c_int, [VP, I32, VP, VP]),
     "nsdg_ice_strength": (C.c_int, [VP, I32, I32, VP, VP, VP]),
+    "nsdg_tracer_weight": (C.c_int, [VP, I32, I32, I32, VP, VP, VP]),
+    "nsdg_tracer_recover": (C.c_int, [VP, I32, I32, I32, VP, VP, VP, D, D, VP]),
     "nsdg_boxtest_forcing": (C.c_int, [VP, D, D, VP, VP, VP, VP]),
     "nsdg_block_set": (C.c_int, [VP, I32, I32]),
     "nsdg_column_forcing": (C.c_int, [VP, I32, D] + [VP] * 7),
@@ -648,6 +650,18 @@ class Context:
     def ice_strength(self, H, A, pg, j0=0, j1=None):
         _check_f64(H, A, pg)
         self._call(self.lib.nsdg_ice_strength(self.h, j0, self.ny if j1 is None else j1, _ptr(H), _ptr(A), _ptr(pg)))
+
+    # ---- column state transport (include/nsdg.h): tice0 rides on the ice as Q = H T
+    def tracer_weight(self, order, j0, j1, H, T, Q):
+        """nsdg_tracer_weight: Q[c] = T * H[c] for every coefficient plane c of the elements of rows [j0, j1)"""
+        _check_f64(H, T, Q)
+        self._call(self.lib.nsdg_tracer_weight(self.h, order, j0, j1, _ptr(H), _ptr(T), _ptr(Q)))
+
+    def tracer_recover(self, order, j0, j1, H, A, Q, min_conc, min_thick, T):
+        """nsdg_tracer_recover: T = Q[0] / H[0] where the element of rows [j0, j1) holds ice (H[0] > 0, A[0] >= min_conc,
+        H[0] >= min_thick A[0]); T keeps its value elsewhere"""
+        _check_f64(H, A, Q, T)
+        self._call(self.lib.nsdg_tracer_recover(self.h, order, j0, j1, _ptr(H), _ptr(A), _ptr(Q), float(min_conc), float(min_thick), _ptr(T)))
 
     def concentration_max(self, H, A, j0=0, j1=None):
         """nsdg_concentration_max: largest clamped concentration at the Gauss points of rows [j0, j1) where there is ice (waits for the

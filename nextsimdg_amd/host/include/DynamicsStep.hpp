@@ -31,6 +31,10 @@
 //     dynamics.closure       ridging cap + scaling limiter in the transport, free drift at ice-free nodes (default true)
 //     dynamics.min_conc/.min_thick   the ice-free-node rule's thresholds (defaults 1e-12, 0.01: the column model's cut-off)
 //     dynamics.thermodynamics  run the column physics first       (false)
+//     dynamics.advect_column_state  the snow and the ice surface temperature move with the ice (false; needs thermodynamics): the snow
+//                            is a DG2 field S advected with H and A (plane 0 = hsnow), tice0 travels as Q = H tice0 (nsdg_tracer_weight
+//                            before the transport, nsdg_tracer_recover after it: include/nsdg.h "column state transport"); a restart
+//                            then also holds hsnow_dg, the higher coefficients of S
 //     dynamics.forcing       thermodynamic forcing: host (the structure's planes, constant in time) | dummy | winter
 //                            (generated on the device at every step's model time, wind speed from the dynamics' wind) | file
 //                            (records of dynamics.forcing_file, sampled on the device at every (sub-)step's model time: bilinear in
@@ -118,6 +122,7 @@ private:
     double L = 512e3, alpha = 0, beta = 0;
     int nsub = 120, rowBlocks = 1, passesPerExchange = 2, loopbackWorld = 0;
     bool thermo = false, overlap = true, graph = false, m_inited = false;
+    bool advectColumn = false; // dynamics.advect_column_state: the snow and the surface temperature ride on the ice
     bool closure = true; // ridging cap + scaling limiter in the transport, free drift at ice-free nodes (dynamics.closure)
     double deltaMin = 0; // dynamics.delta_min; 0: the literature's 2e-9 (keep_alpha: raised to what the mesh needs)
     std::string subcycle = "adaptive"; // dynamics.subcycle

@@ -23,6 +23,9 @@ struct DynamicsState {
     std::vector<double> hdg, adg; //!< coefficients 1..5 of H and A: [5][x][y]
     std::vector<double> u, v; //!< nodal velocity on the (2x+1) x (2y+1) lattice
     std::vector<double> s11, s12, s22; //!< stress coefficients: [8][x][y]
+    //! coefficients 1..5 of the snow S of dynamics.advect_column_state: [5][x][y]; EMPTY without that mode (nothing of it is written)
+    //! and after reading a file that does not hold it (the higher coefficients then start at zero)
+    std::vector<double> sdg;
     void resize(std::size_t nx, std::size_t ny)
     {
         hdg.assign(5 * nx * ny, 0.), adg.assign(5 * nx * ny, 0.);
@@ -32,7 +35,7 @@ struct DynamicsState {
     void clear()
     {
         present = false;
-        for (auto* a : { &hdg, &adg, &u, &v, &s11, &s12, &s22 })
+        for (auto* a : { &hdg, &adg, &u, &v, &s11, &s12, &s22, &sdg })
             a->clear();
     }
 };

@@ -17,7 +17,10 @@
 //     u, v             (xnode = 2x+1, ynode = 2y+1)    CG2 nodal velocity
 //     s11, s12, s22    (stress8 = 8, x, y)             stress coefficients of the 8-function DG space
 //     newice           (x, y)              the column model's persistent new-ice volume (NextsimPhysics::m_newice)
-// (sidecar: header line data.dynamics=1, the arrays in this order after tice).  A file without them starts the dynamics from rest.
+//     hsnow_dg         (dg2 = 5, x, y)     only with dynamics.advect_column_state: DG2 coefficients 1..5 of the advected snow
+//                                          (coefficient 0 = hsnow); a file without it starts them at zero
+// (sidecar: header line data.dynamics=1, the arrays in this order after tice; hsnow_dg last, announced by data.snow_dg=1).  A file
+// without them starts the dynamics from rest.
 #pragma once
 #include "Configured.hpp"
 #include "IStructure.hpp"

@@ -68,7 +68,8 @@ void tileRows(const double* planes, std::size_t planeStride, std::size_t srcRow0
 }
 
 // device arrays of a block; the advected fields, the stress and the velocity exist twice (ping-pong)
-enum Arr { H0, A0, H1, A1, T2H, T2A, S11a, S12a, S22a, S11b, S12b, S22b, PG, VXDG, VYDG, UNX, UNY, Ua, Va, Ub, Vb, UA, VA, UO, VO, PACKED, COL, NARR };
+// (S0 .. T2Q: the snow and the weighted surface temperature of dynamics.advect_column_state; empty without it)
+enum Arr { H0, A0, H1, A1, T2H, T2A, S0, Q0, S1, Q1, T2S, T2Q, S11a, S12a, S22a, S11b, S12b, S22b, PG, VXDG, VYDG, UNX, UNY, Ua, Va, Ub, Vb, UA, VA, UO, VO, PACKED, COL, NARR };
 // column planes inside COL
 enum Col { C_HSNOW, C_TICE, C_SST, C_SSS, C_TAIR, C_TDEW, C_SLP, C_QSW, C_QLW, C_MLD, C_SNOWFALL, C_WIND, C_NEWICE, NCOL };
 } // namespace
@@ -113,6 +114,8 @@ public:
     }
     double* curH() const { return d[tpar == 0 ? H0 : H1]; }
     double* curA() const { return d[tpar == 0 ? A0 : A1]; }
+    double* curS() const { return d[tpar == 0 ? S0 : S1]; }
+    double* curQ() const { return d[tpar == 0 ? Q0 : Q1]; }
     double* curU() const { return d[par == 0 ? Ua : Ub]; }
     double* curV() const { return d[par == 0 ? Va : Vb]; }
     double* col(int k) const { return d[COL] + (long)k * N; }
@@ -124,7 +127,8 @@ const std::map<int, std::string> Configured<DynamicsStep>::keyMap = { { 0, "dyna
     { 6, "dynamics.passes_per_exchange" }, { 7, "dynamics.overlap" }, { 8, "dynamics.graph" }, { 9, "dynamics.forcing" },
     { 10, "dynamics.devices" }, { 11, "dynamics.loopback_world" }, { 12, "dynamics.closure" }, { 13, "dynamics.min_conc" },
     { 14, "dynamics.min_thick" }, { 15, "dynamics.delta_min" }, { 16, "dynamics.subcycle" }, { 17, "dynamics.substeps" },
-    { 18, "dynamics.substep_courant" }, { 19, "dynamics.max_substeps" }, { 20, "dynamics.forcing_file" } };
+    { 18, "dynamics.substep_courant" }, { 19, "dynamics.max_substeps" }, { 20, "dynamics.forcing_file" },
+    { 21, "dynamics.advect_column_state" } };
 
 DynamicsStep::DynamicsStep() = default;
 DynamicsStep::~DynamicsStep() { release(); }
@@ -220,6 +224,11 @@ void DynamicsStep::configure()
     }
     if (loopbackWorld != 0 && loopbackWorld < 3)
         throw std::invalid_argument("dynamics.loopback_world needs an interior block: at least 3");
+    // the snow and the surface temperature ride on the moving ice (include/nsdg.h "column state transport"); off by default
+    advectColumn = getConfiguration(keyMap.at(21), false);
+    if (advectColumn && !thermo)
+        throw std::invalid_argument("dynamics.advect_column_state needs dynamics.thermodynamics = true: without the column model there is no "
+                                    "snow or surface temperature to carry");
 }
 
 void DynamicsStep::init()
@@ -363,6 +372,9 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
             sizes[a] = 0;
         for (int a : { H0, A0, H1, A1, T2H, T2A, VXDG, VYDG })
             sizes[a] = 6 * N;
+        if (advectColumn)
+            for (int a : { S0, Q0, S1, Q1, T2S, T2Q })
+                sizes[a] = 6 * N;
         for (int a : { S11a, S12a, S22a, S11b, S12b, S22b })
             sizes[a] = TS;
         sizes[PG] = TP;
@@ -396,6 +408,8 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
             for (int c = 1; c < 6; ++c) {
                 checkHip(hipMemcpy(b.d[H0] + (long)c * N, dy.hdg.data() + (std::size_t)(c - 1) * NG + first, N * sizeof(double), hipMemcpyHostToDevice), "upload H (DG)");
                 checkHip(hipMemcpy(b.d[A0] + (long)c * N, dy.adg.data() + (std::size_t)(c - 1) * NG + first, N * sizeof(double), hipMemcpyHostToDevice), "upload A (DG)");
+                if (advectColumn && dy.sdg.size() == 5 * NG) // a file without hsnow_dg: the higher coefficients of the snow start at zero
+                    checkHip(hipMemcpy(b.d[S0] + (long)c * N, dy.sdg.data() + (std::size_t)(c - 1) * NG + first, N * sizeof(double), hipMemcpyHostToDevice), "upload S (DG)");
             }
             const std::size_t nn = 2 * (std::size_t)b.nx + 1, nfirst = 2 * (std::size_t)b.lo * nn;
             checkHip(hipMemcpy(b.d[Ua], dy.u.data() + nfirst, NN * sizeof(double), hipMemcpyHostToDevice), "upload u");
@@ -421,6 +435,8 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
                 &f.snowfall, &f.wind, &f.newice };
             for (int c = 0; c < NCOL; ++c)
                 checkHip(hipMemcpy(b.col(c), planes[c]->data() + first, N * sizeof(double), hipMemcpyHostToDevice), "upload column fields");
+            if (advectColumn) // plane 0 of the snow field IS the column's hsnow (C_HSNOW stays unused)
+                checkHip(hipMemcpy(b.d[S0], f.hsnow.data() + first, N * sizeof(double), hipMemcpyHostToDevice), "upload S");
         }
         // driver plans
         nsdg_rb_mevp_desc m;
@@ -436,13 +452,17 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
         std::memset(&t, 0, sizeof t);
         t.nx = b.nx, t.ny = b.ny, t.j0 = b.j0, t.j1 = b.j1, t.depth_below = b.depthBelow, t.depth_above = b.depthAbove;
         t.rank_below = b.peerBelow, t.rank_above = b.peerAbove;
-        t.order = 2, t.nfields = 2;
+        t.order = 2, t.nfields = advectColumn ? 4 : 2;
         t.phi[0] = b.d[H0], t.phi[1] = b.d[A0], t.t1[0] = b.d[H1], t.t1[1] = b.d[A1], t.t2[0] = b.d[T2H], t.t2[1] = b.d[T2A];
+        if (advectColumn) // the snow S and the weighted surface temperature Q = H tice0
+            t.phi[2] = b.d[S0], t.phi[3] = b.d[Q0], t.t1[2] = b.d[S1], t.t1[3] = b.d[Q1], t.t2[2] = b.d[T2S], t.t2[3] = b.d[T2Q];
         t.vx_dg = b.d[VXDG], t.vy_dg = b.d[VYDG], t.un_x = b.d[UNX], t.un_y = b.d[UNY];
         // the closure travels with the plan (its own bounds, not the context's): mean thickness H >= 0; concentration in [0, 1] with the
         // cell mean capped at 1
-        t.own_bounds = 1, t.nbounds = closure ? 2 : 0;
+        // cell mean capped at 1; the snow volume S >= 0; Q unbounded
+        t.own_bounds = 1, t.nbounds = closure ? t.nfields : 0;
         t.bounds[0] = nsdg_field_bounds { 0., HUGE_VAL, 0, 0 }, t.bounds[1] = nsdg_field_bounds { 0., 1., 1, 0 };
+        t.bounds[2] = nsdg_field_bounds { 0., HUGE_VAL, 0, 0 }, t.bounds[3] = nsdg_field_bounds { -HUGE_VAL, HUGE_VAL, 0, 0 };
         check(nsdg_rb_transport_create(b.ctx, &t, &b.transport), "nsdg_rb_transport_create");
         b.par = b.tpar = 0;
     });
@@ -515,7 +535,7 @@ void DynamicsStep::subStep(double dt)
                 check(nsdg_column_wind(ctx, b.d[UA], b.d[VA], b.col(C_WIND)), "nsdg_column_wind");
             }
             // the column physics needs no exchange: it runs on the ghost rows too, redundantly
-            check(nsdg_column_step(ctx, b.N, dt, b.curH(), b.curA(), b.col(C_HSNOW), b.col(C_TICE), b.col(C_SST), b.col(C_SSS), b.col(C_TAIR),
+            check(nsdg_column_step(ctx, b.N, dt, b.curH(), b.curA(), advectColumn ? b.curS() : b.col(C_HSNOW), b.col(C_TICE), b.col(C_SST), b.col(C_SSS), b.col(C_TAIR),
                       b.col(C_TDEW), b.col(C_SLP), b.col(C_QSW), b.col(C_QLW), b.col(C_MLD), b.col(C_SNOWFALL), b.col(C_WIND), b.col(C_NEWICE),
                       nullptr),
                 "nsdg_column_step");
@@ -526,8 +546,13 @@ void DynamicsStep::subStep(double dt)
         check(nsdg_rb_mevp_run(ctx, b.mevp, b.par, &out), "nsdg_rb_mevp_run");
         b.par = out;
         check(nsdg_prepare_advection(ctx, 2, b.curU(), b.curV(), b.d[VXDG], b.d[VYDG], b.d[UNX], b.d[UNY]), "nsdg_prepare_advection");
+        // the surface temperature travels as Q = H tice0 (every local row: element-local, the ghost rows stay equal to their owners)
+        if (advectColumn)
+            check(nsdg_tracer_weight(ctx, 2, 0, b.ny, b.curH(), b.col(C_TICE), b.curQ()), "nsdg_tracer_weight");
         check(nsdg_rb_transport_run(ctx, b.transport, dt, b.tpar, &out), "nsdg_rb_transport_run");
         b.tpar = out;
+        if (advectColumn)
+            check(nsdg_tracer_recover(ctx, 2, 0, b.ny, b.curH(), b.curA(), b.curQ(), p.min_conc, p.min_thick, b.col(C_TICE)), "nsdg_tracer_recover");
     });
 }
 
@@ -609,7 +634,7 @@ void DynamicsStep::stop(const Iterator::TimePoint&)
         checkHip(hipMemcpy(f.hice.data() + first, b.curH() + skip, count * sizeof(double), hipMemcpyDeviceToHost), "download H");
         checkHip(hipMemcpy(f.cice.data() + first, b.curA() + skip, count * sizeof(double), hipMemcpyDeviceToHost), "download A");
         if (thermo) {
-            checkHip(hipMemcpy(f.hsnow.data() + first, b.col(C_HSNOW) + skip, count * sizeof(double), hipMemcpyDeviceToHost), "download hsnow");
+            checkHip(hipMemcpy(f.hsnow.data() + first, (advectColumn ? b.curS() : b.col(C_HSNOW)) + skip, count * sizeof(double), hipMemcpyDeviceToHost), "download hsnow");
             checkHip(hipMemcpy(f.tice.data() + first, b.col(C_TICE) + skip, count * sizeof(double), hipMemcpyDeviceToHost), "download tice");
             checkHip(hipMemcpy(f.newice.data() + first, b.col(C_NEWICE) + skip, count * sizeof(double), hipMemcpyDeviceToHost), "download newice");
         }
@@ -621,7 +646,14 @@ void DynamicsStep::stop(const Iterator::TimePoint&)
         const std::size_t NG = (std::size_t)nxf * nyf;
         if (dy.hdg.size() != 5 * NG)
             dy.resize((std::size_t)nyf, (std::size_t)nxf);
+        // the higher coefficients of the snow exist only in this mode: without it nothing of them is written
+        if (!advectColumn)
+            dy.sdg.clear();
+        else if (dy.sdg.size() != 5 * NG)
+            dy.sdg.assign(5 * NG, 0.);
         for (int c = 1; c < 6; ++c) {
+            if (advectColumn)
+                checkHip(hipMemcpy(dy.sdg.data() + (std::size_t)(c - 1) * NG + first, b.curS() + (long)c * b.N + skip, count * sizeof(double), hipMemcpyDeviceToHost), "download S (DG)");
             checkHip(hipMemcpy(dy.hdg.data() + (std::size_t)(c - 1) * NG + first, b.curH() + (long)c * b.N + skip, count * sizeof(double), hipMemcpyDeviceToHost), "download H (DG)");
             checkHip(hipMemcpy(dy.adg.data() + (std::size_t)(c - 1) * NG + first, b.curA() + (long)c * b.N + skip, count * sizeof(double), hipMemcpyDeviceToHost), "download A (DG)");
         }
@@ -748,6 +780,9 @@ std::vector<double> DynamicsStep::packRows(FieldStore& f, bool thermodynamics, i
         const std::size_t nn = 2 * (std::size_t)nx + 1, nfirst = 2 * (std::size_t)r0 * nn, ncount = ownedNodeRows(r0, r1, (int)(f.n / nx)) * nn;
         for (auto* v : { &f.dyn.u, &f.dyn.v })
             out.insert(out.end(), v->begin() + nfirst, v->begin() + nfirst + ncount);
+        if (f.dyn.sdg.size() == 5 * f.n) // dynamics.advect_column_state: the higher coefficients of the snow last
+            for (int c = 0; c < 5; ++c)
+                out.insert(out.end(), f.dyn.sdg.begin() + (std::size_t)c * f.n + first, f.dyn.sdg.begin() + (std::size_t)c * f.n + first + count);
     }
     return out;
 }
@@ -757,13 +792,14 @@ void DynamicsStep::placeRows(FieldStore& f, bool thermodynamics, int nx, int r0,
     const auto planes = restartPlanes(f, thermodynamics);
     const std::size_t first = (std::size_t)r0 * nx, rows = (std::size_t)(r1 - r0) * nx;
     const std::size_t nn = 2 * (std::size_t)nx + 1, ny = f.n / nx, nrows = ownedNodeRows(r0, r1, (int)ny) * nn;
-    const std::size_t plain = rows * planes.size(), full = plain + rows * (5 + 5 + 24) + 2 * nrows;
-    if (count != plain && count != full)
+    const std::size_t plain = rows * planes.size(), full = plain + rows * (5 + 5 + 24) + 2 * nrows, snow = full + rows * 5;
+    if (count != plain && count != full && count != snow)
         throw std::runtime_error("DynamicsStep: a rank delivered " + std::to_string(count) + " values for its rows, expected "
-            + std::to_string(plain) + " (or " + std::to_string(full) + " with the state of the dynamics)");
+            + std::to_string(plain) + " (or " + std::to_string(full) + " with the state of the dynamics, " + std::to_string(snow)
+            + " with the snow of dynamics.advect_column_state as well)");
     for (std::size_t k = 0; k < planes.size(); ++k)
         std::copy(data + k * rows, data + (k + 1) * rows, planes[k]->begin() + first);
-    if (count == full) {
+    if (count == full || count == snow) {
         if (f.dyn.hdg.size() != 5 * f.n)
             f.dyn.resize(ny, (std::size_t)nx);
         const double* p = data + plain;
@@ -774,6 +810,12 @@ void DynamicsStep::placeRows(FieldStore& f, bool thermodynamics, int nx, int r0,
         for (auto* v : { &f.dyn.u, &f.dyn.v }) {
             std::copy(p, p + nrows, v->begin() + 2 * (std::size_t)r0 * nn);
             p += nrows;
+        }
+        if (count == snow) {
+            if (f.dyn.sdg.size() != 5 * f.n)
+                f.dyn.sdg.assign(5 * f.n, 0.);
+            for (int c = 0; c < 5; ++c, p += rows)
+                std::copy(p, p + rows, f.dyn.sdg.begin() + (std::size_t)c * f.n + first);
         }
         f.dyn.present = true;
     }

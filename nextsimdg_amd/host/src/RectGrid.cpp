@@ -91,7 +91,7 @@ void RectGrid::incrCursor()
 
 namespace {
 const char* MAGIC = "NSDG-RESTART 1";
-bool readHeader(std::istream& f, std::string& type, int& nx, int& ny, int& nl, bool* dynamics = nullptr)
+bool readHeader(std::istream& f, std::string& type, int& nx, int& ny, int& nl, bool* dynamics = nullptr, bool* snowDg = nullptr)
 {
     std::string line;
     if (!std::getline(f, line) || line != MAGIC)
@@ -100,6 +100,8 @@ bool readHeader(std::istream& f, std::string& type, int& nx, int& ny, int& nl, b
     nx = ny = nl = 0;
     if (dynamics)
         *dynamics = false;
+    if (snowDg)
+        *snowDg = false;
     while (std::getline(f, line) && line != "END-HEADER") {
         const auto eq = line.find('=');
         if (eq == std::string::npos)
@@ -115,6 +117,8 @@ bool readHeader(std::istream& f, std::string& type, int& nx, int& ny, int& nl, b
             nl = std::stoi(v);
         else if (k == "data.dynamics" && dynamics)
             *dynamics = v == "1";
+        else if (k == "data.snow_dg" && snowDg)
+            *snowDg = v == "1";
     }
     return nx > 0 && ny > 0 && nl > 0;
 }
@@ -195,6 +199,10 @@ void RectGrid::dump(const std::string& filePath) const
             }
             w.dataset(data + "/newice", { X, Y }, m_store.newice);
             w.attachDimensions(data + "/newice", { data + "/x", data + "/y" });
+            if (!d.sdg.empty()) { // dynamics.advect_column_state: the higher coefficients of the snow, as hice_dg
+                w.dataset(data + "/hsnow_dg", { 5, X, Y }, d.sdg);
+                w.attachDimensions(data + "/hsnow_dg", { data + "/dg2", data + "/x", data + "/y" });
+            }
         }
         w.write(filePath);
         return;
@@ -207,8 +215,10 @@ void RectGrid::dump(const std::string& filePath) const
       << dataNodeName() << ".x=" << m_nx << "\n"
       << dataNodeName() << ".y=" << m_ny << "\n"
       << dataNodeName() << ".nLayers=" << m_store.nLayers << "\n"
-      << (m_store.dyn.present ? "data.dynamics=1\nvariables=hice,cice,hsnow,sst,sss,tice,hice_dg,cice_dg,u,v,s11,s12,s22,newice\nEND-HEADER\n"
-                                : "variables=hice,cice,hsnow,sst,sss,tice\nEND-HEADER\n");
+      << (!m_store.dyn.present ? "variables=hice,cice,hsnow,sst,sss,tice\nEND-HEADER\n"
+              : m_store.dyn.sdg.empty()
+              ? "data.dynamics=1\nvariables=hice,cice,hsnow,sst,sss,tice,hice_dg,cice_dg,u,v,s11,s12,s22,newice\nEND-HEADER\n"
+              : "data.dynamics=1\ndata.snow_dg=1\nvariables=hice,cice,hsnow,sst,sss,tice,hice_dg,cice_dg,u,v,s11,s12,s22,newice,hsnow_dg\nEND-HEADER\n");
     for (const auto* v : { &m_store.hice, &m_store.cice, &m_store.hsnow, &m_store.sst, &m_store.sss })
         f.write(reinterpret_cast<const char*>(v->data()), (std::streamsize)(v->size() * sizeof(double)));
     f.write(reinterpret_cast<const char*>(t.data()), (std::streamsize)(t.size() * sizeof(double)));
@@ -216,6 +226,8 @@ void RectGrid::dump(const std::string& filePath) const
         const DynamicsState& d = m_store.dyn;
         for (const auto* v : { &d.hdg, &d.adg, &d.u, &d.v, &d.s11, &d.s12, &d.s22, &m_store.newice })
             f.write(reinterpret_cast<const char*>(v->data()), (std::streamsize)(v->size() * sizeof(double)));
+        if (!d.sdg.empty())
+            f.write(reinterpret_cast<const char*>(d.sdg.data()), (std::streamsize)(d.sdg.size() * sizeof(double)));
     }
 }
 
@@ -264,6 +276,12 @@ void RectGrid::init(const std::string& filePath)
                     throw std::runtime_error("restart file " + filePath + ": " + v.first + " does not have the size the grid asks for");
                 v.second->swap(a);
             }
+            if (h.exists(g + "hsnow_dg")) { // the snow of dynamics.advect_column_state (optional: absent, its higher coefficients start at zero)
+                std::vector<double> a = h.readDoubles(g + "hsnow_dg");
+                if (a.size() != dy.hdg.size())
+                    throw std::runtime_error("restart file " + filePath + ": hsnow_dg does not have the size the grid asks for");
+                dy.sdg.swap(a);
+            }
             dy.present = true;
         }
         resetCursor();
@@ -272,8 +290,8 @@ void RectGrid::init(const std::string& filePath)
     std::ifstream f(filePath, std::ios::binary);
     std::string type;
     int nx, ny, nl;
-    bool dynamics = false;
-    if (!f || !readHeader(f, type, nx, ny, nl, &dynamics))
+    bool dynamics = false, snowDg = false;
+    if (!f || !readHeader(f, type, nx, ny, nl, &dynamics, &snowDg))
         throw std::runtime_error("cannot read restart file " + filePath);
     if (structureType() == "devgrid" && (nx != 10 || ny != 10))
         throw std::runtime_error("devgrid restart files must be 10x10");
@@ -287,6 +305,10 @@ void RectGrid::init(const std::string& filePath)
         d.resize((std::size_t)nx, (std::size_t)ny);
         for (auto* v : { &d.hdg, &d.adg, &d.u, &d.v, &d.s11, &d.s12, &d.s22, &m_store.newice })
             f.read(reinterpret_cast<char*>(v->data()), (std::streamsize)(v->size() * sizeof(double)));
+        if (snowDg) {
+            d.sdg.assign(d.hdg.size(), 0.);
+            f.read(reinterpret_cast<char*>(d.sdg.data()), (std::streamsize)(d.sdg.size() * sizeof(double)));
+        }
         d.present = true;
     }
     if (!f)

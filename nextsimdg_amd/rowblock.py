@@ -265,6 +265,9 @@ class DynamicsCore:
     # closure of the transported fields (include/nsdg.h "INPUT DOMAIN AND CLOSURE"): mean thickness H >= 0; concentration
     # 0 <= A <= 1 at the quadrature points with the cell mean capped at 1 (ridging) -- (lo, hi, cap_mean) per field
     BOUNDS = ((0.0, float("inf"), False), (0.0, 1.0, True))
+    # the advected DG2 fields (attribute names), in the order of the step calls' field lists and of BOUNDS; CoupledCore with
+    # advect_column_state adds the snow S and the weighted surface temperature Q
+    TRANSPORTED = ("H", "A")
 
     def __init__(self, ops, blk, hx, hy, dt, nsub, device, exchanger=None, overlap=True, native=False, use_graph=False, closure=True):
         self.ops, self.blk, self.hx, self.hy, self.dt, self.nsub = ops, blk, hx, hy, dt, nsub
@@ -276,6 +279,7 @@ class DynamicsCore:
         # them from the context: stated here, put back by close() (they apply to EVERY later step call on the context: include/nsdg.h)
         self._bounds_before = getattr(ops, "transport_bounds", ())
         ops.set_transport_bounds(self.BOUNDS if closure else ())
+        nf = len(self.TRANSPORTED)
         # native: the sub-cycle and the transport of a step are ONE C call each (csrc/rowblock.hip runs the same
         # sequence of passes and exchanges as subcycle() / transport() below); needs the C-ABI ops and, with
         # neighbours, a NativeHaloExchanger (it owns the communicator).  use_graph: replay the launches between
@@ -298,7 +302,8 @@ class DynamicsCore:
         nx, ny = blk.nx, blk.ny
         z = lambda *s: torch.zeros(*s, dtype=torch.float64, device=device)
         nodal = (2 * ny + 1, 2 * nx + 1)
-        self.H, self.A = z(6, ny, nx), z(6, ny, nx)
+        for name in self.TRANSPORTED:
+            setattr(self, name, z(6, ny, nx))
         # stress and ice strength are private to the sub-cycle: the ops object chooses their layout
         self.s = [ops.private_zeros(8, ny, nx, device) for _ in range(3)]
         self.sb = [ops.private_zeros(8, ny, nx, device) for _ in range(3)]
@@ -308,8 +313,8 @@ class DynamicsCore:
         self.uo, self.vo = z(*nodal), z(*nodal)
         self.packed = z(nodal[0] * nodal[1] * 8)  # per-step momentum coefficients, 8 per node
         self.adv = (z(6, ny, nx), z(6, ny, nx), z(3, ny, nx + 1), z(3, ny + 1, nx))
-        self.t1 = [z(6, ny, nx), z(6, ny, nx)]
-        self.t2 = [z(6, ny, nx), z(6, ny, nx)]
+        self.t1 = [z(6, ny, nx) for _ in range(nf)]
+        self.t2 = [z(6, ny, nx) for _ in range(nf)]
         if native:
             self._init_native()
 
@@ -322,8 +327,16 @@ class DynamicsCore:
         self._run_mevp, per_pass, group = self.ops.rb_mevp(b, peers, self.nsub, self.overlap, self.use_graph, self._sbuf, self._uvbuf,
                                                            self.packed, self.pg)
         assert (per_pass, group) == (self.per_pass, self.group_passes), "native plan and driver disagree on the pass structure"
-        self._fbuf, self._tpar = ((self.H, self.A), (self.t1[0], self.t1[1])), 0
+        self._fbuf, self._tpar = (self._fields(), tuple(self.t1)), 0
         self._run_transport = self.ops.rb_transport(b, peers, self._fbuf[0], self._fbuf[1], self.t2, self.adv, bounds=self.BOUNDS if self.closure else ())
+
+    def _fields(self):
+        """the current buffers of the advected fields, in the order of TRANSPORTED"""
+        return tuple(getattr(self, name) for name in self.TRANSPORTED)
+
+    def _set_fields(self, fields):
+        for name, f in zip(self.TRANSPORTED, fields):
+            setattr(self, name, f)
 
     def close(self):
         """releases the native driver plans (device buffers and events of their ghost exchanges); call it before the
@@ -515,9 +528,10 @@ class DynamicsCore:
         ops.prepare_advection(self.ORDER, self.u, self.v, *self.adv)
         if self.native:
             par = self._tpar = self._run_transport(self.dt, self._tpar)
-            (self.H, self.A), (self.t1[0], self.t1[1]) = self._fbuf[par], self._fbuf[1 - par]
+            self._set_fields(self._fbuf[par])
+            self.t1[:] = self._fbuf[1 - par]
             return
-        f = [self.H, self.A]
+        f = list(self._fields())
         # Shu-Osher SSP-RK3: out = a*phi0 + b*(phis + dt L(phis)).  A stage reads one element row on each side
         # of the rows it updates: with at least 3 ghost rows per interior side the first two stages also
         # advance 2 / 1 ghost rows redundantly (bit-identically to their owners) and the ghost rows are
@@ -535,8 +549,9 @@ class DynamicsCore:
             ops.transport_limit(self.ORDER, b.j0, b.j1, self.t1)
         self.halo.element(self.t1)
         # the new state is t1 (ghost rows refreshed); swap buffers instead of copying
-        self.H, self.t1[0] = self.t1[0], self.H
-        self.A, self.t1[1] = self.t1[1], self.A
+        new = list(self.t1)
+        self.t1[:] = f
+        self._set_fields(new)
 
     def step(self):
         self._set_grid()
@@ -636,8 +651,9 @@ class DynamicsCore:
 
         states = sorted(states, key=lambda s: s["rows"][0])
         out = {"rows": (states[0]["rows"][0], states[-1]["rows"][1]), "ny_global": states[0]["ny_global"], "nx": states[0]["nx"]}
-        for k in ("H", "A", "s11", "s12", "s22"):
-            out[k] = np.concatenate([s[k] for s in states], axis=1)
+        for k in ("H", "A", "S", "s11", "s12", "s22"):
+            if k in states[0]:  # S: the snow of a CoupledCore with advect_column_state
+                out[k] = np.concatenate([s[k] for s in states], axis=1)
         for k in ("u", "v"):
             out[k] = np.concatenate([s[k] for s in states], axis=0)
         return out
@@ -707,21 +723,38 @@ class CoupledCore(DynamicsCore):
     and writes those planes in place; higher DG coefficients are left as they are (a thermodynamic
     source changes the mean, not the sub-cell shape).  The column step needs no exchange (elements are
     independent); it runs on the ghost rows too, redundantly, so that they stay consistent without a
-    message."""
+    message.
+
+    advect_column_state = True ("column state transport", include/nsdg.h): the snow and the surface temperature move with the ice.  The
+    snow is a DG2 field S whose plane 0 IS the column's hsnow (col["hsnow"] is a view of it); tice0 travels as Q = H tice0, formed before
+    the transport (nsdg_tracer_weight) and divided back after it (nsdg_tracer_recover, with min_conc / min_thick of the ice-free-node
+    rule).  The transport then carries H, A, S and Q."""
 
     COLUMN_STATE = ("hsnow", "tice0")
+    # closure of the column state transport's extra fields: snow volume S >= 0, the product Q = H T unbounded (include/nsdg.h)
+    COLUMN_STATE_BOUNDS = ((0.0, float("inf"), False), (-float("inf"), float("inf"), False))
     COLUMN_FORCING = ("sst", "sss", "tair", "tdew", "slp", "qsw", "qlw", "mld", "snowfall", "wind")
 
-    def __init__(self, ops, blk, hx, hy, dt, nsub, device, forcing=None, **kw):
+    def __init__(self, ops, blk, hx, hy, dt, nsub, device, forcing=None, advect_column_state=False, min_conc=1e-12, min_thick=0.01, **kw):
         """forcing: None = the forcing planes are whatever load_column() put there (constant in time);
         "dummy" / "winter" = regenerated on the device at every step's model time (nsdg_column_forcing) and the
         column wind speed is |u_a| of the dynamics' wind (nsdg_column_wind) -- the replacement of the reference's
         DummyExternalData (core/src/include/DummyExternalData.hpp:22-34) and of its never-set windSpeed;
         a ForcingSeries = records of a file sampled on the device at every step's model time (ops.forcing_sample): the column planes,
-        and the wind (ua, va) and the ocean current (uo, vo) where the series holds them; the column wind speed as above"""
+        and the wind (ua, va) and the ocean current (uo, vo) where the series holds them; the column wind speed as above.
+        advect_column_state: the snow and the surface temperature ride on the ice (class docstring); min_conc / min_thick: the ice test of
+        nsdg_tracer_recover (the defaults of the ice-free-node rule, nsdg_mevp_default_params; 0 and 0 with closure = False, as the C++ host)"""
+        self.advect_column_state = bool(advect_column_state)
+        if self.advect_column_state:  # before the base class allocates the advected fields and builds the transport plan
+            self.TRANSPORTED = DynamicsCore.TRANSPORTED + ("S", "Q")
+            self.BOUNDS = DynamicsCore.BOUNDS + self.COLUMN_STATE_BOUNDS
         super().__init__(ops, blk, hx, hy, dt, nsub, device, **kw)
+        closure = kw.get("closure", True)
+        self.min_conc, self.min_thick = (min_conc, min_thick) if closure else (0.0, 0.0)
         z = lambda: torch.zeros(blk.ny, blk.nx, dtype=torch.float64, device=device)
         self.col = {k: z() for k in self.COLUMN_STATE + self.COLUMN_FORCING}
+        if self.advect_column_state:
+            self.col["hsnow"] = self.S[0]
         self.newice = z()
         self.forcing, self.time = forcing, 0.0
         if isinstance(forcing, ForcingSeries):
@@ -745,6 +778,33 @@ class CoupledCore(DynamicsCore):
         es = self.blk.elem_slice()
         for k, dst in self.col.items():
             dst.copy_(torch.from_numpy(np.ascontiguousarray(fields[k][es])).to(dst.device))
+
+    def transport(self):
+        if not self.advect_column_state:
+            return super().transport()
+        b = self.blk
+        # every local row, ghost rows included: both calls are element-local, the ghost rows stay equal to their owners
+        self.ops.tracer_weight(self.ORDER, 0, b.ny, self.H, self.col["tice0"], self.Q)
+        super().transport()
+        self.ops.tracer_recover(self.ORDER, 0, b.ny, self.H, self.A, self.Q, self.min_conc, self.min_thick, self.col["tice0"])
+        self.col["hsnow"] = self.S[0]  # the ping-pong buffer that holds the new snow
+
+    def state_dict(self):
+        """DynamicsCore.state_dict and, with advect_column_state, the snow S as [6, rows, nx] (plane 0 = hsnow)"""
+        out = super().state_dict()
+        if self.advect_column_state:
+            out["S"] = self.owned(self.S).detach().cpu().numpy().copy()
+        return out
+
+    def load_state_dict(self, state):
+        """DynamicsCore.load_state_dict and, with advect_column_state, the snow S (required: plane 0 is the column's hsnow)"""
+        import numpy as np
+
+        if self.advect_column_state and "S" not in state:
+            raise ValueError("a CoupledCore with advect_column_state needs the snow S in the state")
+        super().load_state_dict(state)
+        if self.advect_column_state:
+            self.S.copy_(torch.from_numpy(np.ascontiguousarray(state["S"][:, self.blk.elem_slice()])).to(self.S.device))
 
     def thermodynamics(self):
         state = {"hice": self.H[0], "cice": self.A[0], "hsnow": self.col["hsnow"], "tice0": self.col["tice0"]}

@@ -741,73 +741,57 @@ class Context:
         _check_f64(*ts)
         self._call(self.lib.nsdg_mevp_velocity(self.h, j0, j1, *[_ptr(t) for t in ts]))
 
-    def mevp_iterate(self, k0, j0, j1, s_in, s_out, uv_old, uv_new, packed, pg):
+    def _bind_mevp_pass(self, fn, rows, s_in, s_out, uv_old, uv_new, packed, pg):
+        """Checks and marshals the arguments of the nsdg_mevp_iterate* entry point `fn` (row arguments `rows`) once and returns
+        a zero-argument callable that makes the call.  (Argument checking and ctypes marshalling cost ~20 us per call in
+        Python -- comparable to a sub-iteration of a 256-row block -- so the 120-iteration sub-cycle binds its calls once.)"""
         ts = [s_in[0], s_in[1], s_in[2], s_out[0], s_out[1], s_out[2], uv_old[0], uv_old[1], uv_new[0], uv_new[1], packed, pg]
         _check_f64(*ts)
-        self._call(self.lib.nsdg_mevp_iterate(self.h, k0, j0, j1, *[_ptr(t) for t in ts]))
+        args = (self.h,) + tuple(I32(r) for r in rows) + tuple(_ptr(t) for t in ts)
+
+        def call():
+            rc = fn(*args)
+            if rc != 0:
+                self._call(rc)
+            return ts is None  # the tensors must outlive the binding
+
+        return call
+
+    def mevp_iterate(self, k0, j0, j1, s_in, s_out, uv_old, uv_new, packed, pg):
+        self.bind_mevp_iterate(k0, j0, j1, s_in, s_out, uv_old, uv_new, packed, pg)()
+
+    def bind_mevp_iterate(self, k0, j0, j1, s_in, s_out, uv_old, uv_new, packed, pg):
+        """pre-validated, pre-marshalled form of mevp_iterate for inner loops (_bind_mevp_pass)"""
+        return self._bind_mevp_pass(self.lib.nsdg_mevp_iterate, (k0, j0, j1), s_in, s_out, uv_old, uv_new, packed, pg)
 
     def mevp_iterate2(self, j0, j1, s_in, s_out, uv_old, uv_new, packed, pg):
         """two sub-iterations in one pass on the owned rows [j0, j1) (variant 2)"""
         self.bind_mevp_iterate2(j0, j1, s_in, s_out, uv_old, uv_new, packed, pg)()
 
+    def bind_mevp_iterate2(self, j0, j1, s_in, s_out, uv_old, uv_new, packed, pg):
+        return self._bind_mevp_pass(self.lib.nsdg_mevp_iterate2, (j0, j1), s_in, s_out, uv_old, uv_new, packed, pg)
+
     def mevp_iterate3(self, j0, j1, s_in, s_out, uv_old, uv_new, packed, pg):
         """three sub-iterations in one pass on the owned rows [j0, j1) (variant 3)"""
-        self.bind_mevp_iterate2(j0, j1, s_in, s_out, uv_old, uv_new, packed, pg, passes=3)()
+        self.bind_mevp_iterate3(j0, j1, s_in, s_out, uv_old, uv_new, packed, pg)()
+
+    def bind_mevp_iterate3(self, j0, j1, s_in, s_out, uv_old, uv_new, packed, pg):
+        return self._bind_mevp_pass(self.lib.nsdg_mevp_iterate3, (j0, j1), s_in, s_out, uv_old, uv_new, packed, pg)
 
     def mevp_iterate3_pair(self, ra, rb, s_in, s_out, uv_old, uv_new, packed, pg):
         """three sub-iterations on two disjoint row ranges ra = (j0, j1), rb = (j0, j1) in one launch"""
-        ts = [s_in[0], s_in[1], s_in[2], s_out[0], s_out[1], s_out[2], uv_old[0], uv_old[1], uv_new[0], uv_new[1], packed, pg]
-        _check_f64(*ts)
-        self._call(self.lib.nsdg_mevp_iterate3_pair(self.h, ra[0], ra[1], rb[0], rb[1], *[_ptr(t) for t in ts]))
-
-    def bind_mevp_iterate3(self, j0, j1, s_in, s_out, uv_old, uv_new, packed, pg):
-        return self.bind_mevp_iterate2(j0, j1, s_in, s_out, uv_old, uv_new, packed, pg, passes=3)
+        self._bind_mevp_pass(self.lib.nsdg_mevp_iterate3_pair, (ra[0], ra[1], rb[0], rb[1]), s_in, s_out, uv_old, uv_new, packed, pg)()
 
     def mevp_iterate4(self, j0, j1, s_in, s_out, uv_old, uv_new, packed, pg):
         """four sub-iterations in one pass on the owned rows [j0, j1) (variant 4: one pipeline stage per wave)"""
-        self.bind_mevp_iterate2(j0, j1, s_in, s_out, uv_old, uv_new, packed, pg, passes=4)()
+        self.bind_mevp_iterate4(j0, j1, s_in, s_out, uv_old, uv_new, packed, pg)()
+
+    def bind_mevp_iterate4(self, j0, j1, s_in, s_out, uv_old, uv_new, packed, pg):
+        return self._bind_mevp_pass(self.lib.nsdg_mevp_iterate4, (j0, j1), s_in, s_out, uv_old, uv_new, packed, pg)
 
     def mevp_iterate4_pair(self, ra, rb, s_in, s_out, uv_old, uv_new, packed, pg):
         """four sub-iterations on two disjoint row ranges ra = (j0, j1), rb = (j0, j1) in one launch"""
-        ts = [s_in[0], s_in[1], s_in[2], s_out[0], s_out[1], s_out[2], uv_old[0], uv_old[1], uv_new[0], uv_new[1], packed, pg]
-        _check_f64(*ts)
-        self._call(self.lib.nsdg_mevp_iterate4_pair(self.h, ra[0], ra[1], rb[0], rb[1], *[_ptr(t) for t in ts]))
-
-    def bind_mevp_iterate4(self, j0, j1, s_in, s_out, uv_old, uv_new, packed, pg):
-        return self.bind_mevp_iterate2(j0, j1, s_in, s_out, uv_old, uv_new, packed, pg, passes=4)
-
-    def bind_mevp_iterate2(self, j0, j1, s_in, s_out, uv_old, uv_new, packed, pg, passes=2):
-        ts = [s_in[0], s_in[1], s_in[2], s_out[0], s_out[1], s_out[2], uv_old[0], uv_old[1], uv_new[0], uv_new[1], packed, pg]
-        _check_f64(*ts)
-        fn = {2: self.lib.nsdg_mevp_iterate2, 3: self.lib.nsdg_mevp_iterate3, 4: self.lib.nsdg_mevp_iterate4}[passes]
-        args = (self.h, I32(j0), I32(j1)) + tuple(_ptr(t) for t in ts)
-        keep = ts
-
-        def call():
-            rc = fn(*args)
-            if rc != 0:
-                self._call(rc)
-            return keep is None
-
-        return call
-
-    def bind_mevp_iterate(self, k0, j0, j1, s_in, s_out, uv_old, uv_new, packed, pg):
-        """Pre-validated, pre-marshalled form of mevp_iterate for inner loops: returns a zero-argument
-        callable.  (Argument checking and ctypes marshalling cost ~20 us per call in Python -- comparable
-        to a sub-iteration of a 256-row block -- so the 120-iteration sub-cycle binds its calls once.)"""
-        ts = [s_in[0], s_in[1], s_in[2], s_out[0], s_out[1], s_out[2], uv_old[0], uv_old[1], uv_new[0], uv_new[1], packed, pg]
-        _check_f64(*ts)
-        fn, h = self.lib.nsdg_mevp_iterate, self.h
-        args = (h, I32(k0), I32(j0), I32(j1)) + tuple(_ptr(t) for t in ts)
-        keep = ts  # the tensors must outlive the binding
-
-        def call():
-            rc = fn(*args)
-            if rc != 0:
-                self._call(rc)
-            return keep is None
-
-        return call
+        self._bind_mevp_pass(self.lib.nsdg_mevp_iterate4_pair, (ra[0], ra[1], rb[0], rb[1]), s_in, s_out, uv_old, uv_new, packed, pg)()
 
     def mevp_subcycle(self, dt, nsub, s, u, v, u0, v0, tax, tay, uo, vo, cgh, cga, pg, scratch):
         ts = [s[0], s[1], s[2], u, v, u0, v0, tax, tay, uo, vo, cgh, cga, pg, scratch]

@@ -14,6 +14,7 @@
 //                        deterministic and independent of the decomposition -- and applies the
 //                        momentum update.
 // Variant 1 ("fused march") lives in mevp_fused.hip.
+#include <algorithm>
 #include <initializer_list>
 
 #include "mevp_common.h"
@@ -331,11 +332,6 @@ __global__ __launch_bounds__(256) void wind_stress_kernel(long n, double f_atm, 
 
 using namespace nsdg_mevp_detail;
 
-// defined in mevp_fused.hip
-int nsdg_launch_mevp_fused(nsdg_ctx* ctx, int k0, int j0, int j1, const double* s11i, const double* s12i, const double* s22i,
-    double* s11, double* s12, double* s22, const double* u_old, const double* v_old, double* u_new, double* v_new,
-    const double* packed, const double* pg);
-
 // the tiled arrays are accessed 16 bytes at a time
 static inline bool aligned16(std::initializer_list<const void*> ptrs)
 {
@@ -344,12 +340,8 @@ static inline bool aligned16(std::initializer_list<const void*> ptrs)
             return false;
     return true;
 }
-#define NSDG_CHECK_TILED(...) NSDG_CHECK_ARG(aligned16({ __VA_ARGS__ }), "tiled arrays (stress, ice strength) must be 16-byte aligned")
-
-// defined in mevp_fused4.hip: a pass of nst = 2, 3 or 4 sub-iterations on the rows [j0, j1) and, if j0b < j1b, on a second disjoint range
-int nsdg_launch_mevp_fused4_ranges(nsdg_ctx* ctx, int nst, int j0, int j1, int j0b, int j1b, const double* s11i, const double* s12i, const double* s22i,
-    double* s11, double* s12, double* s22, const double* u_old, const double* v_old, double* u_new, double* v_new, const double* packed,
-    const double* pg);
+#define NSDG_CHECK_TILED_IN(fn, ...) NSDG_CHECK_ARG_IN(fn, aligned16({ __VA_ARGS__ }), "tiled arrays (stress, ice strength) must be 16-byte aligned")
+#define NSDG_CHECK_TILED(...) NSDG_CHECK_TILED_IN(__func__, __VA_ARGS__)
 
 static NodalConsts nodal_consts(const nsdg_ctx* ctx) { return nsdg_nodal_consts(ctx); }
 
@@ -487,164 +479,110 @@ int nsdg_mevp_velocity(nsdg_ctx* ctx, int32_t j0, int32_t j1, const double* s11,
     return NSDG_OK;
 }
 
+} // extern "C"
+
+int nsdg_mevp_pass(nsdg_ctx* ctx, int v, int k0, int j0, int j1, bool pair, int j0b, int j1b, const nsdg_mevp_bufs& b)
+{
+    static const char* const names[2][5] = { { "", "nsdg_mevp_iterate", "nsdg_mevp_iterate2", "nsdg_mevp_iterate3", "nsdg_mevp_iterate4" },
+        { "", "", "", "nsdg_mevp_iterate3_pair", "nsdg_mevp_iterate4_pair" } };
+    static const char* const count[] = { "", "one", "two", "three", "four" };
+    static const char* const variants[] = { "", "", "2, 3 or 4 (nsdg_mevp_variant_set) or call nsdg_mevp_iterate twice",
+        "3 or 4 (nsdg_mevp_variant_set)", "4 (nsdg_mevp_variant_set)" };
+    const char* fn = names[pair][v];
+    NSDG_CHECK_ARG_IN(fn, ctx != nullptr, "null context");
+    if (ctx->nx <= 0) {
+        nsdg_set_error("%s: nsdg_grid_set was not called", fn);
+        return NSDG_ERR_STATE;
+    }
+    const int ny = ctx->ny;
+    if (v == 1) {
+        NSDG_CHECK_ARG_IN(fn, 0 <= k0 && k0 <= j0 && j0 <= j1 && j1 <= ny, "need 0 <= k0 <= j0 <= j1 <= ny");
+        NSDG_CHECK_ARG_IN(fn, k0 == j0 - 1 || (k0 == 0 && j0 == 0), "need k0 == j0 - 1 (one ghost row below) or k0 == j0 == 0");
+    } else {
+        // v ghost rows below, v - 1 above (for v = 2 that always holds); a range of a pair must not be empty
+        const char* rows = pair ? "rows of a range" : "owned rows";
+        for (int k = 0; k < (pair ? 2 : 1); ++k) {
+            const int r0 = k ? j0b : j0, r1 = k ? j1b : j1;
+            NSDG_CHECK_ARG_IN(fn, 0 <= r0 && (pair ? r0 < r1 : r0 <= r1) && r1 <= ny, "row range outside the local array%s", pair ? " (or empty)" : "");
+            NSDG_CHECK_ARG_IN(fn, r0 == 0 || r0 >= v, "need %s ghost rows below the %s (or j0 == 0 at the physical boundary)", count[v], rows);
+            NSDG_CHECK_ARG_IN(fn, r1 == ny || r1 + v - 1 <= ny, "need %s ghost rows above the %s (or j1 == ny at the physical boundary)", count[v - 1], rows);
+        }
+        NSDG_CHECK_ARG_IN(fn, !pair || j1 <= j0b || j1b <= j0, "the two row ranges must be disjoint");
+    }
+    NSDG_CHECK_ARG_IN(fn, b.s11i && b.s12i && b.s22i && b.s11 && b.s12 && b.s22 && b.u_old && b.v_old && b.u_new && b.v_new && b.packed && b.pg,
+        "null field pointer");
+    NSDG_CHECK_TILED_IN(fn, b.s11i, b.s12i, b.s22i, b.s11, b.s12, b.s22, b.pg);
+    NSDG_CHECK_ARG_IN(fn, b.u_new != b.u_old && b.v_new != b.v_old, "u_new/v_new must not alias u_old/v_old");
+    NSDG_CHECK_ARG_IN(fn, b.s11 != b.s11i && b.s12 != b.s12i && b.s22 != b.s22i, "the output stress must not alias the input stress");
+    // nothing to do: v = 1 without a stress row, checked before the packing (j0 == j1 > k0 still updates the stress row k0); v >= 2
+    // on an empty range, checked after the packing and before the variant
+    if (v == 1 && k0 == j1)
+        return NSDG_OK;
+    if (!(ctx->pack_dt > 0)) {
+        nsdg_set_error("%s: nsdg_mevp_pack_nodal was not called on this context", fn);
+        return NSDG_ERR_STATE;
+    }
+    if (v >= 2 && j0 == j1)
+        return NSDG_OK;
+    if (v >= 2 && ctx->mevp_variant < v) {
+        nsdg_set_error("%s: select variant %s", fn, variants[v]);
+        return NSDG_ERR_STATE;
+    }
+    const hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) {
+        nsdg_set_error("%s: hipSetDevice(ctx->device) failed: %s", fn, hipGetErrorString(e));
+        return NSDG_ERR_HIP;
+    }
+    if (v >= 2) // a pass of the stage-per-wave pipeline with v stages
+        return nsdg_launch_mevp_fused4_ranges(ctx, v, j0, j1, j0b, j1b, b);
+    if (ctx->mevp_variant >= 1 || nsdg_adaptive(ctx)) // variants 2-4 use the single-iteration fused kernel for one sub-iteration; so does variant 0 in the adaptive form
+        return nsdg_launch_mevp_fused(ctx, k0, j0, j1, b);
+    const int rc = launch_stress(ctx, k0, j1, b.u_old, b.v_old, b.pg, b.s11i, b.s12i, b.s22i, b.s11, b.s12, b.s22);
+    return rc ? rc : nsdg_mevp_velocity(ctx, j0, j1, b.s11, b.s12, b.s22, b.u_old, b.v_old, b.u_new, b.v_new, b.packed);
+}
+
+extern "C" {
+
 int nsdg_mevp_iterate(nsdg_ctx* ctx, int32_t k0, int32_t j0, int32_t j1, const double* s11i, const double* s12i,
     const double* s22i, double* s11, double* s12, double* s22, const double* u_old, const double* v_old, double* u_new,
     double* v_new, const double* packed, const double* pg)
 {
-    NSDG_NEED_GRID(ctx);
-    NSDG_CHECK_ARG(0 <= k0 && k0 <= j0 && j0 <= j1 && j1 <= ctx->ny, "need 0 <= k0 <= j0 <= j1 <= ny");
-    NSDG_CHECK_ARG(k0 == j0 - 1 || (k0 == 0 && j0 == 0), "need k0 == j0 - 1 (one ghost row below) or k0 == j0 == 0");
-    NSDG_CHECK_ARG(s11i && s12i && s22i && s11 && s12 && s22 && u_old && v_old && u_new && v_new && packed && pg,
-        "null field pointer");
-    NSDG_CHECK_TILED(s11i, s12i, s22i, s11, s12, s22, pg);
-    NSDG_CHECK_ARG(u_new != u_old && v_new != v_old, "u_new/v_new must not alias u_old/v_old");
-    NSDG_CHECK_ARG(s11 != s11i && s12 != s12i && s22 != s22i, "the output stress must not alias the input stress");
-    if (k0 == j1)
-        return NSDG_OK;
-    NSDG_CHECK_HIP(hipSetDevice(ctx->device));
-    if (!(ctx->pack_dt > 0)) {
-        nsdg_set_error("nsdg_mevp_iterate: nsdg_mevp_pack_nodal was not called on this context");
-        return NSDG_ERR_STATE;
-    }
-    if (ctx->mevp_variant >= 1 || nsdg_adaptive(ctx)) // variants 2-4 use the single-iteration fused kernel for one sub-iteration; so does variant 0 in the adaptive form
-        return nsdg_launch_mevp_fused(ctx, k0, j0, j1, s11i, s12i, s22i, s11, s12, s22, u_old, v_old, u_new, v_new, packed, pg);
-    int rc = launch_stress(ctx, k0, j1, u_old, v_old, pg, s11i, s12i, s22i, s11, s12, s22);
-    if (rc)
-        return rc;
-    return nsdg_mevp_velocity(ctx, j0, j1, s11, s12, s22, u_old, v_old, u_new, v_new, packed);
+    return nsdg_mevp_pass(ctx, 1, k0, j0, j1, false, 0, 0, { s11i, s12i, s22i, s11, s12, s22, u_old, v_old, u_new, v_new, packed, pg });
 }
 
 int nsdg_mevp_iterate2(nsdg_ctx* ctx, int32_t j0, int32_t j1, const double* s11i, const double* s12i, const double* s22i,
     double* s11, double* s12, double* s22, const double* u_old, const double* v_old, double* u_new, double* v_new,
     const double* packed, const double* pg)
 {
-    NSDG_NEED_GRID(ctx);
-    NSDG_CHECK_ARG(0 <= j0 && j0 <= j1 && j1 <= ctx->ny, "row range outside the local array");
-    NSDG_CHECK_ARG(j0 == 0 || j0 >= 2, "need two ghost rows below the owned rows (or j0 == 0 at the physical boundary)");
-    NSDG_CHECK_ARG(s11i && s12i && s22i && s11 && s12 && s22 && u_old && v_old && u_new && v_new && packed && pg,
-        "null field pointer");
-    NSDG_CHECK_TILED(s11i, s12i, s22i, s11, s12, s22, pg);
-    NSDG_CHECK_ARG(u_new != u_old && v_new != v_old, "u_new/v_new must not alias u_old/v_old");
-    NSDG_CHECK_ARG(s11 != s11i && s12 != s12i && s22 != s22i, "the output stress must not alias the input stress");
-    if (!(ctx->pack_dt > 0)) {
-        nsdg_set_error("nsdg_mevp_iterate2: nsdg_mevp_pack_nodal was not called on this context");
-        return NSDG_ERR_STATE;
-    }
-    if (j0 == j1)
-        return NSDG_OK;
-    NSDG_CHECK_HIP(hipSetDevice(ctx->device));
-    if (ctx->mevp_variant >= 2) // a pass of the stage-per-wave pipeline with two stages
-        return nsdg_launch_mevp_fused4_ranges(ctx, 2, j0, j1, 0, 0, s11i, s12i, s22i, s11, s12, s22, u_old, v_old, u_new, v_new, packed, pg);
-    nsdg_set_error("nsdg_mevp_iterate2: select variant 2, 3 or 4 (nsdg_mevp_variant_set) or call nsdg_mevp_iterate twice");
-    return NSDG_ERR_STATE;
+    return nsdg_mevp_pass(ctx, 2, 0, j0, j1, false, 0, 0, { s11i, s12i, s22i, s11, s12, s22, u_old, v_old, u_new, v_new, packed, pg });
 }
 
 int nsdg_mevp_iterate3(nsdg_ctx* ctx, int32_t j0, int32_t j1, const double* s11i, const double* s12i, const double* s22i,
     double* s11, double* s12, double* s22, const double* u_old, const double* v_old, double* u_new, double* v_new,
     const double* packed, const double* pg)
 {
-    NSDG_NEED_GRID(ctx);
-    NSDG_CHECK_ARG(0 <= j0 && j0 <= j1 && j1 <= ctx->ny, "row range outside the local array");
-    NSDG_CHECK_ARG(j0 == 0 || j0 >= 3, "need three ghost rows below the owned rows (or j0 == 0 at the physical boundary)");
-    NSDG_CHECK_ARG(j1 == ctx->ny || j1 + 2 <= ctx->ny, "need two ghost rows above the owned rows (or j1 == ny at the physical boundary)");
-    NSDG_CHECK_ARG(s11i && s12i && s22i && s11 && s12 && s22 && u_old && v_old && u_new && v_new && packed && pg,
-        "null field pointer");
-    NSDG_CHECK_TILED(s11i, s12i, s22i, s11, s12, s22, pg);
-    NSDG_CHECK_ARG(u_new != u_old && v_new != v_old, "u_new/v_new must not alias u_old/v_old");
-    NSDG_CHECK_ARG(s11 != s11i && s12 != s12i && s22 != s22i, "the output stress must not alias the input stress");
-    if (!(ctx->pack_dt > 0)) {
-        nsdg_set_error("nsdg_mevp_iterate3: nsdg_mevp_pack_nodal was not called on this context");
-        return NSDG_ERR_STATE;
-    }
-    if (j0 == j1)
-        return NSDG_OK;
-    NSDG_CHECK_HIP(hipSetDevice(ctx->device));
-    if (ctx->mevp_variant >= 3) // ... with three stages
-        return nsdg_launch_mevp_fused4_ranges(ctx, 3, j0, j1, 0, 0, s11i, s12i, s22i, s11, s12, s22, u_old, v_old, u_new, v_new, packed, pg);
-    nsdg_set_error("nsdg_mevp_iterate3: select variant 3 or 4 (nsdg_mevp_variant_set)");
-    return NSDG_ERR_STATE;
+    return nsdg_mevp_pass(ctx, 3, 0, j0, j1, false, 0, 0, { s11i, s12i, s22i, s11, s12, s22, u_old, v_old, u_new, v_new, packed, pg });
 }
 
 int nsdg_mevp_iterate3_pair(nsdg_ctx* ctx, int32_t j0a, int32_t j1a, int32_t j0b, int32_t j1b, const double* s11i, const double* s12i,
     const double* s22i, double* s11, double* s12, double* s22, const double* u_old, const double* v_old, double* u_new, double* v_new,
     const double* packed, const double* pg)
 {
-    NSDG_NEED_GRID(ctx);
-    for (int k = 0; k < 2; ++k) {
-        const int j0 = k ? j0b : j0a, j1 = k ? j1b : j1a;
-        NSDG_CHECK_ARG(0 <= j0 && j0 < j1 && j1 <= ctx->ny, "row range outside the local array (or empty)");
-        NSDG_CHECK_ARG(j0 == 0 || j0 >= 3, "need three ghost rows below the rows of a range (or j0 == 0 at the physical boundary)");
-        NSDG_CHECK_ARG(j1 == ctx->ny || j1 + 2 <= ctx->ny, "need two ghost rows above the rows of a range (or j1 == ny at the physical boundary)");
-    }
-    NSDG_CHECK_ARG(j1a <= j0b || j1b <= j0a, "the two row ranges must be disjoint");
-    NSDG_CHECK_ARG(s11i && s12i && s22i && s11 && s12 && s22 && u_old && v_old && u_new && v_new && packed && pg, "null field pointer");
-    NSDG_CHECK_TILED(s11i, s12i, s22i, s11, s12, s22, pg);
-    NSDG_CHECK_ARG(u_new != u_old && v_new != v_old, "u_new/v_new must not alias u_old/v_old");
-    NSDG_CHECK_ARG(s11 != s11i && s12 != s12i && s22 != s22i, "the output stress must not alias the input stress");
-    if (!(ctx->pack_dt > 0)) {
-        nsdg_set_error("nsdg_mevp_iterate3_pair: nsdg_mevp_pack_nodal was not called on this context");
-        return NSDG_ERR_STATE;
-    }
-    if (ctx->mevp_variant < 3) {
-        nsdg_set_error("nsdg_mevp_iterate3_pair: select variant 3 or 4 (nsdg_mevp_variant_set)");
-        return NSDG_ERR_STATE;
-    }
-    NSDG_CHECK_HIP(hipSetDevice(ctx->device));
-    return nsdg_launch_mevp_fused4_ranges(ctx, 3, j0a, j1a, j0b, j1b, s11i, s12i, s22i, s11, s12, s22, u_old, v_old, u_new, v_new, packed, pg);
+    return nsdg_mevp_pass(ctx, 3, 0, j0a, j1a, true, j0b, j1b, { s11i, s12i, s22i, s11, s12, s22, u_old, v_old, u_new, v_new, packed, pg });
 }
 
 int nsdg_mevp_iterate4(nsdg_ctx* ctx, int32_t j0, int32_t j1, const double* s11i, const double* s12i, const double* s22i,
     double* s11, double* s12, double* s22, const double* u_old, const double* v_old, double* u_new, double* v_new,
     const double* packed, const double* pg)
 {
-    NSDG_NEED_GRID(ctx);
-    NSDG_CHECK_ARG(0 <= j0 && j0 <= j1 && j1 <= ctx->ny, "row range outside the local array");
-    NSDG_CHECK_ARG(j0 == 0 || j0 >= 4, "need four ghost rows below the owned rows (or j0 == 0 at the physical boundary)");
-    NSDG_CHECK_ARG(j1 == ctx->ny || j1 + 3 <= ctx->ny, "need three ghost rows above the owned rows (or j1 == ny at the physical boundary)");
-    NSDG_CHECK_ARG(s11i && s12i && s22i && s11 && s12 && s22 && u_old && v_old && u_new && v_new && packed && pg,
-        "null field pointer");
-    NSDG_CHECK_TILED(s11i, s12i, s22i, s11, s12, s22, pg);
-    NSDG_CHECK_ARG(u_new != u_old && v_new != v_old, "u_new/v_new must not alias u_old/v_old");
-    NSDG_CHECK_ARG(s11 != s11i && s12 != s12i && s22 != s22i, "the output stress must not alias the input stress");
-    if (!(ctx->pack_dt > 0)) {
-        nsdg_set_error("nsdg_mevp_iterate4: nsdg_mevp_pack_nodal was not called on this context");
-        return NSDG_ERR_STATE;
-    }
-    if (j0 == j1)
-        return NSDG_OK;
-    NSDG_CHECK_HIP(hipSetDevice(ctx->device));
-    if (ctx->mevp_variant >= 4)
-        return nsdg_launch_mevp_fused4_ranges(ctx, 4, j0, j1, 0, 0, s11i, s12i, s22i, s11, s12, s22, u_old, v_old, u_new, v_new, packed, pg);
-    nsdg_set_error("nsdg_mevp_iterate4: select variant 4 (nsdg_mevp_variant_set)");
-    return NSDG_ERR_STATE;
+    return nsdg_mevp_pass(ctx, 4, 0, j0, j1, false, 0, 0, { s11i, s12i, s22i, s11, s12, s22, u_old, v_old, u_new, v_new, packed, pg });
 }
 
 int nsdg_mevp_iterate4_pair(nsdg_ctx* ctx, int32_t j0a, int32_t j1a, int32_t j0b, int32_t j1b, const double* s11i, const double* s12i,
     const double* s22i, double* s11, double* s12, double* s22, const double* u_old, const double* v_old, double* u_new, double* v_new,
     const double* packed, const double* pg)
 {
-    NSDG_NEED_GRID(ctx);
-    for (int k = 0; k < 2; ++k) {
-        const int j0 = k ? j0b : j0a, j1 = k ? j1b : j1a;
-        NSDG_CHECK_ARG(0 <= j0 && j0 < j1 && j1 <= ctx->ny, "row range outside the local array (or empty)");
-        NSDG_CHECK_ARG(j0 == 0 || j0 >= 4, "need four ghost rows below the rows of a range (or j0 == 0 at the physical boundary)");
-        NSDG_CHECK_ARG(j1 == ctx->ny || j1 + 3 <= ctx->ny, "need three ghost rows above the rows of a range (or j1 == ny at the physical boundary)");
-    }
-    NSDG_CHECK_ARG(j1a <= j0b || j1b <= j0a, "the two row ranges must be disjoint");
-    NSDG_CHECK_ARG(s11i && s12i && s22i && s11 && s12 && s22 && u_old && v_old && u_new && v_new && packed && pg, "null field pointer");
-    NSDG_CHECK_TILED(s11i, s12i, s22i, s11, s12, s22, pg);
-    NSDG_CHECK_ARG(u_new != u_old && v_new != v_old, "u_new/v_new must not alias u_old/v_old");
-    NSDG_CHECK_ARG(s11 != s11i && s12 != s12i && s22 != s22i, "the output stress must not alias the input stress");
-    if (!(ctx->pack_dt > 0)) {
-        nsdg_set_error("nsdg_mevp_iterate4_pair: nsdg_mevp_pack_nodal was not called on this context");
-        return NSDG_ERR_STATE;
-    }
-    if (ctx->mevp_variant < 4) {
-        nsdg_set_error("nsdg_mevp_iterate4_pair: select variant 4 (nsdg_mevp_variant_set)");
-        return NSDG_ERR_STATE;
-    }
-    NSDG_CHECK_HIP(hipSetDevice(ctx->device));
-    return nsdg_launch_mevp_fused4_ranges(ctx, 4, j0a, j1a, j0b, j1b, s11i, s12i, s22i, s11, s12, s22, u_old, v_old, u_new, v_new, packed, pg);
+    return nsdg_mevp_pass(ctx, 4, 0, j0a, j1a, true, j0b, j1b, { s11i, s12i, s22i, s11, s12, s22, u_old, v_old, u_new, v_new, packed, pg });
 }
 
 int nsdg_mevp_subcycle(nsdg_ctx* ctx, double dt, int32_t nsub, double* s11, double* s12, double* s22, double* u, double* v,
@@ -670,20 +608,12 @@ int nsdg_mevp_subcycle(nsdg_ctx* ctx, double dt, int32_t nsub, double* s11, doub
     rc = nsdg_mevp_pack_nodal(ctx, dt, u0, v0, tax, tay, uo, vo, cgh, cga, packed);
     if (rc)
         return rc;
-    for (int it = 0; it < nsub; ++it) {
-        if (ctx->mevp_variant >= 4 && it + 3 < nsub) { // four sub-iterations per pass
-            rc = nsdg_mevp_iterate4(ctx, 0, ctx->ny, sa[0], sa[1], sa[2], sb[0], sb[1], sb[2], ua, va, ub, vb, packed, pg);
-            it += 3;
-        } else if (ctx->mevp_variant >= 3 && it + 2 < nsub) { // three sub-iterations per pass
-            rc = nsdg_mevp_iterate3(ctx, 0, ctx->ny, sa[0], sa[1], sa[2], sb[0], sb[1], sb[2], ua, va, ub, vb, packed, pg);
-            it += 2;
-        } else if (ctx->mevp_variant >= 2 && it + 1 < nsub) { // two sub-iterations per pass
-            rc = nsdg_mevp_iterate2(ctx, 0, ctx->ny, sa[0], sa[1], sa[2], sb[0], sb[1], sb[2], ua, va, ub, vb, packed, pg);
-            ++it;
-        } else
-            rc = nsdg_mevp_iterate(ctx, 0, 0, ctx->ny, sa[0], sa[1], sa[2], sb[0], sb[1], sb[2], ua, va, ub, vb, packed, pg);
+    for (int it = 0; it < nsub;) {
+        const int n = std::max(1, std::min(ctx->mevp_variant, nsub - it)); // sub-iterations of this pass: as many as the variant allows
+        rc = nsdg_mevp_pass(ctx, n, 0, 0, ctx->ny, false, 0, 0, { sa[0], sa[1], sa[2], sb[0], sb[1], sb[2], ua, va, ub, vb, packed, pg });
         if (rc)
             return rc;
+        it += n;
         double* t = ua; ua = ub; ub = t;
         t = va; va = vb; vb = t;
         for (int k = 0; k < 3; ++k) { t = sa[k]; sa[k] = sb[k]; sb[k] = t; }

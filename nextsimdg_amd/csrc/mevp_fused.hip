@@ -187,9 +187,7 @@ __global__ __launch_bounds__(256, MINW) void mevp_fused_kernel(NodalConsts K, Ad
 
 using namespace nsdg_mevp_detail;
 
-int nsdg_launch_mevp_fused(nsdg_ctx* ctx, int k0, int j0, int j1, const double* s11i, const double* s12i, const double* s22i,
-    double* s11, double* s12, double* s22, const double* u_old, const double* v_old, double* u_new, double* v_new,
-    const double* packed, const double* pg)
+int nsdg_launch_mevp_fused(nsdg_ctx* ctx, int k0, int j0, int j1, const nsdg_mevp_bufs& b)
 {
     const int ncw = nsdg_div_up(ctx->nx, 63); // 63 owned columns per wave
     int R = ctx->strip_rows;
@@ -215,7 +213,7 @@ int nsdg_launch_mevp_fused(nsdg_ctx* ctx, int k0, int j0, int j1, const double* 
     }
     const int nstrips = nsdg_div_up(j1 - k0, R);
     const long nwaves = (long)ncw * nstrips;
-    const StressPtrs S = { s11i, s12i, s22i, s11, s12, s22 };
+    const StressPtrs S = { b.s11i, b.s12i, b.s22i, b.s11, b.s12, b.s22 };
     const NodalConsts K = nsdg_nodal_consts(ctx);
     const AdaptConsts AC = nsdg_adapt_consts(ctx);
     const double ialpha = 1. / ctx->mevp.alpha, dmin2 = ctx->mevp.delta_min * ctx->mevp.delta_min;
@@ -224,13 +222,13 @@ int nsdg_launch_mevp_fused(nsdg_ctx* ctx, int k0, int j0, int j1, const double* 
     // alpha, beta: mevp_common.h) runs at 1 wave/SIMD
     if (nsdg_adaptive(ctx))
         hipLaunchKernelGGL((mevp_fused_kernel<1, true>), grid, block, 0, ctx->stream, K, AC, ctx->nx, ctx->ny, k0, j0, j1, R, ncw, ctx->hx, ctx->hy, ialpha, dmin2, S,
-            u_old, v_old, packed, pg, u_new, v_new);
+            b.u_old, b.v_old, b.packed, b.pg, b.u_new, b.v_new);
     else if (ctx->fused_min_waves >= 2)
         hipLaunchKernelGGL((mevp_fused_kernel<2, false>), grid, block, 0, ctx->stream, K, AC, ctx->nx, ctx->ny, k0, j0, j1, R, ncw, ctx->hx, ctx->hy, ialpha, dmin2, S,
-            u_old, v_old, packed, pg, u_new, v_new);
+            b.u_old, b.v_old, b.packed, b.pg, b.u_new, b.v_new);
     else
         hipLaunchKernelGGL((mevp_fused_kernel<1, false>), grid, block, 0, ctx->stream, K, AC, ctx->nx, ctx->ny, k0, j0, j1, R, ncw, ctx->hx, ctx->hy, ialpha, dmin2, S,
-            u_old, v_old, packed, pg, u_new, v_new);
+            b.u_old, b.v_old, b.packed, b.pg, b.u_new, b.v_new);
     NSDG_CHECK_LAUNCH();
     return NSDG_OK;
 }

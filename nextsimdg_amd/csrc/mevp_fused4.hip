@@ -397,9 +397,7 @@ extern "C" int nsdg_debug_p2p_spinstat(unsigned long long* out48) // [16] polls,
 }
 #endif
 
-int nsdg_launch_mevp_fused4_ranges(nsdg_ctx* ctx, int nst, int j0, int j1, int j0b, int j1b, const double* s11i, const double* s12i, const double* s22i,
-    double* s11, double* s12, double* s22, const double* u_old, const double* v_old, double* u_new, double* v_new, const double* packed,
-    const double* pg)
+int nsdg_launch_mevp_fused4_ranges(nsdg_ctx* ctx, int nst, int j0, int j1, int j0b, int j1b, const nsdg_mevp_bufs& b)
 {
     const int ncw = nsdg_div_up(ctx->nx, P4_OWNED);
     const int rowsB = j0b < j1b ? j1b - j0b : 0;
@@ -425,16 +423,16 @@ int nsdg_launch_mevp_fused4_ranges(nsdg_ctx* ctx, int nst, int j0, int j1, int j
     }
     const int nsA = nsdg_div_up(j1 - j0, R), nsB = nsdg_div_up(rowsB, R);
     const long ngroups = (long)ncw * (nsA + nsB);
-    const StressPtrsP S = { s11i, s12i, s22i, s11, s12, s22 };
+    const StressPtrsP S = { b.s11i, b.s12i, b.s22i, b.s11, b.s12, b.s22 };
     const NodalConsts K = nsdg_nodal_consts(ctx);
     const AdaptConsts AC = nsdg_adapt_consts(ctx);
     const P2PReport rep = { ctx->p2p_count_dev, ctx->p2p_flag_dev };
     if (nsdg_adaptive(ctx)) // local, solution-adaptive alpha and beta (mevp_common.h)
         hipLaunchKernelGGL(mevp_fused4_kernel<true>, dim3(ngroups), dim3(256), 0, ctx->stream, K, AC, nst, ctx->nx, ctx->ny, j0, j1, j0b, j1b, nsA, R, ncw, ctx->hx,
-            ctx->hy, 1. / ctx->mevp.alpha, ctx->mevp.delta_min * ctx->mevp.delta_min, rep, S, u_old, v_old, packed, pg, u_new, v_new);
+            ctx->hy, 1. / ctx->mevp.alpha, ctx->mevp.delta_min * ctx->mevp.delta_min, rep, S, b.u_old, b.v_old, b.packed, b.pg, b.u_new, b.v_new);
     else
         hipLaunchKernelGGL(mevp_fused4_kernel<false>, dim3(ngroups), dim3(256), 0, ctx->stream, K, AC, nst, ctx->nx, ctx->ny, j0, j1, j0b, j1b, nsA, R, ncw, ctx->hx,
-            ctx->hy, 1. / ctx->mevp.alpha, ctx->mevp.delta_min * ctx->mevp.delta_min, rep, S, u_old, v_old, packed, pg, u_new, v_new);
+            ctx->hy, 1. / ctx->mevp.alpha, ctx->mevp.delta_min * ctx->mevp.delta_min, rep, S, b.u_old, b.v_old, b.packed, b.pg, b.u_new, b.v_new);
     NSDG_CHECK_LAUNCH();
     return NSDG_OK;
 }

@@ -55,6 +55,16 @@ int nsdg_comm_bounded_drain(nsdg_ctx* ctx); // halo.hip: drain the context's str
         }                                                                \
     } while (0)
 
+// NSDG_CHECK_ARG in a helper that checks on behalf of several exported functions: `fn` is the one the message names, and the
+// message is a printf format
+#define NSDG_CHECK_ARG_IN(fn, cond, fmt, ...)                            \
+    do {                                                                 \
+        if (!(cond)) {                                                   \
+            nsdg_set_error("%s: " fmt, fn, ##__VA_ARGS__);               \
+            return NSDG_ERR_ARG;                                         \
+        }                                                                \
+    } while (0)
+
 #define NSDG_CHECK_HIP(expr)                                                              \
     do {                                                                                  \
         hipError_t e_ = (expr);                                                           \
@@ -76,3 +86,23 @@ int nsdg_comm_bounded_drain(nsdg_ctx* ctx); // halo.hip: drain the context's str
     } while (0)
 
 static inline int nsdg_div_up(long a, long b) { return (int)((a + b - 1) / b); }
+
+// ---- mEVP passes (mevp.hip) -----------------------------------------------------------------------------------------------------
+// the buffers of a pass: the stress S_in -> S_out (tiled), the velocity u_old -> u_new, the packed nodal coefficients, the ice strength
+struct nsdg_mevp_bufs {
+    const double *s11i, *s12i, *s22i;
+    double *s11, *s12, *s22;
+    const double *u_old, *v_old;
+    double *u_new, *v_new;
+    const double *packed, *pg;
+};
+
+// One checked pass of v sub-iterations, the work of every nsdg_mevp_iterate* entry point and reported under its name: v = 1 on the
+// stress rows [k0, j1) and the velocity rows [j0, j1) (nsdg_mevp_iterate); v = 2, 3, 4 on the rows [j0, j1) (nsdg_mevp_iterate2 / 3 / 4)
+// and, for the pair forms, on the disjoint rows [j0b, j1b) as well (nsdg_mevp_iterate3_pair / 4_pair)
+int nsdg_mevp_pass(nsdg_ctx* ctx, int v, int k0, int j0, int j1, bool pair, int j0b, int j1b, const nsdg_mevp_bufs& b);
+
+// the launchers behind it, unchecked: the fused single-iteration kernel (mevp_fused.hip); the stage-per-wave pipeline of nst = 2, 3
+// or 4 sub-iterations on the rows [j0, j1) and, if j0b < j1b, on a second disjoint range (mevp_fused4.hip)
+int nsdg_launch_mevp_fused(nsdg_ctx* ctx, int k0, int j0, int j1, const nsdg_mevp_bufs& b);
+int nsdg_launch_mevp_fused4_ranges(nsdg_ctx* ctx, int nst, int j0, int j1, int j0b, int j1b, const nsdg_mevp_bufs& b);

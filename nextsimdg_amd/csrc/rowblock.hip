@@ -182,28 +182,23 @@ struct nsdg_rb_mevp {
 
 namespace {
 
+// the buffers of a pass that reads the ping-pong set `par` and writes the other one
+nsdg_mevp_bufs pass_bufs(const nsdg_rb_mevp_desc& d, int par)
+{
+    const int q = 1 - par;
+    return { d.s11[par], d.s12[par], d.s22[par], d.s11[q], d.s12[q], d.s22[q], d.u[par], d.v[par], d.u[q], d.v[q], d.packed, d.pg };
+}
+
 int pass_launch(nsdg_rb_mevp* p, int v, Range r, int par)
 { // v sub-iterations on rows r: buffers `par` -> 1 - par
-    const nsdg_rb_mevp_desc& d = p->d;
-    const int q = 1 - par;
     if (r.j0 >= r.j1)
         return NSDG_OK;
-    if (v == 4)
-        return nsdg_mevp_iterate4(p->ctx, r.j0, r.j1, d.s11[par], d.s12[par], d.s22[par], d.s11[q], d.s12[q], d.s22[q], d.u[par], d.v[par], d.u[q],
-            d.v[q], d.packed, d.pg);
-    if (v == 3)
-        return nsdg_mevp_iterate3(p->ctx, r.j0, r.j1, d.s11[par], d.s12[par], d.s22[par], d.s11[q], d.s12[q], d.s22[q], d.u[par], d.v[par], d.u[q],
-            d.v[q], d.packed, d.pg);
-    return nsdg_mevp_iterate2(p->ctx, r.j0, r.j1, d.s11[par], d.s12[par], d.s22[par], d.s11[q], d.s12[q], d.s22[q], d.u[par], d.v[par], d.u[q], d.v[q],
-        d.packed, d.pg);
+    return nsdg_mevp_pass(p->ctx, v, 0, r.j0, r.j1, false, 0, 0, pass_bufs(p->d, par));
 }
 
 int single_launch(nsdg_rb_mevp* p, int k0, int j0, int j1, int par)
 {
-    const nsdg_rb_mevp_desc& d = p->d;
-    const int q = 1 - par;
-    return nsdg_mevp_iterate(p->ctx, k0, j0, j1, d.s11[par], d.s12[par], d.s22[par], d.s11[q], d.s12[q], d.s22[q], d.u[par], d.v[par], d.u[q], d.v[q],
-        d.packed, d.pg);
+    return nsdg_mevp_pass(p->ctx, 1, k0, j0, j1, false, 0, 0, pass_bufs(p->d, par));
 }
 
 // the launches of one pass of a group: ext > 0 -> one launch over the owned rows extended by v*ext ghost rows per side;
@@ -417,9 +412,7 @@ int nsdg_rb_mevp_run(nsdg_ctx* ctx, nsdg_rb_mevp* p, int32_t parity, int32_t* pa
                         const size_t n = (split_ok && last) ? r.size() - 1 : r.size();
                         if (split_ok && last && n == 2 && v >= 3) {
                             // the rows that travel up and the rows that travel down: ONE launch (bit-identical to two)
-                            const nsdg_rb_mevp_desc& d = p->d;
-                            const int e = (v == 4 ? nsdg_mevp_iterate4_pair : nsdg_mevp_iterate3_pair)(p->ctx, r[0].j0, r[0].j1, r[1].j0, r[1].j1, d.s11[q],
-                                d.s12[q], d.s22[q], d.s11[1 - q], d.s12[1 - q], d.s22[1 - q], d.u[q], d.v[q], d.u[1 - q], d.v[1 - q], d.packed, d.pg);
+                            const int e = nsdg_mevp_pass(p->ctx, v, 0, r[0].j0, r[0].j1, true, r[1].j0, r[1].j1, pass_bufs(p->d, q));
                             if (e != NSDG_OK)
                                 return e;
                         } else

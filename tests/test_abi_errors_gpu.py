@@ -144,3 +144,112 @@ def test_parameter_or_grid_change_invalidates_the_packed_coefficients(ctx):
         ctx.mevp_iterate(0, 0, ny, s, so, (u, v), (un, vn), packed, pg)
     ctx.set_mevp_params(ctx.mevp_default_params())
     torch.cuda.synchronize()
+
+
+def test_mevp_pass_contract(gpu):
+    """Every check of the six nsdg_mevp_iterate* entry points, with the status code and the full nsdg_last_error() text
+    (the entry point's name at its front), in the order each makes them: the empty range of nsdg_mevp_iterate (k0 == j1)
+    is checked before the packing, that of iterate2 / 3 / 4 after it and before the variant gate; the pair forms have
+    no empty range and gate the variant after the packing"""
+    nx, ny = 70, 12
+    ARG, STATE = -1, -3
+    not_packed = (STATE, "nsdg_mevp_pack_nodal was not called on this context")
+    below = "need %s ghost rows below the %s (or j0 == 0 at the physical boundary)"
+    above = "need %s ghost rows above the %s (or j1 == ny at the physical boundary)"
+    empty = (ARG, "row range outside the local array (or empty)")
+    variant2 = (STATE, "select variant 2, 3 or 4 (nsdg_mevp_variant_set) or call nsdg_mevp_iterate twice")
+    variant3 = (STATE, "select variant 3 or 4 (nsdg_mevp_variant_set)")
+    variant4 = (STATE, "select variant 4 (nsdg_mevp_variant_set)")
+    fresh, packed_ctx = abi.Context(gpu), abi.Context(gpu)
+    for c in (fresh, packed_ctx):
+        c.set_grid(nx, ny, 1.0, 1.0)
+    s = [fresh.private_zeros(8, ny, nx, "cuda") for _ in range(3)]
+    so = [torch.zeros_like(x) for x in s]
+    pg = fresh.private_zeros(9, ny, nx, "cuda")
+    u, v, un, vn = (z(2 * ny + 1, 2 * nx + 1) for _ in range(4))
+    packed = z(8 * u.numel())
+    packed_ctx.mevp_pack_nodal(120.0, (u, v), (u, v), (u, v), u, v, packed)
+    bufs = dict(s_in=s, s_out=so, uv_old=(u, v), uv_new=(un, vn), packed=packed, pg=pg)
+    cases = [  # (context, variant, entry point, row arguments, buffers replaced, expected status and message; None = NSDG_OK)
+        (fresh, 1, "mevp_iterate", (0, 0, 0), {}, None),
+        (fresh, 1, "mevp_iterate", (0, 0, ny), {}, not_packed),
+        (fresh, 1, "mevp_iterate2", (4, 4), {}, not_packed),
+        (fresh, 1, "mevp_iterate3", (4, 4), {}, not_packed),
+        (fresh, 1, "mevp_iterate4", (4, 4), {}, not_packed),
+        (fresh, 1, "mevp_iterate2", (0, ny), {}, not_packed),
+        (fresh, 1, "mevp_iterate3_pair", ((0, 4), (6, 10)), {}, not_packed),
+        (fresh, 1, "mevp_iterate4_pair", ((0, 4), (6, 8)), {}, not_packed),
+        (packed_ctx, 1, "mevp_iterate2", (4, 4), {}, None),
+        (packed_ctx, 1, "mevp_iterate3", (4, 4), {}, None),
+        (packed_ctx, 1, "mevp_iterate4", (4, 4), {}, None),
+        (packed_ctx, 1, "mevp_iterate2", (0, ny), {}, variant2),
+        (packed_ctx, 2, "mevp_iterate3", (0, ny), {}, variant3),
+        (packed_ctx, 3, "mevp_iterate4", (0, ny), {}, variant4),
+        (packed_ctx, 2, "mevp_iterate3_pair", ((0, 4), (6, 10)), {}, variant3),
+        (packed_ctx, 3, "mevp_iterate4_pair", ((0, 4), (6, 8)), {}, variant4),
+        (packed_ctx, 2, "mevp_iterate3_pair", ((4, 4), (8, 10)), {}, empty),
+        (packed_ctx, 4, "mevp_iterate3_pair", ((4, 4), (8, 10)), {}, empty),
+        (packed_ctx, 4, "mevp_iterate4_pair", ((4, 8), (10, 10)), {}, empty),
+        (packed_ctx, 4, "mevp_iterate3_pair", ((2, 6), (8, 10)), {}, (ARG, below % ("three", "rows of a range"))),
+        (packed_ctx, 4, "mevp_iterate3_pair", ((0, 4), (6, 11)), {}, (ARG, above % ("two", "rows of a range"))),
+        (packed_ctx, 4, "mevp_iterate4_pair", ((4, 8), (2, 3)), {}, (ARG, below % ("four", "rows of a range"))),
+        (packed_ctx, 4, "mevp_iterate4_pair", ((0, 10), (11, 12)), {}, (ARG, above % ("three", "rows of a range"))),
+        (packed_ctx, 4, "mevp_iterate3_pair", ((0, 6), (4, 12)), {}, (ARG, "the two row ranges must be disjoint")),
+        (packed_ctx, 4, "mevp_iterate", (0, 0, ny + 1), {}, (ARG, "need 0 <= k0 <= j0 <= j1 <= ny")),
+        (packed_ctx, 4, "mevp_iterate", (0, 3, ny), {}, (ARG, "need k0 == j0 - 1 (one ghost row below) or k0 == j0 == 0")),
+        (packed_ctx, 4, "mevp_iterate2", (0, ny + 1), {}, (ARG, "row range outside the local array")),
+        (packed_ctx, 4, "mevp_iterate2", (1, 1), {}, (ARG, below % ("two", "owned rows"))),
+        (packed_ctx, 4, "mevp_iterate3", (2, 2), {}, (ARG, below % ("three", "owned rows"))),
+        (packed_ctx, 4, "mevp_iterate3", (0, ny - 1), {}, (ARG, above % ("two", "owned rows"))),
+        (packed_ctx, 4, "mevp_iterate4", (3, ny), {}, (ARG, below % ("four", "owned rows"))),
+        (packed_ctx, 4, "mevp_iterate4", (0, ny - 2), {}, (ARG, above % ("three", "owned rows"))),
+        (packed_ctx, 2, "mevp_iterate2", (0, ny - 1), {}, None),  # a pass of two needs no ghost row above
+        (packed_ctx, 4, "mevp_iterate", (0, 0, ny), {"pg": None}, (ARG, "null field pointer")),
+        (packed_ctx, 4, "mevp_iterate4_pair", ((0, 4), (6, 8)), {"pg": pg.view(-1)[1:]},
+         (ARG, "tiled arrays (stress, ice strength) must be 16-byte aligned")),
+        (packed_ctx, 4, "mevp_iterate3", (0, ny), {"s_out": s}, (ARG, "the output stress must not alias the input stress")),
+        (packed_ctx, 4, "mevp_iterate2", (0, ny), {"uv_new": (u, vn)}, (ARG, "u_new/v_new must not alias u_old/v_old")),
+    ]
+    for c, variant, name, rows, replaced, expected in cases:
+        c.set_mevp_variant(variant)
+        call = lambda: getattr(c, name)(*rows, **dict(bufs, **replaced))
+        if expected is None:
+            call()
+            continue
+        with pytest.raises(abi.NsdgError) as e:
+            call()
+        assert str(e.value) == "nsdg error %d: nsdg_%s: %s" % (expected[0], name, expected[1]), (variant, name, rows)
+    torch.cuda.synchronize()
+    fresh.close()
+    packed_ctx.close()
+
+
+def test_iterate_without_velocity_rows_updates_stress_row_k0(gpu):
+    """nsdg_mevp_iterate(k0 = j0 - 1, j0 = j1) computes the stress rows [k0, j1) (include/nsdg.h): row k0 equals that row of a call
+    on the whole array bit for bit, and neither another stress row nor any velocity is written -- in the two-kernel form and in the
+    fused kernel"""
+    nx, ny, k0 = 70, 12, 4
+    gen = torch.Generator().manual_seed(11)
+    rnd = lambda lo, hi, *shape: (lo + (hi - lo) * torch.rand(*shape, generator=gen, dtype=torch.float64)).cuda()
+    c = abi.Context(gpu)
+    c.set_grid(nx, ny, 1000.0, 1000.0)
+    nodes = (2 * ny + 1, 2 * nx + 1)
+    u, v = rnd(-0.1, 0.1, *nodes), rnd(-0.1, 0.1, *nodes)
+    packed = z(8 * u.numel())
+    c.mevp_pack_nodal(120.0, (u, v), (rnd(-0.1, 0.1, *nodes), rnd(-0.1, 0.1, *nodes)), (rnd(-0.1, 0.1, *nodes), rnd(-0.1, 0.1, *nodes)),
+                      rnd(0.5, 1.5, *nodes), rnd(0.5, 1.0, *nodes), packed)
+    s = [abi.tile(rnd(-1e3, 1e3, 8, ny, nx)) for _ in range(3)]
+    pg = abi.tile(rnd(1e4, 3e4, 9, ny, nx))
+    for variant in (0, 1):
+        c.set_mevp_variant(variant)
+        out = []
+        for rows in ((0, 0, ny), (k0, k0 + 1, k0 + 1)):
+            so, uvn = [torch.full_like(x, 7.0) for x in s], (torch.full_like(u, 7.0), torch.full_like(v, 7.0))
+            c.mevp_iterate(*rows, s, so, (u, v), uvn, packed, pg)
+            out.append((so, uvn))
+        (full, _), (one, one_uv) = out
+        for a, b in zip(full, one):
+            assert not torch.all(a[k0] == 7.0) and torch.equal(b[k0], a[k0]), variant
+            assert torch.all(b[:k0] == 7.0) and torch.all(b[k0 + 1:] == 7.0), variant
+        assert all(torch.all(t == 7.0) for t in one_uv), variant
+    c.close()

@@ -54,7 +54,8 @@ extern "C" {
 
 /* 6: a pipeline wait that gives up is an error status.  Since then the ABI has only grown, without a new number: nsdg_concentration_max,
  * nsdg_substep_count and nsdg_comm_max_f64 (sub-stepping of the model time step), nsdg_forcing_sample (forcing from a file) and
- * nsdg_tracer_weight / nsdg_tracer_recover (column state transport) are additions; nothing that existed changed. */
+ * nsdg_tracer_weight / nsdg_tracer_recover (column state transport) and nsdg_phase_timing_set / nsdg_phase_mark / nsdg_phase_times (per-phase
+ * device timing) are additions; nothing that existed changed. */
 #define NSDG_ABI_VERSION 6
 
 typedef enum {
@@ -88,6 +89,49 @@ int nsdg_ctx_synchronize(nsdg_ctx* ctx);
  * SURVEY.md section 8(d) asks the roofline fraction to be quoted against, measured on the box the bench runs on
  * (bench.py: roofline.copy_peak_GBs).  dst and src 16-byte aligned, not overlapping. */
 int nsdg_copy_f64(nsdg_ctx* ctx, double* dst, const double* src, int64_t n);
+
+/* ---- per-phase device timing (csrc/phase_timer.hip; DESIGN.md section 6 "phase timing") -------------------------
+ * An opt-in answer to "where does my step go?": the host brackets the parts of its model step with MARKS, each mark records one event
+ * on the context's stream, and the device time between two consecutive marks belongs to the phase the first of them opened.  The
+ * ids below are shared by both hosts (the C++ DynamicsStep / HipStep and the Python DynamicsCore) so that their tables read alike;
+ * any id in [0, NSDG_PHASE_MAX) is accepted.
+ *
+ * nsdg_phase_timing_set: on / off; a new context starts off.  Turning it on allocates the ring of NSDG_PHASE_RING events, turning it off
+ *   discards whatever was pending and zeroes the table.
+ * nsdg_phase_mark: closes the running phase, if there is one, and opens `phase`; NSDG_PHASE_END closes the running phase and opens
+ *   nothing (and is a no-op when nothing runs) -- the stretch up to the next mark then belongs to no phase.  With timing off it
+ *   returns NSDG_OK and does nothing (no event, no allocation): a host can call it unconditionally.  It never waits for recently
+ *   enqueued work: intervals whose closing event has completed are harvested with hipEventQuery, and only when every event of the
+ *   ring is outstanding does it wait -- for the OLDEST one.  No interval is dropped or counted twice.  On a stream that is being
+ *   captured it returns NSDG_ERR_STATE (an event query inside a capture would invalidate the capture): mark between the captured
+ *   regions, e.g. around nsdg_rb_mevp_run, never inside one.
+ * nsdg_phase_times: waits for the last mark (on a context with a communicator: the bounded drain of nsdg_ctx_synchronize, NSDG_ERR_COMM
+ *   on expiry) and returns, per phase id, the accumulated device time and the number of closed intervals.  A SPAN runs from the mark
+ *   that opened a phase while none was running to the NSDG_PHASE_END that closes the sequence; total_ms sums hipEventElapsedTime(first,
+ *   end) over the spans -- its own pair of events, not the sum of the phases -- so a table can be checked against it.  A phase that is
+ *   still open stays open (its interval is counted once it is closed).  reset != 0 zeroes the table after it was copied; reset between
+ *   spans (after an NSDG_PHASE_END) if the next table is to add up: a span that is open keeps its first mark.
+ * Null context, a phase outside [0, NSDG_PHASE_MAX) other than NSDG_PHASE_END, or a null `out`: NSDG_ERR_ARG. */
+enum {
+    NSDG_PHASE_FORCING = 0, /* external forcing: box test or file sampling, nsdg_column_forcing, nsdg_column_wind */
+    NSDG_PHASE_COLUMN = 1, /* nsdg_column_step */
+    NSDG_PHASE_PREPARE = 2, /* nsdg_ice_strength, nsdg_mevp_prepare */
+    NSDG_PHASE_SUBCYCLE = 3, /* the mEVP sub-iterations (nsdg_rb_mevp_run / nsdg_mevp_subcycle) */
+    NSDG_PHASE_TRANSPORT = 4, /* nsdg_prepare_advection, tracer weight / recover, the transport step */
+    NSDG_PHASE_REDUCTION = 5, /* nsdg_concentration_max of the sub-stepping rule */
+    NSDG_PHASE_MAX = 16,
+    NSDG_PHASE_END = -1
+};
+#define NSDG_PHASE_RING 256 /* events per context: a mark waits (for the oldest) only when this many are outstanding */
+typedef struct {
+    double ms[NSDG_PHASE_MAX]; /* accumulated device time of the phase's closed intervals */
+    int64_t count[NSDG_PHASE_MAX]; /* closed intervals */
+    double total_ms; /* sum over the closed spans of hipEventElapsedTime(first mark, closing NSDG_PHASE_END) */
+    int64_t spans;
+} nsdg_phase_table;
+int nsdg_phase_timing_set(nsdg_ctx* ctx, int32_t enable);
+int nsdg_phase_mark(nsdg_ctx* ctx, int32_t phase);
+int nsdg_phase_times(nsdg_ctx* ctx, nsdg_phase_table* out, int32_t reset);
 
 /* ---- column physics (the reference's per-element step) ---------------------------------------- */
 enum { NSDG_ALBEDO_SMU = 0, NSDG_ALBEDO_SMU2 = 1, NSDG_ALBEDO_CCSM = 2 }; /* physics/src/modules/modules.json:4-8 */

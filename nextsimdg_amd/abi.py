@@ -58,6 +58,16 @@ class HaloStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+# NSDG_PHASE_*: the phase ids both hosts share (include/nsdg.h "per-phase device timing"), in id order
+PHASES = ("forcing", "column", "prepare", "sub-cycle", "transport", "reduction")
+PHASE_MAX, PHASE_END, PHASE_RING = 16, -1, 256
+
+
+class PhaseTable(C.Structure):
+    """nsdg_phase_table"""
+    _fields_ = [("ms", C.c_double * PHASE_MAX), ("count", C.c_int64 * PHASE_MAX), ("total_ms", C.c_double), ("spans", C.c_int64)]
+
+
 COMM_ID_BYTES = 128
 RB_MAX_FIELDS = 4
 
@@ -92,6 +102,9 @@ SYMBOLS = {
     "nsdg_ctx_destroy": (C.c_int, [VP]),
     "nsdg_ctx_synchronize": (C.c_int, [VP]),
     "nsdg_copy_f64": (C.c_int, [VP, VP, VP, I64]),
+    "nsdg_phase_timing_set": (C.c_int, [VP, I32]),
+    "nsdg_phase_mark": (C.c_int, [VP, I32]),
+    "nsdg_phase_times": (C.c_int, [VP, C.POINTER(PhaseTable), I32]),
     "nsdg_column_default_params": (None, [C.POINTER(ColumnParams)]),
     "nsdg_column_params_set": (C.c_int, [VP, C.POINTER(ColumnParams)]),
     "nsdg_column_step": (C.c_int, [VP, I64, D] + [VP] * 16),
@@ -386,6 +399,21 @@ class Context:
         if dst.numel() != src.numel():
             raise NsdgError("copy_f64: sizes differ")
         self._call(self.lib.nsdg_copy_f64(self.h, dst.data_ptr(), src.data_ptr(), src.numel()))
+
+    def phase_timing(self, enable):
+        """per-phase device timing on / off (nsdg_phase_timing_set); off discards what was pending"""
+        self._call(self.lib.nsdg_phase_timing_set(self.h, int(bool(enable))))
+
+    def phase_mark(self, phase):
+        """one timing event on the context's stream: closes the running phase and opens `phase` (an id below PHASE_MAX, or PHASE_END);
+        does nothing while timing is off"""
+        self._call(self.lib.nsdg_phase_mark(self.h, int(phase)))
+
+    def phase_times(self, reset=False):
+        """waits for the last mark; ({phase id: (ms, count)} for the ids that closed an interval, (total_ms, spans)) (nsdg_phase_times)"""
+        t = PhaseTable()
+        self._call(self.lib.nsdg_phase_times(self.h, C.byref(t), int(bool(reset))))
+        return {k: (float(t.ms[k]), int(t.count[k])) for k in range(PHASE_MAX) if t.count[k]}, (float(t.total_ms), int(t.spans))
 
     def comm_deadline(self, seconds):
         """upper bound on any wait for a neighbour rank (0 = for ever)"""

@@ -174,6 +174,7 @@ int nsdg_ctx_create(int device_id, void* stream, nsdg_ctx** out)
         e = hipHostGetDevicePointer((void**)&c->p2p_flag_dev, c->p2p_flag_host, 0);
     }
     c->scalar_dev = nullptr, c->scalar_host = nullptr;
+    c->phase = nullptr;
     if (e == hipSuccess)
         e = hipMalloc((void**)&c->scalar_dev, 2 * sizeof(double));
     if (e == hipSuccess)
@@ -204,6 +205,7 @@ int nsdg_ctx_destroy(nsdg_ctx* ctx)
         if (ctx->scalar_host)
             (void)hipHostFree(ctx->scalar_host);
     }
+    nsdg_phase_timer_free(ctx);
     delete ctx;
     return NSDG_OK;
 }

@@ -8,6 +8,7 @@
 #include "../../include/nsdg.h"
 
 struct nsdg_comm; // halo.hip
+struct nsdg_phase_timer; // phase_timer.hip
 
 struct nsdg_ctx {
     int device;
@@ -39,6 +40,7 @@ struct nsdg_ctx {
     // nsdg_comm_max_f64 (halo.hip)
     double* scalar_dev;
     double* scalar_host; // hipHostMalloc'ed
+    nsdg_phase_timer* phase; // per-phase device timing (phase_timer.hip), null until nsdg_phase_timing_set turns it on
 };
 
 void nsdg_set_error(const char* fmt, ...);
@@ -46,6 +48,7 @@ void nsdg_set_error(const char* fmt, ...);
 // in a launch that has completed; does not synchronise
 int nsdg_p2p_check(nsdg_ctx* ctx, const char* where);
 int nsdg_comm_bounded_drain(nsdg_ctx* ctx); // halo.hip: drain the context's streams within the communicator's deadline
+void nsdg_phase_timer_free(nsdg_ctx* ctx); // phase_timer.hip: the event ring of nsdg_phase_timing_set, if there is one
 
 #define NSDG_CHECK_ARG(cond, msg)                                        \
     do {                                                                 \

@@ -47,6 +47,7 @@
 //                            step (forcing, column, strength, sub-cycle, transport) runs n times with dt / n
 //     dynamics.substep_courant  cells the strength wave may cross per sub-step under auto (1.5)
 //     dynamics.max_substeps  the largest n auto may choose (16); a state that needs more stops the run with the needed n
+//     model.phase_timing, model.phase_timing_file   per-phase device time of the step (include/PhaseTiming.hpp)
 //     dynamics.row_blocks, dynamics.devices, dynamics.passes_per_exchange (2), dynamics.overlap (true),
 //     dynamics.graph (false), dynamics.loopback_world (0: off; N: rehearse an interior block of N on one GPU with
 //     real RCCL send/recv to the rank itself -- values wrap around, for timing and call-path checks only)
@@ -111,7 +112,10 @@ public:
 
 private:
     void release();
-    void subStep(double dt); //!< forcing at m_time, column step, ice strength, prepare, sub-cycle and transport with dt
+    //! forcing at m_time, column step, ice strength, prepare, sub-cycle and transport with dt, each opened by its phase mark; `last`: the
+    //! model step ends with this sub-step (NSDG_PHASE_END)
+    void subStep(double dt, bool last);
+    void resolvePhaseTimes(); //!< model.phase_timing: every block's table -> the timer tree and model.phase_timing_file (PhaseTiming.hpp)
     //! dynamics.forcing = file: records k0, k1 resident on the block's device, sampled with time weight w into the block's wind / ocean
     //! (the pairs the file holds) and, with thermodynamics, its column forcing planes
     void sampleForcingFile(DynamicsBlock& b, std::size_t k0, std::size_t k1, double w);
@@ -133,6 +137,9 @@ private:
     double substepCourant = 1.5; // dynamics.substep_courant (NSDG_SUBSTEP_COURANT)
     int maxSubsteps = 16; // dynamics.max_substeps
     bool timing = false; // model.timing: one line whenever auto changes n
+    bool phaseTiming = false; // model.phase_timing: the contexts time the step's phases with stream events (PhaseTiming.hpp)
+    std::vector<std::string> m_iteratePath; // the timer node of iterate()
+    long m_substepsRun = 0;
     int m_lastSubsteps = 0; // n of the previous model step (auto)
     int m_world = 1, m_rank = 0; // multi-process run (one block per process)
     long m_steps = 0;

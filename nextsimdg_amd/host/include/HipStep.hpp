@@ -7,6 +7,7 @@
 // Fields stay resident in HBM between steps: they are uploaded at start() and downloaded at stop() /
 // writeRestartFile() / syncToHost() only.
 #pragma once
+#include <string>
 #include <vector>
 
 #include "Iterator.hpp"
@@ -43,6 +44,8 @@ private:
     std::size_t n = 0;
     bool resident = false;
     long m_launches = 0;
+    bool phaseTiming = false; // model.phase_timing: `column` as a device-time child of iterate (PhaseTiming.hpp)
+    std::vector<std::string> m_iteratePath; // the timer node of iterate()
 };
 
 } // namespace Nextsim

@@ -16,6 +16,7 @@
 #include "../../../include/nsdg.h"
 #include "ForcingFile.hpp"
 #include "ModuleLoader.hpp"
+#include "PhaseTiming.hpp"
 #include "PhysicsModules.hpp"
 #include "Rendezvous.hpp"
 #include "Timer.hpp"
@@ -207,6 +208,7 @@ void DynamicsStep::configure()
     if (maxSubsteps < 1)
         throw std::invalid_argument("dynamics.max_substeps must be >= 1");
     timing = getConfiguration(std::string("model.timing"), false);
+    phaseTiming = PhaseTiming::enabled();
     if (rowBlocks < 1 || passesPerExchange < 1 || nsub < 0)
         throw std::invalid_argument("dynamics.row_blocks and dynamics.passes_per_exchange must be >= 1, dynamics.nsub >= 0");
     if (forcing != "host" && forcing != "dummy" && forcing != "winter" && forcing != "file")
@@ -349,6 +351,8 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
     forEachBlock([&](DynamicsBlock& b) {
         checkHip(hipSetDevice(b.device), "hipSetDevice");
         check(nsdg_ctx_create(b.device, nullptr, &b.ctx), "nsdg_ctx_create");
+        if (phaseTiming)
+            check(nsdg_phase_timing_set(b.ctx, 1), "nsdg_phase_timing_set");
         if (world > 1) {
             if (m_world > 1)
                 check(nsdg_comm_init(b.ctx, m_rank, m_world, commId), "nsdg_comm_init");
@@ -471,6 +475,8 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
 void DynamicsStep::iterate(const Iterator::Duration& dtSeconds)
 {
     ScopedTimer timer("iterate");
+    if (phaseTiming && m_iteratePath.empty())
+        m_iteratePath = Timer::main.currentPath(); // where resolvePhaseTimes() hangs the phases
     if (m_blocks.empty())
         start(0);
     const double dt = dtSeconds;
@@ -480,6 +486,7 @@ void DynamicsStep::iterate(const Iterator::Duration& dtSeconds)
         nsdg_mevp_default_params(&p);
         forEachBlock([&](DynamicsBlock& b) {
             checkHip(hipSetDevice(b.device), "hipSetDevice");
+            check(nsdg_phase_mark(b.ctx, NSDG_PHASE_REDUCTION), "nsdg_phase_mark"); // (the marks do nothing unless model.phase_timing is on)
             check(nsdg_concentration_max(b.ctx, b.j0, b.j1, b.curH(), b.curA(), &b.amax), "nsdg_concentration_max");
         });
         double amax = 0.; // the blocks of this process are its threads: their maximum is taken here ...
@@ -497,13 +504,14 @@ void DynamicsStep::iterate(const Iterator::Duration& dtSeconds)
     }
     const double sub = dt / n;
     for (int k = 0; k < n; ++k) {
-        subStep(sub);
+        subStep(sub, k + 1 == n);
         m_time += sub;
     }
+    m_substepsRun += n;
     ++m_steps;
 }
 
-void DynamicsStep::subStep(double dt)
+void DynamicsStep::subStep(double dt, bool last)
 {
     nsdg_mevp_params p;
     nsdg_mevp_default_params(&p);
@@ -522,6 +530,7 @@ void DynamicsStep::subStep(double dt)
         checkHip(hipSetDevice(b.device), "hipSetDevice");
         nsdg_ctx* ctx = b.ctx;
         check(nsdg_mevp_params_set(ctx, &p), "nsdg_mevp_params_set");
+        check(nsdg_phase_mark(ctx, NSDG_PHASE_FORCING), "nsdg_phase_mark");
         if (!ff || !ff->hasWind())
             check(nsdg_boxtest_forcing(ctx, L, t, b.d[UA], b.d[VA], nullptr, nullptr), "nsdg_boxtest_forcing"); // the cyclone moves
         if (ff)
@@ -534,17 +543,21 @@ void DynamicsStep::subStep(double dt)
                         "nsdg_column_forcing");
                 check(nsdg_column_wind(ctx, b.d[UA], b.d[VA], b.col(C_WIND)), "nsdg_column_wind");
             }
+            check(nsdg_phase_mark(ctx, NSDG_PHASE_COLUMN), "nsdg_phase_mark");
             // the column physics needs no exchange: it runs on the ghost rows too, redundantly
             check(nsdg_column_step(ctx, b.N, dt, b.curH(), b.curA(), advectColumn ? b.curS() : b.col(C_HSNOW), b.col(C_TICE), b.col(C_SST), b.col(C_SSS), b.col(C_TAIR),
                       b.col(C_TDEW), b.col(C_SLP), b.col(C_QSW), b.col(C_QLW), b.col(C_MLD), b.col(C_SNOWFALL), b.col(C_WIND), b.col(C_NEWICE),
                       nullptr),
                 "nsdg_column_step");
         }
+        check(nsdg_phase_mark(ctx, NSDG_PHASE_PREPARE), "nsdg_phase_mark");
         check(nsdg_ice_strength(ctx, 0, b.ny, b.curH(), b.curA(), b.d[PG]), "nsdg_ice_strength");
         check(nsdg_mevp_prepare(ctx, dt, b.curH(), b.curA(), b.d[UA], b.d[VA], b.d[UO], b.d[VO], b.curU(), b.curV(), b.d[PACKED]), "nsdg_mevp_prepare");
         int32_t out = 0;
+        check(nsdg_phase_mark(ctx, NSDG_PHASE_SUBCYCLE), "nsdg_phase_mark");
         check(nsdg_rb_mevp_run(ctx, b.mevp, b.par, &out), "nsdg_rb_mevp_run");
         b.par = out;
+        check(nsdg_phase_mark(ctx, NSDG_PHASE_TRANSPORT), "nsdg_phase_mark");
         check(nsdg_prepare_advection(ctx, 2, b.curU(), b.curV(), b.d[VXDG], b.d[VYDG], b.d[UNX], b.d[UNY]), "nsdg_prepare_advection");
         // the surface temperature travels as Q = H tice0 (every local row: element-local, the ghost rows stay equal to their owners)
         if (advectColumn)
@@ -553,7 +566,33 @@ void DynamicsStep::subStep(double dt)
         b.tpar = out;
         if (advectColumn)
             check(nsdg_tracer_recover(ctx, 2, 0, b.ny, b.curH(), b.curA(), b.curQ(), p.min_conc, p.min_thick, b.col(C_TICE)), "nsdg_tracer_recover");
+        if (last) // the model step ends here: what follows until its next mark belongs to no phase
+            check(nsdg_phase_mark(ctx, NSDG_PHASE_END), "nsdg_phase_mark");
     });
+}
+
+void DynamicsStep::resolvePhaseTimes()
+{
+    // once, after the run: the only place where the host waits for the marks (nsdg_phase_times; stop() has drained the streams already)
+    std::vector<PhaseBlockTimes> tables;
+    for (auto& bp : m_blocks) {
+        DynamicsBlock& b = *bp;
+        checkHip(hipSetDevice(b.device), "hipSetDevice");
+        PhaseBlockTimes t;
+        t.block = b.rank;
+        check(nsdg_phase_times(b.ctx, &t.table, 0), "nsdg_phase_times");
+        t.hasExchange = b.peerBelow >= 0 || b.peerAbove >= 0;
+        if (t.hasExchange) {
+            check(nsdg_rb_mevp_stats(b.ctx, b.mevp, &t.subcycleExchange, 0), "nsdg_rb_mevp_stats");
+            check(nsdg_rb_transport_stats(b.ctx, b.transport, &t.transportExchange, 0), "nsdg_rb_transport_stats");
+        }
+        tables.push_back(t);
+    }
+    if (!m_iteratePath.empty())
+        PhaseTiming::toTimer(Timer::main, m_iteratePath, tables);
+    const std::string path = PhaseTiming::file();
+    if (!path.empty())
+        PhaseTiming::write(path, m_rank, m_world, m_steps, m_substepsRun, tables);
 }
 
 void DynamicsStep::sampleForcingFile(DynamicsBlock& b, std::size_t k0, std::size_t k1, double w)
@@ -676,6 +715,8 @@ void DynamicsStep::stop(const Iterator::TimePoint&)
         ++idx;
     }
     f.dyn.present = true;
+    if (phaseTiming)
+        resolvePhaseTimes();
     m_umax = *std::max_element(umax.begin(), umax.end());
     m_sumH = m_sumA = 0;
     for (auto& bp : m_blocks)

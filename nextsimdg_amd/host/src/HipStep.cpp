@@ -7,6 +7,7 @@
 
 #include "../../../include/nsdg.h"
 #include "ModuleLoader.hpp"
+#include "PhaseTiming.hpp"
 #include "Timer.hpp"
 #include "PhysicsModules.hpp"
 
@@ -46,6 +47,8 @@ void HipStep::init()
 {
     if (!ctx)
         check(nsdg_ctx_create(0, nullptr, &ctx), "HipStep::init");
+    phaseTiming = PhaseTiming::enabled();
+    check(nsdg_phase_timing_set(ctx, phaseTiming ? 1 : 0), "nsdg_phase_timing_set");
     // the selected plugins describe themselves into the parameter block that crosses the ABI
     nsdg_column_params p;
     IPhysics1d& phys = ModuleLoader::getLoader().getImplementation<IPhysics1d>();
@@ -82,13 +85,17 @@ void HipStep::start(const Iterator::TimePoint&) { upload(); }
 void HipStep::iterate(const Iterator::Duration& dt)
 {
     ScopedTimer timer("iterate");
+    if (phaseTiming && m_iteratePath.empty())
+        m_iteratePath = Timer::main.currentPath();
     if (!resident)
         upload();
     double* b = d_block;
+    check(nsdg_phase_mark(ctx, NSDG_PHASE_COLUMN), "nsdg_phase_mark"); // (does nothing unless model.phase_timing is on)
     check(nsdg_column_step(ctx, (int64_t)n, (double)dt, b + P_HICE * n, b + P_CICE * n, b + P_HSNOW * n, b + P_TICE0 * n, b + P_SST * n,
               b + P_SSS * n, b + P_TAIR * n, b + P_TDEW * n, b + P_SLP * n, b + P_QSW * n, b + P_QLW * n, b + P_MLD * n, b + P_SNOWFALL * n,
               b + P_WIND * n, b + P_NEWICE * n, nullptr),
         "HipStep::iterate");
+    check(nsdg_phase_mark(ctx, NSDG_PHASE_END), "nsdg_phase_mark");
     ++m_launches;
 }
 
@@ -111,7 +118,19 @@ void HipStep::syncToHost()
             std::fill(f.tice.begin() + (std::size_t)l * n, f.tice.begin() + (std::size_t)(l + 1) * n, 0.);
 }
 
-void HipStep::stop(const Iterator::TimePoint&) { syncToHost(); }
+void HipStep::stop(const Iterator::TimePoint&)
+{
+    syncToHost();
+    if (phaseTiming && resident) { // once, after the run: the phase table -> the timer tree and model.phase_timing_file
+        PhaseBlockTimes t;
+        check(nsdg_phase_times(ctx, &t.table, 0), "nsdg_phase_times");
+        const std::vector<PhaseBlockTimes> tables(1, t);
+        if (!m_iteratePath.empty())
+            PhaseTiming::toTimer(Timer::main, m_iteratePath, tables);
+        if (!PhaseTiming::file().empty())
+            PhaseTiming::write(PhaseTiming::file(), 0, 1, m_launches, m_launches, tables);
+    }
+}
 
 void HipStep::writeRestartFile(const std::string& filePath)
 {

@@ -9,6 +9,7 @@
 #include "DynamicsStep.hpp"
 #include "Model.hpp"
 #include "ModuleLoader.hpp"
+#include "PhaseTiming.hpp"
 
 int main(int argc, char* argv[])
 {
@@ -24,6 +25,8 @@ int main(int argc, char* argv[])
         ModuleLoader::getLoader().setAllDefaults();
         ConfiguredModule::parseConfigurator();
         const bool timing = Configured<Model>::getConfiguration("model.timing", false);
+        // the phases of the step timed on the device with stream events (PhaseTiming.hpp): the tree is printed, NO sync hook is installed
+        const bool phaseTiming = PhaseTiming::enabled();
         Model model;
         model.configure();
         if (timing) // charge the asynchronous device work to the node that enqueued it
@@ -35,7 +38,7 @@ int main(int argc, char* argv[])
             f.hice[0], f.cice[0], f.hsnow[0], f.tice[0], f.sst[0]);
         if (auto* dyn = dynamic_cast<DynamicsStep*>(&model.step()))
             std::printf("dynamics umax=%.17g sumH=%.17g sumA=%.17g\n", dyn->maxSpeed(), dyn->sumH(), dyn->sumA());
-        if (timing)
+        if (timing || phaseTiming)
             Timer::main.report(std::cout);
     } catch (const std::exception& e) {
         std::cerr << "nextsim_amd: " << e.what() << std::endl;

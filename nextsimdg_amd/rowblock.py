@@ -31,6 +31,9 @@ import os
 import torch
 import torch.distributed as dist
 
+# NSDG_PHASE_* of include/nsdg.h: the ids of step()'s phase marks (names: abi.PHASES)
+PHASE_FORCING, PHASE_COLUMN, PHASE_PREPARE, PHASE_SUBCYCLE, PHASE_TRANSPORT, PHASE_REDUCTION, PHASE_END = 0, 1, 2, 3, 4, 5, -1
+
 
 def split_rows(ny, world, rank):
     return (rank * ny) // world, ((rank + 1) * ny) // world
@@ -269,8 +272,19 @@ class DynamicsCore:
     # advect_column_state adds the snow S and the weighted surface temperature Q
     TRANSPORTED = ("H", "A")
 
-    def __init__(self, ops, blk, hx, hy, dt, nsub, device, exchanger=None, overlap=True, native=False, use_graph=False, closure=True):
+    def __init__(self, ops, blk, hx, hy, dt, nsub, device, exchanger=None, overlap=True, native=False, use_graph=False, closure=True,
+                 phase_timing=False):
         self.ops, self.blk, self.hx, self.hy, self.dt, self.nsub = ops, blk, hx, hy, dt, nsub
+        # phase_timing: step() brackets its parts with the library's phase marks (include/nsdg.h "per-phase device timing": one event per
+        # mark on the ops' stream, read by phase_times()); off, nothing is asked of `ops` beyond the kernels
+        self._phase_timing = bool(phase_timing)
+        self._in_advance, self._phase_open = False, PHASE_END
+        if self._phase_timing:
+            missing = [m for m in ("phase_timing", "phase_mark", "phase_times") if not callable(getattr(ops, m, None))]
+            if missing:
+                raise ValueError("phase_timing=True needs an ops object with the phase calls of the C ABI (abi.Context); %s has no %s"
+                                 % (type(ops).__name__, ", ".join(missing)))
+            ops.phase_timing(True)
         self.overlap = overlap
         # closure: cap + scaling limiter at the end of every transport step (the ice-free-node rule is a parameter of the
         # sub-cycle, on by default).  False: the bare scheme of rounds 1-4 (frozen fixtures of that scheme)
@@ -375,8 +389,27 @@ class DynamicsCore:
         self._set_grid()
         self.ops.boxtest_forcing(domain_size, t, wind=(self.ua, self.va))
 
+    def _mark(self, phase):
+        if self._phase_timing and phase != self._phase_open:  # (a phase that already runs goes on: CoupledCore.transport wraps this class's)
+            self.ops.phase_mark(phase)
+            self._phase_open = phase
+
+    def phase_times(self, reset=False):
+        """{phase name: (device ms, closed intervals), "total": (ms, spans)} of the steps so far; waits for the last mark.  A span is one
+        step() -- or one advance(), with all its sub-steps -- timed from its first mark to its end by its own pair of events"""
+        from nextsimdg_amd import abi
+
+        if not self._phase_timing:
+            raise ValueError("phase_times() needs a core constructed with phase_timing=True")
+        phases, total = self.ops.phase_times(reset)
+        out = {(abi.PHASES[k] if k < len(abi.PHASES) else "phase %d" % k): v for k, v in phases.items()}
+        out["total"] = total
+        return out
+
     def momentum(self):
+        self._mark(PHASE_PREPARE)
         self.prepare()
+        self._mark(PHASE_SUBCYCLE)
         self.subcycle()
 
     def prepare(self):
@@ -525,6 +558,7 @@ class DynamicsCore:
 
     def transport(self):
         ops, b = self.ops, self.blk
+        self._mark(PHASE_TRANSPORT)
         ops.prepare_advection(self.ORDER, self.u, self.v, *self.adv)
         if self.native:
             par = self._tpar = self._run_transport(self.dt, self._tpar)
@@ -557,6 +591,8 @@ class DynamicsCore:
         self._set_grid()
         self.momentum()
         self.transport()
+        if not self._in_advance:
+            self._mark(PHASE_END)
 
     # ---- sub-stepping (include/nsdg.h "sub-stepping"): a model step of model_dt run as n steps of model_dt / n
     def substep_count(self, model_dt, courant=None, max_substeps=16, params=None):
@@ -586,6 +622,7 @@ class DynamicsCore:
         """one model step of model_dt as n calls of step() with self.dt = model_dt / n (restored afterwards); substeps: an int >= 1, or
         "auto" (n from the state at the start of the step, substep_count).  Returns n; substeps = 1 is step() at model_dt, bit for bit"""
         if substeps == "auto":
+            self._mark(PHASE_REDUCTION)
             n = self.substep_count(model_dt, courant, max_substeps, params)[0]
         elif isinstance(substeps, int) and not isinstance(substeps, bool) and substeps >= 1:
             n = substeps
@@ -593,11 +630,14 @@ class DynamicsCore:
             raise ValueError("substeps must be an integer >= 1 or 'auto', got %r" % (substeps,))
         dt = self.dt
         self.dt = model_dt / n
+        self._in_advance = True  # the span of the phase table is the model step: one end mark after the last sub-step
         try:
             for _ in range(n):
                 self.step()
         finally:
             self.dt = dt
+            self._in_advance = False
+            self._mark(PHASE_END)
         return n
 
     def owned(self, f):
@@ -783,6 +823,7 @@ class CoupledCore(DynamicsCore):
         if not self.advect_column_state:
             return super().transport()
         b = self.blk
+        self._mark(PHASE_TRANSPORT)
         # every local row, ghost rows included: both calls are element-local, the ghost rows stay equal to their owners
         self.ops.tracer_weight(self.ORDER, 0, b.ny, self.H, self.col["tice0"], self.Q)
         super().transport()
@@ -807,6 +848,7 @@ class CoupledCore(DynamicsCore):
             self.S.copy_(torch.from_numpy(np.ascontiguousarray(state["S"][:, self.blk.elem_slice()])).to(self.S.device))
 
     def thermodynamics(self):
+        self._mark(PHASE_COLUMN)
         state = {"hice": self.H[0], "cice": self.A[0], "hsnow": self.col["hsnow"], "tice0": self.col["tice0"]}
         forcing = {k: self.col[k] for k in self.COLUMN_FORCING}
         self.ops.column_step(self.dt, state, forcing, self.newice)
@@ -818,6 +860,7 @@ class CoupledCore(DynamicsCore):
         return self._records[k]
 
     def external_forcing(self):
+        self._mark(PHASE_FORCING)
         if isinstance(self.forcing, ForcingSeries):
             # the two records around the model time stay resident; a record is uploaded when the model time crosses into it
             k0, k1, w = self.forcing.bracket(self.time)
@@ -838,3 +881,5 @@ class CoupledCore(DynamicsCore):
         self.momentum()
         self.transport()
         self.time += self.dt
+        if not self._in_advance:
+            self._mark(PHASE_END)

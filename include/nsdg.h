@@ -55,7 +55,7 @@ extern "C" {
 /* 6: a pipeline wait that gives up is an error status.  Since then the ABI has only grown, without a new number: nsdg_concentration_max,
  * nsdg_substep_count and nsdg_comm_max_f64 (sub-stepping of the model time step), nsdg_forcing_sample (forcing from a file) and
  * nsdg_tracer_weight / nsdg_tracer_recover (column state transport) and nsdg_phase_timing_set / nsdg_phase_mark / nsdg_phase_times (per-phase
- * device timing) are additions; nothing that existed changed. */
+ * device timing) and nsdg_land_mask_set / nsdg_land_clear / nsdg_land_clear_nodes (land mask) are additions; nothing that existed changed. */
 #define NSDG_ABI_VERSION 6
 
 typedef enum {
@@ -533,6 +533,28 @@ int nsdg_mevp_pipeline_health(nsdg_ctx* ctx, uint32_t* waits_given_up);
 int nsdg_mevp_strip_rows_set(nsdg_ctx* ctx, int32_t rows);
 /* register budget of the fused kernel: 1 or 2 resident waves per SIMD (performance knob) */
 int nsdg_mevp_occupancy_set(nsdg_ctx* ctx, int32_t waves_per_simd);
+
+/* ---- land mask: coastlines as fixed nodes of the mEVP sub-cycle (csrc/landmask.hip) ------------------------------
+ * No counterpart in the reference snapshot.  land[iy * nx + ix] (1 = land, 0 = ocean) is an element mask on the LOCAL array, ghost rows
+ * included.  A CG2 node is a land node if any element adjacent to it inside the local array is land; a land node holds u = v = 0 in every
+ * sub-iteration, exactly as the nodes on the array edge do (no-slip coast).  Nothing else changes: an ocean node has only ocean elements
+ * around it (its nodal means, the ice-free rule and the adaptive alpha / beta are what they were), no flux crosses a coast edge (three land
+ * nodes: the edge-normal velocity at its Gauss points is exactly 0), so the unchanged transport keeps land elements that start at
+ * H = A = 0 at exactly 0, and land carries no stress (P = 0, strain rate 0).  The caller starts with H = A = 0, u = v = 0 on land
+ * (nsdg_land_clear*) and clears what a source outside the scheme -- the column step -- writes there.
+ *
+ * nsdg_land_mask_set: `land` is a device pointer to nx * ny bytes, owned by the caller and valid while it is set; stream-ordered like every
+ *   other array argument.  NULL clears the mask.  Before nsdg_grid_set: NSDG_ERR_STATE.  An nsdg_grid_set that changes the shape clears the
+ *   mask, the same shape keeps it.  The mask acts through the coefficient packing: nsdg_mevp_prepare / nsdg_mevp_pack_nodal (and
+ *   nsdg_mevp_subcycle, which packs) mark the land nodes, land taking precedence over the ice-free rule, and every pass that reads that
+ *   packing -- nsdg_mevp_iterate*, nsdg_mevp_velocity, nsdg_rb_mevp_run -- holds them at 0.  The passes read no array and no byte they
+ *   did not read before; a context without a mask runs the same kernels as ever.
+ * nsdg_land_clear: f[c * nx * ny + e] = 0 for c < nplanes at the land elements e of the rows [j0, j1) -- a store, so a NaN is cleared.
+ *   Rows outside the local array, nplanes < 1 or a null f: NSDG_ERR_ARG.  Without a mask it does nothing.  One launch.
+ * nsdg_land_clear_nodes: u = v = 0 at the land nodes of the local array's CG2 lattice.  Without a mask it does nothing.  One launch. */
+int nsdg_land_mask_set(nsdg_ctx* ctx, const uint8_t* land);
+int nsdg_land_clear(nsdg_ctx* ctx, int32_t j0, int32_t j1, int32_t nplanes, double* f);
+int nsdg_land_clear_nodes(nsdg_ctx* ctx, double* u, double* v);
 
 /* ---- row-block decomposition: ghost-row exchange (SURVEY.md section 8(b) "nsdg_halo_exchange", 8(e)) ----------
  * The reference is a single-process, single-thread program; these entry points have no

@@ -116,6 +116,9 @@ SYMBOLS = {
     "nsdg_substep_count": (C.c_int, [C.POINTER(MevpParams), D, D, D, D, I32, C.POINTER(I32), C.POINTER(D)]),
     "nsdg_tiled_len": (C.c_int64, [I32, I32, I32]),
     "nsdg_grid_set": (C.c_int, [VP, I32, I32, D, D]),
+    "nsdg_land_mask_set": (C.c_int, [VP, VP]),
+    "nsdg_land_clear": (C.c_int, [VP, I32, I32, I32, VP]),
+    "nsdg_land_clear_nodes": (C.c_int, [VP, VP, VP]),
     "nsdg_mevp_variant_set": (C.c_int, [VP, I32]),
     "nsdg_prepare_advection": (C.c_int, [VP, I32] + [VP] * 6),
     "nsdg_transport_variant_set": (C.c_int, [VP, I32, I32]),
@@ -366,6 +369,7 @@ class Context:
         self.h = h
         self.nx = self.ny = 0
         self.mevp_variant = DEFAULT_MEVP_VARIANT  # the library default (four sub-iterations per pass)
+        self.land_mask = None  # the tensor behind nsdg_land_mask_set (set_land_mask keeps it alive)
 
     def _call(self, rc):
         if rc != 0:
@@ -601,7 +605,39 @@ class Context:
 
     def set_grid(self, nx, ny, hx, hy):
         self._call(self.lib.nsdg_grid_set(self.h, nx, ny, float(hx), float(hy)))
+        if (nx, ny) != (self.nx, self.ny):
+            self.land_mask = None  # the library dropped a mask of the old shape
         self.nx, self.ny = nx, ny
+
+    # ---- land mask (include/nsdg.h "land mask"): coastlines as fixed nodes of the sub-cycle
+    def set_land_mask(self, land):
+        """nsdg_land_mask_set: `land` = a contiguous uint8 or bool CUDA tensor [ny, nx] of the local array (1 = land), kept alive by this
+        object while it is set; None clears the mask.  Acts from the next coefficient packing on"""
+        import torch
+
+        if land is not None:
+            if land.dtype not in (torch.uint8, torch.bool) or not land.is_contiguous() or not land.is_cuda:
+                raise NsdgError("expected a contiguous uint8 or bool CUDA tensor")
+            if tuple(land.shape) != (self.ny, self.nx):
+                raise NsdgError("the land mask has shape %s, the local array is [%d, %d]" % (tuple(land.shape), self.ny, self.nx))
+        self._call(self.lib.nsdg_land_mask_set(self.h, _ptr(land)))
+        self.land_mask = land
+
+    def land_clear(self, f, j0=0, j1=None):
+        """nsdg_land_clear: 0 in every coefficient plane of f ([nc, ny, nx] or one plane [ny, nx]) at the land elements of rows [j0, j1)"""
+        _check_f64(f)
+        nplanes = f.shape[0] if f.dim() == 3 else 1
+        if f.numel() != nplanes * self.nx * self.ny:
+            raise NsdgError("land_clear: %d values, the planes of the grid need %d" % (f.numel(), nplanes * self.nx * self.ny))
+        self._call(self.lib.nsdg_land_clear(self.h, j0, self.ny if j1 is None else j1, nplanes, _ptr(f)))
+
+    def land_clear_nodes(self, u, v):
+        """nsdg_land_clear_nodes: u = v = 0 at the land nodes of the CG2 lattice"""
+        _check_f64(u, v)
+        n = (2 * self.nx + 1) * (2 * self.ny + 1)
+        if u.numel() != n or v.numel() != n:
+            raise NsdgError("land_clear_nodes: the nodal arrays of the grid hold %d values" % n)
+        self._call(self.lib.nsdg_land_clear_nodes(self.h, _ptr(u), _ptr(v)))
 
     def set_mevp_variant(self, variant):
         self._call(self.lib.nsdg_mevp_variant_set(self.h, variant))

@@ -59,7 +59,9 @@ __device__ __forceinline__ void load_stress(const double* __restrict__ S11, cons
     tile_load8(S22, ts, s22);
 }
 
-__global__ __launch_bounds__(256) void mevp_velocity_kernel(NodalConsts K, int nx, int ny, int j0, int j1, double hx, double hy,
+// the velocity kernel's body; LAND: the instantiation that holds land nodes at 0 (mevp_common.h: node_update_packed)
+template <bool LAND>
+__device__ __forceinline__ void mevp_velocity_body(NodalConsts K, int nx, int ny, int j0, int j1, double hx, double hy,
     const double* __restrict__ S11, const double* __restrict__ S12, const double* __restrict__ S22,
     const double* __restrict__ u_old, const double* __restrict__ v_old, const double* __restrict__ packed,
     double* __restrict__ u_new, double* __restrict__ v_new)
@@ -110,24 +112,24 @@ __global__ __launch_bounds__(256) void mevp_velocity_kernel(NodalConsts K, int n
     // inverse lumped masses: 4, 2, 2, 1 adjacent elements times LUMP = 1/36, 1/9, 1/9, 4/9 of the cell area
     if (hasL && hasB) { // vertex
         load_nodal(packed, nplane, nV, c);
-        node_update_packed(K, c, u_old[nV], v_old[nV], vx_, vy_, 9. * iarea, un, vn);
+        node_update_packed<LAND>(K, c, u_old[nV], v_old[nV], vx_, vy_, 9. * iarea, un, vn);
     } else
         un = vn = 0.;
     u_new[nV] = un, v_new[nV] = vn;
     if (hasB) { // bottom edge-mid
         load_nodal(packed, nplane, nV + 1, c);
-        node_update_packed(K, c, u_old[nV + 1], v_old[nV + 1], exx, exy, 4.5 * iarea, un, vn);
+        node_update_packed<LAND>(K, c, u_old[nV + 1], v_old[nV + 1], exx, exy, 4.5 * iarea, un, vn);
     } else
         un = vn = 0.;
     u_new[nV + 1] = un, v_new[nV + 1] = vn;
     if (hasL) { // left edge-mid
         load_nodal(packed, nplane, nV + nn, c);
-        node_update_packed(K, c, u_old[nV + nn], v_old[nV + nn], eyx, eyy, 4.5 * iarea, un, vn);
+        node_update_packed<LAND>(K, c, u_old[nV + nn], v_old[nV + nn], eyx, eyy, 4.5 * iarea, un, vn);
     } else
         un = vn = 0.;
     u_new[nV + nn] = un, v_new[nV + nn] = vn;
     load_nodal(packed, nplane, nV + nn + 1, c); // centre
-    node_update_packed(K, c, u_old[nV + nn + 1], v_old[nV + nn + 1], ccx, ccy, 2.25 * iarea, un, vn);
+    node_update_packed<LAND>(K, c, u_old[nV + nn + 1], v_old[nV + nn + 1], ccx, ccy, 2.25 * iarea, un, vn);
     u_new[nV + nn + 1] = un, v_new[nV + nn + 1] = vn;
     // right column / top row of the local lattice are boundary nodes (v = 0)
     if (ix == nx - 1) {
@@ -140,6 +142,23 @@ __global__ __launch_bounds__(256) void mevp_velocity_kernel(NodalConsts K, int n
         if (ix == nx - 1)
             u_new[nV + 2 * nn + 2] = 0., v_new[nV + 2 * nn + 2] = 0.;
     }
+}
+
+__global__ __launch_bounds__(256) void mevp_velocity_kernel(NodalConsts K, int nx, int ny, int j0, int j1, double hx, double hy,
+    const double* __restrict__ S11, const double* __restrict__ S12, const double* __restrict__ S22,
+    const double* __restrict__ u_old, const double* __restrict__ v_old, const double* __restrict__ packed,
+    double* __restrict__ u_new, double* __restrict__ v_new)
+{
+    mevp_velocity_body<false>(K, nx, ny, j0, j1, hx, hy, S11, S12, S22, u_old, v_old, packed, u_new, v_new);
+}
+
+// the same after a packing that saw a land mask
+__global__ __launch_bounds__(256) void mevp_velocity_land_kernel(NodalConsts K, int nx, int ny, int j0, int j1, double hx, double hy,
+    const double* __restrict__ S11, const double* __restrict__ S12, const double* __restrict__ S22,
+    const double* __restrict__ u_old, const double* __restrict__ v_old, const double* __restrict__ packed,
+    double* __restrict__ u_new, double* __restrict__ v_new)
+{
+    mevp_velocity_body<true>(K, nx, ny, j0, j1, hx, hy, S11, S12, S22, u_old, v_old, packed, u_new, v_new);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -180,8 +199,16 @@ __device__ __forceinline__ double node_average(int nx, int ny, int nc, const dou
 
 // per-step momentum coefficients of one node, 6 doubles (layout: mevp_common.h)
 __device__ __forceinline__ void pack_node(const nsdg_mevp_params& P, double dt, double u0, double v0, double tax, double tay,
-    double uoc, double voc, double cgh, double cga, double* __restrict__ packed, long plane, long n)
+    double uoc, double voc, double cgh, double cga, double* __restrict__ packed, long plane, long n, bool land = false)
 {
+    // Land node (csrc/landmask.hip; before the ice-free rule): the flag cd = c[1] < 0 -- every real node has cd >= 0, and a signed zero
+    // cannot serve under -fno-signed-zeros -- beside fixed finite constants that depend neither on the forcing nor on H and A there
+    // (h' = h_min: the adaptive form divides by the centre node's h').  The LAND kernels hold such a node at u = v = 0.
+    if (land) {
+        const double c[6] = { P.h_min, -1., 0., 0., 0., 0. };
+        store_nodal(packed, plane, n, c);
+        return;
+    }
     const double h = fmax(cgh, P.h_min);
     // Ice-free-node rule (round 5; the shape of the column model's cut-off  c_new < minc || hi < minh,
     // physics/src/modules/NextsimPhysics.cpp:210-219): a node whose mean concentration is below min_conc, whose TRUE thickness
@@ -206,15 +233,22 @@ __device__ __forceinline__ void wind_tau(double f_atm, double ua, double va, dou
     tay = f_atm * m * va;
 }
 
+// LAND: with the element land mask of the local array (nx x ny elements), land nodes are packed with the flag
+template <bool LAND>
 __global__ __launch_bounds__(256) void mevp_pack_nodal_kernel(nsdg_mevp_params P, long nnodes, double dt,
     const double* __restrict__ u0, const double* __restrict__ v0, const double* __restrict__ tax,
     const double* __restrict__ tay, const double* __restrict__ uo, const double* __restrict__ vo,
-    const double* __restrict__ cgh, const double* __restrict__ cga, double* __restrict__ packed)
+    const double* __restrict__ cgh, const double* __restrict__ cga, double* __restrict__ packed, int nx, int ny, const uint8_t* __restrict__ land)
 {
     const long n = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= nnodes)
         return;
-    pack_node(P, dt, u0[n], v0[n], tax[n], tay[n], uo[n], vo[n], cgh[n], cga[n], packed, nodal_plane(nnodes), n);
+    bool is_land = false;
+    if constexpr (LAND) {
+        const int nn = 2 * nx + 1;
+        is_land = land_node(land, nx, ny, (int)(n % nn), (int)(n / nn));
+    }
+    pack_node(P, dt, u0[n], v0[n], tax[n], tay[n], uo[n], vo[n], cgh[n], cga[n], packed, nodal_plane(nnodes), n, is_land);
 }
 
 // node_average() on a tile of DG coefficients staged in LDS: tile[c][iy - ey0][ix - ex0]; same loops, same order of
@@ -245,12 +279,15 @@ __device__ __forceinline__ double node_average_tile(int nx, int ny, const double
 // handles 64 x 4 nodes; the DG coefficients of the 33 x 3 elements under them are staged in LDS once (9.5 KB)
 // instead of being gathered by every node lane from memory (a vertex node reads 4 elements x 6 coefficients x 2
 // fields: the gather form issued ~57 loads per lane and was bound by vector-memory issue, 0.67 ms at 2048^2).
+// LAND: the mask bytes of the same 33 x 3 elements are staged beside the tile and land nodes are packed with the flag.
+template <bool LAND>
 __global__ __launch_bounds__(256) void mevp_prepare_kernel(nsdg_mevp_params P, int nx, int ny, double dt,
     const double* __restrict__ H, const double* __restrict__ A, const double* __restrict__ ua, const double* __restrict__ va,
     const double* __restrict__ uo, const double* __restrict__ vo, const double* __restrict__ u0, const double* __restrict__ v0,
-    double* __restrict__ packed)
+    double* __restrict__ packed, const uint8_t* __restrict__ land)
 {
     __shared__ double tile[2][6][PREP_TH][PREP_TW];
+    __shared__ uint8_t ltile[LAND ? PREP_TH : 1][PREP_TW];
     const int gx0 = blockIdx.x * 64, gy0 = blockIdx.y * 4;
     const int ex0 = gx0 / 2 - 1, ey0 = gy0 / 2 - 1;
     const long N = (long)nx * ny;
@@ -263,6 +300,13 @@ __global__ __launch_bounds__(256) void mevp_prepare_kernel(nsdg_mevp_params P, i
             val = (fld == 0 ? H : A)[c * N + (long)iy * nx + ix];
         tile[fld][c][r][col] = val;
     }
+    if constexpr (LAND) {
+        if (tid < PREP_TH * PREP_TW) {
+            const int col = tid % PREP_TW, r = tid / PREP_TW;
+            const int ix = ex0 + col, iy = ey0 + r;
+            ltile[r][col] = (ix >= 0 && ix < nx && iy >= 0 && iy < ny) ? land[(long)iy * nx + ix] : 0;
+        }
+    }
     __syncthreads();
     const int gx = gx0 + threadIdx.x;
     const int gy = gy0 + threadIdx.y;
@@ -273,7 +317,10 @@ __global__ __launch_bounds__(256) void mevp_prepare_kernel(nsdg_mevp_params P, i
     const double cgh = node_average_tile(nx, ny, tile[0], ex0, ey0, gx, gy), cga = node_average_tile(nx, ny, tile[1], ex0, ey0, gx, gy);
     double tax, tay;
     wind_tau(P.c_atm * P.rho_atm, ua[n], va[n], tax, tay);
-    pack_node(P, dt, u0[n], v0[n], tax, tay, uo[n], vo[n], cgh, cga, packed, nodal_plane((long)nn * nm), n);
+    bool is_land = false;
+    if constexpr (LAND)
+        is_land = land_node_of(nx, ny, gx, gy, [&](int ix, int iy) { return ltile[iy - ey0][ix - ex0]; });
+    pack_node(P, dt, u0[n], v0[n], tax, tay, uo[n], vo[n], cgh, cga, packed, nodal_plane((long)nn * nm), n, is_land);
 }
 
 // one lane per CG2 node
@@ -433,10 +480,15 @@ int nsdg_mevp_pack_nodal(nsdg_ctx* ctx, double dt, const double* u0, const doubl
     NSDG_CHECK_ARG(((uintptr_t)packed & 15) == 0, "packed must be 16-byte aligned");
     NSDG_CHECK_HIP(hipSetDevice(ctx->device));
     const long nnodes = (long)(2 * ctx->nx + 1) * (2 * ctx->ny + 1);
-    hipLaunchKernelGGL(mevp_pack_nodal_kernel, dim3(nsdg_div_up(nnodes, 256)), dim3(256), 0, ctx->stream, ctx->mevp, nnodes, dt, u0,
-        v0, tax, tay, uo, vo, cgh, cga, packed);
+    if (ctx->land)
+        hipLaunchKernelGGL(mevp_pack_nodal_kernel<true>, dim3(nsdg_div_up(nnodes, 256)), dim3(256), 0, ctx->stream, ctx->mevp, nnodes, dt, u0,
+            v0, tax, tay, uo, vo, cgh, cga, packed, ctx->nx, ctx->ny, ctx->land);
+    else
+        hipLaunchKernelGGL(mevp_pack_nodal_kernel<false>, dim3(nsdg_div_up(nnodes, 256)), dim3(256), 0, ctx->stream, ctx->mevp, nnodes, dt, u0,
+            v0, tax, tay, uo, vo, cgh, cga, packed, ctx->nx, ctx->ny, ctx->land);
     NSDG_CHECK_LAUNCH();
     ctx->pack_dt = dt; // the launch constants K1, K2 of the velocity update belong to this packing
+    ctx->pack_land = ctx->land != nullptr; // and so does the choice of the passes' instantiation: this packing flagged land nodes, or not
     return NSDG_OK;
 }
 
@@ -449,10 +501,15 @@ int nsdg_mevp_prepare(nsdg_ctx* ctx, double dt, const double* H, const double* A
     NSDG_CHECK_ARG(((uintptr_t)packed & 15) == 0, "packed must be 16-byte aligned");
     NSDG_CHECK_HIP(hipSetDevice(ctx->device));
     const dim3 block(64, 4), grid(nsdg_div_up(2 * ctx->nx + 1, 64), nsdg_div_up(2 * ctx->ny + 1, 4));
-    hipLaunchKernelGGL(mevp_prepare_kernel, grid, block, 0, ctx->stream, ctx->mevp, ctx->nx, ctx->ny, dt, H, A, ua, va, uo, vo, u0, v0,
-        packed);
+    if (ctx->land)
+        hipLaunchKernelGGL(mevp_prepare_kernel<true>, grid, block, 0, ctx->stream, ctx->mevp, ctx->nx, ctx->ny, dt, H, A, ua, va, uo, vo, u0, v0,
+            packed, ctx->land);
+    else
+        hipLaunchKernelGGL(mevp_prepare_kernel<false>, grid, block, 0, ctx->stream, ctx->mevp, ctx->nx, ctx->ny, dt, H, A, ua, va, uo, vo, u0, v0,
+            packed, ctx->land);
     NSDG_CHECK_LAUNCH();
     ctx->pack_dt = dt;
+    ctx->pack_land = ctx->land != nullptr;
     return NSDG_OK;
 }
 
@@ -473,8 +530,8 @@ int nsdg_mevp_velocity(nsdg_ctx* ctx, int32_t j0, int32_t j1, const double* s11,
         nsdg_set_error("nsdg_mevp_velocity: nsdg_mevp_pack_nodal was not called on this context");
         return NSDG_ERR_STATE;
     }
-    hipLaunchKernelGGL(mevp_velocity_kernel, grid, block, 0, ctx->stream, nodal_consts(ctx), ctx->nx, ctx->ny, j0, j1, ctx->hx, ctx->hy, s11, s12, s22,
-        u_old, v_old, packed, u_new, v_new);
+    hipLaunchKernelGGL(ctx->pack_land ? mevp_velocity_land_kernel : mevp_velocity_kernel, grid, block, 0, ctx->stream, nodal_consts(ctx), ctx->nx, ctx->ny, j0, j1,
+        ctx->hx, ctx->hy, s11, s12, s22, u_old, v_old, packed, u_new, v_new);
     NSDG_CHECK_LAUNCH();
     return NSDG_OK;
 }
@@ -533,10 +590,13 @@ int nsdg_mevp_pass(nsdg_ctx* ctx, int v, int k0, int j0, int j1, bool pair, int 
         nsdg_set_error("%s: hipSetDevice(ctx->device) failed: %s", fn, hipGetErrorString(e));
         return NSDG_ERR_HIP;
     }
+    // masked or not: the instantiation goes with the packing the pass reads (nsdg_mevp_pack_nodal / nsdg_mevp_prepare remembered whether
+    // they flagged land nodes); the two-kernel form's velocity kernel (nsdg_mevp_velocity) reads the same flag
+    const bool land = ctx->pack_land;
     if (v >= 2) // a pass of the stage-per-wave pipeline with v stages
-        return nsdg_launch_mevp_fused4_ranges(ctx, v, j0, j1, j0b, j1b, b);
+        return nsdg_launch_mevp_fused4_ranges(ctx, land, v, j0, j1, j0b, j1b, b);
     if (ctx->mevp_variant >= 1 || nsdg_adaptive(ctx)) // variants 2-4 use the single-iteration fused kernel for one sub-iteration; so does variant 0 in the adaptive form
-        return nsdg_launch_mevp_fused(ctx, k0, j0, j1, b);
+        return nsdg_launch_mevp_fused(ctx, land, k0, j0, j1, b);
     const int rc = launch_stress(ctx, k0, j1, b.u_old, b.v_old, b.pg, b.s11i, b.s12i, b.s22i, b.s11, b.s12, b.s22);
     return rc ? rc : nsdg_mevp_velocity(ctx, j0, j1, b.s11, b.s12, b.s22, b.u_old, b.v_old, b.u_new, b.v_new, b.packed);
 }

@@ -583,6 +583,9 @@ struct NodalConsts {
     double rdt; // rho_ice / dt (the adaptive form: K1 = rdt beta_n, K2 = rdt (1 + beta_n) per node)
 };
 
+// LAND (the kernels launched when the packing saw a land mask, csrc/landmask.hip): a land node is packed with cd = c[1] < 0 -- every
+// real node has cd >= 0 -- and holds u = v = 0 like a node on the array edge.  LAND = false is the code without the test.
+template <bool LAND = false>
 __device__ __forceinline__ void node_update_packed(const NodalConsts& K, const double (&c)[6], double uu, double vv, double divx,
     double divy, double ilumped, double& un, double& vn)
 {
@@ -592,10 +595,15 @@ __device__ __forceinline__ void node_update_packed(const NodalConsts& K, const d
     const double c1 = K.k1 * c[0], cor = K.k3 * c[0];
     un = denom * (c1 * uu + c[2] + drag * c[4] + cor * vv + divx * ilumped);
     vn = denom * (c1 * vv + c[3] + drag * c[5] - cor * uu + divy * ilumped);
+    if constexpr (LAND) {
+        if (c[1] < 0.)
+            un = vn = 0.;
+    }
 }
 
 // the same with the node's own beta (adaptive form): qmax = the largest offer alpha_e h'_c of the adjacent elements, beta_n h'_n = max(alpha_min
 // h'_n, qmax) -- at an ice-free node c[0] is h'_n scaled by 2^100 and the first argument wins: beta_n = alpha_min
+template <bool LAND = false>
 __device__ __forceinline__ void node_update_packed_adaptive(const NodalConsts& K, const double (&c)[6], double uu, double vv, double divx,
     double divy, double ilumped, double qmax, double amin, double& un, double& vn)
 {
@@ -606,6 +614,28 @@ __device__ __forceinline__ void node_update_packed_adaptive(const NodalConsts& K
     const double c1 = K.rdt * bh, cor = K.k3 * c[0];
     un = denom * (c1 * uu + c[2] + drag * c[4] + cor * vv + divx * ilumped);
     vn = denom * (c1 * vv + c[3] + drag * c[5] - cor * uu + divy * ilumped);
+    if constexpr (LAND) {
+        if (c[1] < 0.)
+            un = vn = 0.;
+    }
+}
+
+// Land mask (include/nsdg.h "land mask"): a CG2 node (gx, gy) is a land node if any of the 1 / 2 / 4 elements adjacent to it inside
+// the local array is land.  `at(ix, iy)` reads the mask byte of an element inside the array.
+template <class At>
+__device__ __forceinline__ bool land_node_of(int nx, int ny, int gx, int gy, At at)
+{
+    const int ix_hi = min(gx >> 1, nx - 1), ix_lo = max((gx & 1) ? gx >> 1 : (gx >> 1) - 1, 0);
+    const int iy_hi = min(gy >> 1, ny - 1), iy_lo = max((gy & 1) ? gy >> 1 : (gy >> 1) - 1, 0);
+    bool land = false;
+    for (int iy = iy_lo; iy <= iy_hi; ++iy)
+        for (int ix = ix_lo; ix <= ix_hi; ++ix)
+            land = land || at(ix, iy) != 0;
+    return land;
+}
+__device__ __forceinline__ bool land_node(const uint8_t* __restrict__ land, int nx, int ny, int gx, int gy)
+{
+    return land_node_of(nx, ny, gx, gy, [&](int ix, int iy) { return land[(long)iy * nx + ix]; });
 }
 
 // launch constants of the velocity update / of the adaptive alpha from the context's parameters and the packing's time step

@@ -38,7 +38,8 @@ __device__ __forceinline__ double shift_up(double x)
     return lane_from_left(x);
 }
 
-template <int MINW, bool AD>
+// LAND: the instantiation that holds land nodes at 0 (mevp_common.h: node_update_packed), launched after a packing that saw a land mask
+template <int MINW, bool AD, bool LAND>
 __global__ __launch_bounds__(256, MINW) void mevp_fused_kernel(NodalConsts K, AdaptConsts AC, int nx, int ny, int k0, int j0, int j1, int R, int ncw, double hx,
     double hy, double ialpha, double dmin2, StressPtrs S, const double* __restrict__ u_old, const double* __restrict__ v_old,
     const double* __restrict__ packed, const double* __restrict__ pg, double* __restrict__ u_new, double* __restrict__ v_new)
@@ -124,10 +125,10 @@ __global__ __launch_bounds__(256, MINW) void mevp_fused_kernel(NodalConsts K, Ad
             if (hasL && hasB) {
                 load_nodal(packed, nplane, nV, c);
                 if constexpr (AD)
-                    node_update_packed_adaptive(K, c, ul[0], vl[0], ((bl8x + b6x) + l2x) + cx[0], ((bl8y + b6y) + l2y) + cy[0], 9. * iarea,
+                    node_update_packed_adaptive<LAND>(K, c, ul[0], vl[0], ((bl8x + b6x) + l2x) + cx[0], ((bl8y + b6y) + l2y) + cy[0], 9. * iarea,
                         __builtin_fmax(__builtin_fmax(qbl, qb), __builtin_fmax(ql, qe)), AC.amin, un, vn);
                 else
-                    node_update_packed(K, c, ul[0], vl[0], ((bl8x + b6x) + l2x) + cx[0], ((bl8y + b6y) + l2y) + cy[0], 9. * iarea, un, vn);
+                    node_update_packed<LAND>(K, c, ul[0], vl[0], ((bl8x + b6x) + l2x) + cx[0], ((bl8y + b6y) + l2y) + cy[0], 9. * iarea, un, vn);
             } else
                 un = vn = 0.;
             if (own)
@@ -136,9 +137,9 @@ __global__ __launch_bounds__(256, MINW) void mevp_fused_kernel(NodalConsts K, Ad
             if (hasB) {
                 load_nodal(packed, nplane, nV + 1, c);
                 if constexpr (AD)
-                    node_update_packed_adaptive(K, c, ul[1], vl[1], b7x + cx[1], b7y + cy[1], 4.5 * iarea, __builtin_fmax(qb, qe), AC.amin, un, vn);
+                    node_update_packed_adaptive<LAND>(K, c, ul[1], vl[1], b7x + cx[1], b7y + cy[1], 4.5 * iarea, __builtin_fmax(qb, qe), AC.amin, un, vn);
                 else
-                    node_update_packed(K, c, ul[1], vl[1], b7x + cx[1], b7y + cy[1], 4.5 * iarea, un, vn);
+                    node_update_packed<LAND>(K, c, ul[1], vl[1], b7x + cx[1], b7y + cy[1], 4.5 * iarea, un, vn);
             } else
                 un = vn = 0.;
             if (own)
@@ -147,9 +148,9 @@ __global__ __launch_bounds__(256, MINW) void mevp_fused_kernel(NodalConsts K, Ad
             if (hasL) {
                 load_nodal(packed, nplane, nV + nn, c);
                 if constexpr (AD)
-                    node_update_packed_adaptive(K, c, ul[3], vl[3], l5x + cx[3], l5y + cy[3], 4.5 * iarea, __builtin_fmax(ql, qe), AC.amin, un, vn);
+                    node_update_packed_adaptive<LAND>(K, c, ul[3], vl[3], l5x + cx[3], l5y + cy[3], 4.5 * iarea, __builtin_fmax(ql, qe), AC.amin, un, vn);
                 else
-                    node_update_packed(K, c, ul[3], vl[3], l5x + cx[3], l5y + cy[3], 4.5 * iarea, un, vn);
+                    node_update_packed<LAND>(K, c, ul[3], vl[3], l5x + cx[3], l5y + cy[3], 4.5 * iarea, un, vn);
             } else
                 un = vn = 0.;
             if (own)
@@ -157,9 +158,9 @@ __global__ __launch_bounds__(256, MINW) void mevp_fused_kernel(NodalConsts K, Ad
             // centre: own
             load_nodal(packed, nplane, nV + nn + 1, c);
             if constexpr (AD)
-                node_update_packed_adaptive(K, c, ul[4], vl[4], cx[4], cy[4], 2.25 * iarea, qe, AC.amin, un, vn);
+                node_update_packed_adaptive<LAND>(K, c, ul[4], vl[4], cx[4], cy[4], 2.25 * iarea, qe, AC.amin, un, vn);
             else
-                node_update_packed(K, c, ul[4], vl[4], cx[4], cy[4], 2.25 * iarea, un, vn);
+                node_update_packed<LAND>(K, c, ul[4], vl[4], cx[4], cy[4], 2.25 * iarea, un, vn);
             if (own) {
                 u_new[nV + nn + 1] = un, v_new[nV + nn + 1] = vn;
                 // right column / top row of the local lattice are boundary nodes (v = 0)
@@ -187,7 +188,7 @@ __global__ __launch_bounds__(256, MINW) void mevp_fused_kernel(NodalConsts K, Ad
 
 using namespace nsdg_mevp_detail;
 
-int nsdg_launch_mevp_fused(nsdg_ctx* ctx, int k0, int j0, int j1, const nsdg_mevp_bufs& b)
+int nsdg_launch_mevp_fused(nsdg_ctx* ctx, bool land, int k0, int j0, int j1, const nsdg_mevp_bufs& b)
 {
     const int ncw = nsdg_div_up(ctx->nx, 63); // 63 owned columns per wave
     int R = ctx->strip_rows;
@@ -220,15 +221,16 @@ int nsdg_launch_mevp_fused(nsdg_ctx* ctx, int k0, int j0, int j1, const nsdg_mev
     const dim3 grid(nsdg_div_up(nwaves, 4)), block(256);
     // two register budgets of the same kernel: 1 wave/SIMD (no spills) or 2 waves/SIMD (a few scratch spills); the adaptive form (local
     // alpha, beta: mevp_common.h) runs at 1 wave/SIMD
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, K, AC, ctx->nx, ctx->ny, k0, j0, j1, R, ncw, ctx->hx, ctx->hy, ialpha, dmin2, S, b.u_old, b.v_old,
+            b.packed, b.pg, b.u_new, b.v_new);
+    };
     if (nsdg_adaptive(ctx))
-        hipLaunchKernelGGL((mevp_fused_kernel<1, true>), grid, block, 0, ctx->stream, K, AC, ctx->nx, ctx->ny, k0, j0, j1, R, ncw, ctx->hx, ctx->hy, ialpha, dmin2, S,
-            b.u_old, b.v_old, b.packed, b.pg, b.u_new, b.v_new);
+        land ? launch(mevp_fused_kernel<1, true, true>) : launch(mevp_fused_kernel<1, true, false>);
     else if (ctx->fused_min_waves >= 2)
-        hipLaunchKernelGGL((mevp_fused_kernel<2, false>), grid, block, 0, ctx->stream, K, AC, ctx->nx, ctx->ny, k0, j0, j1, R, ncw, ctx->hx, ctx->hy, ialpha, dmin2, S,
-            b.u_old, b.v_old, b.packed, b.pg, b.u_new, b.v_new);
+        land ? launch(mevp_fused_kernel<2, false, true>) : launch(mevp_fused_kernel<2, false, false>);
     else
-        hipLaunchKernelGGL((mevp_fused_kernel<1, false>), grid, block, 0, ctx->stream, K, AC, ctx->nx, ctx->ny, k0, j0, j1, R, ncw, ctx->hx, ctx->hy, ialpha, dmin2, S,
-            b.u_old, b.v_old, b.packed, b.pg, b.u_new, b.v_new);
+        land ? launch(mevp_fused_kernel<1, false, true>) : launch(mevp_fused_kernel<1, false, false>);
     NSDG_CHECK_LAUNCH();
     return NSDG_OK;
 }

@@ -121,7 +121,7 @@ __device__ __forceinline__ void request_c2_p(const MarchConst3& M, int nrow, dou
     load_nodal2(packed, M.nplane, nVn + M.nn + 1, c[3]);
 }
 // One row of one stage.  FIRST: the loader (stage 0): inputs from memory, ice strength into the ring.
-template <bool FIRST, bool AD>
+template <bool FIRST, bool AD, bool LAND>
 __device__ __forceinline__ void p2p_row(const MarchConst3& M, const StageP& G, int row, FetchP& f, TopCarry3& carry, double* __restrict__ lds,
     volatile lds_int* flags, const P2PReport& rep, const StressPtrsP& S, const double* __restrict__ u_old, const double* __restrict__ v_old,
     const double* __restrict__ packed, const double* __restrict__ pg, double* __restrict__ u_new, double* __restrict__ v_new NSDG_SPIN_ARG)
@@ -228,7 +228,7 @@ __device__ __forceinline__ void p2p_row(const MarchConst3& M, const StageP& G, i
     {
         double cx[9], cy[9];
         node_contrib_all(s11, s12, s22, M.hx, M.hy, cx, cy);
-        owned_node_updates<AD>(M, row > 0, f.c, uu, vv, carry, cx, cy, un, vn, qe);
+        owned_node_updates<AD, LAND>(M, row > 0, f.c, uu, vv, carry, cx, cy, un, vn, qe);
         if (row < G.upd0) { // wave-uniform: the first row of a stage only feeds the carried contributions
 #pragma unroll
             for (int k = 0; k < 4; ++k)
@@ -280,7 +280,8 @@ __device__ __forceinline__ void p2p_row(const MarchConst3& M, const StageP& G, i
     NSDG_PHASE(6); // outputs: slot wait, LDS writes, done[] published / global stores
 }
 
-template <bool AD>
+// LAND: the instantiation that holds land nodes at 0 (mevp_common.h: node_update_packed), launched after a packing that saw a land mask
+template <bool AD, bool LAND>
 __global__ __launch_bounds__(256) void mevp_fused4_kernel(NodalConsts K, AdaptConsts AC, int nst, int nx, int ny, int j0, int j1, int j0b, int j1b, int nsA, int R, int ncw,
     double hx, double hy, double ialpha, double dmin2, P2PReport rep, StressPtrsP S, const double* __restrict__ u_old, const double* __restrict__ v_old,
     const double* __restrict__ packed, const double* __restrict__ pg, double* __restrict__ u_new, double* __restrict__ v_new)
@@ -362,10 +363,10 @@ __global__ __launch_bounds__(256) void mevp_fused4_kernel(NodalConsts K, AdaptCo
         tile_load9_p<(NSDG_P2P_NT & 4) != 0>(pg, tile_off(M.ix, row, M.ntx, 9), M.ix & 63, f.P);
         request_c_p(M, row, f.c, packed);
         for (int row = G.first; row <= G.last; ++row)
-            p2p_row<true, AD>(M, G, row, f, carry, lds, flags, rep, S, u_old, v_old, packed, pg, u_new, v_new NSDG_SPIN_PASS);
+            p2p_row<true, AD, LAND>(M, G, row, f, carry, lds, flags, rep, S, u_old, v_old, packed, pg, u_new, v_new NSDG_SPIN_PASS);
     } else {
         for (int row = G.first; row <= G.last; ++row)
-            p2p_row<false, AD>(M, G, row, f, carry, lds, flags, rep, S, u_old, v_old, packed, pg, u_new, v_new NSDG_SPIN_PASS);
+            p2p_row<false, AD, LAND>(M, G, row, f, carry, lds, flags, rep, S, u_old, v_old, packed, pg, u_new, v_new NSDG_SPIN_PASS);
     }
 #ifdef NSDG_P2P_SPINSTAT
     if (lane == 0) {
@@ -397,7 +398,7 @@ extern "C" int nsdg_debug_p2p_spinstat(unsigned long long* out48) // [16] polls,
 }
 #endif
 
-int nsdg_launch_mevp_fused4_ranges(nsdg_ctx* ctx, int nst, int j0, int j1, int j0b, int j1b, const nsdg_mevp_bufs& b)
+int nsdg_launch_mevp_fused4_ranges(nsdg_ctx* ctx, bool land, int nst, int j0, int j1, int j0b, int j1b, const nsdg_mevp_bufs& b)
 {
     const int ncw = nsdg_div_up(ctx->nx, P4_OWNED);
     const int rowsB = j0b < j1b ? j1b - j0b : 0;
@@ -427,12 +428,15 @@ int nsdg_launch_mevp_fused4_ranges(nsdg_ctx* ctx, int nst, int j0, int j1, int j
     const NodalConsts K = nsdg_nodal_consts(ctx);
     const AdaptConsts AC = nsdg_adapt_consts(ctx);
     const P2PReport rep = { ctx->p2p_count_dev, ctx->p2p_flag_dev };
-    if (nsdg_adaptive(ctx)) // local, solution-adaptive alpha and beta (mevp_common.h)
-        hipLaunchKernelGGL(mevp_fused4_kernel<true>, dim3(ngroups), dim3(256), 0, ctx->stream, K, AC, nst, ctx->nx, ctx->ny, j0, j1, j0b, j1b, nsA, R, ncw, ctx->hx,
-            ctx->hy, 1. / ctx->mevp.alpha, ctx->mevp.delta_min * ctx->mevp.delta_min, rep, S, b.u_old, b.v_old, b.packed, b.pg, b.u_new, b.v_new);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(ngroups), dim3(256), 0, ctx->stream, K, AC, nst, ctx->nx, ctx->ny, j0, j1, j0b, j1b, nsA, R, ncw, ctx->hx, ctx->hy,
+            1. / ctx->mevp.alpha, ctx->mevp.delta_min * ctx->mevp.delta_min, rep, S, b.u_old, b.v_old, b.packed, b.pg, b.u_new, b.v_new);
+    };
+    // adaptive: local, solution-adaptive alpha and beta (mevp_common.h); land: the packing flagged land nodes (nsdg_mevp_pass)
+    if (!land)
+        nsdg_adaptive(ctx) ? launch(mevp_fused4_kernel<true, false>) : launch(mevp_fused4_kernel<false, false>);
     else
-        hipLaunchKernelGGL(mevp_fused4_kernel<false>, dim3(ngroups), dim3(256), 0, ctx->stream, K, AC, nst, ctx->nx, ctx->ny, j0, j1, j0b, j1b, nsA, R, ncw, ctx->hx,
-            ctx->hy, 1. / ctx->mevp.alpha, ctx->mevp.delta_min * ctx->mevp.delta_min, rep, S, b.u_old, b.v_old, b.packed, b.pg, b.u_new, b.v_new);
+        nsdg_adaptive(ctx) ? launch(mevp_fused4_kernel<true, true>) : launch(mevp_fused4_kernel<false, true>);
     NSDG_CHECK_LAUNCH();
     return NSDG_OK;
 }

@@ -26,7 +26,8 @@ struct TopCarry3 {
 // the four owned nodes of one element row from the carried contributions of the row below (`carry`), the
 // contributions of this row (cx, cy) and the left neighbour's right-column contributions
 // (AD: adaptive form -- `q` is this element's offer q_e = alpha_e h'_c of this sub-iteration, a node takes the largest offer of its adjacent elements)
-template <bool AD = false>
+// (LAND: land nodes stay at 0, node_update_packed)
+template <bool AD = false, bool LAND = false>
 __device__ __forceinline__ void owned_node_updates(const MarchConst3& M, bool hasB, const double (&c)[4][6], const double (&uu)[4],
     const double (&vv)[4], const TopCarry3& carry, const double (&cx)[9], const double (&cy)[9], double (&un)[4], double (&vn)[4], double q = 0.)
 {
@@ -36,35 +37,35 @@ __device__ __forceinline__ void owned_node_updates(const MarchConst3& M, bool ha
         const double ql = lane_from_left(q); // the left neighbour's (0 without one: it never wins the max)
         const double qmid = __builtin_fmax(ql, q), qbot = __builtin_fmax(carry.q, q);
         if (M.hasL && hasB)
-            node_update_packed_adaptive(M.K, c[0], uu[0], vv[0], ((carry.xl8 + carry.x6) + l2x) + cx[0], ((carry.yl8 + carry.y6) + l2y) + cy[0], 9. * M.iarea,
+            node_update_packed_adaptive<LAND>(M.K, c[0], uu[0], vv[0], ((carry.xl8 + carry.x6) + l2x) + cx[0], ((carry.yl8 + carry.y6) + l2y) + cy[0], 9. * M.iarea,
                 __builtin_fmax(__builtin_fmax(carry.ql, carry.q), qmid), M.AC.amin, un[0], vn[0]);
         else
             un[0] = vn[0] = 0.;
         if (hasB)
-            node_update_packed_adaptive(M.K, c[1], uu[1], vv[1], carry.x7 + cx[1], carry.y7 + cy[1], 4.5 * M.iarea, qbot, M.AC.amin, un[1], vn[1]);
+            node_update_packed_adaptive<LAND>(M.K, c[1], uu[1], vv[1], carry.x7 + cx[1], carry.y7 + cy[1], 4.5 * M.iarea, qbot, M.AC.amin, un[1], vn[1]);
         else
             un[1] = vn[1] = 0.;
         if (M.hasL)
-            node_update_packed_adaptive(M.K, c[2], uu[2], vv[2], l5x + cx[3], l5y + cy[3], 4.5 * M.iarea, qmid, M.AC.amin, un[2], vn[2]);
+            node_update_packed_adaptive<LAND>(M.K, c[2], uu[2], vv[2], l5x + cx[3], l5y + cy[3], 4.5 * M.iarea, qmid, M.AC.amin, un[2], vn[2]);
         else
             un[2] = vn[2] = 0.;
-        node_update_packed_adaptive(M.K, c[3], uu[3], vv[3], cx[4], cy[4], 2.25 * M.iarea, q, M.AC.amin, un[3], vn[3]);
+        node_update_packed_adaptive<LAND>(M.K, c[3], uu[3], vv[3], cx[4], cy[4], 2.25 * M.iarea, q, M.AC.amin, un[3], vn[3]);
         return;
     }
     if (M.hasL && hasB)
-        node_update_packed(M.K, c[0], uu[0], vv[0], ((carry.xl8 + carry.x6) + l2x) + cx[0], ((carry.yl8 + carry.y6) + l2y) + cy[0], 9. * M.iarea,
+        node_update_packed<LAND>(M.K, c[0], uu[0], vv[0], ((carry.xl8 + carry.x6) + l2x) + cx[0], ((carry.yl8 + carry.y6) + l2y) + cy[0], 9. * M.iarea,
             un[0], vn[0]);
     else
         un[0] = vn[0] = 0.;
     if (hasB)
-        node_update_packed(M.K, c[1], uu[1], vv[1], carry.x7 + cx[1], carry.y7 + cy[1], 4.5 * M.iarea, un[1], vn[1]);
+        node_update_packed<LAND>(M.K, c[1], uu[1], vv[1], carry.x7 + cx[1], carry.y7 + cy[1], 4.5 * M.iarea, un[1], vn[1]);
     else
         un[1] = vn[1] = 0.;
     if (M.hasL)
-        node_update_packed(M.K, c[2], uu[2], vv[2], l5x + cx[3], l5y + cy[3], 4.5 * M.iarea, un[2], vn[2]);
+        node_update_packed<LAND>(M.K, c[2], uu[2], vv[2], l5x + cx[3], l5y + cy[3], 4.5 * M.iarea, un[2], vn[2]);
     else
         un[2] = vn[2] = 0.;
-    node_update_packed(M.K, c[3], uu[3], vv[3], cx[4], cy[4], 2.25 * M.iarea, un[3], vn[3]);
+    node_update_packed<LAND>(M.K, c[3], uu[3], vv[3], cx[4], cy[4], 2.25 * M.iarea, un[3], vn[3]);
 }
 
 template <bool AD = false>

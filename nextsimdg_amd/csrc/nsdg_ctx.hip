@@ -153,6 +153,7 @@ int nsdg_ctx_create(int device_id, void* stream, nsdg_ctx** out)
     c->transport_rows = 0;
     c->nbounds = 0;
     c->pack_dt = 0.;
+    c->land = nullptr, c->pack_land = false;
     c->d_ptrs = nullptr;
     c->comm = nullptr;
     c->comm_group = 0;
@@ -293,6 +294,8 @@ int nsdg_grid_set(nsdg_ctx* ctx, int32_t nx, int32_t ny, double hx, double hy)
     NSDG_CHECK_ARG((long)(2 * (long)nx + 1) * (2 * (long)ny + 1) < (1L << 31), "grid too large for 32-bit node indices");
     if (ctx->nx != nx || ctx->ny != ny || ctx->hx != hx || ctx->hy != hy)
         ctx->pack_dt = 0.; // packed nodal coefficients belong to the old grid
+    if (ctx->nx != nx || ctx->ny != ny)
+        ctx->land = nullptr; // and so does the land mask (nsdg_land_mask_set): nx * ny bytes of the old shape
     ctx->nx = nx;
     ctx->ny = ny;
     ctx->hx = hx;

@@ -121,11 +121,11 @@ int make_plan(nsdg_ctx* ctx, const Geometry& g, const SegList& L, nsdg_halo** ou
 
 // ---- hipGraph replay of a fixed launch sequence -------------------------------------------------------------
 // A captured launch bakes in the launch constants the kernels take from the context (K = rho beta / dt, 1/alpha,
-// Delta_min^2, the cell size, the strip height, the kernel variant): the cache remembers the values its graphs were
+// Delta_min^2, the cell size, the strip height, the kernel variant, the masked or unmasked instantiation): the cache remembers the values its graphs were
 // recorded with and is dropped when any of them has changed, so a replay never mixes two parameter sets.
 struct GraphStamp {
     double v[10];
-    int k[6];
+    int k[8];
     bool operator==(const GraphStamp& o) const { return std::memcmp(this, &o, sizeof *this) == 0; }
 };
 
@@ -137,7 +137,8 @@ GraphStamp graph_stamp(const nsdg_ctx* c)
     // aevp_c and aevp_alpha_min: the adaptive form's constants (alpha_min follows dt under NSDG_SUBCYCLE_ADAPTIVE_CONVERGED, so a host that
     // sub-steps changes it between model steps)
     const double v[10] = { c->pack_dt, P.alpha, P.beta, P.rho_ice, P.fc, P.delta_min, c->hx, c->hy, P.aevp_c, P.aevp_alpha_min };
-    const int k[6] = { c->strip_rows, c->mevp_variant, c->fused_min_waves, c->nx, c->ny, c->num_cus };
+    // pack_land: a captured launch is the kernel that was recorded -- a packing with a land mask must not replay the unmasked passes
+    const int k[8] = { c->strip_rows, c->mevp_variant, c->fused_min_waves, c->nx, c->ny, c->num_cus, (int)c->pack_land, 0 };
     std::memcpy(s.v, v, sizeof v);
     std::memcpy(s.k, k, sizeof k);
     return s;

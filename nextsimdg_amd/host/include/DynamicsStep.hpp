@@ -41,6 +41,10 @@
 //                            space, linear in time -- nsdg_forcing_sample; the file's wind_u / wind_v and ocean_u / ocean_v pairs, where
 //                            present, replace the box test's cyclone and gyre; host/include/ForcingFile.hpp has the file layout)
 //     dynamics.forcing_file  the forcing file of forcing = file; read and checked when the step is configured
+//     dynamics.land_mask_file  a .npy array of uint8 or bool, shape (rectgrid.nx, rectgrid.ny) like the structure's planes, 1 = land
+//                            (include/LandMaskFile.hpp; include/nsdg.h "land mask"): the nodes of land elements hold u = v = 0, H, A, the
+//                            snow and the new ice are cleared on land at the start and after every column step; read and checked when the
+//                            step is configured.  The restart file holds no mask: a resumed run names the same file
 //     dynamics.substeps      sub-steps per model step: an integer >= 1 (default 1: the unsplit step, bit for bit) or auto -- n decided at
 //                            the start of every model step from the state's strength wave speed, the same on every block
 //                            (nsdg_concentration_max, nsdg_comm_max_f64, nsdg_substep_count: include/nsdg.h "sub-stepping"); the whole
@@ -68,6 +72,7 @@ struct nsdg_ctx;
 namespace Nextsim {
 
 class ForcingFile;
+class LandMaskFile;
 
 class DynamicsBlock; // one row block: context, device arrays, driver plans (DynamicsStep.cpp)
 
@@ -133,6 +138,7 @@ private:
     double minConc = 1e-12, minThick = 0.01; // ice-free-node rule (dynamics.min_conc / min_thick; the column model's cut-off values)
     std::string forcing = "host", devices;
     std::shared_ptr<const ForcingFile> m_forcingFile; // dynamics.forcing = file: the records, read and checked in configure()
+    std::shared_ptr<const LandMaskFile> m_landMask; // dynamics.land_mask_file: the element mask, read and checked in configure()
     int substeps = 1; // dynamics.substeps; 0 = auto
     double substepCourant = 1.5; // dynamics.substep_courant (NSDG_SUBSTEP_COURANT)
     int maxSubsteps = 16; // dynamics.max_substeps

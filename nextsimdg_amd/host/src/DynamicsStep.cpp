@@ -15,6 +15,7 @@
 
 #include "../../../include/nsdg.h"
 #include "ForcingFile.hpp"
+#include "LandMaskFile.hpp"
 #include "ModuleLoader.hpp"
 #include "PhaseTiming.hpp"
 #include "PhysicsModules.hpp"
@@ -94,6 +95,7 @@ public:
     // order of ForcingFile::variables()), and which record each slot holds (-1: none)
     double* records = nullptr;
     long recordOf[2] = { -1, -1 };
+    std::uint8_t* land = nullptr; // dynamics.land_mask_file: the mask of the local rows, ghost rows included (set on the context)
 
     ~DynamicsBlock() { release(); }
     void release()
@@ -111,6 +113,9 @@ public:
         records = nullptr;
         if (ctx)
             nsdg_ctx_destroy(ctx); // finalises the communicator too
+        if (land) // after the context, which held the pointer
+            (void)hipFree(land);
+        land = nullptr;
         ctx = nullptr;
     }
     double* curH() const { return d[tpar == 0 ? H0 : H1]; }
@@ -129,7 +134,7 @@ const std::map<int, std::string> Configured<DynamicsStep>::keyMap = { { 0, "dyna
     { 10, "dynamics.devices" }, { 11, "dynamics.loopback_world" }, { 12, "dynamics.closure" }, { 13, "dynamics.min_conc" },
     { 14, "dynamics.min_thick" }, { 15, "dynamics.delta_min" }, { 16, "dynamics.subcycle" }, { 17, "dynamics.substeps" },
     { 18, "dynamics.substep_courant" }, { 19, "dynamics.max_substeps" }, { 20, "dynamics.forcing_file" },
-    { 21, "dynamics.advect_column_state" } };
+    { 21, "dynamics.advect_column_state" }, { 22, "dynamics.land_mask_file" } };
 
 DynamicsStep::DynamicsStep() = default;
 DynamicsStep::~DynamicsStep() { release(); }
@@ -224,6 +229,16 @@ void DynamicsStep::configure()
             throw std::invalid_argument("dynamics.forcing_file " + path + ": without dynamics.thermodynamics the run uses only wind_u / wind_v "
                                         "and ocean_u / ocean_v, and the file holds neither pair");
     }
+    // the land mask: read and checked here, before any device is touched (the shape against the structure, once there is one)
+    m_landMask.reset();
+    {
+        const std::string path = getConfiguration(keyMap.at(22), std::string(""));
+        if (!path.empty()) {
+            m_landMask = std::make_shared<const LandMaskFile>(path);
+            if (pStructure)
+                m_landMask->checkShape((std::size_t)pStructure->nx(), (std::size_t)pStructure->ny());
+        }
+    }
     if (loopbackWorld != 0 && loopbackWorld < 3)
         throw std::invalid_argument("dynamics.loopback_world needs an interior block: at least 3");
     // the snow and the surface temperature ride on the moving ice (include/nsdg.h "column state transport"); off by default
@@ -288,6 +303,12 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
     nxf = pStructure->ny(); // fast dimension of the x-major index i*ny + j
     nyf = pStructure->nx();
     m_time = (double)startTime;
+    if (m_landMask) {
+        m_landMask->checkShape((std::size_t)nyf, (std::size_t)nxf);
+        if (m_rank == 0)
+            std::printf("dynamics land mask: %zu of %zu elements are land (%s)\n", m_landMask->landElements(), (std::size_t)nxf * nyf,
+                m_landMask->path().c_str());
+    }
 
     // ---- the blocks of this process
     const bool loop = loopbackWorld > 0;
@@ -400,6 +421,11 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
         }
         check(nsdg_grid_set(b.ctx, b.nx, b.ny, hx, hy), "nsdg_grid_set");
         check(nsdg_block_set(b.ctx, b.lo, b.nyGlobal), "nsdg_block_set");
+        if (m_landMask) { // the block's rows of the mask, ghost rows included: the mask is static, nothing is ever exchanged
+            checkHip(hipMalloc(reinterpret_cast<void**>(&b.land), (std::size_t)N), "DynamicsStep: hipMalloc (land mask)");
+            checkHip(hipMemcpy(b.land, m_landMask->data() + (std::size_t)b.lo * b.nx, (std::size_t)N, hipMemcpyHostToDevice), "upload land mask");
+            check(nsdg_land_mask_set(b.ctx, b.land), "nsdg_land_mask_set");
+        }
         // cell means -> DG coefficient 0 (the local rows, ghost rows included, are one contiguous slice)
         const std::size_t first = (std::size_t)b.lo * b.nx;
         checkHip(hipMemcpy(b.d[H0], f.hice.data() + first, N * sizeof(double), hipMemcpyHostToDevice), "upload H");
@@ -441,6 +467,17 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
                 checkHip(hipMemcpy(b.col(c), planes[c]->data() + first, N * sizeof(double), hipMemcpyHostToDevice), "upload column fields");
             if (advectColumn) // plane 0 of the snow field IS the column's hsnow (C_HSNOW stays unused)
                 checkHip(hipMemcpy(b.d[S0], f.hsnow.data() + first, N * sizeof(double), hipMemcpyHostToDevice), "upload S");
+        }
+        if (m_landMask) { // no ice on land, no motion at land nodes, whatever the initial state or the restart file held there
+            check(nsdg_land_clear(b.ctx, 0, b.ny, 6, b.d[H0]), "nsdg_land_clear");
+            check(nsdg_land_clear(b.ctx, 0, b.ny, 6, b.d[A0]), "nsdg_land_clear");
+            if (advectColumn)
+                check(nsdg_land_clear(b.ctx, 0, b.ny, 6, b.d[S0]), "nsdg_land_clear");
+            if (thermo) {
+                check(nsdg_land_clear(b.ctx, 0, b.ny, 1, b.col(C_HSNOW)), "nsdg_land_clear");
+                check(nsdg_land_clear(b.ctx, 0, b.ny, 1, b.col(C_NEWICE)), "nsdg_land_clear");
+            }
+            check(nsdg_land_clear_nodes(b.ctx, b.d[Ua], b.d[Va]), "nsdg_land_clear_nodes");
         }
         // driver plans
         nsdg_rb_mevp_desc m;
@@ -549,6 +586,14 @@ void DynamicsStep::subStep(double dt, bool last)
                       b.col(C_TDEW), b.col(C_SLP), b.col(C_QSW), b.col(C_QLW), b.col(C_MLD), b.col(C_SNOWFALL), b.col(C_WIND), b.col(C_NEWICE),
                       nullptr),
                 "nsdg_column_step");
+            if (b.land) {
+                // the column step computes on land elements too and its result there is discarded: the cell means of H, A (and S), the
+                // snow and the new ice (still the column phase)
+                check(nsdg_land_clear(ctx, 0, b.ny, 1, b.curH()), "nsdg_land_clear");
+                check(nsdg_land_clear(ctx, 0, b.ny, 1, b.curA()), "nsdg_land_clear");
+                check(nsdg_land_clear(ctx, 0, b.ny, 1, advectColumn ? b.curS() : b.col(C_HSNOW)), "nsdg_land_clear");
+                check(nsdg_land_clear(ctx, 0, b.ny, 1, b.col(C_NEWICE)), "nsdg_land_clear");
+            }
         }
         check(nsdg_phase_mark(ctx, NSDG_PHASE_PREPARE), "nsdg_phase_mark");
         check(nsdg_ice_strength(ctx, 0, b.ny, b.curH(), b.curA(), b.d[PG]), "nsdg_ice_strength");

@@ -19,80 +19,11 @@
 
 #include "ForcingFile.hpp"
 #include "Hdf5Subset.hpp"
+#include "NpyFile.hpp"
 
 using namespace Nextsim;
 
 namespace {
-
-struct Npy {
-    std::vector<std::uint64_t> shape;
-    std::vector<double> values;
-};
-
-// a float64 .npy file (format versions 1-3), little-endian, C order
-Npy readNpy(const std::string& path)
-{
-    std::ifstream f(path, std::ios::binary);
-    if (!f)
-        throw std::runtime_error("cannot open " + path);
-    const std::vector<char> b((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-    if (b.size() < 10 || std::memcmp(b.data(), "\x93NUMPY", 6) != 0)
-        throw std::runtime_error(path + " is not a .npy file");
-    const int major = (unsigned char)b[6];
-    std::size_t hlen = 0, start = 0;
-    if (major == 1) {
-        hlen = (unsigned char)b[8] | ((std::size_t)(unsigned char)b[9] << 8), start = 10;
-    } else if (major == 2 || major == 3) {
-        if (b.size() < 12)
-            throw std::runtime_error(path + ": truncated header");
-        for (int i = 0; i < 4; ++i)
-            hlen |= (std::size_t)(unsigned char)b[8 + i] << (8 * i);
-        start = 12;
-    } else
-        throw std::runtime_error(path + ": .npy format version " + std::to_string(major) + " is not supported");
-    if (start + hlen > b.size())
-        throw std::runtime_error(path + ": truncated header");
-    const std::string h(b.data() + start, hlen);
-    auto value = [&](const std::string& key) {
-        const std::size_t k = h.find("'" + key + "'");
-        if (k == std::string::npos)
-            throw std::runtime_error(path + ": no " + key + " in the header");
-        std::size_t p = h.find(':', k);
-        while (p + 1 < h.size() && h[p + 1] == ' ')
-            ++p;
-        return p + 1;
-    };
-    const std::size_t d = value("descr");
-    if (h.compare(d, 5, "'<f8'") != 0 && h.compare(d, 5, "'f8'") != 0)
-        throw std::runtime_error(path + ": the array must be float64 ('<f8'), the header says " + h.substr(d, 6));
-    if (h.compare(value("fortran_order"), 5, "False") != 0)
-        throw std::runtime_error(path + ": the array must be in C order");
-    const std::size_t s = value("shape");
-    const std::size_t e = h.find(')', s);
-    if (h[s] != '(' || e == std::string::npos)
-        throw std::runtime_error(path + ": unreadable shape");
-    Npy out;
-    std::uint64_t n = 1;
-    for (std::size_t p = s + 1; p < e;) {
-        while (p < e && (h[p] == ' ' || h[p] == ','))
-            ++p;
-        if (p >= e)
-            break;
-        char* end = nullptr;
-        const unsigned long long v = std::strtoull(h.c_str() + p, &end, 10);
-        if (end == h.c_str() + p)
-            throw std::runtime_error(path + ": unreadable shape");
-        out.shape.push_back(v);
-        n *= v;
-        p = end - h.c_str();
-    }
-    const std::size_t data = start + hlen;
-    if (b.size() - data != n * sizeof(double))
-        throw std::runtime_error(path + ": " + std::to_string(b.size() - data) + " bytes of data for " + std::to_string(n) + " float64 values");
-    out.values.resize(n);
-    std::memcpy(out.values.data(), b.data() + data, n * sizeof(double));
-    return out;
-}
 
 void usage()
 {

@@ -272,9 +272,26 @@ class DynamicsCore:
     # advect_column_state adds the snow S and the weighted surface temperature Q
     TRANSPORTED = ("H", "A")
 
+    LAND_OPS = ("set_land_mask", "land_clear", "land_clear_nodes")
+
     def __init__(self, ops, blk, hx, hy, dt, nsub, device, exchanger=None, overlap=True, native=False, use_graph=False, closure=True,
-                 phase_timing=False):
+                 phase_timing=False, land=None):
         self.ops, self.blk, self.hx, self.hy, self.dt, self.nsub = ops, blk, hx, hy, dt, nsub
+        # land: bool array [ny_global, nx] of the WHOLE domain (True = land; include/nsdg.h "land mask"): the nodes of
+        # land elements hold u = v = 0 like the array edge.  This rank keeps its rows, ghost rows included -- the mask is static, nothing
+        # is exchanged -- and sets them on the ops object whenever it sets the grid
+        self.land, self._land_on_ops = None, False
+        if land is not None:
+            import numpy as np
+
+            missing = [m for m in self.LAND_OPS if not callable(getattr(ops, m, None))]
+            if missing:
+                raise ValueError("land= needs an ops object with the land-mask calls of the C ABI (abi.Context); %s has no %s"
+                                 % (type(ops).__name__, ", ".join(missing)))
+            land = np.asarray(land)
+            if land.shape != (blk.ny_glob, blk.nx):
+                raise ValueError("land must be a [ny_global, nx] = [%d, %d] array, got shape %s" % (blk.ny_glob, blk.nx, land.shape))
+            self.land = torch.from_numpy(np.ascontiguousarray(land[blk.elem_slice()] != 0).astype(np.uint8)).to(device)
         # phase_timing: step() brackets its parts with the library's phase marks (include/nsdg.h "per-phase device timing": one event per
         # mark on the ops' stream, read by phase_times()); off, nothing is asked of `ops` beyond the kernels
         self._phase_timing = bool(phase_timing)
@@ -363,6 +380,9 @@ class DynamicsCore:
         if self._bounds_before is not None:  # the context is as this core found it
             self.ops.set_transport_bounds(self._bounds_before)
             self._bounds_before = None
+        if self._land_on_ops:  # set with the grid (_set_grid)
+            self.ops.set_land_mask(None)
+        self.land, self._land_on_ops = None, False
 
     def load_global(self, H, A, uo, vo, ua, va, u=None, v=None):
         """fill the local arrays (ghost rows included) from global numpy arrays"""
@@ -377,9 +397,22 @@ class DynamicsCore:
         if u is not None:
             put(self.u, np.ascontiguousarray(u[ns]))
             put(self.v, np.ascontiguousarray(v[ns]))
+        self._clear_land()
+
+    def _clear_land(self):
+        """no ice on land, no motion at land nodes: whatever a caller loaded there is cleared (a store: a NaN goes too)"""
+        if self.land is None:
+            return
+        self._set_grid()
+        for f in self._fields():
+            self.ops.land_clear(f)
+        self.ops.land_clear_nodes(self.u, self.v)
 
     def _set_grid(self):
         self.ops.set_grid(self.blk.nx, self.blk.ny, self.hx, self.hy)
+        if self.land is not None:
+            self.ops.set_land_mask(self.land)
+            self._land_on_ops = True
         place = getattr(self.ops, "set_block", None)
         if place is not None:  # where the local array sits in the global domain (device-side forcing providers)
             place(self.blk.lo, self.blk.ny_glob)
@@ -683,6 +716,7 @@ class DynamicsCore:
         put(self.v, state["v"][ns])
         for f, name in zip(self.s, ("s11", "s12", "s22")):
             f.copy_(self.ops.planes_to_private(torch.from_numpy(np.ascontiguousarray(state[name][:, es])).to(f.device)))
+        self._clear_land()
 
     @staticmethod
     def merge_states(states):
@@ -846,12 +880,18 @@ class CoupledCore(DynamicsCore):
         super().load_state_dict(state)
         if self.advect_column_state:
             self.S.copy_(torch.from_numpy(np.ascontiguousarray(state["S"][:, self.blk.elem_slice()])).to(self.S.device))
+            self._clear_land()
 
     def thermodynamics(self):
         self._mark(PHASE_COLUMN)
         state = {"hice": self.H[0], "cice": self.A[0], "hsnow": self.col["hsnow"], "tice0": self.col["tice0"]}
         forcing = {k: self.col[k] for k in self.COLUMN_FORCING}
         self.ops.column_step(self.dt, state, forcing, self.newice)
+        if self.land is not None:
+            # the column step computes on land elements too (it is pinned to the reference case by case); its result there is discarded:
+            # the cell means of H, A (and S), the snow and the new ice (still the COLUMN phase of the phase table)
+            for f in (self.H[0], self.A[0], self.col["hsnow"], self.newice):
+                self.ops.land_clear(f)
 
     def _record(self, k):
         """record k of the forcing series on the device: {name: [nyr, nxr] tensor}"""

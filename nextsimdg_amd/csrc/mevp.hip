@@ -17,7 +17,7 @@
 #include <algorithm>
 #include <initializer_list>
 
-#include "mevp_common.h"
+#include "mevp_pipeline.h"
 
 namespace nsdg_mevp_detail {
 
@@ -59,7 +59,7 @@ __device__ __forceinline__ void load_stress(const double* __restrict__ S11, cons
     tile_load8(S22, ts, s22);
 }
 
-// the velocity kernel's body; LAND: the instantiation that holds land nodes at 0 (mevp_common.h: node_update_packed)
+// the velocity kernel's body; LAND: the instantiation that holds land nodes at 0 (mevp_common.h: node_update)
 template <bool LAND>
 __device__ __forceinline__ void mevp_velocity_body(NodalConsts K, int nx, int ny, int j0, int j1, double hx, double hy,
     const double* __restrict__ S11, const double* __restrict__ S12, const double* __restrict__ S22,
@@ -108,40 +108,27 @@ __device__ __forceinline__ void mevp_velocity_body(NodalConsts K, int nx, int ny
     node_contrib<4>(s11, s12, s22, hx, hy, ccx, ccy);
 
     const long nV = (long)(2 * iy) * nn + 2 * ix; // vertex; EX = nV+1; EY = nV+nn; C = nV+nn+1
-    double un, vn, c[6];
+    double un[4], vn[4], c[6];
     // inverse lumped masses: 4, 2, 2, 1 adjacent elements times LUMP = 1/36, 1/9, 1/9, 4/9 of the cell area
     if (hasL && hasB) { // vertex
         load_nodal(packed, nplane, nV, c);
-        node_update_packed<LAND>(K, c, u_old[nV], v_old[nV], vx_, vy_, 9. * iarea, un, vn);
+        node_update<false, LAND>(K, c, u_old[nV], v_old[nV], vx_, vy_, 9. * iarea, un[0], vn[0]);
     } else
-        un = vn = 0.;
-    u_new[nV] = un, v_new[nV] = vn;
+        un[0] = vn[0] = 0.;
     if (hasB) { // bottom edge-mid
         load_nodal(packed, nplane, nV + 1, c);
-        node_update_packed<LAND>(K, c, u_old[nV + 1], v_old[nV + 1], exx, exy, 4.5 * iarea, un, vn);
+        node_update<false, LAND>(K, c, u_old[nV + 1], v_old[nV + 1], exx, exy, 4.5 * iarea, un[1], vn[1]);
     } else
-        un = vn = 0.;
-    u_new[nV + 1] = un, v_new[nV + 1] = vn;
+        un[1] = vn[1] = 0.;
     if (hasL) { // left edge-mid
         load_nodal(packed, nplane, nV + nn, c);
-        node_update_packed<LAND>(K, c, u_old[nV + nn], v_old[nV + nn], eyx, eyy, 4.5 * iarea, un, vn);
+        node_update<false, LAND>(K, c, u_old[nV + nn], v_old[nV + nn], eyx, eyy, 4.5 * iarea, un[2], vn[2]);
     } else
-        un = vn = 0.;
-    u_new[nV + nn] = un, v_new[nV + nn] = vn;
+        un[2] = vn[2] = 0.;
     load_nodal(packed, nplane, nV + nn + 1, c); // centre
-    node_update_packed<LAND>(K, c, u_old[nV + nn + 1], v_old[nV + nn + 1], ccx, ccy, 2.25 * iarea, un, vn);
-    u_new[nV + nn + 1] = un, v_new[nV + nn + 1] = vn;
-    // right column / top row of the local lattice are boundary nodes (v = 0)
-    if (ix == nx - 1) {
-        u_new[nV + 2] = 0., v_new[nV + 2] = 0.;
-        u_new[nV + nn + 2] = 0., v_new[nV + nn + 2] = 0.;
-    }
-    if (iy == ny - 1) {
-        u_new[nV + 2 * nn] = 0., v_new[nV + 2 * nn] = 0.;
-        u_new[nV + 2 * nn + 1] = 0., v_new[nV + 2 * nn + 1] = 0.;
-        if (ix == nx - 1)
-            u_new[nV + 2 * nn + 2] = 0., v_new[nV + 2 * nn + 2] = 0.;
-    }
+    node_update<false, LAND>(K, c, u_old[nV + nn + 1], v_old[nV + nn + 1], ccx, ccy, 2.25 * iarea, un[3], vn[3]);
+    // with the zeros of the right column / top row of the local lattice: boundary nodes (v = 0)
+    store_owned_nodes(nV, nn, ix == nx - 1, iy == ny - 1, un, vn, u_new, v_new);
 }
 
 __global__ __launch_bounds__(256) void mevp_velocity_kernel(NodalConsts K, int nx, int ny, int j0, int j1, double hx, double hy,

@@ -1,6 +1,9 @@
-// mevp_common.h -- per-element / per-node device functions shared by the two mEVP kernel variants
-// (mevp.hip: two kernels per sub-iteration; mevp_fused.hip: fused marching kernel).  Using the very
-// same inlined functions in both variants keeps their results bit-identical.
+// mevp_common.h -- the element and node arithmetic of the mEVP sub-cycle, each formula stated ONCE and inlined by every kernel that
+// needs it: the two-kernel form (mevp.hip), the single-iteration marching kernel (mevp_fused.hip) and the stage-per-wave pipeline
+// (mevp_fused4.hip).  The tiled layout of the element arrays and the packed layout of the nodal coefficients; the sum-factorised
+// element operators; the projected stress and its relaxation, uniform and adaptive; the nodal contributions; the node update
+// node_update<AD, LAND>; the land-node rule.  -ffp-contract=on fuses per source expression, so one statement of a formula is also what
+// makes the marching kernels agree bit for bit: an expression that is regrouped rounds differently.
 #pragma once
 #include "dg_tables.h"
 #include "nsdg_internal.h"
@@ -97,48 +100,24 @@ __device__ __forceinline__ int xcd_contiguous_block(int b, int nblocks)
 // subnormal range (Delta^2 >= Delta_min^2 = 4e-18; denominators >= rho h_min/dt).
 __device__ __forceinline__ double fast_rcp(double x)
 {
-#ifdef NSDG_OLD_ELEMENTARY
-    double r = __builtin_amdgcn_rcp(x);
-    r = __builtin_fma(__builtin_fma(-x, r, 1.0), r, r);
-    r = __builtin_fma(__builtin_fma(-x, r, 1.0), r, r);
-    return r;
-#else
     // the seed is good to 2^-24 (profiles/r02_seed_accuracy.txt): ONE second-order step r (1 + e + e^2), e = 1 - x r,
     // leaves an error of e^3 = 2^-72 -- 3 instructions instead of the 4 of two Newton steps, same 1.0 ulp maximum
     const double r = __builtin_amdgcn_rcp(x);
     const double e = __builtin_fma(-x, r, 1.0);
     return __builtin_fma(__builtin_fma(e, e, e), r, r);
-#endif
 }
 __device__ __forceinline__ double fast_rsqrt(double x)
 {
-#ifdef NSDG_OLD_ELEMENTARY
-    double y = __builtin_amdgcn_rsq(x);
-    // y <- y + y*(1 - x y^2)/2, twice
-    double e = __builtin_fma(-x * y, y, 1.0);
-    y = __builtin_fma(0.5 * y, e, y);
-    e = __builtin_fma(-x * y, y, 1.0);
-    y = __builtin_fma(0.5 * y, e, y);
-    return y;
-#else
     // one third-order step y (1 + e/2 + 3 e^2/8), e = 1 - x y^2: 5 instructions instead of 8, the same 1.24 ulp maximum
     const double y = __builtin_amdgcn_rsq(x);
     const double e = __builtin_fma(-x * y, y, 1.0);
     return __builtin_fma(y * e, __builtin_fma(0.375, e, 0.5), y);
-#endif
 }
 __device__ __forceinline__ double fast_sqrt(double x)
 {
     const double y = fast_rsqrt(x);
-#ifdef NSDG_OLD_ELEMENTARY
-    // sqrt(x) = x * rsqrt(x), one Goldschmidt-style correction on the product; exact zero stays zero
-    double g = x * y;
-    g = __builtin_fma(__builtin_fma(-g, g, x), 0.5 * y, g);
-    return x > 0. ? g : 0.;
-#else
     // sqrt(x) = x * rsqrt(x) (within 2 ulp: it only scales the ocean drag); exact zero stays zero
     return x > 0. ? x * y : 0.;
-#endif
 }
 
 // Neighbour-lane exchange of the marching kernels as DPP moves (GFX9 wave_shr:1 / wave_shl:1 shift the
@@ -241,61 +220,30 @@ __device__ __forceinline__ void sf_eval(const double (&c)[8], double (&V)[9])
     }
 }
 
-// L2 projection of Gauss-point values t[3*qy+qx] on the DG8 basis: R_i = (1/m_i) sum_q w_q psi_i(q) t_q
-__device__ __forceinline__ void sf_project(const double (&t)[9], double (&R)[8])
+// L2 projection of Gauss-point values t[3*qy+qx] on the DG8 basis: R_i = (1/m_i) sum_q w_q psi_i(q) t_q, in two sweeps.  The five factors
+// of the second sweep are the argument F: ProjUnit, compile-time constants -- the plain projection, whose instantiation sees literals --,
+// or a ProjScale, the same five times a run-time factor f (the adaptive form's 1 / alpha_e): 5 multiplications per element (the caller
+// forms them once for the three stress components) instead of 24 on the result.
+constexpr double SF_K1 = 12. * SF_W0 * SF_G; // (1/m1) w0 p1(g)
+constexpr double SF_K2S = 180. * SF_W0 * SF_P2E, SF_K2M = 180. * SF_W1 * SF_P2M; // (1/m2) w p2
+struct ProjUnit {
+    static constexpr double w0 = SF_W0, w1 = SF_W1, k1 = SF_K1, k2s = SF_K2S, k2m = SF_K2M;
+};
+struct ProjScale {
+    double w0, w1, k1, k2s, k2m;
+};
+__device__ __forceinline__ ProjScale proj_scale(double f) { return ProjScale { f * SF_W0, f * SF_W1, f * SF_K1, f * SF_K2S, f * SF_K2M }; }
+template <class Factors>
+__device__ __forceinline__ void sf_project(const double (&t)[9], const Factors& F, double (&R)[8])
 {
-    constexpr double K1 = 12. * SF_W0 * SF_G; // (1/m1) w0 p1(g)
-    constexpr double K2S = 180. * SF_W0 * SF_P2E, K2M = 180. * SF_W1 * SF_P2M; // (1/m2) w p2
     double Y0[3], Y1[3], Y2[3]; // Y_b[qx] = (1/m_b) sum_qy w_qy p_b(eta_qy) t(qx,qy)
 #pragma unroll
     for (int qx = 0; qx < 3; ++qx) {
         const double t0 = t[qx], t1 = t[3 + qx], t2 = t[6 + qx];
         const double sm = t0 + t2;
         Y0[qx] = SF_W0 * sm + SF_W1 * t1;
-        Y1[qx] = K1 * (t2 - t0);
-        Y2[qx] = K2S * sm + K2M * t1;
-    }
-    {
-        const double sm = Y0[0] + Y0[2];
-        R[0] = SF_W0 * sm + SF_W1 * Y0[1];
-        R[1] = K1 * (Y0[2] - Y0[0]);
-        R[3] = K2S * sm + K2M * Y0[1];
-    }
-    {
-        const double sm = Y1[0] + Y1[2];
-        R[2] = SF_W0 * sm + SF_W1 * Y1[1];
-        R[5] = K1 * (Y1[2] - Y1[0]);
-        R[6] = K2S * sm + K2M * Y1[1];
-    }
-    {
-        const double sm = Y2[0] + Y2[2];
-        R[4] = SF_W0 * sm + SF_W1 * Y2[1];
-        R[7] = K1 * (Y2[2] - Y2[0]);
-    }
-}
-
-// the same projection times a run-time factor f (the adaptive form's 1 / alpha_e): the factor goes into the five constants of the second
-// sweep -- 5 multiplications per element (the caller forms them once for the three stress components) instead of 24 on the result
-struct ProjScale {
-    double w0, w1, k1, k2s, k2m;
-};
-__device__ __forceinline__ ProjScale proj_scale(double f)
-{
-    constexpr double K1 = 12. * SF_W0 * SF_G, K2S = 180. * SF_W0 * SF_P2E, K2M = 180. * SF_W1 * SF_P2M;
-    return ProjScale { f * SF_W0, f * SF_W1, f * K1, f * K2S, f * K2M };
-}
-__device__ __forceinline__ void sf_project_scaled(const double (&t)[9], const ProjScale& F, double (&R)[8])
-{
-    constexpr double K1 = 12. * SF_W0 * SF_G;
-    constexpr double K2S = 180. * SF_W0 * SF_P2E, K2M = 180. * SF_W1 * SF_P2M;
-    double Y0[3], Y1[3], Y2[3];
-#pragma unroll
-    for (int qx = 0; qx < 3; ++qx) {
-        const double t0 = t[qx], t1 = t[3 + qx], t2 = t[6 + qx];
-        const double sm = t0 + t2;
-        Y0[qx] = SF_W0 * sm + SF_W1 * t1;
-        Y1[qx] = K1 * (t2 - t0);
-        Y2[qx] = K2S * sm + K2M * t1;
+        Y1[qx] = SF_K1 * (t2 - t0);
+        Y2[qx] = SF_K2S * sm + SF_K2M * t1;
     }
     {
         const double sm = Y0[0] + Y0[2];
@@ -353,13 +301,11 @@ __device__ __forceinline__ void sf_geta(const double (&c)[8], double (&G)[9])
     }
 }
 
-// (1/alpha) Proj sigma(v): the projected viscous-plastic stress of one element from its 9 nodal velocities, ALREADY SCALED
-// by 1/alpha.  Round 4 (the four-wave pipeline is bound by vector-instruction issue, so instructions are time): sigma is
-// linear in the ice strength, so 1/alpha and the 1/2 of "- P/2" are folded into it once (hp = P/(2 alpha): 9 multiplies
-// that replace the 9 of P/2 and the 24 of the relaxation); the strain-rate coefficients that vanish identically -- a
-// d/dxi of a biquadratic has no xi^2 part, a d/deta no eta^2 part -- are neither formed nor evaluated (28 operations).
-__device__ __forceinline__ void stress_projected(const double (&ul)[9], const double (&vl)[9], const double (&P)[9], double ihx,
-    double ihy, double ialpha, double dmin2, double (&r11)[8], double (&r12)[8], double (&r22)[8])
+// the strain rate at the 3x3 Gauss points of one element from its 9 nodal velocities.  The strain-rate coefficients that vanish
+// identically -- a d/dxi of a biquadratic has no xi^2 part (entries 3, 6), a d/deta no eta^2 part (entries 4, 7) -- are neither formed nor
+// evaluated (28 operations).
+__device__ __forceinline__ void strain_rate_gauss(const double (&ul)[9], const double (&vl)[9], double ihx, double ihy, double (&e11)[9],
+    double (&e12)[9], double (&e22)[9])
 {
     double E11[8], E12[8], E22[8];
     {
@@ -367,7 +313,6 @@ __device__ __forceinline__ void stress_projected(const double (&ul)[9], const do
         sf_grad(ul, uxi, ueta);
         sf_grad(vl, vxi, veta);
         const double hihx = 0.5 * ihx, hihy = 0.5 * ihy;
-        // d/dxi: entries 3, 6 vanish; d/deta: entries 4, 7 vanish
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const bool zx = i == 3 || i == 6, zy = i == 4 || i == 7;
@@ -376,10 +321,20 @@ __device__ __forceinline__ void stress_projected(const double (&ul)[9], const do
             E12[i] = zx ? ueta[i] * hihy : (zy ? vxi[i] * hihx : ueta[i] * hihy + vxi[i] * hihx);
         }
     }
-    double e11[9], e12[9], e22[9];
     sf_eval<1>(E11, e11);
     sf_eval<0>(E12, e12);
     sf_eval<2>(E22, e22);
+}
+
+// (1/alpha) Proj sigma(v): the projected viscous-plastic stress of one element from its 9 nodal velocities, ALREADY SCALED
+// by 1/alpha.  Round 4 (the four-wave pipeline is bound by vector-instruction issue, so instructions are time): sigma is
+// linear in the ice strength, so 1/alpha and the 1/2 of "- P/2" are folded into it once (hp = P/(2 alpha): 9 multiplies
+// that replace the 9 of P/2 and the 24 of the relaxation).
+__device__ __forceinline__ void stress_projected(const double (&ul)[9], const double (&vl)[9], const double (&P)[9], double ihx,
+    double ihy, double ialpha, double dmin2, double (&r11)[8], double (&r12)[8], double (&r22)[8])
+{
+    double e11[9], e12[9], e22[9];
+    strain_rate_gauss(ul, vl, ihx, ihy, e11, e12, e22);
     double t11[9], t12[9], t22[9];
     const double hps = 0.5 * ialpha;
 #pragma unroll
@@ -395,12 +350,12 @@ __device__ __forceinline__ void stress_projected(const double (&ul)[9], const do
         t22[q] = __builtin_fma(pd, __builtin_fma(-0.5, hb, a), -hp);
         t12[q] = (0.5 * pd) * e12[q];
     }
-    sf_project(t11, r11);
-    sf_project(t12, r12);
-    sf_project(t22, r22);
+    sf_project(t11, ProjUnit {}, r11);
+    sf_project(t12, ProjUnit {}, r12);
+    sf_project(t22, ProjUnit {}, r22);
 }
 
-// S <- (1 - 1/alpha) S + r, r = (1/alpha) Proj sigma(v) from stress_projected
+// S <- (1 - 1/alpha) S + r, r = (1/alpha) Proj sigma(v) from stress_projected, or with alpha_e from stress_projected_adaptive
 __device__ __forceinline__ void stress_relax(double ialpha, const double (&r11)[8], const double (&r12)[8], const double (&r22)[8],
     double (&s11)[8], double (&s12)[8], double (&s22)[8])
 {
@@ -447,24 +402,8 @@ struct AdaptConsts {
 __device__ __forceinline__ void stress_projected_adaptive(const double (&ul)[9], const double (&vl)[9], const double (&P)[9], double ihx,
     double ihy, double dmin2, double hc, const AdaptConsts& AC, double (&r11)[8], double (&r12)[8], double (&r22)[8], double& q, double& ialpha)
 {
-    double E11[8], E12[8], E22[8];
-    {
-        double uxi[8], ueta[8], vxi[8], veta[8];
-        sf_grad(ul, uxi, ueta);
-        sf_grad(vl, vxi, veta);
-        const double hihx = 0.5 * ihx, hihy = 0.5 * ihy;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const bool zx = i == 3 || i == 6, zy = i == 4 || i == 7;
-            E11[i] = zx ? 0. : uxi[i] * ihx;
-            E22[i] = zy ? 0. : veta[i] * ihy;
-            E12[i] = zx ? ueta[i] * hihy : (zy ? vxi[i] * hihx : ueta[i] * hihy + vxi[i] * hihx);
-        }
-    }
     double e11[9], e12[9], e22[9];
-    sf_eval<1>(E11, e11);
-    sf_eval<0>(E12, e12);
-    sf_eval<2>(E22, e22);
+    strain_rate_gauss(ul, vl, ihx, ihy, e11, e12, e22);
     double t11[9], t12[9], t22[9];
     double zmax = 0.;
 #pragma unroll
@@ -482,22 +421,9 @@ __device__ __forceinline__ void stress_projected_adaptive(const double (&ul)[9],
     ialpha = fast_rsqrt(a2);
     q = (a2 * ialpha) * (hc > 0x1p50 ? hc * 0x1p-100 : hc); // alpha_e times the centre node's h' (stored scaled by 2^100 where that node is ice-free)
     const ProjScale F = proj_scale(ialpha); // 1 / alpha_e rides on the projection's constants
-    sf_project_scaled(t11, F, r11);
-    sf_project_scaled(t12, F, r12);
-    sf_project_scaled(t22, F, r22);
-}
-
-// S <- (1 - 1/alpha_e) S + r, r = (1/alpha_e) Proj sigma(v) from stress_projected_adaptive
-__device__ __forceinline__ void stress_relax_adaptive(double ialpha, const double (&r11)[8], const double (&r12)[8], const double (&r22)[8],
-    double (&s11)[8], double (&s12)[8], double (&s22)[8])
-{
-    const double keep = 1. - ialpha;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        s11[i] = __builtin_fma(keep, s11[i], r11[i]);
-        s12[i] = __builtin_fma(keep, s12[i], r12[i]);
-        s22[i] = __builtin_fma(keep, s22[i], r22[i]);
-    }
+    sf_project(t11, F, r11);
+    sf_project(t12, F, r12);
+    sf_project(t22, F, r22);
 }
 
 // all 18 nodal contributions -(sigma, grad phi_n)_K of one element
@@ -544,74 +470,42 @@ __device__ __forceinline__ void node_contrib(const double (&s11)[8], const doubl
 // the update of DESIGN.md section 3.2 reads
 //   drag = cd*|v_o - v|;  u' = (K1 h' u + c2 + drag*u_o + K3 h' v + div_x/M) / (K2 h' + drag)
 //                         v' = (K1 h' v + c3 + drag*v_o - K3 h' u + div_y/M) / (K2 h' + drag)
-// Layout (NSDG_NODAL_LAYOUT).  Rounds 1-3: node-major, six consecutive doubles per node, three 16-byte loads at a lane stride of
-// 96 bytes; the pair-plane form -- pair k = (c[2k], c[2k+1]) of node n at packed[k * 2 NN + 2 n], lane stride 32 bytes -- was
-// 0.4 % slower in the single-wave three-iteration kernel (profiles/r03_fused3_levers.md).  Round 4: in the four-wave
-// pipeline all four waves of a CU read these coefficients, 36 instructions per march step that each touch 48 cache lines in the
-// node-major form against 16; pair planes measured 0.9349-0.9385 ms per pass against 0.9450-0.9491 node-major and 0.9393-0.9394 for
-// planes split by node parity (one contiguous kilobyte per access), alternating runs on one box -> pair planes are the default.
-// All three are bit-identical in their results.
-#ifndef NSDG_NODAL_LAYOUT
-#define NSDG_NODAL_LAYOUT 1
-#endif
-// NSDG_NODAL_LAYOUT: 0 node-major; 1 three pair planes (lane stride 32 bytes); 2 three pair planes, each split by the parity of
-// the node index -- the marching kernels read nodes n0 + 2 lane, so the 64 lanes of every access touch ONE contiguous kilobyte.
+// Layout: three PAIR PLANES -- pair k = (c[2k], c[2k+1]) of node n at packed[k * plane + 2 n], plane = 2 * (number of nodes), a lane stride
+// of 32 bytes.  nodal_plane and nodal_off are the single statement of it.  Two alternatives were measured and closed, all three bit-identical
+// in their results: node-major (six consecutive doubles per node, lane stride 96 bytes; rounds 1-3, profiles/r03_fused3_levers.md) --
+// in the four-wave pipeline all four waves of a CU read these coefficients, 36 instructions per march step that each touch 48 cache lines
+// node-major against 16 -- at 0.9450-0.9491 ms per pass, and pair planes split by node parity at 0.9393-0.9394, against 0.9349-0.9385 for
+// this one (alternating runs on one box, profiles/r04_fused4_development.md).
 // `plane` = doubles between two pair planes (what nodal_plane returns); nodal_off = where pair 0 of node n starts.
-__host__ __device__ __forceinline__ long nodal_plane(long nnodes)
-{
-#if NSDG_NODAL_LAYOUT == 0
-    return 2; // pair k at + 2 k
-#elif NSDG_NODAL_LAYOUT == 1
-    return 2 * nnodes;
-#else
-    return 4 * ((nnodes + 1) / 2); // [even nodes | odd nodes], two doubles each
-#endif
-}
-__host__ __device__ __forceinline__ long nodal_off(long n, long plane)
-{
-#if NSDG_NODAL_LAYOUT == 0
-    return n * 6;
-#elif NSDG_NODAL_LAYOUT == 1
-    return 2 * n;
-#else
-    return (n & 1) * (plane >> 1) + 2 * (n >> 1);
-#endif
-}
+__host__ __device__ __forceinline__ long nodal_plane(long nnodes) { return 2 * nnodes; }
+__host__ __device__ __forceinline__ long nodal_off(long n) { return 2 * n; }
 
 struct NodalConsts {
     double k1, k2, k3;
     double rdt; // rho_ice / dt (the adaptive form: K1 = rdt beta_n, K2 = rdt (1 + beta_n) per node)
 };
 
+// The node update.  AD selects only the denominator and c1: the uniform form with the launch constants K1, K2; the adaptive form with the
+// node's own beta -- qmax = the largest offer alpha_e h'_c of the adjacent elements, beta_n h'_n = max(alpha_min h'_n, qmax); at an ice-free
+// node c[0] is h'_n scaled by 2^100 and the first argument wins: beta_n = alpha_min.
 // LAND (the kernels launched when the packing saw a land mask, csrc/landmask.hip): a land node is packed with cd = c[1] < 0 -- every
 // real node has cd >= 0 -- and holds u = v = 0 like a node on the array edge.  LAND = false is the code without the test.
-template <bool LAND = false>
-__device__ __forceinline__ void node_update_packed(const NodalConsts& K, const double (&c)[6], double uu, double vv, double divx,
-    double divy, double ilumped, double& un, double& vn)
+template <bool AD, bool LAND>
+__device__ __forceinline__ void node_update(const NodalConsts& K, const double (&c)[6], double uu, double vv, double divx, double divy,
+    double ilumped, double& un, double& vn, double qmax = 0., double amin = 0.)
 {
     const double du = c[4] - uu, dv = c[5] - vv;
     const double drag = c[1] * fast_sqrt(du * du + dv * dv);
-    const double denom = fast_rcp(K.k2 * c[0] + drag);
-    const double c1 = K.k1 * c[0], cor = K.k3 * c[0];
-    un = denom * (c1 * uu + c[2] + drag * c[4] + cor * vv + divx * ilumped);
-    vn = denom * (c1 * vv + c[3] + drag * c[5] - cor * uu + divy * ilumped);
-    if constexpr (LAND) {
-        if (c[1] < 0.)
-            un = vn = 0.;
+    double denom, c1;
+    if constexpr (AD) {
+        const double bh = __builtin_fmax(amin * c[0], qmax); // beta_n h'_n
+        denom = fast_rcp(__builtin_fma(K.rdt, bh + c[0], drag));
+        c1 = K.rdt * bh;
+    } else {
+        denom = fast_rcp(K.k2 * c[0] + drag);
+        c1 = K.k1 * c[0];
     }
-}
-
-// the same with the node's own beta (adaptive form): qmax = the largest offer alpha_e h'_c of the adjacent elements, beta_n h'_n = max(alpha_min
-// h'_n, qmax) -- at an ice-free node c[0] is h'_n scaled by 2^100 and the first argument wins: beta_n = alpha_min
-template <bool LAND = false>
-__device__ __forceinline__ void node_update_packed_adaptive(const NodalConsts& K, const double (&c)[6], double uu, double vv, double divx,
-    double divy, double ilumped, double qmax, double amin, double& un, double& vn)
-{
-    const double du = c[4] - uu, dv = c[5] - vv;
-    const double drag = c[1] * fast_sqrt(du * du + dv * dv);
-    const double bh = __builtin_fmax(amin * c[0], qmax); // beta_n h'_n
-    const double denom = fast_rcp(__builtin_fma(K.rdt, bh + c[0], drag));
-    const double c1 = K.rdt * bh, cor = K.k3 * c[0];
+    const double cor = K.k3 * c[0];
     un = denom * (c1 * uu + c[2] + drag * c[4] + cor * vv + divx * ilumped);
     vn = denom * (c1 * vv + c[3] + drag * c[5] - cor * uu + divy * ilumped);
     if constexpr (LAND) {
@@ -654,7 +548,7 @@ static inline AdaptConsts nsdg_adapt_consts(const nsdg_ctx* ctx)
 // plane = nodal_plane(number of nodes of the local array)
 __device__ __forceinline__ void load_nodal(const double* __restrict__ packed, long plane, long n, double (&c)[6])
 {
-    const double* p = packed + nodal_off(n, plane);
+    const double* p = packed + nodal_off(n);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const double2 t = *reinterpret_cast<const double2*>(p + k * plane);
@@ -665,7 +559,7 @@ __device__ __forceinline__ void load_nodal(const double* __restrict__ packed, lo
 
 __device__ __forceinline__ void store_nodal(double* __restrict__ packed, long plane, long n, const double (&c)[6])
 {
-    double* p = packed + nodal_off(n, plane);
+    double* p = packed + nodal_off(n);
 #pragma unroll
     for (int k = 0; k < 3; ++k)
         *reinterpret_cast<double2*>(p + k * plane) = make_double2(c[2 * k], c[2 * k + 1]);

@@ -22,23 +22,16 @@
 // why the stress is updated out of place (S_in -> S_out): a recomputing strip must never read a value
 // its owner has already overwritten.  No barrier, no atomics, no inter-workgroup communication: every
 // wave is independent and runs to completion.
-#include "mevp_common.h"
-
+//
+// The march itself -- the carried contributions, the update of the four owned nodes, their store -- is the one of mevp_pipeline.h,
+// shared with the stage-per-wave pipeline (mevp_fused4.hip): a pass of n sub-iterations there is bit-identical to n launches of this
+// kernel.  What is this kernel's own is where its inputs come from (memory, every row) and the order of its loads.
+#include "mevp_pipeline.h"
 
 namespace nsdg_mevp_detail {
 
-struct StressPtrs {
-    const double *i11, *i12, *i22;
-    double *o11, *o12, *o22;
-};
-
-__device__ __forceinline__ double shift_up(double x)
-{
-    // value of lane-1 (lane 0 keeps its own; it is a redundant column whose result is discarded)
-    return lane_from_left(x);
-}
-
-// LAND: the instantiation that holds land nodes at 0 (mevp_common.h: node_update_packed), launched after a packing that saw a land mask
+// MINW: the register budget, 1 or 2 waves per SIMD; AD: local, solution-adaptive alpha and beta (mevp_common.h)
+// LAND: the instantiation that holds land nodes at 0 (mevp_common.h: node_update), launched after a packing that saw a land mask
 template <int MINW, bool AD, bool LAND>
 __global__ __launch_bounds__(256, MINW) void mevp_fused_kernel(NodalConsts K, AdaptConsts AC, int nx, int ny, int k0, int j0, int j1, int R, int ncw, double hx,
     double hy, double ialpha, double dmin2, StressPtrs S, const double* __restrict__ u_old, const double* __restrict__ v_old,
@@ -47,28 +40,30 @@ __global__ __launch_bounds__(256, MINW) void mevp_fused_kernel(NodalConsts K, Ad
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int strip = wave / ncw, cw = wave - strip * ncw;
-    const int y0 = k0 + strip * R;
-    if (y0 >= j1)
+    MarchConst M;
+    M.y0 = k0 + strip * R;
+    if (M.y0 >= j1)
         return; // wave-uniform
-    const int y1 = min(y0 + R, j1);
+    M.y1 = min(M.y0 + R, j1);
     const int ixr = cw * 63 - 1 + lane;
     const bool valid = ixr >= 0 && ixr < nx; // lanes outside the array load a clamped column and store nothing
-    const bool own = valid && lane > 0;
-    const int ix = min(max(ixr, 0), nx - 1);
-    const bool hasL = ix > 0;
-    const int ntx = tiles_per_row(nx);
-    const int nn = 2 * nx + 1;
-    const long nplane = nodal_plane((long)nn * (2 * ny + 1));
-    const double ihx = 1. / hx, ihy = 1. / hy, iarea = ihx * ihy;
+    M.K = K, M.AC = AC;
+    M.nx = nx, M.ny = ny, M.lane = lane;
+    M.own = valid && lane > 0;
+    M.ix = min(max(ixr, 0), nx - 1);
+    M.hasL = M.ix > 0, M.lastcol = M.ix == nx - 1;
+    M.ntx = tiles_per_row(nx);
+    M.nn = 2 * nx + 1;
+    M.nplane = nodal_plane((long)M.nn * (2 * ny + 1));
+    M.hx = hx, M.hy = hy, M.ihx = 1. / hx, M.ihy = 1. / hy, M.iarea = M.ihx * M.ihy;
+    M.ialpha = ialpha, M.dmin2 = dmin2;
+    const int ix = M.ix, nn = M.nn;
 
-    // contributions of the row below to its top-row nodes: b6 (top-left), b7 (top-mid) of my column and
-    // bl8 = top-right of the column to my left
-    double b6x = 0., b6y = 0., b7x = 0., b7y = 0., bl8x = 0., bl8y = 0.;
-    double qb = 0., qbl = 0.; // adaptive form: the offers q_e of the element below and below-left
+    TopCarry carry; // zero by its member initialisers: the first row of the march adds nothing from a row below
 
-    for (int iy = (y0 > k0 ? y0 - 1 : y0); iy < y1; ++iy) {
-        const bool prologue = iy < y0; // recomputed row owned by the strip below: nothing is stored
-        const long ts = tile_off(ix, iy, ntx, 8), tp = tile_off(ix, iy, ntx, 9);
+    for (int iy = (M.y0 > k0 ? M.y0 - 1 : M.y0); iy < M.y1; ++iy) {
+        const bool prologue = iy < M.y0; // recomputed row owned by the strip below: nothing is stored
+        const long ts = tile_off(ix, iy, M.ntx, 8), tp = tile_off(ix, iy, M.ntx, 9);
         const long nV = (long)(2 * iy) * nn + 2 * ix;
         double ul[9], vl[9], Pq[9], s11[8], s12[8], s22[8];
 #pragma unroll
@@ -81,18 +76,18 @@ __global__ __launch_bounds__(256, MINW) void mevp_fused_kernel(NodalConsts K, Ad
         double qe = 0.; // adaptive form: this element's offer q_e = alpha_e h'_c of this sub-iteration (mevp_common.h)
         if constexpr (AD) {
             // local, solution-adaptive alpha (mevp_common.h); h' of the element's centre node is its packed coefficient [0]
-            const double hc = packed[nodal_off(nV + nn + 1, nplane)];
-            double r11[8], r12[8], r22[8], ialpha;
-            stress_projected_adaptive(ul, vl, Pq, ihx, ihy, dmin2, hc, AC, r11, r12, r22, qe, ialpha);
+            const double hc = packed[nodal_off(nV + nn + 1)];
+            double r11[8], r12[8], r22[8], ialpha_e;
+            stress_projected_adaptive(ul, vl, Pq, M.ihx, M.ihy, dmin2, hc, AC, r11, r12, r22, qe, ialpha_e);
             tile_load8(S.i11, ts, s11);
             tile_load8(S.i12, ts, s12);
             tile_load8(S.i22, ts, s22);
-            stress_relax_adaptive(ialpha, r11, r12, r22, s11, s12, s22);
+            stress_relax(ialpha_e, r11, r12, r22, s11, s12, s22);
         } else if constexpr (MINW >= 2) {
             // 2 waves/SIMD build: stage the loads so that the live set stays under 256 registers -- the old
             // stress is fetched only after the projected stress is formed, the partner wave covers the latency
             double r11[8], r12[8], r22[8];
-            stress_projected(ul, vl, Pq, ihx, ihy, ialpha, dmin2, r11, r12, r22);
+            stress_projected(ul, vl, Pq, M.ihx, M.ihy, ialpha, dmin2, r11, r12, r22);
             asm volatile("" ::: "memory");
             tile_load8(S.i11, ts, s11);
             tile_load8(S.i12, ts, s12);
@@ -102,9 +97,9 @@ __global__ __launch_bounds__(256, MINW) void mevp_fused_kernel(NodalConsts K, Ad
             tile_load8(S.i11, ts, s11);
             tile_load8(S.i12, ts, s12);
             tile_load8(S.i22, ts, s22);
-            stress_update(ul, vl, Pq, ihx, ihy, ialpha, dmin2, s11, s12, s22);
+            stress_update(ul, vl, Pq, M.ihx, M.ihy, ialpha, dmin2, s11, s12, s22);
         }
-        if (!prologue && own) {
+        if (!prologue && M.own) {
             tile_store8(S.o11, ts, s11);
             tile_store8(S.o12, ts, s12);
             tile_store8(S.o22, ts, s22);
@@ -113,74 +108,16 @@ __global__ __launch_bounds__(256, MINW) void mevp_fused_kernel(NodalConsts K, Ad
         node_contrib_all(s11, s12, s22, hx, hy, cx, cy);
         if constexpr (MINW >= 2)
             asm volatile("" ::: "memory"); // keep the nodal-coefficient loads below this point
-        // wavefront-level edge exchange: right-column contributions of the element to my left
-        const double l2x = shift_up(cx[2]), l2y = shift_up(cy[2]);
-        const double l5x = shift_up(cx[5]), l5y = shift_up(cy[5]);
-        const double ql = AD ? shift_up(qe) : 0.;
 
         if (!prologue && iy >= j0) { // wave-uniform
-            const bool hasB = iy > 0;
-            double un, vn, c[6];
-            // vertex: below-left + below + left + own (the oracle's summation order)
-            if (hasL && hasB) {
-                load_nodal(packed, nplane, nV, c);
-                if constexpr (AD)
-                    node_update_packed_adaptive<LAND>(K, c, ul[0], vl[0], ((bl8x + b6x) + l2x) + cx[0], ((bl8y + b6y) + l2y) + cy[0], 9. * iarea,
-                        __builtin_fmax(__builtin_fmax(qbl, qb), __builtin_fmax(ql, qe)), AC.amin, un, vn);
-                else
-                    node_update_packed<LAND>(K, c, ul[0], vl[0], ((bl8x + b6x) + l2x) + cx[0], ((bl8y + b6y) + l2y) + cy[0], 9. * iarea, un, vn);
-            } else
-                un = vn = 0.;
-            if (own)
-                u_new[nV] = un, v_new[nV] = vn;
-            // bottom edge-mid: below + own
-            if (hasB) {
-                load_nodal(packed, nplane, nV + 1, c);
-                if constexpr (AD)
-                    node_update_packed_adaptive<LAND>(K, c, ul[1], vl[1], b7x + cx[1], b7y + cy[1], 4.5 * iarea, __builtin_fmax(qb, qe), AC.amin, un, vn);
-                else
-                    node_update_packed<LAND>(K, c, ul[1], vl[1], b7x + cx[1], b7y + cy[1], 4.5 * iarea, un, vn);
-            } else
-                un = vn = 0.;
-            if (own)
-                u_new[nV + 1] = un, v_new[nV + 1] = vn;
-            // left edge-mid: left + own
-            if (hasL) {
-                load_nodal(packed, nplane, nV + nn, c);
-                if constexpr (AD)
-                    node_update_packed_adaptive<LAND>(K, c, ul[3], vl[3], l5x + cx[3], l5y + cy[3], 4.5 * iarea, __builtin_fmax(ql, qe), AC.amin, un, vn);
-                else
-                    node_update_packed<LAND>(K, c, ul[3], vl[3], l5x + cx[3], l5y + cy[3], 4.5 * iarea, un, vn);
-            } else
-                un = vn = 0.;
-            if (own)
-                u_new[nV + nn] = un, v_new[nV + nn] = vn;
-            // centre: own
-            load_nodal(packed, nplane, nV + nn + 1, c);
-            if constexpr (AD)
-                node_update_packed_adaptive<LAND>(K, c, ul[4], vl[4], cx[4], cy[4], 2.25 * iarea, qe, AC.amin, un, vn);
-            else
-                node_update_packed<LAND>(K, c, ul[4], vl[4], cx[4], cy[4], 2.25 * iarea, un, vn);
-            if (own) {
-                u_new[nV + nn + 1] = un, v_new[nV + nn + 1] = vn;
-                // right column / top row of the local lattice are boundary nodes (v = 0)
-                if (ix == nx - 1) {
-                    u_new[nV + 2] = 0., v_new[nV + 2] = 0.;
-                    u_new[nV + nn + 2] = 0., v_new[nV + nn + 2] = 0.;
-                }
-                if (iy == ny - 1) {
-                    u_new[nV + 2 * nn] = 0., v_new[nV + 2 * nn] = 0.;
-                    u_new[nV + 2 * nn + 1] = 0., v_new[nV + 2 * nn + 1] = 0.;
-                    if (ix == nx - 1)
-                        u_new[nV + 2 * nn + 2] = 0., v_new[nV + 2 * nn + 2] = 0.;
-                }
-            }
+            double c[4][6], un[4], vn[4];
+            load_owned_nodal(M, iy, c, packed);
+            const double uu[4] = { ul[0], ul[1], ul[3], ul[4] }, vv[4] = { vl[0], vl[1], vl[3], vl[4] };
+            owned_node_updates<AD, LAND>(M, iy > 0, c, uu, vv, carry, cx, cy, un, vn, qe);
+            if (M.own)
+                store_owned_nodes(nV, nn, M.lastcol, iy == ny - 1, un, vn, u_new, v_new);
         }
-        // carry the top-row contributions to the next row of the march
-        b6x = cx[6], b6y = cy[6], b7x = cx[7], b7y = cy[7];
-        bl8x = shift_up(cx[8]), bl8y = shift_up(cy[8]);
-        if constexpr (AD)
-            qb = qe, qbl = ql;
+        carry_top<AD>(carry, cx, cy, qe); // the top-row contributions go to the next row of the march
     }
 }
 

@@ -63,14 +63,14 @@ constexpr int P4_PSLOT = P2P_PSLOT; // ice strength (mevp_p2p.h)
 constexpr int P4_CSLOT = 8 * 64; // third pair of the nodal coefficients (u_ocean, v_ocean): node n of lane l at n * 128 + 2 l
 constexpr int P4_LDS = 3 * P4_HSLOTS * P4_SLOT + P4_PRING * (P4_PSLOT + P4_CSLOT); // doubles: 96 + 31.5 + 28 KB of the 160 KB of a CU
 
-struct FetchP {
+struct Fetch {
     double P[9]; // ice strength at the Gauss points of the row the stage works on next
     double c[4][6]; // packed momentum coefficients of its 4 owned nodes
     double s11[8], s12[8], s22[8]; // stage 0 only: the stress the pass starts from
     double ub[3], vb[3], um[3], vm[3], ut[3], vt[3]; // stage 0 only: u, v of the pass's start on the three node rows
 };
 
-struct StageP {
+struct Stage {
     int s; // pipeline stage of this wave = sub-iteration p + s
     int nst; // stages of this pass = its sub-iterations (4; 3 or 2 for what is left of a sub-cycle whose length is no multiple of 4)
     int first, last; // element rows this stage works on
@@ -80,7 +80,7 @@ struct StageP {
 };
 
 // counters: done[k] at k, read[k] at 3 + k, the sticky give-up flag at 6
-struct FlagsP {
+struct Flags {
     int v[8];
 };
 
@@ -105,14 +105,14 @@ __device__ __forceinline__ void ring_write_c(double* __restrict__ cring, int row
 // the first two pairs of the nodal coefficients from memory (the third comes from the ring)
 __device__ __forceinline__ void load_nodal2(const double* __restrict__ packed, long plane, long n, double (&c)[6])
 {
-    const double* p = packed + nodal_off(n, plane);
+    const double* p = packed + nodal_off(n);
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         const double2 t = *reinterpret_cast<const double2*>(p + k * plane);
         c[2 * k] = t.x, c[2 * k + 1] = t.y;
     }
 }
-__device__ __forceinline__ void request_c2_p(const MarchConst3& M, int nrow, double (&c)[4][6], const double* __restrict__ packed)
+__device__ __forceinline__ void load_owned_nodal2(const MarchConst& M, int nrow, double (&c)[4][6], const double* __restrict__ packed)
 {
     const long nVn = (long)(2 * nrow) * M.nn + 2 * M.ix;
     load_nodal2(packed, M.nplane, nVn, c[0]);
@@ -122,8 +122,8 @@ __device__ __forceinline__ void request_c2_p(const MarchConst3& M, int nrow, dou
 }
 // One row of one stage.  FIRST: the loader (stage 0): inputs from memory, ice strength into the ring.
 template <bool FIRST, bool AD, bool LAND>
-__device__ __forceinline__ void p2p_row(const MarchConst3& M, const StageP& G, int row, FetchP& f, TopCarry3& carry, double* __restrict__ lds,
-    volatile lds_int* flags, const P2PReport& rep, const StressPtrsP& S, const double* __restrict__ u_old, const double* __restrict__ v_old,
+__device__ __forceinline__ void p2p_row(const MarchConst& M, const Stage& G, int row, Fetch& f, TopCarry& carry, double* __restrict__ lds,
+    volatile lds_int* flags, const P2PReport& rep, const StressPtrs& S, const double* __restrict__ u_old, const double* __restrict__ v_old,
     const double* __restrict__ packed, const double* __restrict__ pg, double* __restrict__ u_new, double* __restrict__ v_new NSDG_SPIN_ARG)
 {
     const int stage = FIRST ? 0 : G.s;
@@ -134,9 +134,9 @@ __device__ __forceinline__ void p2p_row(const MarchConst3& M, const StageP& G, i
     // the coefficients of row r: a stage >= 1 takes two pairs from memory and the third from the ring
     auto request_c = [&](int r) {
         if (FIRST)
-            request_c_p(M, r, f.c, packed);
+            load_owned_nodal(M, r, f.c, packed);
         else {
-            request_c2_p(M, r, f.c, packed);
+            load_owned_nodal2(M, r, f.c, packed);
             ring_read_c(cring, r, M.lane, f.c);
         }
     };
@@ -162,10 +162,10 @@ __device__ __forceinline__ void p2p_row(const MarchConst3& M, const StageP& G, i
         const double* top = lds + ((stage - 1) * P4_HSLOTS + ((row + 1) & 1)) * P4_SLOT + 2 * M.lane;
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-            const double2 a = lds_pair_p(in, 12 + k), b = lds_pair_p(in, 14 + k);
+            const double2 a = lds_pair(in, 12 + k), b = lds_pair(in, 14 + k);
             uu[2 * k] = a.x, uu[2 * k + 1] = a.y, vv[2 * k] = b.x, vv[2 * k + 1] = b.y;
         }
-        double2 tu = lds_pair_p(top, 12), tv = lds_pair_p(top, 14);
+        double2 tu = lds_pair(top, 12), tv = lds_pair(top, 14);
         if (row + 1 > G.last_prev) // wave-uniform: node row 2*ny is the top boundary
             tu = tv = make_double2(0., 0.);
         gather_nodes(M, uu, tu.x, tu.y, ul);
@@ -187,16 +187,16 @@ __device__ __forceinline__ void p2p_row(const MarchConst3& M, const StageP& G, i
         NSDG_SPIN_COUNT(2, flag_wait(flags, 3 + G.nst - 2, min(row - P4_PRING, G.last_final), rep)); // read[] of the LAST link: the last stage has passed that row
         ring_write_P<P4_PRING>(ring, row, M.lane, f.P);
         ring_write_c(cring, row, M.lane, f.c); // this row's coefficients were requested a step ago; the stages 1-3 take the pair from here
-        tile_load9_p<(NSDG_P2P_NT & 4) != 0>(pg, tile_off(ix, nrow, M.ntx, 9), ix & 63, f.P);
+        tile_load9_nt<(NSDG_P2P_NT & 4) != 0>(pg, tile_off(ix, nrow, M.ntx, 9), ix & 63, f.P);
         if (nrow > row) { // wave-uniform: the top node row of this element row is the bottom one of the next
 #pragma unroll
             for (int a = 0; a < 3; ++a)
                 f.ub[a] = f.ut[a], f.vb[a] = f.vt[a];
         }
-        fetch_nodes_p(u_old, nVn + nn, f.um);
-        fetch_nodes_p(v_old, nVn + nn, f.vm);
-        fetch_nodes_p(u_old, nVn + 2 * nn, f.ut);
-        fetch_nodes_p(v_old, nVn + 2 * nn, f.vt);
+        fetch_nodes(u_old, nVn + nn, f.um);
+        fetch_nodes(v_old, nVn + nn, f.vm);
+        fetch_nodes(u_old, nVn + 2 * nn, f.ut);
+        fetch_nodes(v_old, nVn + 2 * nn, f.vt);
 #pragma unroll
         for (int i = 0; i < 8; ++i)
             s11[i] = f.s11[i], s12[i] = f.s12[i], s22[i] = f.s22[i];
@@ -205,23 +205,20 @@ __device__ __forceinline__ void p2p_row(const MarchConst3& M, const StageP& G, i
         const double* in = lds + ((stage - 1) * P4_HSLOTS + (row & 1)) * P4_SLOT + 2 * M.lane;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const double2 a = lds_pair_p(in, k), b = lds_pair_p(in, 4 + k), c = lds_pair_p(in, 8 + k);
+            const double2 a = lds_pair(in, k), b = lds_pair(in, 4 + k), c = lds_pair(in, 8 + k);
             s11[2 * k] = a.x, s11[2 * k + 1] = a.y, s12[2 * k] = b.x, s12[2 * k + 1] = b.y, s22[2 * k] = c.x, s22[2 * k + 1] = c.y;
         }
         // this row's slot (stress, u, v) and the next row's ice strength have been taken: the producer may write row + 2 into the slot
         flag_publish(flags, 3 + stage - 1, row);
     }
     NSDG_PHASE(2); // loader: ring wait, ring writes, requests of P, u, v; stages: ring read, stress read, read[] published
-    if constexpr (AD)
-        stress_relax_adaptive(ialpha, r11, r12, r22, s11, s12, s22);
-    else
-        stress_relax(M.ialpha, r11, r12, r22, s11, s12, s22);
+    stress_relax(ialpha, r11, r12, r22, s11, s12, s22); // AD: alpha_e of this element; else ialpha = M.ialpha
     __builtin_amdgcn_sched_barrier(0);
     if (FIRST) { // stress of the next row
         const long ts = tile_off(ix, nrow, M.ntx, 8);
-        tile_load8_p<(NSDG_P2P_NT & 1) != 0>(S.i11, ts, f.s11);
-        tile_load8_p<(NSDG_P2P_NT & 1) != 0>(S.i12, ts, f.s12);
-        tile_load8_p<(NSDG_P2P_NT & 1) != 0>(S.i22, ts, f.s22);
+        tile_load8_nt<(NSDG_P2P_NT & 1) != 0>(S.i11, ts, f.s11);
+        tile_load8_nt<(NSDG_P2P_NT & 1) != 0>(S.i12, ts, f.s12);
+        tile_load8_nt<(NSDG_P2P_NT & 1) != 0>(S.i22, ts, f.s22);
     }
     NSDG_PHASE(3); // relaxation, (loader) stress request
     // ------------------------------------------------------------------------------------------ contributions, node updates
@@ -246,48 +243,35 @@ __device__ __forceinline__ void p2p_row(const MarchConst3& M, const StageP& G, i
         double* out = lds + (stage * P4_HSLOTS + (row & 1)) * P4_SLOT + 2 * M.lane;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            lds_pair_p(out, k, s11[2 * k], s11[2 * k + 1]);
-            lds_pair_p(out, 4 + k, s12[2 * k], s12[2 * k + 1]);
-            lds_pair_p(out, 8 + k, s22[2 * k], s22[2 * k + 1]);
+            lds_pair(out, k, s11[2 * k], s11[2 * k + 1]);
+            lds_pair(out, 4 + k, s12[2 * k], s12[2 * k + 1]);
+            lds_pair(out, 8 + k, s22[2 * k], s22[2 * k + 1]);
         }
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-            lds_pair_p(out, 12 + k, un[2 * k], un[2 * k + 1]);
-            lds_pair_p(out, 14 + k, vn[2 * k], vn[2 * k + 1]);
+            lds_pair(out, 12 + k, un[2 * k], un[2 * k + 1]);
+            lds_pair(out, 14 + k, vn[2 * k], vn[2 * k + 1]);
         }
         flag_publish(flags, stage, row);
     } else if (M.own && row >= M.y0) { // the last stage runs on rows y0-1 .. y1-1
         const long ts = tile_off(ix, row, M.ntx, 8);
         const long nV = (long)(2 * row) * nn + 2 * ix;
-        tile_store8_p<(NSDG_P2P_NT & 2) != 0>(S.o11, ts, s11);
-        tile_store8_p<(NSDG_P2P_NT & 2) != 0>(S.o12, ts, s12);
-        tile_store8_p<(NSDG_P2P_NT & 2) != 0>(S.o22, ts, s22);
-        u_new[nV] = un[0], v_new[nV] = vn[0];
-        u_new[nV + 1] = un[1], v_new[nV + 1] = vn[1];
-        u_new[nV + nn] = un[2], v_new[nV + nn] = vn[2];
-        u_new[nV + nn + 1] = un[3], v_new[nV + nn + 1] = vn[3];
-        if (M.lastcol) {
-            u_new[nV + 2] = 0., v_new[nV + 2] = 0.;
-            u_new[nV + nn + 2] = 0., v_new[nV + nn + 2] = 0.;
-        }
-        if (row == M.ny - 1) {
-            u_new[nV + 2 * nn] = 0., v_new[nV + 2 * nn] = 0.;
-            u_new[nV + 2 * nn + 1] = 0., v_new[nV + 2 * nn + 1] = 0.;
-            if (M.lastcol)
-                u_new[nV + 2 * nn + 2] = 0., v_new[nV + 2 * nn + 2] = 0.;
-        }
+        tile_store8_nt<(NSDG_P2P_NT & 2) != 0>(S.o11, ts, s11);
+        tile_store8_nt<(NSDG_P2P_NT & 2) != 0>(S.o12, ts, s12);
+        tile_store8_nt<(NSDG_P2P_NT & 2) != 0>(S.o22, ts, s22);
+        store_owned_nodes(nV, nn, M.lastcol, row == M.ny - 1, un, vn, u_new, v_new);
     }
     NSDG_PHASE(6); // outputs: slot wait, LDS writes, done[] published / global stores
 }
 
-// LAND: the instantiation that holds land nodes at 0 (mevp_common.h: node_update_packed), launched after a packing that saw a land mask
+// LAND: the instantiation that holds land nodes at 0 (mevp_common.h: node_update), launched after a packing that saw a land mask
 template <bool AD, bool LAND>
 __global__ __launch_bounds__(256) void mevp_fused4_kernel(NodalConsts K, AdaptConsts AC, int nst, int nx, int ny, int j0, int j1, int j0b, int j1b, int nsA, int R, int ncw,
-    double hx, double hy, double ialpha, double dmin2, P2PReport rep, StressPtrsP S, const double* __restrict__ u_old, const double* __restrict__ v_old,
+    double hx, double hy, double ialpha, double dmin2, P2PReport rep, StressPtrs S, const double* __restrict__ u_old, const double* __restrict__ v_old,
     const double* __restrict__ packed, const double* __restrict__ pg, double* __restrict__ u_new, double* __restrict__ v_new)
 {
     __shared__ __attribute__((aligned(16))) double lds[P4_LDS]; // 96 KB of hand-over slots + 31.5 + 28 KB of rings (ice strength, one coefficient pair)
-    __shared__ FlagsP flagmem;
+    __shared__ Flags flagmem;
     volatile lds_int* flags = (volatile lds_int*)flagmem.v;
     const int lane = threadIdx.x & 63;
     const int group = xcd_contiguous_block(blockIdx.x, gridDim.x);
@@ -297,7 +281,7 @@ __global__ __launch_bounds__(256) void mevp_fused4_kernel(NodalConsts K, AdaptCo
         strip -= nsA;
         j0 = j0b, j1 = j1b;
     }
-    MarchConst3 M;
+    MarchConst M;
     M.y0 = j0 + strip * R;
     if (M.y0 >= j1)
         return; // workgroup-uniform: no wave of this workgroup reaches the barrier or a counter
@@ -315,11 +299,10 @@ __global__ __launch_bounds__(256) void mevp_fused4_kernel(NodalConsts K, AdaptCo
     M.hx = hx, M.hy = hy, M.ihx = 1. / hx, M.ihy = 1. / hy, M.iarea = M.ihx * M.ihy;
     M.ialpha = ialpha, M.dmin2 = dmin2;
     M.AC = AC;
-    M.tbeg = M.tendA = M.tendB = 0; // (fields of the other pipelines)
 
     // a pass of nst sub-iterations (2 <= nst <= 4): stage s works on the rows y0 - nst + s .. y1 + nst - 2 - s, the last one (nst - 1)
     // on y0 - 1 .. y1 - 1; the waves s >= nst have nothing to do
-    StageP G;
+    Stage G;
     G.s = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     G.nst = nst;
     auto first_of = [&](int s) { return max(M.y0 - nst + s, 0); };
@@ -342,8 +325,8 @@ __global__ __launch_bounds__(256) void mevp_fused4_kernel(NodalConsts K, AdaptCo
     if (G.s >= nst)
         return; // wave-uniform
 
-    FetchP f;
-    TopCarry3 carry; // zero by its member initialisers: the first row of a stage adds nothing from a row below
+    Fetch f;
+    TopCarry carry; // zero by its member initialisers: the first row of a stage adds nothing from a row below
 #ifdef NSDG_P2P_SPINSTAT
     unsigned spins[3] = { 0, 0, 0 }, phase[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     unsigned stamp_last = (unsigned)__builtin_amdgcn_s_memtime();
@@ -351,17 +334,17 @@ __global__ __launch_bounds__(256) void mevp_fused4_kernel(NodalConsts K, AdaptCo
     if (G.s == 0) {
         const int row = G.first;
         const long nV = (long)(2 * row) * M.nn + 2 * M.ix, ts = tile_off(M.ix, row, M.ntx, 8);
-        fetch_nodes_p(u_old, nV, f.ub);
-        fetch_nodes_p(v_old, nV, f.vb);
-        fetch_nodes_p(u_old, nV + M.nn, f.um);
-        fetch_nodes_p(v_old, nV + M.nn, f.vm);
-        fetch_nodes_p(u_old, nV + 2 * M.nn, f.ut);
-        fetch_nodes_p(v_old, nV + 2 * M.nn, f.vt);
-        tile_load8_p<(NSDG_P2P_NT & 1) != 0>(S.i11, ts, f.s11);
-        tile_load8_p<(NSDG_P2P_NT & 1) != 0>(S.i12, ts, f.s12);
-        tile_load8_p<(NSDG_P2P_NT & 1) != 0>(S.i22, ts, f.s22);
-        tile_load9_p<(NSDG_P2P_NT & 4) != 0>(pg, tile_off(M.ix, row, M.ntx, 9), M.ix & 63, f.P);
-        request_c_p(M, row, f.c, packed);
+        fetch_nodes(u_old, nV, f.ub);
+        fetch_nodes(v_old, nV, f.vb);
+        fetch_nodes(u_old, nV + M.nn, f.um);
+        fetch_nodes(v_old, nV + M.nn, f.vm);
+        fetch_nodes(u_old, nV + 2 * M.nn, f.ut);
+        fetch_nodes(v_old, nV + 2 * M.nn, f.vt);
+        tile_load8_nt<(NSDG_P2P_NT & 1) != 0>(S.i11, ts, f.s11);
+        tile_load8_nt<(NSDG_P2P_NT & 1) != 0>(S.i12, ts, f.s12);
+        tile_load8_nt<(NSDG_P2P_NT & 1) != 0>(S.i22, ts, f.s22);
+        tile_load9_nt<(NSDG_P2P_NT & 4) != 0>(pg, tile_off(M.ix, row, M.ntx, 9), M.ix & 63, f.P);
+        load_owned_nodal(M, row, f.c, packed);
         for (int row = G.first; row <= G.last; ++row)
             p2p_row<true, AD, LAND>(M, G, row, f, carry, lds, flags, rep, S, u_old, v_old, packed, pg, u_new, v_new NSDG_SPIN_PASS);
     } else {
@@ -424,7 +407,7 @@ int nsdg_launch_mevp_fused4_ranges(nsdg_ctx* ctx, bool land, int nst, int j0, in
     }
     const int nsA = nsdg_div_up(j1 - j0, R), nsB = nsdg_div_up(rowsB, R);
     const long ngroups = (long)ncw * (nsA + nsB);
-    const StressPtrsP S = { b.s11i, b.s12i, b.s22i, b.s11, b.s12, b.s22 };
+    const StressPtrs S = { b.s11i, b.s12i, b.s22i, b.s11, b.s12, b.s22 };
     const NodalConsts K = nsdg_nodal_consts(ctx);
     const AdaptConsts AC = nsdg_adapt_consts(ctx);
     const P2PReport rep = { ctx->p2p_count_dev, ctx->p2p_flag_dev };

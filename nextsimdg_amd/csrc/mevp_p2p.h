@@ -1,7 +1,7 @@
-// mevp_p2p.h -- the point-to-point primitives of the stage-per-wave pipeline of the mEVP sub-cycle (mevp_fused4.hip; round 6 built a second
-// pipeline on them, two sub-iterations per stage wave, and withdrew it: profiles/r06_fused8.md): the hand-over between the waves of a workgroup --
-// counters in LDS, a bounded wait, the report of a wait that gave up --, the streaming 16-byte accesses, the rings of a row's ice
-// strength / nodal coefficients in LDS.
+// mevp_p2p.h -- what the stage-per-wave pipeline of the mEVP sub-cycle (mevp_fused4.hip) adds to the shared march (mevp_pipeline.h): the
+// point-to-point hand-over between the waves of a workgroup -- counters in LDS, a bounded wait, the report of a wait that gave up --,
+// the 16-byte pairs of a hand-over slot, the ring of a row's ice strength in LDS, and the streaming (non-temporal) accesses to the
+// data a pass touches once.
 //
 // Memory ordering.  All hand-over traffic is LDS traffic of ONE compute unit; the LDS executes the instructions of a wave in order.
 // A producer waits for its own LDS writes (s_waitcnt lgkmcnt(0)) before it raises its counter; a consumer reads the counter,
@@ -20,11 +20,6 @@ namespace nsdg_mevp_detail {
 #ifndef NSDG_P2P_SPIN_LIMIT
 #define NSDG_P2P_SPIN_LIMIT (1 << 20) // polls of ~0.2 us: a fifth of a second; a legitimate wait is a few march steps (a few microseconds)
 #endif
-
-struct StressPtrsP {
-    const double *i11, *i12, *i22;
-    double *o11, *o12, *o22;
-};
 
 // where a wait that gave up is reported: both belong to the context (nsdg_internal.h)
 struct P2PReport {
@@ -69,8 +64,8 @@ __device__ __forceinline__ void flag_publish(volatile lds_int* flags, int which,
     asm volatile("" ::: "memory");
 }
 
-__device__ __forceinline__ double2 lds_pair_p(const double* slot, int k) { return *reinterpret_cast<const double2*>(slot + k * 128); }
-__device__ __forceinline__ void lds_pair_p(double* slot, int k, double a, double b) { *reinterpret_cast<double2*>(slot + k * 128) = make_double2(a, b); }
+__device__ __forceinline__ double2 lds_pair(const double* slot, int k) { return *reinterpret_cast<const double2*>(slot + k * 128); }
+__device__ __forceinline__ void lds_pair(double* slot, int k, double a, double b) { *reinterpret_cast<double2*>(slot + k * 128) = make_double2(a, b); }
 
 // Streaming accesses (NSDG_P2P_NT bits: 1 the loader's stress loads, 2 the last stage's stress stores, 4 the loader's ice-strength
 // loads): data a pass touches exactly once need not displace the coefficient rows the later stages re-read through the L2.  Measured
@@ -79,57 +74,47 @@ __device__ __forceinline__ void lds_pair_p(double* slot, int k, double a, double
 #ifndef NSDG_P2P_NT
 #define NSDG_P2P_NT 3
 #endif
-typedef double nsdg_pair16p __attribute__((ext_vector_type(2)));
+typedef double nsdg_pair16 __attribute__((ext_vector_type(2)));
 template <bool NT>
-__device__ __forceinline__ void tile_load8_p(const double* __restrict__ a, long t, double (&c)[8])
+__device__ __forceinline__ void tile_load8_nt(const double* __restrict__ a, long t, double (&c)[8])
 {
     if (!NT)
         return tile_load8(a, t, c);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const nsdg_pair16p v = __builtin_nontemporal_load(reinterpret_cast<const nsdg_pair16p*>(a + t + 128 * k));
+        const nsdg_pair16 v = __builtin_nontemporal_load(reinterpret_cast<const nsdg_pair16*>(a + t + 128 * k));
         c[2 * k] = v.x, c[2 * k + 1] = v.y;
     }
 }
 template <bool NT>
-__device__ __forceinline__ void tile_load9_p(const double* __restrict__ a, long t, int l, double (&c)[9])
+__device__ __forceinline__ void tile_load9_nt(const double* __restrict__ a, long t, int l, double (&c)[9])
 {
     if (!NT)
         return tile_load9(a, t, l, c);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const nsdg_pair16p v = __builtin_nontemporal_load(reinterpret_cast<const nsdg_pair16p*>(a + t + 128 * k));
+        const nsdg_pair16 v = __builtin_nontemporal_load(reinterpret_cast<const nsdg_pair16*>(a + t + 128 * k));
         c[2 * k] = v.x, c[2 * k + 1] = v.y;
     }
     c[8] = __builtin_nontemporal_load(a + t + 512 - l);
 }
 template <bool NT>
-__device__ __forceinline__ void tile_store8_p(double* __restrict__ a, long t, const double (&c)[8])
+__device__ __forceinline__ void tile_store8_nt(double* __restrict__ a, long t, const double (&c)[8])
 {
     if (!NT)
         return tile_store8(a, t, c);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        nsdg_pair16p v;
+        nsdg_pair16 v;
         v.x = c[2 * k], v.y = c[2 * k + 1];
-        __builtin_nontemporal_store(v, reinterpret_cast<nsdg_pair16p*>(a + t + 128 * k));
+        __builtin_nontemporal_store(v, reinterpret_cast<nsdg_pair16*>(a + t + 128 * k));
     }
 }
-typedef double nsdg_pair8p __attribute__((ext_vector_type(2), aligned(8)));
-__device__ __forceinline__ void fetch_nodes_p(const double* __restrict__ w, long n, double (&o)[3])
+typedef double nsdg_pair8 __attribute__((ext_vector_type(2), aligned(8)));
+__device__ __forceinline__ void fetch_nodes(const double* __restrict__ w, long n, double (&o)[3])
 {
-    const nsdg_pair8p a = *reinterpret_cast<const nsdg_pair8p*>(w + n);
+    const nsdg_pair8 a = *reinterpret_cast<const nsdg_pair8*>(w + n);
     o[0] = a.x, o[1] = a.y, o[2] = w[n + 2];
-}
-
-// all three pairs of the packed coefficients of the 4 owned nodes of element row nrow
-__device__ __forceinline__ void request_c_p(const MarchConst3& M, int nrow, double (&c)[4][6], const double* __restrict__ packed)
-{
-    const long nVn = (long)(2 * nrow) * M.nn + 2 * M.ix;
-    load_nodal(packed, M.nplane, nVn, c[0]);
-    load_nodal(packed, M.nplane, nVn + 1, c[1]);
-    load_nodal(packed, M.nplane, nVn + M.nn, c[2]);
-    load_nodal(packed, M.nplane, nVn + M.nn + 1, c[3]);
 }
 
 // Rings of NR rows in LDS.  Ice strength: a row takes 9 * 64 doubles, pairs k < 4 of lane l at k * 128 + 2 l, the ninth value at 512 + l.

@@ -22,11 +22,12 @@ for r in range(rounds):
         env = dict(os.environ)
         if n != "default":
             env["NSDG_LIB"] = os.path.join(root, "nextsimdg_amd", "lib", "alt", n, "libnsdg.so")
-        out = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + extra.split(), env=env, capture_output=True, text=True)
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + extra.split(), env=env, capture_output=True, text=True, timeout=600)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")]
-        if not line:
-            print(n, "FAILED", out.stderr[-500:], flush=True)
-            continue
+        if out.returncode != 0 or not line:  # a run that failed may have faulted the device: start nothing after it
+            print(n, "FAILED rc", out.returncode, out.stderr[-500:], flush=True)
+            print(json.dumps(res))
+            sys.exit(1)
         j = json.loads(line[-1])
         res[n].append((j["ms_per_step"], j.get("roofline", {}).get("avg_launch_ms")))
         print(n, "ms/step %.3f" % j["ms_per_step"], "launch ms", j.get("roofline", {}).get("avg_launch_ms"), flush=True)

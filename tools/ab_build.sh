@@ -1,16 +1,26 @@
 #!/bin/bash
-# tools/ab_build.sh NAME [extra hipcc flags...] : builds nextsimdg_amd/lib/alt/NAME/libnsdg.so with the
-# extra flags applied to the mEVP sources only (A/B experiments; see tools/ab_bench.py)
+# tools/ab_build.sh [--csrc DIR] NAME [extra hipcc flags...] : builds nextsimdg_amd/lib/alt/NAME/libnsdg.so for an A/B run
+# (tools/ab_bench.py, NSDG_LIB).  Sources and flags are those of the build.py beside the csrc directory, so the library is whole
+# and loads.  --csrc DIR takes the sources from another checkout (DIR = <checkout>/nextsimdg_amd/csrc): that is how the parent
+# commit is built next to the working tree.
 set -e
 cd "$(dirname "$0")/.."
+csrc=nextsimdg_amd/csrc
+if [ "$1" = --csrc ]; then
+  csrc=$2; shift 2
+fi
 name=$1; shift
 out=nextsimdg_amd/lib/alt/$name
-mkdir -p $out
-FLAGS="-O3 --offload-arch=gfx950 -std=c++17 -fPIC -fno-signed-zeros -ffp-contract=on -Wno-unused-function"
-for s in column_step transport mevp mevp_fused mevp_fused4; do
-  hipcc $FLAGS "$@" -c nextsimdg_amd/csrc/$s.hip -o $out/$s.o &
+mkdir -p "$out"
+recipe=$(python3 -c 'import runpy, sys; b = runpy.run_path(sys.argv[1]); print(*b["SOURCES"]); print(*b["FLAGS"])' "$(dirname "$csrc")/build.py")
+read -r -a SOURCES <<< "$(sed -n 1p <<< "$recipe")"
+read -r -a FLAGS <<< "$(sed -n 2p <<< "$recipe")"
+objs=(); pids=()
+for s in "${SOURCES[@]}"; do
+  o=$out/${s%.hip}.o
+  hipcc "${FLAGS[@]}" "$@" -c "$csrc/$s" -o "$o" &
+  pids+=($!); objs+=("$o")
 done
-wait
-hipcc --offload-arch=gfx950 -shared -fPIC -o $out/libnsdg.so nextsimdg_amd/lib/nsdg_ctx.o nextsimdg_amd/lib/halo.o nextsimdg_amd/lib/rowblock.o \
-  nextsimdg_amd/lib/forcing.o $out/column_step.o $out/transport.o $out/mevp.o $out/mevp_fused.o $out/mevp_fused4.o -ldl -lpthread
-echo built $out/libnsdg.so
+for p in "${pids[@]}"; do wait "$p"; done
+hipcc --offload-arch=gfx950 -shared -fPIC -o "$out/libnsdg.so" "${objs[@]}" -ldl -lpthread
+echo built "$out/libnsdg.so"

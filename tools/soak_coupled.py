@@ -91,7 +91,7 @@ def dump(step):
     y0, y1, x0, x1 = max(iy - 2, 0), min(iy + 3, ny), max(ix - 2, 0), min(ix + 3, nx)
     Hw, Aw = core.H[:, y0:y1, x0:x1], core.A[:, y0:y1, x0:x1]
     Hg, Ag = torch.einsum("qc,cyx->qyx", GP, Hw), torch.einsum("qc,cyx->qyx", GP, Aw)
-    hnode = core.packed[:2 * (2 * ny + 1) * (2 * nx + 1)].view(2 * ny + 1, 2 * nx + 1, 2)[:, :, 0]  # h' = max(cgH, h_min) of the last packing: first entry of pair plane 0 (csrc/mevp_common.h, NSDG_NODAL_LAYOUT 1)
+    hnode = core.packed[:2 * (2 * ny + 1) * (2 * nx + 1)].view(2 * ny + 1, 2 * nx + 1, 2)[:, :, 0]  # h' = max(cgH, h_min) of the last packing: first entry of pair plane 0 (csrc/mevp_common.h: nodal_plane, nodal_off)
     hnode = torch.where(hnode > 1e20, hnode * 2.0 ** -100, hnode)  # ice-free nodes store it scaled by 2^100 (csrc/mevp.hip: pack_node)
     pgw = abi.untile(core.pg, nx)[:, y0:y1, x0:x1]
     # strain rate at the element centres of the window from the nodal velocities (central differences over the element)

@@ -4,6 +4,8 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <functional>
+#include <type_traits>
 
 #include "../../include/nsdg.h"
 
@@ -92,6 +94,21 @@ void nsdg_phase_timer_free(nsdg_ctx* ctx); // phase_timer.hip: the event ring of
 
 static inline int nsdg_div_up(long a, long b) { return (int)((a + b - 1) / b); }
 
+// coefficients per element of a DG field of the order 0, 1 or 2
+constexpr int nsdg_nc(int order) { return order == 0 ? 1 : (order == 1 ? 3 : 6); }
+
+// ONE dispatch from an order the caller has checked (0, 1 or 2) to the instantiation for it: f receives the order as a
+// std::integral_constant, `[&](auto O) { constexpr int ORDER = decltype(O)::value; ... }`
+template <class F>
+inline auto nsdg_with_order(int order, F&& f)
+{
+    switch (order) {
+    case 0: return f(std::integral_constant<int, 0>());
+    case 1: return f(std::integral_constant<int, 1>());
+    default: return f(std::integral_constant<int, 2>());
+    }
+}
+
 // ---- mEVP passes (mevp.hip) -----------------------------------------------------------------------------------------------------
 // the buffers of a pass: the stress S_in -> S_out (tiled), the velocity u_old -> u_new, the packed nodal coefficients, the ice strength
 struct nsdg_mevp_bufs {
@@ -112,3 +129,14 @@ int nsdg_mevp_pass(nsdg_ctx* ctx, int v, int k0, int j0, int j1, bool pair, int 
 // land: run the instantiation that holds land nodes at 0 -- chosen in ONE place, nsdg_mevp_pass, from what the packing saw
 int nsdg_launch_mevp_fused(nsdg_ctx* ctx, bool land, int k0, int j0, int j1, const nsdg_mevp_bufs& b);
 int nsdg_launch_mevp_fused4_ranges(nsdg_ctx* ctx, bool land, int nst, int j0, int j1, int j0b, int j1b, const nsdg_mevp_bufs& b);
+
+// ---- transport (transport.hip) --------------------------------------------------------------------------------------------------
+// One checked transport step on the rows [j0, j1) as stage launches, reported under the name `fn` of the entry point it works for:
+// the order + 1 stages of the SSP Runge-Kutta tableau -- stage k reads the state (k = 0) or the stage buffer k - 1 and writes the
+// stage buffer k (buf0, buf1), the last stage writes `out` -- then the closure on [j0, j1) of `out` if bounds are set.  after_stage(k) runs once stage k has been launched,
+// for every stage but the last (a row block exchanges the ghost rows of the buffer just written); a result != NSDG_OK ends the step.
+// A stage reads one row on each side of its rows and never the array it writes: `out` may be the state itself from the second stage
+// on (the last stage reads the state only at the element it writes), or buf0 from the third
+int nsdg_transport_staged_step(nsdg_ctx* ctx, const char* fn, int order, int j0, int j1, double dt, int nfields, const double* const* state,
+    double* const* buf0, double* const* buf1, double* const* out, const double* vx_dg, const double* vy_dg, const double* un_x, const double* un_y,
+    const std::function<int(int)>& after_stage);

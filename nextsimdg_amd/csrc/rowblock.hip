@@ -523,7 +523,7 @@ int nsdg_rb_transport_create(nsdg_ctx* ctx, const nsdg_rb_transport_desc* desc, 
     p->ctx = ctx;
     p->g = g;
     p->d = d;
-    p->nc = 6;
+    p->nc = nsdg_nc(d.order);
     p->deep = g.multi() && std::min(g.depth_below, g.depth_above) >= 3;
     if (g.multi()) {
         for (int par = 0; par < 2 && rc == NSDG_OK; ++par) {
@@ -611,20 +611,13 @@ int nsdg_rb_transport_run(nsdg_ctx* ctx, nsdg_rb_transport* p, double dt, int32_
         if ((rc = nsdg_transport_step_oop_rows(ctx, d.order, g.j0, g.j1, dt, d.nfields, cur, nxt, d.vx_dg, d.vy_dg, d.un_x, d.un_y)) != NSDG_OK)
             return rc;
     } else {
-        // Shu-Osher SSP-RK3: out = a*phi0 + b*(phis + dt L(phis)); a stage reads one element row on each side of its rows
-        if ((rc = nsdg_transport_stage(ctx, d.order, g.j0, g.j1, dt, 0.0, 1.0, d.nfields, cur, cur, nxt, d.vx_dg, d.vy_dg, d.un_x, d.un_y)) != NSDG_OK)
-            return rc;
-        if ((rc = exchange(p->new_plan[parity])) != NSDG_OK)
-            return rc;
-        if ((rc = nsdg_transport_stage(ctx, d.order, g.j0, g.j1, dt, 0.75, 0.25, d.nfields, cur, nxt, d.t2, d.vx_dg, d.vy_dg, d.un_x, d.un_y)) != NSDG_OK)
-            return rc;
-        if ((rc = exchange(p->t2_plan)) != NSDG_OK)
-            return rc;
-        if ((rc = nsdg_transport_stage(ctx, d.order, g.j0, g.j1, dt, 1.0 / 3.0, 2.0 / 3.0, d.nfields, cur, d.t2, nxt, d.vx_dg, d.vy_dg, d.un_x, d.un_y))
+        // shallow ghost zones: the stages as launches of their own on the block's own rows -- a stage reads one element row on each side
+        // of its rows, so the ghost rows of the buffer a stage has written are exchanged before the next one -- and the closure on the
+        // same rows (the march applies it in its epilogue); the ghost rows receive limited values
+        nsdg_halo* const after[2] = { p->new_plan[parity], p->t2_plan };
+        if ((rc = nsdg_transport_staged_step(ctx, __func__, d.order, g.j0, g.j1, dt, d.nfields, cur, nxt, d.t2, nxt, d.vx_dg, d.vy_dg, d.un_x,
+                 d.un_y, [&](int k) { return exchange(after[k]); }))
             != NSDG_OK)
-            return rc;
-        // the closure of the step on the block's own rows (the march applies it in its epilogue); the ghost rows receive limited values
-        if (ctx->nbounds > 0 && (rc = nsdg_transport_limit(ctx, d.order, g.j0, g.j1, d.nfields, nxt)) != NSDG_OK)
             return rc;
     }
     if ((rc = exchange(p->new_plan[parity])) != NSDG_OK)

@@ -65,12 +65,9 @@ int nsdg_tracer_weight(nsdg_ctx* ctx, int32_t order, int32_t j0, int32_t j1, con
     NSDG_CHECK_HIP(hipSetDevice(ctx->device));
     const long N = (long)ctx->nx * ctx->ny, e0 = (long)j0 * ctx->nx, e1 = (long)j1 * ctx->nx;
     const dim3 grid((unsigned)launch_blocks(ctx, e1 - e0)), block(256);
-    if (order == 0)
-        hipLaunchKernelGGL(tracer_weight_kernel<1>, grid, block, 0, ctx->stream, e0, e1, N, H, T, Q);
-    else if (order == 1)
-        hipLaunchKernelGGL(tracer_weight_kernel<3>, grid, block, 0, ctx->stream, e0, e1, N, H, T, Q);
-    else
-        hipLaunchKernelGGL(tracer_weight_kernel<6>, grid, block, 0, ctx->stream, e0, e1, N, H, T, Q);
+    nsdg_with_order(order, [&](auto O) {
+        hipLaunchKernelGGL(tracer_weight_kernel<nsdg_nc(decltype(O)::value)>, grid, block, 0, ctx->stream, e0, e1, N, H, T, Q);
+    });
     NSDG_CHECK_LAUNCH();
     return NSDG_OK;
 }

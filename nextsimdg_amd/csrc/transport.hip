@@ -1,9 +1,23 @@
-// transport.hip -- DG upwind transport on a uniform rectangular mesh: advection-velocity preparation
-// and the Runge-Kutta stage kernel (DG0 / DG1 / DG2).
+// transport.hip -- DG upwind transport on a uniform rectangular mesh (DG0 / DG1 / DG2): advection-velocity preparation, the
+// Runge-Kutta step and its closure.
 //
 // No counterpart in the reference snapshot (CMakeLists.txt:43-46 comments the dynamics component
 // out); the scheme is the one stated in DESIGN.md section 3.1 and restated on the CPU in
 // oracle/dyn_oracle.c (parity unpinned).
+//
+// What the file states ONCE, for every kernel and entry point:
+//   RK               the SSP Runge-Kutta tableau (march kernel, staged step)
+//   rk_update        the arithmetic of a stage            transport_rhs   L(phi) of one element
+//   edge_trace       an element's values on one edge      limit_cell      the closure of a step on one element
+//   check_args, bind_fields, nsdg_with_order (nsdg_internal.h), nsdg_transport_staged_step: the host side of every entry point
+// Five kernel templates, each at the orders 0, 1, 2:
+//   prepare_advection_kernel   CG2 velocity -> DG velocity and edge-normal velocities
+//   transport_stage_kernel     one stage, one element per lane (the default of nsdg_transport_stage and of the staged step)
+//   transport_pair_kernel      one stage, two elements per lane (nsdg_transport_variant_set(ctx, 2, rows))
+//   transport_march_kernel     all stages and the closure in one launch (nsdg_transport_step_oop[_rows])
+//   transport_limit_kernel     the closure as a pass of its own (nsdg_transport_limit, the end of the staged step)
+// All of them run the same inlined transport_rhs / rk_update / limit_cell on the same operands: a step is bit-identical whichever
+// way it is composed, and for any row-block decomposition.
 //
 // Stage kernel shape: one lane per element, gather formulation -- every element evaluates the
 // upwind flux on its own four edges (a shared edge is evaluated twice with bit-identical
@@ -12,7 +26,7 @@
 // the nc + 4*nc neighbour loads and the nc stores is a unit-stride wave access.  Basis values at the
 // quadrature points are compile-time constants (tools/gen_tables.py) folded into the instruction
 // stream by full unrolling; zero entries cost nothing.  HBM-bound: 1008 B / element-step for
-// DG2 x 2 fields x RK3.
+// DG2 x 2 fields x RK3.  The march is described at transport_march_kernel.
 #include <cmath>
 #include <cstdint>
 
@@ -25,7 +39,7 @@ using namespace nsdg_tab;
 
 template <int ORDER>
 struct DG {
-    static constexpr int NC = ORDER == 0 ? 1 : (ORDER == 1 ? 3 : 6);
+    static constexpr int NC = nsdg_nc(ORDER);
     static constexpr int NG = ORDER + 1; // edge Gauss points
     static constexpr int NQ = (ORDER + 1) * (ORDER + 1); // volume Gauss points
 };
@@ -62,6 +76,14 @@ struct FieldPtrs {
         if (t_ != 0.0)           \
             acc += t_ * (val);   \
     } while (0)
+
+// The strong-stability-preserving Runge-Kutta scheme of ORDER + 1 stages that advances DG<ORDER> (Euler / Heun / Shu-Osher RK3), in
+// Shu-Osher form: stage k makes a phi0 + b (c + dt L(c)) of the state phi0 and of the stage k - 1 values c (the state for k = 0).
+// Stated once, for the march kernel and for the stage launches of the host side (staged_step)
+struct RkStage {
+    double a, b;
+};
+constexpr RkStage RK[3][3] = { { { 0., 1. } }, { { 0., 1. }, { 0.5, 0.5 } }, { { 0., 1. }, { 0.75, 0.25 }, { 1. / 3., 2. / 3. } } };
 
 // out = a phi0 + b (c + dt L_i), ONE expression for every kernel that performs a Runge-Kutta stage (the stage kernels and the
 // fused-stages kernel round it identically); a == 0: the first stage, which does not read phi0
@@ -174,51 +196,22 @@ template <int NG>
 struct NbTrace {
     double l[NG], r[NG], b[NG], t[NG]; // the left / right / bottom / top neighbour's values on my edges
 };
-template <int ORDER>
-__device__ __forceinline__ void trace_of_left(const double (&cl)[DG<ORDER>::NC], double (&tr)[DG<ORDER>::NG])
+enum Side { LEFT, RIGHT, BOTTOM, TOP };
+template <int ORDER, Side SIDE> __device__ __forceinline__ constexpr double t_side(int g, int i)
 {
-#pragma unroll
-    for (int g = 0; g < DG<ORDER>::NG; ++g) {
-        double s = 0.;
-#pragma unroll
-        for (int k = 0; k < DG<ORDER>::NC; ++k)
-            FMA_TAB(s, t_r<ORDER>(g, k), cl[k]); // the left neighbour's right trace
-        tr[g] = s;
-    }
+    return SIDE == LEFT ? t_l<ORDER>(g, i) : (SIDE == RIGHT ? t_r<ORDER>(g, i) : (SIDE == BOTTOM ? t_b<ORDER>(g, i) : t_t<ORDER>(g, i)));
 }
-template <int ORDER>
-__device__ __forceinline__ void trace_of_right(const double (&cr)[DG<ORDER>::NC], double (&tr)[DG<ORDER>::NG])
+// the trace of the element with the coefficients c at the NG Gauss points of its SIDE edge.  A neighbour's trace on my left edge is
+// its RIGHT trace, on my bottom edge its TOP trace, and so on
+template <int ORDER, Side SIDE>
+__device__ __forceinline__ void edge_trace(const double (&c)[DG<ORDER>::NC], double (&tr)[DG<ORDER>::NG])
 {
 #pragma unroll
     for (int g = 0; g < DG<ORDER>::NG; ++g) {
         double s = 0.;
 #pragma unroll
         for (int k = 0; k < DG<ORDER>::NC; ++k)
-            FMA_TAB(s, t_l<ORDER>(g, k), cr[k]);
-        tr[g] = s;
-    }
-}
-template <int ORDER>
-__device__ __forceinline__ void trace_of_bottom(const double (&cb)[DG<ORDER>::NC], double (&tr)[DG<ORDER>::NG])
-{
-#pragma unroll
-    for (int g = 0; g < DG<ORDER>::NG; ++g) {
-        double s = 0.;
-#pragma unroll
-        for (int k = 0; k < DG<ORDER>::NC; ++k)
-            FMA_TAB(s, t_t<ORDER>(g, k), cb[k]);
-        tr[g] = s;
-    }
-}
-template <int ORDER>
-__device__ __forceinline__ void trace_of_top(const double (&ct)[DG<ORDER>::NC], double (&tr)[DG<ORDER>::NG])
-{
-#pragma unroll
-    for (int g = 0; g < DG<ORDER>::NG; ++g) {
-        double s = 0.;
-#pragma unroll
-        for (int k = 0; k < DG<ORDER>::NC; ++k)
-            FMA_TAB(s, t_b<ORDER>(g, k), ct[k]);
+            FMA_TAB(s, (t_side<ORDER, SIDE>(g, k)), c[k]);
         tr[g] = s;
     }
 }
@@ -327,19 +320,19 @@ __global__ __launch_bounds__(256, NSDG_TR_WAVES) void transport_stage_kernel(int
 #pragma unroll
             for (int k = 0; k < NC; ++k)
                 w[k] = hasL ? phis[k * N + e - 1] : 0.;
-            trace_of_left<ORDER>(w, nb.l);
+            edge_trace<ORDER, RIGHT>(w, nb.l);
 #pragma unroll
             for (int k = 0; k < NC; ++k)
                 w[k] = hasR ? phis[k * N + e + 1] : 0.;
-            trace_of_right<ORDER>(w, nb.r);
+            edge_trace<ORDER, LEFT>(w, nb.r);
 #pragma unroll
             for (int k = 0; k < NC; ++k)
                 w[k] = hasB ? phis[k * N + e - nx] : 0.;
-            trace_of_bottom<ORDER>(w, nb.b);
+            edge_trace<ORDER, TOP>(w, nb.b);
 #pragma unroll
             for (int k = 0; k < NC; ++k)
                 w[k] = hasT ? phis[k * N + e + nx] : 0.;
-            trace_of_top<ORDER>(w, nb.t);
+            edge_trace<ORDER, BOTTOM>(w, nb.t);
         }
 #pragma unroll
         for (int k = 0; k < NC; ++k)
@@ -410,33 +403,33 @@ __global__ __launch_bounds__(256, 2) void transport_pair_kernel(int nx, int ny, 
 #pragma unroll
             for (int k = 0; k < NC; ++k)
                 w0[k] = hasL ? phis[k * N + e - 1] : 0.;
-            trace_of_left<ORDER>(w0, nb0.l);
+            edge_trace<ORDER, RIGHT>(w0, nb0.l);
 #pragma unroll
             for (int k = 0; k < NC; ++k)
                 w1[k] = hasR ? phis[k * N + e + 2] : 0.;
-            trace_of_right<ORDER>(w1, nb1.r);
+            edge_trace<ORDER, LEFT>(w1, nb1.r);
 #pragma unroll
             for (int k = 0; k < NC; ++k) {
                 const double2 t = hasB ? ld2(phis + k * N + e - nx) : make_double2(0., 0.);
                 w0[k] = t.x, w1[k] = t.y;
             }
-            trace_of_bottom<ORDER>(w0, nb0.b);
-            trace_of_bottom<ORDER>(w1, nb1.b);
+            edge_trace<ORDER, TOP>(w0, nb0.b);
+            edge_trace<ORDER, TOP>(w1, nb1.b);
 #pragma unroll
             for (int k = 0; k < NC; ++k) {
                 const double2 t = hasT ? ld2(phis + k * N + e + nx) : make_double2(0., 0.);
                 w0[k] = t.x, w1[k] = t.y;
             }
-            trace_of_top<ORDER>(w0, nb0.t);
-            trace_of_top<ORDER>(w1, nb1.t);
+            edge_trace<ORDER, BOTTOM>(w0, nb0.t);
+            edge_trace<ORDER, BOTTOM>(w1, nb1.t);
         }
 #pragma unroll
         for (int k = 0; k < NC; ++k) {
             const double2 t = ld2(phis + k * N + e);
             c0[k] = t.x, c1[k] = t.y;
         }
-        trace_of_right<ORDER>(c1, nb0.r); // across the inner edge: the partner element's coefficients are in registers
-        trace_of_left<ORDER>(c0, nb1.l);
+        edge_trace<ORDER, LEFT>(c1, nb0.r); // across the inner edge: the partner element's coefficients are in registers
+        edge_trace<ORDER, RIGHT>(c0, nb1.l);
         double r0[NC], r1[NC];
         transport_rhs<ORDER>(c0, nb0, vx0, vy0, E0, ihx, ihy, r0);
         transport_rhs<ORDER>(c1, nb1, vx1, vy1, E1, ihx, ihy, r1);
@@ -510,12 +503,12 @@ __device__ __forceinline__ void march_rhs(const double (&below)[DG<ORDER>::NC], 
     const RowVel<ORDER>& V, const double (&eb_above)[DG<ORDER>::NG], bool hasL, bool hasR, bool hasB, bool hasT, double ihx, double ihy,
     double (&rhs)[DG<ORDER>::NC])
 {
-    constexpr int NC = DG<ORDER>::NC, NG = DG<ORDER>::NG;
+    constexpr int NG = DG<ORDER>::NG;
     NbTrace<NG> nb;
     EdgeVel<NG> E;
     double mine_r[NG], mine_l[NG];
-    trace_of_left<ORDER>(c, mine_r); // my right trace: what my right neighbour calls "the left neighbour's trace"
-    trace_of_right<ORDER>(c, mine_l);
+    edge_trace<ORDER, RIGHT>(c, mine_r); // what my right neighbour takes as its left neighbour's trace
+    edge_trace<ORDER, LEFT>(c, mine_l);
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
         const double fl = dpp_from_left(mine_r[g]), fr = dpp_from_right(mine_l[g]);
@@ -525,14 +518,14 @@ __device__ __forceinline__ void march_rhs(const double (&below)[DG<ORDER>::NC], 
     // hasB / hasT are wave-uniform (a row of the array): a branch instead of NC selects; the trace of "no neighbour" is the sum over
     // zero coefficients of the other kernels, +0
     if (hasB)
-        trace_of_bottom<ORDER>(below, nb.b);
+        edge_trace<ORDER, TOP>(below, nb.b);
     else {
 #pragma unroll
         for (int g = 0; g < NG; ++g)
             nb.b[g] = 0.;
     }
     if (hasT)
-        trace_of_top<ORDER>(above, nb.t);
+        edge_trace<ORDER, BOTTOM>(above, nb.t);
     else {
 #pragma unroll
         for (int g = 0; g < NG; ++g)
@@ -626,6 +619,21 @@ __global__ __launch_bounds__(64 * NSDG_MARCH_WG_WAVES) void transport_march_kern
             for (int g = 0; g < NG; ++g)
                 ebn[g] = plane_load(un_y + g * NEY, d);
         }
+        // the end of the last stage on the row a, from the state p0 and the values c of the stage before: the new value, the closure,
+        // the store of the owned lanes
+        auto finish_row = [&](int a, const double (&p0)[NC], const double (&c)[NC], const double (&rhs)[NC]) {
+            double o[NC];
+#pragma unroll
+            for (int i = 0; i < NC; ++i)
+                o[i] = rk_update(RK[ORDER][S - 1].a, RK[ORDER][S - 1].b, dt, IMASS[i], p0[i], c[i], rhs[i]);
+            if (fp.limit) // wave-uniform
+                limit_cell<ORDER>(o, fp.lo[f], fp.hi[f], fp.cap[f] != 0);
+            if (own) {
+#pragma unroll
+                for (int i = 0; i < NC; ++i)
+                    out[i * N + (long)a * nx + x] = o[i];
+            }
+        };
         auto step = [&](int r, Ahead& Q) {
             // ---- the rows move down by one; the requested values arrive
 #pragma unroll
@@ -653,22 +661,12 @@ __global__ __launch_bounds__(64 * NSDG_MARCH_WG_WAVES) void transport_march_kern
                 if (a >= max(y0 - (S - 1), 0) && a <= min(y1 - 1 + (S - 1), ny - 1)) { // wave-uniform
                     double rhs[NC];
                     march_rhs<ORDER>(PH[NR0 - 3], PH[NR0 - 2], PH[NR0 - 1], VR[0], ebn, hasL, hasR, a > 0, a + 1 < ny, ihx, ihy, rhs);
-                    if (S == 1) {
-                        double o[NC];
+                    if (S == 1)
+                        finish_row(a, PH[NR0 - 2], PH[NR0 - 2], rhs);
+                    else {
 #pragma unroll
                         for (int i = 0; i < NC; ++i)
-                            o[i] = rk_update(0., 1., dt, IMASS[i], 0., PH[NR0 - 2][i], rhs[i]);
-                        if (fp.limit) // wave-uniform
-                            limit_cell<ORDER>(o, fp.lo[f], fp.hi[f], fp.cap[f] != 0);
-                        if (own) {
-#pragma unroll
-                            for (int i = 0; i < NC; ++i)
-                                out[i * N + (long)a * nx + x] = o[i];
-                        }
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < NC; ++i)
-                            T1[2][i] = rk_update(0., 1., dt, IMASS[i], 0., PH[NR0 - 2][i], rhs[i]);
+                            T1[2][i] = rk_update(RK[ORDER][0].a, RK[ORDER][0].b, dt, IMASS[i], 0., PH[NR0 - 2][i], rhs[i]);
                     }
                 }
             }
@@ -678,17 +676,7 @@ __global__ __launch_bounds__(64 * NSDG_MARCH_WG_WAVES) void transport_march_kern
                 if (a >= y0 && a <= y1 - 1) {
                     double rhs[NC];
                     march_rhs<ORDER>(T1[0], T1[1], T1[2], VR[S - 1], VR[S - 2].eb, hasL, hasR, a > 0, a + 1 < ny, ihx, ihy, rhs);
-                    double o[NC];
-#pragma unroll
-                    for (int i = 0; i < NC; ++i)
-                        o[i] = rk_update(0.5, 0.5, dt, IMASS[i], PH[NR0 - 3][i], T1[1][i], rhs[i]);
-                    if (fp.limit) // wave-uniform
-                        limit_cell<ORDER>(o, fp.lo[f], fp.hi[f], fp.cap[f] != 0);
-                    if (own) {
-#pragma unroll
-                        for (int i = 0; i < NC; ++i)
-                            out[i * N + (long)a * nx + x] = o[i];
-                    }
+                    finish_row(a, PH[NR0 - 3], T1[1], rhs);
                 }
             }
             if (S == 3) {
@@ -700,7 +688,7 @@ __global__ __launch_bounds__(64 * NSDG_MARCH_WG_WAVES) void transport_march_kern
                         march_rhs<ORDER>(T1[0], T1[1], T1[2], VR[1], VR[0].eb, hasL, hasR, a > 0, a + 1 < ny, ihx, ihy, rhs);
 #pragma unroll
                         for (int i = 0; i < NC; ++i)
-                            T2[2][i] = rk_update(0.75, 0.25, dt, IMASS[i], PH[NR0 - 3][i], T1[1][i], rhs[i]);
+                            T2[2][i] = rk_update(RK[ORDER][1].a, RK[ORDER][1].b, dt, IMASS[i], PH[NR0 - 3][i], T1[1][i], rhs[i]);
                     }
                 }
                 {
@@ -708,17 +696,7 @@ __global__ __launch_bounds__(64 * NSDG_MARCH_WG_WAVES) void transport_march_kern
                     if (a >= y0 && a <= y1 - 1) {
                         double rhs[NC];
                         march_rhs<ORDER>(T2[0], T2[1], T2[2], VR[S - 1], VR[S - 2].eb, hasL, hasR, a > 0, a + 1 < ny, ihx, ihy, rhs);
-                        double o[NC];
-#pragma unroll
-                        for (int i = 0; i < NC; ++i)
-                            o[i] = rk_update(1. / 3., 2. / 3., dt, IMASS[i], PH[0][i], T2[1][i], rhs[i]);
-                        if (fp.limit) // wave-uniform
-                            limit_cell<ORDER>(o, fp.lo[f], fp.hi[f], fp.cap[f] != 0);
-                        if (own) {
-#pragma unroll
-                            for (int i = 0; i < NC; ++i)
-                                out[i * N + (long)a * nx + x] = o[i];
-                        }
+                        finish_row(a, PH[0], T2[1], rhs);
                     }
                 }
             }
@@ -864,48 +842,115 @@ int launch_stage(nsdg_ctx* ctx, int j0, int j1, double dt, double a, double b, i
             bits |= (uintptr_t)fp.phi0[f] | (uintptr_t)fp.phis[f] | (uintptr_t)fp.out[f];
         pairs = (bits & 15) == 0;
     }
-    if (pairs) {
-        const int br = ctx->transport_rows > 0 ? ctx->transport_rows : 4;
-        const dim3 block(64, br), grid(nsdg_div_up(ctx->nx / 2, 64), nsdg_div_up(j1 - j0, br));
+    // rows per workgroup: the rows above / below a workgroup's band are read a second time by the neighbouring
+    // workgroup, so taller bands mean fewer redundant reads (band + 2 rows read per band)
+    const int br = ctx->transport_rows > 0 ? ctx->transport_rows : 4;
+    const dim3 block(64, br), grid(nsdg_div_up(pairs ? ctx->nx / 2 : ctx->nx, 64), nsdg_div_up(j1 - j0, br));
+    if (pairs)
         hipLaunchKernelGGL(transport_pair_kernel<ORDER>, grid, block, 0, ctx->stream, ctx->nx, ctx->ny, j0, j1, nfields, 1. / ctx->hx, 1. / ctx->hy, dt, a,
             b, fp, vx, vy, unx, uny);
-    } else {
-        // rows per workgroup: the rows above / below a workgroup's band are read a second time by the neighbouring
-        // workgroup, so taller bands mean fewer redundant reads (band + 2 rows read per band)
-        const int br = ctx->transport_rows > 0 ? ctx->transport_rows : 4;
-        const dim3 block(64, br), grid(nsdg_div_up(ctx->nx, 64), nsdg_div_up(j1 - j0, br));
+    else
         hipLaunchKernelGGL(transport_stage_kernel<ORDER>, grid, block, 0, ctx->stream, ctx->nx, ctx->ny, j0, j1, nfields, 1. / ctx->hx,
             1. / ctx->hy, dt, a, b, fp, vx, vy, unx, uny);
-    }
     NSDG_CHECK_LAUNCH();
     return NSDG_OK;
 }
 
-int stage_dispatch(nsdg_ctx* ctx, int order, int j0, int j1, double dt, double a, double b, int nfields, const FieldPtrs& fp,
-    const double* vx, const double* vy, const double* unx, const double* uny)
+// ---- what the entry points share: every check is reported under the name `fn` of the exported function it is made for ----------------
+
+// the context with its grid, the order, the rows [j0, j1) and the number of fields; an entry point without a row range passes
+// (0, 0), one without a field list nfields = 1
+int check_args(const char* fn, const nsdg_ctx* ctx, int order, int j0, int j1, int nfields)
 {
-    switch (order) {
-    case 0: return launch_stage<0>(ctx, j0, j1, dt, a, b, nfields, fp, vx, vy, unx, uny);
-    case 1: return launch_stage<1>(ctx, j0, j1, dt, a, b, nfields, fp, vx, vy, unx, uny);
-    default: return launch_stage<2>(ctx, j0, j1, dt, a, b, nfields, fp, vx, vy, unx, uny);
+    NSDG_CHECK_ARG_IN(fn, ctx != nullptr, "null context");
+    if (ctx->nx <= 0) {
+        nsdg_set_error("%s: nsdg_grid_set was not called", fn);
+        return NSDG_ERR_STATE;
     }
+    NSDG_CHECK_ARG_IN(fn, order >= 0 && order <= 2, "order must be 0, 1 or 2");
+    NSDG_CHECK_ARG_IN(fn, 0 <= j0 && j0 <= j1 && j1 <= ctx->ny, "row range outside the local array");
+    NSDG_CHECK_ARG_IN(fn, nfields >= 1 && nfields <= MAXF, "nfields must be 1..4");
+    return NSDG_OK;
 }
 
-// the context's bounds for the nfields fields of a full step (nsdg_transport_bounds_set); false: the field counts disagree
-bool bounds_into(const nsdg_ctx* ctx, int nfields, FieldPtrs& fp)
+#define NSDG_BOUNDS_MISMATCH "nsdg_transport_bounds_set was given a different number of fields than this call advances"
+
+// the (phi0, phis, out) arrays of the nfields fields of a launch, the unused slots padded with field 0, and its closure: the
+// context's bounds for these fields (nsdg_transport_bounds_set) or, for a bare stage, none
+int bind_fields(const char* fn, const nsdg_ctx* ctx, int nfields, const double* const* phi0, const double* const* phis, double* const* out,
+    bool closure, FieldPtrs& fp)
 {
-    fp.limit = ctx->nbounds > 0;
+    fp.limit = closure && ctx->nbounds > 0;
+    NSDG_CHECK_ARG_IN(fn, !fp.limit || ctx->nbounds == nfields, NSDG_BOUNDS_MISMATCH);
     for (int f = 0; f < MAXF; ++f) {
-        const int s = (fp.limit && f < ctx->nbounds) ? f : 0;
+        const int s = f < nfields ? f : 0;
+        NSDG_CHECK_ARG_IN(fn, phi0[s] && phis[s] && out[s], "null field pointer");
+        fp.phi0[f] = phi0[s], fp.phis[f] = phis[s], fp.out[f] = out[s];
         fp.lo[f] = fp.limit ? ctx->bounds[s].lo : 0.;
         fp.hi[f] = fp.limit ? ctx->bounds[s].hi : 0.;
         fp.cap[f] = fp.limit ? ctx->bounds[s].cap_mean : 0;
     }
-    return !fp.limit || ctx->nbounds == nfields;
+    return NSDG_OK;
 }
-#define NSDG_BOUNDS_MISMATCH "nsdg_transport_bounds_set was given a different number of fields than this call advances"
+
+// one Runge-Kutta stage on the rows [j0, j1), arguments checked by check_args.  A bare stage: the closure belongs to the END of a
+// step (limit_rows, or the epilogue of the march)
+int stage_rows(const char* fn, nsdg_ctx* ctx, int order, int j0, int j1, double dt, RkStage rk, int nfields, const double* const* phi0,
+    const double* const* phis, double* const* out, const double* vx_dg, const double* vy_dg, const double* un_x, const double* un_y)
+{
+    if (j0 == j1)
+        return NSDG_OK;
+    FieldPtrs fp;
+    if (int rc = bind_fields(fn, ctx, nfields, phi0, phis, out, false, fp))
+        return rc;
+    for (int f = 0; f < nfields; ++f)
+        NSDG_CHECK_ARG_IN(fn, out[f] != phis[f], "out must not alias phis (neighbours are read)");
+    NSDG_CHECK_HIP(hipSetDevice(ctx->device));
+    return nsdg_with_order(order, [&](auto O) { return launch_stage<decltype(O)::value>(ctx, j0, j1, dt, rk.a, rk.b, nfields, fp, vx_dg, vy_dg, un_x, un_y); });
+}
+
+// the closure in place on the rows [j0, j1) of phi, arguments checked by check_args; bounds are set
+int limit_rows(const char* fn, nsdg_ctx* ctx, int order, int j0, int j1, int nfields, double* const* phi)
+{
+    FieldPtrs fp;
+    if (int rc = bind_fields(fn, ctx, nfields, phi, phi, phi, true, fp))
+        return rc;
+    if (j0 == j1)
+        return NSDG_OK;
+    NSDG_CHECK_HIP(hipSetDevice(ctx->device));
+    const dim3 block(64, 4), grid(nsdg_div_up(ctx->nx, 64), nsdg_div_up(j1 - j0, 4));
+    nsdg_with_order(order, [&](auto O) {
+        hipLaunchKernelGGL(transport_limit_kernel<decltype(O)::value>, grid, block, 0, ctx->stream, ctx->nx, ctx->ny, j0, j1, nfields, fp);
+    });
+    NSDG_CHECK_LAUNCH();
+    return NSDG_OK;
+}
 
 } // namespace
+
+int nsdg_transport_staged_step(nsdg_ctx* ctx, const char* fn, int order, int j0, int j1, double dt, int nfields, const double* const* state,
+    double* const* buf0, double* const* buf1, double* const* out, const double* vx_dg, const double* vy_dg, const double* un_x, const double* un_y,
+    const std::function<int(int)>& after_stage)
+{
+    int rc;
+    if ((rc = check_args(fn, ctx, order, j0, j1, nfields)) != NSDG_OK)
+        return rc;
+    NSDG_CHECK_ARG_IN(fn, state && buf0 && buf1 && out && vx_dg && vy_dg && un_x && un_y, "null pointer");
+    NSDG_CHECK_ARG_IN(fn, ctx->nbounds == 0 || ctx->nbounds == nfields, NSDG_BOUNDS_MISMATCH); // before anything is advanced
+    const int last = order; // SSP Runge-Kutta of order + 1 stages
+    double* const* const buf[2] = { buf0, buf1 };
+    for (int k = 0; k <= last; ++k) {
+        if ((rc = stage_rows(fn, ctx, order, j0, j1, dt, RK[order][k], nfields, state, k == 0 ? state : buf[k - 1], k == last ? out : buf[k], vx_dg,
+                 vy_dg, un_x, un_y))
+            != NSDG_OK)
+            return rc;
+        if (k < last && after_stage && (rc = after_stage(k)) != NSDG_OK)
+            return rc;
+    }
+    if (ctx->nbounds > 0) // the closure of the step (nsdg_transport_bounds_set): one more pass over the new state
+        return limit_rows(fn, ctx, order, j0, j1, nfields, out);
+    return NSDG_OK;
+}
 
 extern "C" {
 
@@ -926,33 +971,14 @@ int nsdg_transport_bounds_set(nsdg_ctx* ctx, int32_t nfields, const nsdg_field_b
 
 int nsdg_transport_limit(nsdg_ctx* ctx, int32_t order, int32_t j0, int32_t j1, int32_t nfields, double* const* phi)
 {
-    NSDG_NEED_GRID(ctx);
-    NSDG_CHECK_ARG(order >= 0 && order <= 2, "order must be 0, 1 or 2");
-    NSDG_CHECK_ARG(0 <= j0 && j0 <= j1 && j1 <= ctx->ny, "row range outside the local array");
-    NSDG_CHECK_ARG(nfields >= 1 && nfields <= MAXF && phi, "nfields must be 1..4");
+    if (int rc = check_args(__func__, ctx, order, j0, j1, nfields))
+        return rc;
+    NSDG_CHECK_ARG(phi, "nfields must be 1..4"); // a missing list is reported as a list of no fields
     if (ctx->nbounds == 0) {
         nsdg_set_error("nsdg_transport_limit: no bounds set (nsdg_transport_bounds_set)");
         return NSDG_ERR_STATE;
     }
-    FieldPtrs fp;
-    NSDG_CHECK_ARG(bounds_into(ctx, nfields, fp), NSDG_BOUNDS_MISMATCH);
-    for (int f = 0; f < MAXF; ++f) {
-        const int s = f < nfields ? f : 0;
-        NSDG_CHECK_ARG(phi[s] != nullptr, "null field pointer");
-        fp.phi0[f] = fp.phis[f] = fp.out[f] = phi[s];
-    }
-    if (j0 == j1)
-        return NSDG_OK;
-    NSDG_CHECK_HIP(hipSetDevice(ctx->device));
-    const dim3 block(64, 4), grid(nsdg_div_up(ctx->nx, 64), nsdg_div_up(j1 - j0, 4));
-    if (order == 0)
-        hipLaunchKernelGGL(transport_limit_kernel<0>, grid, block, 0, ctx->stream, ctx->nx, ctx->ny, j0, j1, nfields, fp);
-    else if (order == 1)
-        hipLaunchKernelGGL(transport_limit_kernel<1>, grid, block, 0, ctx->stream, ctx->nx, ctx->ny, j0, j1, nfields, fp);
-    else
-        hipLaunchKernelGGL(transport_limit_kernel<2>, grid, block, 0, ctx->stream, ctx->nx, ctx->ny, j0, j1, nfields, fp);
-    NSDG_CHECK_LAUNCH();
-    return NSDG_OK;
+    return limit_rows(__func__, ctx, order, j0, j1, nfields, phi);
 }
 
 int nsdg_transport_variant_set(nsdg_ctx* ctx, int32_t variant, int32_t strip_rows)
@@ -969,17 +995,14 @@ int nsdg_transport_variant_set(nsdg_ctx* ctx, int32_t variant, int32_t strip_row
 int nsdg_prepare_advection(nsdg_ctx* ctx, int32_t order, const double* u, const double* v, double* vx_dg, double* vy_dg,
     double* un_x, double* un_y)
 {
-    NSDG_NEED_GRID(ctx);
-    NSDG_CHECK_ARG(order >= 0 && order <= 2, "order must be 0, 1 or 2");
+    if (int rc = check_args(__func__, ctx, order, 0, 0, 1))
+        return rc;
     NSDG_CHECK_ARG(u && v && vx_dg && vy_dg && un_x && un_y, "null field pointer");
     NSDG_CHECK_HIP(hipSetDevice(ctx->device));
     const dim3 block(64, 4), grid(nsdg_div_up(ctx->nx, 64), nsdg_div_up(ctx->ny, 4));
-    if (order == 0)
-        hipLaunchKernelGGL(prepare_advection_kernel<0>, grid, block, 0, ctx->stream, ctx->nx, ctx->ny, u, v, vx_dg, vy_dg, un_x, un_y);
-    else if (order == 1)
-        hipLaunchKernelGGL(prepare_advection_kernel<1>, grid, block, 0, ctx->stream, ctx->nx, ctx->ny, u, v, vx_dg, vy_dg, un_x, un_y);
-    else
-        hipLaunchKernelGGL(prepare_advection_kernel<2>, grid, block, 0, ctx->stream, ctx->nx, ctx->ny, u, v, vx_dg, vy_dg, un_x, un_y);
+    nsdg_with_order(order, [&](auto O) {
+        hipLaunchKernelGGL(prepare_advection_kernel<decltype(O)::value>, grid, block, 0, ctx->stream, ctx->nx, ctx->ny, u, v, vx_dg, vy_dg, un_x, un_y);
+    });
     NSDG_CHECK_LAUNCH();
     return NSDG_OK;
 }
@@ -988,93 +1011,49 @@ int nsdg_transport_stage(nsdg_ctx* ctx, int32_t order, int32_t j0, int32_t j1, d
     const double* const* phi0, const double* const* phis, double* const* out, const double* vx_dg, const double* vy_dg,
     const double* un_x, const double* un_y)
 {
-    NSDG_NEED_GRID(ctx);
-    NSDG_CHECK_ARG(order >= 0 && order <= 2, "order must be 0, 1 or 2");
-    NSDG_CHECK_ARG(0 <= j0 && j0 <= j1 && j1 <= ctx->ny, "row range outside the local array");
-    NSDG_CHECK_ARG(nfields >= 1 && nfields <= MAXF, "nfields must be 1..4");
+    if (int rc = check_args(__func__, ctx, order, j0, j1, nfields))
+        return rc;
     NSDG_CHECK_ARG(phi0 && phis && out && vx_dg && vy_dg && un_x && un_y, "null pointer");
-    if (j0 == j1)
-        return NSDG_OK;
-    FieldPtrs fp;
-    for (int f = 0; f < MAXF; ++f) {
-        const int s = f < nfields ? f : 0;
-        NSDG_CHECK_ARG(phi0[s] && phis[s] && out[s], "null field pointer");
-        NSDG_CHECK_ARG(out[s] != phis[s], "out must not alias phis (neighbours are read)");
-        fp.phi0[f] = phi0[s];
-        fp.phis[f] = phis[s];
-        fp.out[f] = out[s];
-        fp.lo[f] = fp.hi[f] = 0., fp.cap[f] = 0;
-    }
-    fp.limit = 0; // a bare stage: the closure belongs to the END of a step (nsdg_transport_limit, or the step entry points)
-    NSDG_CHECK_HIP(hipSetDevice(ctx->device));
-    return stage_dispatch(ctx, order, j0, j1, dt, a, b, nfields, fp, vx_dg, vy_dg, un_x, un_y);
+    return stage_rows(__func__, ctx, order, j0, j1, dt, RkStage { a, b }, nfields, phi0, phis, out, vx_dg, vy_dg, un_x, un_y);
 }
 
 int nsdg_transport_step(nsdg_ctx* ctx, int32_t order, double dt, int32_t nfields, double* const* phi, const double* vx_dg,
     const double* vy_dg, const double* un_x, const double* un_y, double* scratch)
 {
-    NSDG_NEED_GRID(ctx);
-    NSDG_CHECK_ARG(order >= 0 && order <= 2, "order must be 0, 1 or 2");
-    NSDG_CHECK_ARG(nfields >= 1 && nfields <= MAXF, "nfields must be 1..4");
+    if (int rc = check_args(__func__, ctx, order, 0, 0, nfields))
+        return rc;
     NSDG_CHECK_ARG(phi && scratch && vx_dg && vy_dg && un_x && un_y, "null pointer");
-    NSDG_CHECK_ARG(ctx->nbounds == 0 || ctx->nbounds == nfields, NSDG_BOUNDS_MISMATCH); // before anything is advanced
-    const int nc = order == 0 ? 1 : (order == 1 ? 3 : 6);
-    const long M = (long)nc * ctx->nx * ctx->ny;
-    const double *p0[MAXF], *ps[MAXF];
-    double *t1[MAXF], *t2[MAXF], *ph[MAXF];
+    const long M = (long)nsdg_nc(order) * ctx->nx * ctx->ny;
+    double *t1[MAXF], *t2[MAXF];
     for (int f = 0; f < nfields; ++f) {
-        NSDG_CHECK_ARG(phi[f] != nullptr, "null field pointer");
-        ph[f] = phi[f];
         t1[f] = scratch + (2 * f) * M;
         t2[f] = scratch + (2 * f + 1) * M;
-        p0[f] = phi[f];
     }
-    const int ny = ctx->ny;
-    int rc;
-    // SSP Runge-Kutta of order (order+1): Euler / Heun / Shu-Osher RK3; the last stage writes phi
+    // in place: the LAST stage writes phi itself -- it reads phi only as phi0, at the element it writes (the neighbours come from a
+    // stage buffer) -- except at order 0, whose only stage reads the neighbours in phi: it writes t1, copied back
+    if (int rc = nsdg_transport_staged_step(ctx, __func__, order, 0, ctx->ny, dt, nfields, phi, t1, t2, order == 0 ? t1 : phi, vx_dg, vy_dg, un_x,
+            un_y, nullptr))
+        return rc;
     if (order == 0) {
-        for (int f = 0; f < nfields; ++f) ps[f] = phi[f];
-        if ((rc = nsdg_transport_stage(ctx, order, 0, ny, dt, 0., 1., nfields, p0, ps, t1, vx_dg, vy_dg, un_x, un_y))) return rc;
         for (int f = 0; f < nfields; ++f)
             NSDG_CHECK_HIP(hipMemcpyAsync(phi[f], t1[f], M * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    } else if (order == 1) {
-        for (int f = 0; f < nfields; ++f) ps[f] = phi[f];
-        if ((rc = nsdg_transport_stage(ctx, order, 0, ny, dt, 0., 1., nfields, p0, ps, t1, vx_dg, vy_dg, un_x, un_y))) return rc;
-        // the LAST stage writes phi itself: it reads phi only as phi0, at the element it writes (the neighbours come from t1)
-        for (int f = 0; f < nfields; ++f) ps[f] = t1[f];
-        if ((rc = nsdg_transport_stage(ctx, order, 0, ny, dt, 0.5, 0.5, nfields, p0, ps, ph, vx_dg, vy_dg, un_x, un_y))) return rc;
-    } else {
-        for (int f = 0; f < nfields; ++f) ps[f] = phi[f];
-        if ((rc = nsdg_transport_stage(ctx, order, 0, ny, dt, 0., 1., nfields, p0, ps, t1, vx_dg, vy_dg, un_x, un_y))) return rc;
-        for (int f = 0; f < nfields; ++f) ps[f] = t1[f];
-        if ((rc = nsdg_transport_stage(ctx, order, 0, ny, dt, 0.75, 0.25, nfields, p0, ps, t2, vx_dg, vy_dg, un_x, un_y))) return rc;
-        for (int f = 0; f < nfields; ++f) ps[f] = t2[f];
-        if ((rc = nsdg_transport_stage(ctx, order, 0, ny, dt, 1. / 3., 2. / 3., nfields, p0, ps, ph, vx_dg, vy_dg, un_x, un_y))) return rc;
     }
-    if (ctx->nbounds > 0) // the closure of the step (nsdg_transport_bounds_set): one more pass over the new state
-        return nsdg_transport_limit(ctx, order, 0, ny, nfields, phi);
     return NSDG_OK;
 }
 
 int nsdg_transport_step_oop_rows(nsdg_ctx* ctx, int32_t order, int32_t j0, int32_t j1, double dt, int32_t nfields, const double* const* phi_in,
     double* const* phi_out, const double* vx_dg, const double* vy_dg, const double* un_x, const double* un_y)
 {
-    NSDG_NEED_GRID(ctx);
-    NSDG_CHECK_ARG(order >= 0 && order <= 2, "order must be 0, 1 or 2");
-    NSDG_CHECK_ARG(0 <= j0 && j0 <= j1 && j1 <= ctx->ny, "row range outside the local array");
-    NSDG_CHECK_ARG(nfields >= 1 && nfields <= MAXF, "nfields must be 1..4");
+    if (int rc = check_args(__func__, ctx, order, j0, j1, nfields))
+        return rc;
     NSDG_CHECK_ARG(phi_in && phi_out && vx_dg && vy_dg && un_x && un_y, "null pointer");
     FieldPtrs fp;
-    for (int f = 0; f < MAXF; ++f) {
-        const int s = f < nfields ? f : 0;
-        NSDG_CHECK_ARG(phi_in[s] && phi_out[s], "null field pointer");
-        fp.phi0[f] = fp.phis[f] = phi_in[s];
-        fp.out[f] = phi_out[s];
-    }
+    if (int rc = bind_fields(__func__, ctx, nfields, phi_in, phi_in, phi_out, true, fp)) // the closure runs in the epilogue of the march
+        return rc;
     {
         // the fields of a launch are advanced one after the other by waves that run concurrently: an output that overlaps ANY
         // input (not only its own) or another output would be read half-written -- compared as ranges of nc nx ny doubles
-        const long len = (long)(order == 0 ? 1 : (order == 1 ? 3 : 6)) * ctx->nx * ctx->ny;
+        const long len = (long)nsdg_nc(order) * ctx->nx * ctx->ny;
         auto overlap = [len](const double* a, const double* b) { return a < b + len && b < a + len; };
         for (int i = 0; i < nfields; ++i) {
             for (int j = 0; j < nfields; ++j)
@@ -1084,15 +1063,10 @@ int nsdg_transport_step_oop_rows(nsdg_ctx* ctx, int32_t order, int32_t j0, int32
                 NSDG_CHECK_ARG(!overlap(phi_out[i], phi_out[j]), "two phi_out arrays alias or overlap");
         }
     }
-    NSDG_CHECK_ARG(bounds_into(ctx, nfields, fp), NSDG_BOUNDS_MISMATCH); // the closure runs in the epilogue of the march
     if (j0 == j1)
         return NSDG_OK;
     NSDG_CHECK_HIP(hipSetDevice(ctx->device));
-    switch (order) {
-    case 0: return launch_march<0>(ctx, j0, j1, dt, nfields, fp, vx_dg, vy_dg, un_x, un_y);
-    case 1: return launch_march<1>(ctx, j0, j1, dt, nfields, fp, vx_dg, vy_dg, un_x, un_y);
-    default: return launch_march<2>(ctx, j0, j1, dt, nfields, fp, vx_dg, vy_dg, un_x, un_y);
-    }
+    return nsdg_with_order(order, [&](auto O) { return launch_march<decltype(O)::value>(ctx, j0, j1, dt, nfields, fp, vx_dg, vy_dg, un_x, un_y); });
 }
 
 int nsdg_transport_step_oop(nsdg_ctx* ctx, int32_t order, double dt, int32_t nfields, const double* const* phi_in, double* const* phi_out,

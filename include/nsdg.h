@@ -55,7 +55,8 @@ extern "C" {
 /* 6: a pipeline wait that gives up is an error status.  Since then the ABI has only grown, without a new number: nsdg_concentration_max,
  * nsdg_substep_count and nsdg_comm_max_f64 (sub-stepping of the model time step), nsdg_forcing_sample (forcing from a file) and
  * nsdg_tracer_weight / nsdg_tracer_recover (column state transport) and nsdg_phase_timing_set / nsdg_phase_mark / nsdg_phase_times (per-phase
- * device timing) and nsdg_land_mask_set / nsdg_land_clear / nsdg_land_clear_nodes (land mask) are additions; nothing that existed changed. */
+ * device timing) and nsdg_land_mask_set / nsdg_land_clear / nsdg_land_clear_nodes (land mask) and nsdg_bbm_default_params / nsdg_bbm_params_set /
+ * nsdg_bbm_prepare / nsdg_bbm_iterate / nsdg_bbm_substep_count (brittle rheology) are additions; nothing that existed changed. */
 #define NSDG_ABI_VERSION 6
 
 typedef enum {
@@ -555,6 +556,80 @@ int nsdg_mevp_occupancy_set(nsdg_ctx* ctx, int32_t waves_per_simd);
 int nsdg_land_mask_set(nsdg_ctx* ctx, const uint8_t* land);
 int nsdg_land_clear(nsdg_ctx* ctx, int32_t j0, int32_t j1, int32_t nplanes, double* f);
 int nsdg_land_clear_nodes(nsdg_ctx* ctx, double* u, double* v);
+
+/* ---- brittle rheology: the brittle Bingham-Maxwell (BBM) sub-cycle (csrc/bbm.hip, csrc/bbm_common.h) ------------
+ * A second rheology beside mEVP: damage, a Mohr-Coulomb envelope, Maxwell relaxation.  No counterpart in the reference snapshot; built from
+ * the published formulation (Olason et al. 2022, "A new brittle rheology and numerical framework for large-scale sea-ice models", JAMES;
+ * Dansereau et al. 2016) -- parity unpinned like the rest of the dynamics.  The DEFAULTS of nsdg_bbm_default_params follow the publication
+ * as far as it could be recalled when this was written; no source at hand confirmed them: check them against the paper before relying on them.
+ *
+ * State.  sigma: three DG8 stress components in Pa (NOT thickness-integrated), the tiled arrays the mEVP sub-cycle uses.  D: damage in
+ * [0, 1], a DG2 field of 6 coefficient planes (plane layout), updated in the sub-cycle and carried by the transport as a third field
+ * with the bounds (0, 1, cap_mean = 0).
+ *
+ * Per model step, nsdg_bbm_prepare writes what the sub-cycle does not change: three tiled 9-component arrays with the layout of pg,
+ *     hg_q = max(H(q), 0),   eg_q = exp(-C (1 - clamp(A(q), 0, 1))),   pm_q = p0 hg_q sqrt(hg_q) eg_q
+ * (C = nsdg_mevp_params.compaction; the Gauss points and clamps of nsdg_ice_strength), and the caller packs the nodal coefficients with
+ * nsdg_mevp_prepare(dt = dt_s, ..., u0 = v0 = an array of zeros): nothing in the packing changes, the term (m / dt) u0 is exactly 0,
+ * and ice-free nodes, free drift and land nodes cost the BBM pass nothing new.
+ *
+ * Per sub-iteration and Gauss point q, in THIS order (dt_s = the packing's time step; the strain rate from u_old, v_old; sigma_q and d
+ * from the old coefficients, the damage with coefficients 6 and 7 zero):
+ *   1. clamp and heal      d = min(max(d, 0), d_max);   d <- max(0, d - dt_s / t_heal)
+ *   2. stiffness           x = (1 - d) eg_q;   E = young x;   lambda = lambda0 x^(n - 1),  n = relax_exponent, by repeated multiplication
+ *   3. compressive limit   from the OLD stress: sigma_n = (sigma11 + sigma22) / 2;   Pt = sigma_n < 0 ? min(1, -pm_q / sigma_n) : 0
+ *   4. relaxation          m = min(1 - 1e-12, lambda / (lambda + dt_s (1 - Pt)))
+ *   5. predictor           k1 = 1 / (1 + nu), k2 = nu / (1 - nu^2), tr = e11 + e22:
+ *                          sigma11 <- (sigma11 + dt_s E (k1 e11 + k2 tr)) m;   sigma22 likewise;   sigma12 <- (sigma12 + dt_s E k1 e12) m
+ *   6. Mohr-Coulomb        on the new stress: sigma_n as above, sigma_s = sqrt((sigma11 - sigma22)^2 / 4 + sigma12^2),
+ *                          den = sigma_s + tan_phi sigma_n,  c = cohesion_lab sqrt(0.1 / h), h = min(hx, hy) (formed on the host per launch);
+ *                          sigma_n < -N (N = compr_strength): d_c = -N / sigma_n;   else den > c: d_c = c / den;   else d_c = 1
+ *   7. damage              r = min(1, dt_s sqrt(E) / (h sqrt(2 (1 + nu) rho_ice)))  (the sub-step over the time an elastic shear wave needs
+ *                          to cross a cell);   f = (1 - d_c) r;   d <- min(d_max, d + (1 - d) f);   sigma <- sigma (1 - f), all three
+ *   8. projection          S_out = Proj8(sigma_q);   D_out = coefficients 0..5 of Proj8(d_q) (the basis is orthogonal: the DG2 projection)
+ *   9. momentum            the nodal contributions of Proj8(hg_q sigma_q) -- the momentum equation takes the thickness-integrated stress --
+ *                          enter the mEVP node update with K1 = K2 = rho_ice / dt_s:
+ *                          u' = ((m / dt_s) u + a tau_x + c_d u_o + m f_c (v - v_o) + div_x / M) / (m / dt_s + c_d),
+ *                          explicit in stress and Coriolis, implicit in ocean drag.
+ * The scheme is discontinuous in two places only: Pt jumps at sigma_n = 0 and d_c jumps at sigma_n = -N; the envelope test is continuous
+ * at den = c.  alpha, beta and aevp_* of nsdg_mevp_params are ignored by the BBM pass (an adaptive context may run it); rho_ice, fc, the
+ * drags and compaction are those of nsdg_mevp_params.
+ *
+ * nsdg_bbm_params_set: NSDG_ERR_ARG for a non-finite member, relax_exponent < 1, d_max outside (0, 1) or a non-positive young, lambda0 or
+ *   t_heal.
+ * nsdg_bbm_iterate: one sub-iteration, the stress and damage on element rows [k0, j1), the velocity of the nodes owned by rows [j0, j1);
+ *   the row conventions of nsdg_mevp_iterate (k0 == j0 - 1 or k0 == j0 == 0).  Stress AND damage are out of place: a row may be updated
+ *   redundantly by two owners with bit-identical results, so a row block needs no exchange of D inside the sub-cycle.  A null pointer, an
+ *   *_out that aliases its *_in or a bad range: NSDG_ERR_ARG; before a packing: NSDG_ERR_STATE.  The instantiation that holds land nodes
+ *   at 0 is chosen from what the packing saw, as for the mEVP passes; nsdg_mevp_strip_rows_set applies (results do not depend on it).
+ * nsdg_bbm_substep_count: host only, the elastic-wave rule stated once: nsub = max(1, ceil(dt c_E / (courant h))), c_E = sqrt(young /
+ *   (rho_ice (1 - nu^2))).  If that exceeds max_nsub: NSDG_ERR_ARG with the needed value in the message; the result is never capped.
+ *   NSDG_BBM_COURANT, the default the hosts pass: 0.25, measured (profiles/r09_bbm.md).  On the 64 x 64 box test at 1 km (full undamaged
+ *   cover, cyclone wind, 200 model steps of 120 s) all of 1, 0.7, 0.5, 0.35, 0.25 stay finite and below 1 m/s, but only 0.35 and 0.25 agree
+ *   with each other (largest speed 1.24e-4 / 1.25e-4 m/s, no damage); at 0.5 and above the sub-cycle rings at element scale, the noise
+ *   reaches the envelope and breaks the cover (damage up to 0.86, speeds 100 to 1000 times larger): finite, and wrong.  0.35 is the
+ *   largest value that works, 0.25 the next smaller one of the list. */
+typedef struct {
+    double young; /* Pa, undamaged elastic modulus */
+    double nu; /* Poisson ratio */
+    double p0; /* scale of the compressive limit pm = p0 h^(3/2) exp(-C (1 - a)) */
+    double lambda0; /* s, undamaged relaxation time */
+    double tan_phi; /* internal friction */
+    double cohesion_lab; /* Pa, cohesion at the laboratory scale of 0.1 m */
+    double compr_strength; /* Pa, N */
+    double t_heal; /* s */
+    double d_max; /* in (0, 1) */
+    int32_t relax_exponent; /* n >= 1 */
+    int32_t reserved;
+} nsdg_bbm_params;
+#define NSDG_BBM_COURANT 0.25
+void nsdg_bbm_default_params(nsdg_bbm_params* p);
+int nsdg_bbm_params_set(nsdg_ctx* ctx, const nsdg_bbm_params* p);
+int nsdg_bbm_prepare(nsdg_ctx* ctx, int32_t j0, int32_t j1, const double* H, const double* A, double* hg, double* eg, double* pm);
+int nsdg_bbm_iterate(nsdg_ctx* ctx, int32_t k0, int32_t j0, int32_t j1, const double* s11_in, const double* s12_in, const double* s22_in,
+    double* s11_out, double* s12_out, double* s22_out, const double* D_in, double* D_out, const double* u_old, const double* v_old,
+    double* u_new, double* v_new, const double* packed, const double* hg, const double* eg, const double* pm);
+int nsdg_bbm_substep_count(const nsdg_bbm_params* p, double rho_ice, double h, double dt, double courant, int32_t max_nsub, int32_t* nsub);
 
 /* ---- row-block decomposition: ghost-row exchange (SURVEY.md section 8(b) "nsdg_halo_exchange", 8(e)) ----------
  * The reference is a single-process, single-thread program; these entry points have no

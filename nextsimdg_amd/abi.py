@@ -34,6 +34,13 @@ class MevpParams(C.Structure):
         "alpha", "beta", "h_min", "min_conc", "min_thick", "aevp_c", "aevp_alpha_min")]
 
 
+class BbmParams(C.Structure):
+    """nsdg_bbm_params: the brittle rheology (include/nsdg.h "brittle rheology")"""
+    _fields_ = [(n, C.c_double) for n in (
+        "young", "nu", "p0", "lambda0", "tan_phi", "cohesion_lab", "compr_strength", "t_heal", "d_max")] + [
+        ("relax_exponent", C.c_int32), ("reserved", C.c_int32)]
+
+
 SUBCYCLE_ADAPTIVE, SUBCYCLE_KEEP_ALPHA, SUBCYCLE_KEEP_DELTA_MIN, SUBCYCLE_ADAPTIVE_CONVERGED = 0, 1, 2, 3  # modes of nsdg_mevp_stable_params
 
 
@@ -119,6 +126,11 @@ SYMBOLS = {
     "nsdg_land_mask_set": (C.c_int, [VP, VP]),
     "nsdg_land_clear": (C.c_int, [VP, I32, I32, I32, VP]),
     "nsdg_land_clear_nodes": (C.c_int, [VP, VP, VP]),
+    "nsdg_bbm_default_params": (None, [C.POINTER(BbmParams)]),
+    "nsdg_bbm_params_set": (C.c_int, [VP, C.POINTER(BbmParams)]),
+    "nsdg_bbm_prepare": (C.c_int, [VP, I32, I32] + [VP] * 5),
+    "nsdg_bbm_iterate": (C.c_int, [VP, I32, I32, I32] + [VP] * 16),
+    "nsdg_bbm_substep_count": (C.c_int, [C.POINTER(BbmParams), D, D, D, D, I32, C.POINTER(I32)]),
     "nsdg_mevp_variant_set": (C.c_int, [VP, I32]),
     "nsdg_prepare_advection": (C.c_int, [VP, I32] + [VP] * 6),
     "nsdg_transport_variant_set": (C.c_int, [VP, I32, I32]),
@@ -230,6 +242,31 @@ def substep_count(p, amax, h, dt, courant=SUBSTEP_COURANT, max_substeps=16):
     if rc != 0:
         raise NsdgError("nsdg error %d: %s" % (rc, lib.nsdg_last_error().decode()))
     return int(n.value), float(c.value)
+
+
+BBM_COURANT = 0.25  # NSDG_BBM_COURANT: the default of the elastic-wave rule (include/nsdg.h "brittle rheology"; profiles/r09_bbm.md)
+
+
+def bbm_default_params(**kw):
+    """nsdg_bbm_default_params with members replaced by keyword (host only)"""
+    p = BbmParams()
+    load_library().nsdg_bbm_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise NsdgError("unknown BBM parameter " + k)
+        setattr(p, k, v)
+    return p
+
+
+def bbm_substep_count(p, rho_ice, h, dt, courant=BBM_COURANT, max_nsub=100000):
+    """nsdg_bbm_substep_count: the number of sub-iterations of a model step dt that keeps the elastic wave of the undamaged ice within
+    `courant` cells of size h per sub-iteration; NsdgError (with the needed number) if it exceeds max_nsub"""
+    lib = load_library()
+    n = I32(0)
+    rc = lib.nsdg_bbm_substep_count(C.byref(p), float(rho_ice), float(h), float(dt), float(courant), int(max_nsub), C.byref(n))
+    if rc != 0:
+        raise NsdgError("nsdg error %d: %s" % (rc, lib.nsdg_last_error().decode()))
+    return int(n.value)
 
 
 def creep_percent_per_day(p):
@@ -827,6 +864,39 @@ class Context:
     def bind_mevp_iterate(self, k0, j0, j1, s_in, s_out, uv_old, uv_new, packed, pg):
         """pre-validated, pre-marshalled form of mevp_iterate for inner loops (_bind_mevp_pass)"""
         return self._bind_mevp_pass(self.lib.nsdg_mevp_iterate, (k0, j0, j1), s_in, s_out, uv_old, uv_new, packed, pg)
+
+    # ---- brittle rheology (include/nsdg.h "brittle rheology"; csrc/bbm.hip)
+    def bbm_default_params(self, **kw):
+        return bbm_default_params(**kw)
+
+    def set_bbm_params(self, p):
+        self._call(self.lib.nsdg_bbm_params_set(self.h, C.byref(p)))
+
+    def bbm_prepare(self, H, A, hg, eg, pm, j0=0, j1=None):
+        """nsdg_bbm_prepare: hg = max(H, 0), eg = exp(-C (1 - clamp(A))), pm = p0 hg^(3/2) eg at the Gauss points of rows [j0, j1) (tiled)"""
+        _check_f64(H, A, hg, eg, pm)
+        self._call(self.lib.nsdg_bbm_prepare(self.h, j0, self.ny if j1 is None else j1, *[_ptr(t) for t in (H, A, hg, eg, pm)]))
+
+    def bbm_iterate(self, k0, j0, j1, s_in, s_out, d_in, d_out, uv_old, uv_new, packed, gauss):
+        """one BBM sub-iteration: stress and damage on rows [k0, j1) (out of place), velocity of the nodes owned by rows [j0, j1);
+        gauss = (hg, eg, pm) of bbm_prepare"""
+        self.bind_bbm_iterate(k0, j0, j1, s_in, s_out, d_in, d_out, uv_old, uv_new, packed, gauss)()
+
+    def bind_bbm_iterate(self, k0, j0, j1, s_in, s_out, d_in, d_out, uv_old, uv_new, packed, gauss):
+        """pre-validated, pre-marshalled form of bbm_iterate for inner loops (as bind_mevp_iterate)"""
+        ts = [s_in[0], s_in[1], s_in[2], s_out[0], s_out[1], s_out[2], d_in, d_out, uv_old[0], uv_old[1], uv_new[0], uv_new[1], packed,
+              gauss[0], gauss[1], gauss[2]]
+        _check_f64(*ts)
+        fn = self.lib.nsdg_bbm_iterate
+        args = (self.h, I32(k0), I32(j0), I32(j1)) + tuple(_ptr(t) for t in ts)
+
+        def call():
+            rc = fn(*args)
+            if rc != 0:
+                self._call(rc)
+            return ts is None  # the tensors must outlive the binding
+
+        return call
 
     def mevp_iterate2(self, j0, j1, s_in, s_out, uv_old, uv_new, packed, pg):
         """two sub-iterations in one pass on the owned rows [j0, j1) (variant 2)"""

@@ -137,6 +137,7 @@ int nsdg_ctx_create(int device_id, void* stream, nsdg_ctx** out)
     c->stream = (hipStream_t)stream;
     nsdg_column_default_params(&c->column);
     nsdg_mevp_default_params(&c->mevp);
+    nsdg_bbm_default_params(&c->bbm);
     c->nx = c->ny = 0;
     c->row0 = c->ny_global = 0;
     c->hx = c->hy = 0.;

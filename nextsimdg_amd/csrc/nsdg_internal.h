@@ -17,6 +17,7 @@ struct nsdg_ctx {
     hipStream_t stream;
     nsdg_column_params column;
     nsdg_mevp_params mevp;
+    nsdg_bbm_params bbm; // brittle rheology (bbm.hip)
     int nx, ny; // local element array
     int row0, ny_global; // its placement in the global domain (analytic forcing providers); ny_global 0 = single domain
     double hx, hy;

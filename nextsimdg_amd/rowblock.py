@@ -273,10 +273,37 @@ class DynamicsCore:
     TRANSPORTED = ("H", "A")
 
     LAND_OPS = ("set_land_mask", "land_clear", "land_clear_nodes")
+    BBM_OPS = ("bbm_prepare", "bbm_iterate")
+    DAMAGE_BOUNDS = (0.0, 1.0, False)  # the damage D of the brittle rheology: in [0, 1], no cap of the cell mean
 
     def __init__(self, ops, blk, hx, hy, dt, nsub, device, exchanger=None, overlap=True, native=False, use_graph=False, closure=True,
-                 phase_timing=False, land=None):
+                 phase_timing=False, land=None, rheology="mevp", bbm=None):
         self.ops, self.blk, self.hx, self.hy, self.dt, self.nsub = ops, blk, hx, hy, dt, nsub
+        # rheology: "mevp", or "bbm" -- the brittle Bingham-Maxwell sub-cycle (include/nsdg.h "brittle rheology"):
+        # nsub explicit sub-iterations of dt / nsub, a damage field D updated in the sub-cycle and advected with H and A.  bbm: an
+        # abi.BbmParams set on the ops object (None: whatever the ops object holds, the library's defaults on a new context)
+        if rheology not in ("mevp", "bbm"):
+            raise ValueError("rheology must be 'mevp' or 'bbm', got %r" % (rheology,))
+        self.rheology = rheology
+        if rheology == "bbm":
+            if native:
+                raise ValueError("rheology='bbm' is not built in the native row-block plan (nsdg_rb_mevp_*): use native=False")
+            if blk.world > 1 and (blk.depth_below, blk.depth_above) != (1, 1):
+                raise ValueError("rheology='bbm' runs one sub-iteration per pass: a row block needs the ghost depth (1, 1), got (%d, %d)"
+                                 % (blk.depth_below, blk.depth_above))
+            missing = [m for m in self.BBM_OPS if not callable(getattr(ops, m, None))]
+            if missing:
+                raise ValueError("rheology='bbm' needs an ops object with the BBM calls of the C ABI (abi.Context); %s has no %s"
+                                 % (type(ops).__name__, ", ".join(missing)))
+            if len(self.TRANSPORTED) + 1 > 4:  # NSDG_RB_MAX_FIELDS
+                raise ValueError("rheology='bbm' with advect_column_state=True would advect %d fields (%s and D); a transport step carries at most 4"
+                                 % (len(self.TRANSPORTED) + 1, ", ".join(self.TRANSPORTED)))
+            self.TRANSPORTED = self.TRANSPORTED + ("D",)
+            self.BOUNDS = self.BOUNDS + (self.DAMAGE_BOUNDS,)
+            if bbm is not None:
+                ops.set_bbm_params(bbm)
+        elif bbm is not None:
+            raise ValueError("bbm= parameters need rheology='bbm'")
         # land: bool array [ny_global, nx] of the WHOLE domain (True = land; include/nsdg.h "land mask"): the nodes of
         # land elements hold u = v = 0 like the array edge.  This rank keeps its rows, ghost rows included -- the mask is static, nothing
         # is exchanged -- and sets them on the ops object whenever it sets the grid
@@ -327,6 +354,8 @@ class DynamicsCore:
             if variant is not None and variant >= v and (blk.world == 1 or deep):
                 self.per_pass = v
                 break
+        if rheology == "bbm":  # multi-iteration passes of the brittle sub-cycle are not built
+            self.per_pass = 1
         self.two_per_pass = self.per_pass >= 2  # the ghost zones hold stress rows as well as velocity rows
         self.group_passes = blk.depth_below // self.per_pass if (self.per_pass >= 2 and blk.world > 1) else 1  # passes between two exchanges
         self.halo = exchanger if exchanger is not None else HaloExchanger(blk)
@@ -346,6 +375,11 @@ class DynamicsCore:
         self.adv = (z(6, ny, nx), z(6, ny, nx), z(3, ny, nx + 1), z(3, ny + 1, nx))
         self.t1 = [z(6, ny, nx) for _ in range(nf)]
         self.t2 = [z(6, ny, nx) for _ in range(nf)]
+        if rheology == "bbm":
+            # the damage ping-pong of the sub-cycle, the three per-step Gauss arrays (layout of pg) and the zeros the packing takes as u0, v0
+            self.Db = z(6, ny, nx)
+            self.hg, self.eg, self.pm = (ops.private_zeros(9, ny, nx, device) for _ in range(3))
+            self._zero_nodal = z(*nodal)
         if native:
             self._init_native()
 
@@ -384,8 +418,8 @@ class DynamicsCore:
             self.ops.set_land_mask(None)
         self.land, self._land_on_ops = None, False
 
-    def load_global(self, H, A, uo, vo, ua, va, u=None, v=None):
-        """fill the local arrays (ghost rows included) from global numpy arrays"""
+    def load_global(self, H, A, uo, vo, ua, va, u=None, v=None, D=None):
+        """fill the local arrays (ghost rows included) from global numpy arrays; D: the damage of rheology="bbm" (None: left as it is)"""
         es, ns = self.blk.elem_slice(), self.blk.node_slice()
         put = lambda dst, src: dst.copy_(torch.from_numpy(src).to(dst.device))
         import numpy as np
@@ -397,6 +431,10 @@ class DynamicsCore:
         if u is not None:
             put(self.u, np.ascontiguousarray(u[ns]))
             put(self.v, np.ascontiguousarray(v[ns]))
+        if D is not None:
+            if self.rheology != "bbm":
+                raise ValueError("a damage field needs rheology='bbm'")
+            put(self.D, np.ascontiguousarray(D[:, es]))
         self._clear_land()
 
     def _clear_land(self):
@@ -450,6 +488,12 @@ class DynamicsCore:
         momentum coefficients (one launch); the velocity at the start of the step is read from the current iterate
         (it is only needed inside the packing)"""
         ops, b = self.ops, self.blk
+        if self.rheology == "bbm":
+            # the Gauss arrays of the brittle sub-cycle, and the mEVP packing for the sub-step dt / nsub with u0 = v0 = 0
+            ops.bbm_prepare(self.H, self.A, self.hg, self.eg, self.pm, 0, b.ny)
+            ops.mevp_prepare(self.dt / self.nsub, self.H, self.A, (self.ua, self.va), (self.uo, self.vo), (self._zero_nodal, self._zero_nodal),
+                             self.packed)
+            return
         ops.ice_strength(self.H, self.A, self.pg, 0, b.ny)
         ops.mevp_prepare(self.dt, self.H, self.A, (self.ua, self.va), (self.uo, self.vo), (self.u, self.v), self.packed)
 
@@ -521,6 +565,12 @@ class DynamicsCore:
             self.u, self.ub = self.ub, self.u
             self.v, self.vb = self.vb, self.v
             self.s, self.sb = self.sb, self.s
+            if self.rheology == "bbm":
+                self.D, self.Db = self.Db, self.D
+        if self.rheology == "bbm" and b.world > 1 and self.nsub > 0:
+            # inside the sub-cycle the damage of the ghost row below is recomputed and the ghost row above is never read: one exchange
+            # hands the transport its ghost rows
+            self.halo.element([self.D])
 
     def _ghost_exchange_start(self):
         """ghost zones of the multi-iteration passes, depth (d, d-1) with d = v k: velocity node rows (2d up, 2d-1
@@ -564,15 +614,17 @@ class DynamicsCore:
 
     def _iterate_calls(self, split):
         """the launches of one sub-iteration for the current ping-pong parity, bound once and cached"""
-        key = (self.u.data_ptr(), self.s[0].data_ptr(), split)
+        bbm = self.rheology == "bbm"
+        key = (self.u.data_ptr(), self.s[0].data_ptr(), split) + ((self.D.data_ptr(), self.Db.data_ptr()) if bbm else ())
         calls = self._calls.get(key)
         if calls is not None:
             return calls
         ops, b = self.ops, self.blk
         uv, uvn = (self.u, self.v), (self.ub, self.vb)
-        bind = getattr(ops, "bind_mevp_iterate", None)
+        name = "bbm_iterate" if bbm else "mevp_iterate"
+        bind = getattr(ops, "bind_" + name, None)
         if bind is None:  # ops without a binding fast path (the CPU test stand-in)
-            bind = lambda *a: (lambda: ops.mevp_iterate(*a))
+            bind = lambda *a: (lambda: getattr(ops, name)(*a))
         rng = []
         if not split:
             rng.append((b.k0, b.j0, b.j1))  # k0 = j0 - 1: the ghost row just below is updated redundantly
@@ -585,7 +637,10 @@ class DynamicsCore:
                 rng.append((b.j0 - 1, b.j0, b.j0 + 1))
                 lo = b.j0 + 1
             rng.append((lo - 1 if lo > 0 else 0, lo, hi))  # interior, launched after the exchange is posted
-        calls = [bind(k0, j0, j1, self.s, self.sb, uv, uvn, self.packed, self.pg) for (k0, j0, j1) in rng]
+        if bbm:
+            calls = [bind(k0, j0, j1, self.s, self.sb, self.D, self.Db, uv, uvn, self.packed, (self.hg, self.eg, self.pm)) for (k0, j0, j1) in rng]
+        else:
+            calls = [bind(k0, j0, j1, self.s, self.sb, uv, uvn, self.packed, self.pg) for (k0, j0, j1) in rng]
         self._calls[key] = calls
         return calls
 
@@ -676,7 +731,7 @@ class DynamicsCore:
     def owned(self, f):
         """owned element rows of a DG array / owned node rows of a nodal array (for gathering)"""
         b = self.blk
-        if any(f is x for x in self.s + self.sb + [self.pg]):
+        if any(f is x for x in self.s + self.sb + [self.pg] + ([self.hg, self.eg, self.pm] if self.rheology == "bbm" else [])):
             return self.ops.private_rows(f, b.j0, b.j1)
         if f.dim() == 3:
             return f[:, b.j0:b.j1]
@@ -698,6 +753,8 @@ class DynamicsCore:
             out[name] = self.owned(f).detach().cpu().numpy().copy()
         for name, f in zip(("s11", "s12", "s22"), self.s):
             out[name] = self.ops.private_to_planes(f, nx)[:, b.j0:b.j1].detach().cpu().numpy().copy()
+        if self.rheology == "bbm":
+            out["D"] = self.owned(self.D).detach().cpu().numpy().copy()
         return out
 
     def load_state_dict(self, state):
@@ -716,6 +773,10 @@ class DynamicsCore:
         put(self.v, state["v"][ns])
         for f, name in zip(self.s, ("s11", "s12", "s22")):
             f.copy_(self.ops.planes_to_private(torch.from_numpy(np.ascontiguousarray(state[name][:, es])).to(f.device)))
+        if self.rheology == "bbm":
+            if "D" not in state:
+                raise ValueError("a core with rheology='bbm' needs the damage D in the state")
+            put(self.D, state["D"][:, es])
         self._clear_land()
 
     @staticmethod
@@ -725,8 +786,8 @@ class DynamicsCore:
 
         states = sorted(states, key=lambda s: s["rows"][0])
         out = {"rows": (states[0]["rows"][0], states[-1]["rows"][1]), "ny_global": states[0]["ny_global"], "nx": states[0]["nx"]}
-        for k in ("H", "A", "S", "s11", "s12", "s22"):
-            if k in states[0]:  # S: the snow of a CoupledCore with advect_column_state
+        for k in ("H", "A", "S", "D", "s11", "s12", "s22"):
+            if k in states[0]:  # S: the snow of a CoupledCore with advect_column_state; D: the damage of rheology="bbm"
                 out[k] = np.concatenate([s[k] for s in states], axis=1)
         for k in ("u", "v"):
             out[k] = np.concatenate([s[k] for s in states], axis=0)

@@ -1,0 +1,306 @@
+"""Brittle Bingham-Maxwell rheology without a GPU: the reference restatement (tests/bbm_ref.py) held to the
+literature on its own, the row-block driver rowblock.DynamicsCore(rheology="bbm") on that reference (one rank against gloo worlds of 2 and
+3, bit for bit), the host-only entry points of the C ABI, and the driver's refusals."""
+import ctypes as C
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.distributed as dist
+import torch.multiprocessing as mp
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+for p in (ROOT, HERE):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import bbm_ref as R  # noqa: E402
+from nextsimdg_amd import rowblock, synthetic  # noqa: E402
+
+
+def uniform_state(nx, ny, h=1.0, a=0.95, d=0.2, s=(0.0, 0.0, 0.0)):
+    H, A, D = np.zeros((6, ny, nx)), np.zeros((6, ny, nx)), np.zeros((6, ny, nx))
+    H[0], A[0], D[0] = h, a, d
+    S = [np.zeros((8, ny, nx)) for _ in range(3)]
+    for c, val in zip(S, s):
+        c[0] = val
+    return H, A, D, S
+
+
+def envelope_case():
+    """uniform supercritical stress (sigma11, sigma12, sigma22) on a cover at rest, h = 1 km, dt_s = 100 s >= t_d (2.7 s): r = 1"""
+    return dict(hx=1000.0, hy=1000.0, dts=100.0, s=(-3.0e4, 6.0e4, -1.0e4), h=1.0, a=0.95, d=0.2)
+
+
+def envelope_expectation(mpar, bp, c):
+    """closed form of one sub-iteration of the envelope case: (d_healed, d_c, cohesion) -- the relaxed stress is the old one times m"""
+    dh = max(0.0, c["d"] - c["dts"] / bp["t_heal"])
+    eg = math.exp(-mpar["compaction"] * (1.0 - c["a"]))
+    x = (1.0 - dh) * eg
+    lam = bp["lambda0"] * x ** (bp["relax_exponent"] - 1)
+    sn = 0.5 * (c["s"][0] + c["s"][2])
+    Pt = min(1.0, -bp["p0"] * c["h"] ** 1.5 * eg / sn)
+    m = min(1.0 - 1e-12, lam / (lam + c["dts"] * (1.0 - Pt)))
+    s11, s12, s22 = (m * v for v in c["s"])
+    coh = bp["cohesion_lab"] * math.sqrt(0.1 / min(c["hx"], c["hy"]))
+    den = math.sqrt(0.25 * (s11 - s22) ** 2 + s12 ** 2) + bp["tan_phi"] * 0.5 * (s11 + s22)
+    assert den > 1.5 * coh and 0.5 * (s11 + s22) > -bp["compr_strength"]
+    t_d = min(c["hx"], c["hy"]) * math.sqrt(2.0 * (1.0 + bp["nu"]) * mpar["rho_ice"]) / math.sqrt(bp["young"] * x)
+    assert c["dts"] >= t_d
+    return dh, coh / den, coh
+
+
+def test_reference_returns_a_supercritical_stress_to_the_envelope():
+    """(i) after one sub-iteration with r = 1 the stress sits ON the Mohr-Coulomb envelope, sigma_s + tan(phi) sigma_n = c, to 1e-12 relative
+    at every Gauss point, and D' = D_healed + (1 - D_healed)(1 - d_c)"""
+    mpar, bp, c = R.mevp_par(), R.bbm_par(), envelope_case()
+    nx, ny = 4, 3
+    H, A, D, S = uniform_state(nx, ny, c["h"], c["a"], c["d"], c["s"])
+    z = np.zeros((2 * ny + 1, 2 * nx + 1))
+    So, Do, un, vn = R.iterate(mpar, bp, c["hx"], c["hy"], c["dts"], S, D, z, z, R.prepare(mpar, bp, H, A), R.nodal_fields(mpar, H, A, z, z, z, z))
+    s11, s12, s22 = (R.apply(R.PSI_Q, x) for x in So)
+    env = np.sqrt(0.25 * (s11 - s22) ** 2 + s12 ** 2) + bp["tan_phi"] * 0.5 * (s11 + s22)
+    dh, dc, coh = envelope_expectation(mpar, bp, c)
+    assert np.max(np.abs(env - coh)) <= 1e-12 * coh
+    want = dh + (1.0 - dh) * (1.0 - dc)
+    d = R.apply(R.PSI_Q[:, :6], Do)
+    assert 0.2 < want < bp["d_max"] and np.max(np.abs(d - want)) <= 1e-12
+
+
+def hooke_case(nx, ny, hx, hy):
+    """a linear velocity u = (a x + b y, c x + d y) on the CG2 lattice and its constant strain rate"""
+    a, b, c, d = 3e-7, -2e-7, 5e-7, -4e-7
+    X = hx * 0.5 * np.arange(2 * nx + 1)[None, :] + 0.0 * np.arange(2 * ny + 1)[:, None]
+    Y = hy * 0.5 * np.arange(2 * ny + 1)[:, None] + 0.0 * np.arange(2 * nx + 1)[None, :]
+    return a * X + b * Y, c * X + d * Y, (a, 0.5 * (b + c), d)
+
+
+def hooke_expectation(bp, dts, s0, eps, d0):
+    """sigma' = (sigma + dt_s E (k1 eps + k2 tr)) (1 - 1e-12) with E = young (1 - d_healed) (A = 1)"""
+    E = bp["young"] * (1.0 - max(0.0, d0 - dts / bp["t_heal"]))
+    nu = bp["nu"]
+    k1, k2 = 1.0 / (1.0 + nu), nu / (1.0 - nu ** 2)
+    tr = eps[0] + eps[2]
+    keep = 1.0 - 1e-12
+    return ((s0[0] + dts * E * (k1 * eps[0] + k2 * tr)) * keep, (s0[1] + dts * E * k1 * eps[1]) * keep, (s0[2] + dts * E * (k1 * eps[2] + k2 * tr)) * keep)
+
+
+def test_reference_without_relaxation_and_failure_is_hookes_law():
+    """(ii) cohesion_lab = lambda0 = 1e30 and a linear velocity: the stress is the closed-form Hooke increment times (1 - 1e-12)"""
+    mpar, bp = R.mevp_par(), R.bbm_par(cohesion_lab=1e30, lambda0=1e30)
+    nx, ny, hx, hy, dts = 5, 4, 1000.0, 800.0, 1.0
+    s0, d0 = (2.0e3, -1.0e3, 3.0e3), 0.1
+    H, A, D, S = uniform_state(nx, ny, 1.0, 1.0, d0, s0)
+    u, v, eps = hooke_case(nx, ny, hx, hy)
+    z = np.zeros_like(u)
+    So, Do, _, _ = R.iterate(mpar, bp, hx, hy, dts, S, D, u, v, R.prepare(mpar, bp, H, A), R.nodal_fields(mpar, H, A, z, z, z, z))
+    for got, want in zip(So, hooke_expectation(bp, dts, s0, eps, d0)):
+        assert np.max(np.abs(got[0] - want)) <= 1e-12 * abs(want)
+        assert np.max(np.abs(got[1:])) <= 1e-12 * abs(want)
+    # the damage only heals; the projection's higher coefficients carry the round-off of a constant 0.1 times the largest inverse mass, 180
+    assert np.max(np.abs(Do[0] - (d0 - dts / bp["t_heal"]))) <= 1e-15 and np.max(np.abs(Do[1:])) <= 180 * 0.1 * 2.0 ** -52 * 4
+
+
+def test_reference_keeps_the_damage_in_range_under_random_input():
+    """(iii) D at the Gauss points stays in [0, d_max], whatever comes in: damage outside [0, 1], stress far outside the envelope"""
+    mpar, bp = R.mevp_par(), R.bbm_par()
+    rng = np.random.default_rng(3)
+    nx, ny = 9, 7
+    H, A, D, S = uniform_state(nx, ny)
+    H[:] = rng.uniform(-0.2, 1.0, H.shape) * np.array([1, .2, .2, .1, .1, .1])[:, None, None]
+    A[:] = rng.uniform(-0.2, 1.2, A.shape) * np.array([1, .2, .2, .1, .1, .1])[:, None, None]
+    D[:] = rng.uniform(-0.5, 1.5, D.shape) * np.array([1, .5, .5, .3, .3, .3])[:, None, None]
+    S = [rng.uniform(-1e6, 1e6, (8, ny, nx)) for _ in range(3)]
+    u, v = rng.uniform(-1, 1, (2, 2 * ny + 1, 2 * nx + 1))
+    diag = {}
+    z = np.zeros_like(u)
+    So, Do, un, vn = R.iterate(mpar, bp, 1000.0, 1000.0, 5.0, S, D, u, v, R.prepare(mpar, bp, H, A), R.nodal_fields(mpar, H, A, z, z, z, z), diag=diag)
+    assert diag["d"].min() >= 0.0 and diag["d"].max() <= bp["d_max"] and diag["d"].max() > 0.9
+    assert all(np.all(np.isfinite(x)) for x in So + [Do, un, vn])
+
+
+# ---- the row-block driver on the reference ops -----------------------------------------------------------------------------------------
+NX, NY, NSUB, NSTEPS, DT = 12, 18, 8, 3, 8.0
+
+
+def island():
+    """12 x 18: an island across the block boundaries of worlds 2 (row 9) and 3 (rows 6, 12), and a rock on a boundary row itself"""
+    m = np.zeros((NY, NX), dtype=bool)
+    m[4:14, 4:7] = True
+    m[9, 10] = True
+    return m
+
+
+def run_core(rank, world, nsteps=NSTEPS, overlap=True):
+    bt = synthetic.BoxTest(NX, NY, L=36e3)
+    rng = np.random.default_rng(41)
+    H, A = bt.dg_fields()
+    H[0] += 0.7
+    A[0] -= 0.2 * rng.random((NY, NX))
+    H[1:3] += 0.02 * rng.standard_normal((2, NY, NX))
+    D = np.zeros_like(H)
+    D[0] = 0.5 * rng.random((NY, NX))
+    uo, vo = bt.ocean()
+    ua, va = bt.wind(0.0)
+    blk = rowblock.RowBlock(NX, NY, rank, world, 1, 1)
+    core = rowblock.DynamicsCore(R.make_ops(), blk, bt.hx, bt.hy, DT, NSUB, torch.device("cpu"), overlap=overlap, land=island(), rheology="bbm")
+    core.load_global(H, A, np.ascontiguousarray(uo), np.ascontiguousarray(vo), np.ascontiguousarray(20.0 * ua), np.ascontiguousarray(20.0 * va), D=D)
+    for _ in range(nsteps):
+        core.step()
+    return core
+
+
+def worker(rank, world, port, outdir):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        core = run_core(rank, world)
+        out = {k: core.owned(getattr(core, k)).clone() for k in ("H", "A", "D", "u", "v")}
+        out["s11"] = core.owned(core.s[0]).clone()
+        out["state"] = core.state_dict()
+        torch.save(out, os.path.join(outdir, "rank%d.pt" % rank))
+        dist.barrier()
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.fixture(scope="module")
+def single_domain():
+    return run_core(0, 1)
+
+
+def test_driver_on_the_reference_moves_breaks_and_keeps_land_at_zero(single_domain):
+    ref = single_domain
+    assert ref.TRANSPORTED == ("H", "A", "D") and ref.BOUNDS[2] == (0.0, 1.0, False)
+    land = island()
+    assert float(ref.u.abs().max()) > 1e-4 and all(bool(torch.isfinite(x).all()) for x in (ref.H, ref.A, ref.D, ref.u, ref.v, *ref.s))
+    D = ref.D.numpy()
+    assert np.all(D[:, land] == 0.0) and np.all(ref.H.numpy()[:, land] == 0.0) and all(np.all(x.numpy()[:, land] == 0.0) for x in ref.s)
+    ln = R.land_nodes(land)
+    assert np.all(ref.u.numpy()[ln] == 0.0) and np.all(ref.v.numpy()[ln] == 0.0)
+    assert D[0][~land].min() >= 0.0 and D[0].max() <= 1.0
+    st = ref.state_dict()
+    assert st["D"].shape == (6, NY, NX) and np.array_equal(st["D"], D)
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_bbm_row_blocks_equal_the_single_domain_bitwise(world, single_domain, tmp_path):
+    from test_rowblock_gloo import free_port
+
+    ref = single_domain
+    mp.spawn(worker, args=(world, free_port(), str(tmp_path)), nprocs=world, join=True)
+    parts = [torch.load(os.path.join(str(tmp_path), "rank%d.pt" % r), weights_only=False) for r in range(world)]
+    for key, full in (("H", ref.H), ("A", ref.A), ("D", ref.D), ("s11", ref.s[0])):
+        assert torch.equal(torch.cat([p[key] for p in parts], dim=1), full), key
+    for key, full in (("u", ref.u), ("v", ref.v)):
+        assert torch.equal(torch.cat([p[key] for p in parts], dim=0), full), key
+    merged = rowblock.DynamicsCore.merge_states([p["state"] for p in parts])
+    assert merged["rows"] == (0, NY) and np.array_equal(merged["D"], ref.D.numpy())
+
+
+def test_checkpoint_and_resume_carry_the_damage(single_domain):
+    """2 steps + state_dict + load_state_dict on a fresh core + 1 step == 3 steps, bit for bit; a state without D is refused"""
+    first = run_core(0, 1, nsteps=2)
+    state = rowblock.DynamicsCore.merge_states([first.state_dict()])
+    core = run_core(0, 1, nsteps=0)
+    core.load_state_dict(state)
+    core.step()
+    for k in ("H", "A", "D", "u", "v"):
+        assert torch.equal(getattr(core, k), getattr(single_domain, k)), k
+    del state["D"]
+    with pytest.raises(ValueError, match="damage"):
+        core.load_state_dict(state)
+
+
+def test_substeps_divide_the_sub_iteration_length():
+    """advance(dt, substeps=2) is two steps of dt / 2, each with sub-iterations of dt / (2 nsub)"""
+    a = run_core(0, 1, nsteps=0)
+    a.advance(DT, substeps=2)
+    b = run_core(0, 1, nsteps=0)
+    b.dt = DT / 2
+    b.step()
+    b.step()
+    assert b.ops.bbm_dts == DT / 2 / NSUB and a.ops.bbm_dts == b.ops.bbm_dts
+    assert torch.equal(a.u, b.u) and torch.equal(a.D, b.D)
+
+
+# ---- refusals ---------------------------------------------------------------------------------------------------------------------------
+def test_the_driver_refuses_what_is_not_built():
+    from oracle_ops import OracleOps
+
+    bt = synthetic.BoxTest(8, 8)
+    dev = torch.device("cpu")
+    mk = lambda **kw: rowblock.DynamicsCore(kw.pop("ops", None) or R.make_ops(), kw.pop("blk", None) or rowblock.RowBlock(8, 8), bt.hx, bt.hy, 8.0, 4, dev, **kw)
+    with pytest.raises(ValueError, match="native"):
+        mk(rheology="bbm", native=True)
+    with pytest.raises(ValueError, match=r"\(1, 1\)"):
+        mk(rheology="bbm", blk=rowblock.RowBlock(8, 16, 0, 2, 2, 1))
+    with pytest.raises(ValueError, match="rheology"):
+        mk(rheology="evp")
+    with pytest.raises(ValueError, match="bbm_prepare"):
+        mk(rheology="bbm", ops=OracleOps())
+    with pytest.raises(ValueError, match="advect_column_state"):
+        rowblock.CoupledCore(R.make_ops(), rowblock.RowBlock(8, 8), bt.hx, bt.hy, 8.0, 4, dev, advect_column_state=True, rheology="bbm")
+    with pytest.raises(ValueError, match="rheology='bbm'"):
+        mk(bbm=object())
+    # a coupled core without the column state transport carries H, A and D
+    c = rowblock.CoupledCore(R.make_ops(), rowblock.RowBlock(8, 8), bt.hx, bt.hy, 8.0, 4, dev, rheology="bbm")
+    assert c.TRANSPORTED == ("H", "A", "D")
+    # the default is today's path: no damage, no new array
+    m = mk(ops=OracleOps())
+    assert m.rheology == "mevp" and m.TRANSPORTED == ("H", "A") and not hasattr(m, "D")
+
+
+# ---- host-only entry points of the C ABI ------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def lib():
+    from nextsimdg_amd import abi, build
+
+    build.build_lib(verbose=False)
+    return abi.load_library()
+
+
+def test_default_parameters(lib):
+    from nextsimdg_amd import abi
+
+    p = abi.BbmParams()
+    lib.nsdg_bbm_default_params(C.byref(p))
+    want = R.bbm_par()
+    for k, v in want.items():
+        assert getattr(p, k) == v, k
+    assert p.d_max == 1.0 - 1e-6 and p.nu == 1.0 / 3.0 and p.reserved == 0
+    assert abi.bbm_default_params(young=1.0).young == 1.0 and abi.BBM_COURANT == 0.25
+
+
+def test_params_set_and_the_device_calls_refuse_a_null_context(lib):
+    from nextsimdg_amd import abi
+
+    p = abi.bbm_default_params()
+    assert lib.nsdg_bbm_params_set(None, C.byref(p)) == -1
+    assert b"null" in lib.nsdg_last_error()
+    assert lib.nsdg_bbm_prepare(None, 0, 1, None, None, None, None, None) == -1
+    assert lib.nsdg_bbm_iterate(None, 0, 0, 1, *([None] * 16)) == -1
+
+
+def test_substep_count_states_the_elastic_wave_rule(lib):
+    from nextsimdg_amd import abi
+
+    p = abi.bbm_default_params()
+    bp = R.bbm_par()
+    for h, dt, courant in ((1000.0, 120.0, 0.5), (250.0, 30.0, 1.0), (4000.0, 1.0, 0.35), (1000.0, 120.0, 0.7)):
+        assert abi.bbm_substep_count(p, 900.0, h, dt, courant) == R.substep_count(bp, 900.0, h, dt, courant)
+    assert abi.bbm_substep_count(p, 900.0, 1000.0, 120.0, 0.5) == math.ceil(120.0 * math.sqrt(5.9605e8 / (900.0 * (1 - 1 / 9))) / 500.0) == 208
+    assert abi.bbm_substep_count(p, 900.0, 1e6, 1.0) == 1
+    n = C.c_int32(-7)
+    rc = lib.nsdg_bbm_substep_count(C.byref(p), 900.0, 1000.0, 120.0, 0.5, 100, C.byref(n))
+    assert rc == -1 and n.value == -7 and b"208" in lib.nsdg_last_error()  # refused with the needed value, never capped
+    for bad in (dict(rho_ice=0.0), dict(h=-1.0), dict(dt=float("nan")), dict(courant=0.0), dict(max_nsub=0)):
+        a = dict(rho_ice=900.0, h=1000.0, dt=1.0, courant=0.5, max_nsub=10)
+        a.update(bad)
+        assert lib.nsdg_bbm_substep_count(C.byref(p), a["rho_ice"], a["h"], a["dt"], a["courant"], a["max_nsub"], C.byref(n)) == -1, bad
+    assert lib.nsdg_bbm_substep_count(None, 900.0, 1000.0, 1.0, 0.5, 10, C.byref(n)) == -1

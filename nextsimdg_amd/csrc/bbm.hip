@@ -3,12 +3,13 @@
 // No counterpart in the reference snapshot (its dynamics component is commented out); the scheme is stated in include/nsdg.h "brittle
 // rheology" and DESIGN.md section 3.8 from the published formulation (Olason et al. 2022; Dansereau et al. 2016), parity unpinned.
 //
-// The march is the one of mevp_pipeline.h, unchanged: a wave owns a strip of 63 element columns x R element rows, one element per lane
-// per row; lane 0 recomputes the column left of the strip and every strip recomputes the row below it as a prologue; the contributions of
-// a row to its top nodes are carried in registers to the next row; the four owned nodes are updated by owned_node_updates<false, LAND>
-// with the BBM launch constants K1 = K2 = rho_i / dt_s (explicit in stress and Coriolis, implicit in ocean drag) and stored by
-// store_owned_nodes.  What is this kernel's own is the element step (bbm_common.h: bbm_element_step): elastic predictor, Maxwell
-// relaxation, Mohr-Coulomb test and damage update at the 3x3 Gauss points.
+// The march is the one of mevp_pipeline.h, all of it: the frame of a wave that owns 63 element columns x R element rows (march_frame), the
+// row loop with its prologue row, velocity gather, carried contributions, update of the four owned nodes by
+// owned_node_updates<false, LAND> with the BBM launch constants K1 = K2 = rho_i / dt_s (explicit in stress and Coriolis, implicit in ocean
+// drag) and their store (march_strip); the strip height is the rule of mevp_fused.hip at this kernel's one wave per SIMD
+// (nsdg_march_strip_rows), the checks of a pass those of nsdg_pass_check (mevp.hip).  What is this file's own is the element step inside
+// the march (bbm_common.h: bbm_element_step): elastic predictor, Maxwell relaxation, Mohr-Coulomb test and damage update at the 3x3 Gauss
+// points, with the loads and stores of its state -- and the damage, which the mEVP pass does not know.
 //
 // Stress AND damage are out of place (S_in -> S_out, D_in -> D_out): a strip that recomputes a row must never read what its owner has
 // overwritten.  No barrier, no atomics: every wave is independent.
@@ -23,20 +24,6 @@
 #include "mevp_pipeline.h"
 
 namespace nsdg_mevp_detail {
-
-// DG2 field in plane layout: the 6 coefficients of element e, N elements per plane
-__device__ __forceinline__ void plane_load6(const double* __restrict__ f, long N, long e, double (&c)[6])
-{
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-        c[k] = f[k * N + e];
-}
-__device__ __forceinline__ void plane_store6(double* __restrict__ f, long N, long e, const double (&c)[6])
-{
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-        f[k * N + e] = c[k];
-}
 
 // 1 wave per SIMD: the element step holds 9 Gauss points x (3 strain rates + 3 stresses + damage + 3 per-step values) beside the march's
 // carried contributions (resource figures: profiles/r09_bbm.md)
@@ -55,65 +42,32 @@ __global__ __launch_bounds__(256, 1) void bbm_fused_kernel(NodalConsts K, BbmCon
     if (M.y0 >= j1)
         return; // wave-uniform
     M.y1 = min(M.y0 + R, j1);
-    const int ixr = cw * 63 - 1 + lane;
-    const bool valid = ixr >= 0 && ixr < nx; // lanes outside the array load a clamped column and store nothing
-    M.K = K, M.AC = AdaptConsts { 0., 0., 0. };
-    M.nx = nx, M.ny = ny, M.lane = lane;
-    M.own = valid && lane > 0;
-    M.ix = min(max(ixr, 0), nx - 1);
-    M.hasL = M.ix > 0, M.lastcol = M.ix == nx - 1;
-    M.ntx = tiles_per_row(nx);
-    M.nn = 2 * nx + 1;
-    M.nplane = nodal_plane((long)M.nn * (2 * ny + 1));
-    M.hx = hx, M.hy = hy, M.ihx = 1. / hx, M.ihy = 1. / hy, M.iarea = M.ihx * M.ihy;
-    M.ialpha = 0., M.dmin2 = 0.;
-    const int ix = M.ix, nn = M.nn;
+    march_frame<63, 1>(M, K, AdaptConsts { 0., 0., 0. }, nx, ny, lane, cw, hx, hy, 0., 0.); // 63 owned columns, lane 0 recomputes the column left of them
     const long N = (long)nx * ny;
 
-    TopCarry carry; // zero by its member initialisers: the first row of the march adds nothing from a row below
-
-    for (int iy = (M.y0 > k0 ? M.y0 - 1 : M.y0); iy < M.y1; ++iy) {
-        const bool prologue = iy < M.y0; // recomputed row owned by the strip below: nothing is stored
-        const long ts = tile_off(ix, iy, M.ntx, 8), tp = tile_off(ix, iy, M.ntx, 9);
-        const long nV = (long)(2 * iy) * nn + 2 * ix, e = (long)iy * nx + ix;
-        double ul[9], vl[9], hg[9], eg[9], pm[9], s11[8], s12[8], s22[8], d[6], m11[8], m12[8], m22[8];
-#pragma unroll
-        for (int a = 0; a < 9; ++a) {
-            const long n = nV + (a / 3) * nn + a % 3;
-            ul[a] = u_old[n];
-            vl[a] = v_old[n];
-        }
-        tile_load9(hgp, tp, ix & 63, hg);
-        tile_load9(egp, tp, ix & 63, eg);
-        tile_load9(pmp, tp, ix & 63, pm);
-        tile_load8(S.i11, ts, s11);
-        tile_load8(S.i12, ts, s12);
-        tile_load8(S.i22, ts, s22);
-        plane_load6(D_in, N, e, d);
-        bbm_element_step(B, ul, vl, M.ihx, M.ihy, hg, eg, pm, s11, s12, s22, d, m11, m12, m22);
-        if (!prologue && M.own) {
-            tile_store8(S.o11, ts, s11);
-            tile_store8(S.o12, ts, s12);
-            tile_store8(S.o22, ts, s22);
-            plane_store6(D_out, N, e, d);
-        }
-        double cx[9], cy[9];
-        node_contrib_all(m11, m12, m22, hx, hy, cx, cy);
-
-        if (!prologue && iy >= j0) { // wave-uniform
-            double c[4][6], un[4], vn[4];
-            load_owned_nodal(M, iy, c, packed);
-            const double uu[4] = { ul[0], ul[1], ul[3], ul[4] }, vv[4] = { vl[0], vl[1], vl[3], vl[4] };
-            owned_node_updates<false, LAND>(M, iy > 0, c, uu, vv, carry, cx, cy, un, vn);
-            if (M.own)
-                store_owned_nodes(nV, nn, M.lastcol, iy == ny - 1, un, vn, u_new, v_new);
-        }
-        carry_top<false>(carry, cx, cy); // the top-row contributions go to the next row of the march
-    }
+    march_strip<false, LAND, false>(M, k0, j0, u_old, v_old, packed, u_new, v_new,
+        [&](int iy, bool store, long, const double (&ul)[9], const double (&vl)[9], double (&m11)[8], double (&m12)[8], double (&m22)[8], double&) {
+            const long ts = tile_off(M.ix, iy, M.ntx, 8), tp = tile_off(M.ix, iy, M.ntx, 9), e = (long)iy * nx + M.ix;
+            double hg[9], eg[9], pm[9], s11[8], s12[8], s22[8], d[6];
+            tile_load9(hgp, tp, M.ix & 63, hg);
+            tile_load9(egp, tp, M.ix & 63, eg);
+            tile_load9(pmp, tp, M.ix & 63, pm);
+            tile_load8(S.i11, ts, s11);
+            tile_load8(S.i12, ts, s12);
+            tile_load8(S.i22, ts, s22);
+            plane_load6(D_in, N, e, d);
+            bbm_element_step(B, ul, vl, M.ihx, M.ihy, hg, eg, pm, s11, s12, s22, d, m11, m12, m22);
+            if (store) {
+                tile_store8(S.o11, ts, s11);
+                tile_store8(S.o12, ts, s12);
+                tile_store8(S.o22, ts, s22);
+                plane_store6(D_out, N, e, d);
+            }
+        });
 }
 
 // what the sub-cycle does not change, once per model step: hg = max(H, 0), eg = exp(-C (1 - clamp(A, 0, 1))), pm = p0 hg^(3/2) eg at the
-// 3x3 Gauss points (the points and clamps of ice_strength_kernel, mevp.hip), tiled like pg
+// 3x3 Gauss points (the points and clamps of mevp_common.h: clamp_thickness_conc, as the ice strength), tiled like pg
 __global__ __launch_bounds__(256) void bbm_prepare_kernel(int nx, int ny, int j0, int j1, double p0, double compaction,
     const double* __restrict__ H, const double* __restrict__ A, double* __restrict__ hgp, double* __restrict__ egp, double* __restrict__ pmp)
 {
@@ -130,14 +84,9 @@ __global__ __launch_bounds__(256) void bbm_prepare_kernel(int nx, int ny, int j0
     double hg[9], eg[9], pm[9];
 #pragma unroll
     for (int q = 0; q < 9; ++q) {
-        double h = 0., a = 0.;
-#pragma unroll
-        for (int c = 0; c < 6; ++c) {
-            FMA_TAB(h, PSI_G3[q][c], hc[c]);
-            FMA_TAB(a, PSI_G3[q][c], ac[c]);
-        }
-        h = fmax(h, 0.);
-        a = fmin(fmax(a, 0.), 1.);
+        double h, a;
+        gauss_thickness_conc(q, hc, ac, h, a);
+        clamp_thickness_conc(h, a);
         hg[q] = h;
         eg[q] = exp(-compaction * (1. - a));
         pm[q] = p0 * h * sqrt(h) * eg[q];
@@ -150,14 +99,6 @@ __global__ __launch_bounds__(256) void bbm_prepare_kernel(int nx, int ny, int j0
 } // namespace nsdg_mevp_detail
 
 using namespace nsdg_mevp_detail;
-
-static inline bool bbm_aligned16(std::initializer_list<const void*> ptrs)
-{
-    for (const void* p : ptrs)
-        if ((uintptr_t)p & 15)
-            return false;
-    return true;
-}
 
 // launch constants of the element step from the context's parameters and the packing's time step
 static BbmConsts nsdg_bbm_consts(const nsdg_ctx* ctx)
@@ -210,7 +151,7 @@ int nsdg_bbm_prepare(nsdg_ctx* ctx, int32_t j0, int32_t j1, const double* H, con
     NSDG_NEED_GRID(ctx);
     NSDG_CHECK_ARG(0 <= j0 && j0 <= j1 && j1 <= ctx->ny, "row range outside the local array");
     NSDG_CHECK_ARG(H && A && hg && eg && pm, "null field pointer");
-    NSDG_CHECK_ARG(bbm_aligned16({ hg, eg, pm }), "tiled arrays must be 16-byte aligned");
+    NSDG_CHECK_ARG(nsdg_aligned16({ hg, eg, pm }), "tiled arrays must be 16-byte aligned");
     if (j0 == j1)
         return NSDG_OK;
     NSDG_CHECK_HIP(hipSetDevice(ctx->device));
@@ -224,43 +165,18 @@ int nsdg_bbm_iterate(nsdg_ctx* ctx, int32_t k0, int32_t j0, int32_t j1, const do
     double* s11_out, double* s12_out, double* s22_out, const double* D_in, double* D_out, const double* u_old, const double* v_old, double* u_new,
     double* v_new, const double* packed, const double* hg, const double* eg, const double* pm)
 {
+    // the damage is this rheology's own; everything else is a single-iteration pass like nsdg_mevp_iterate's, with three Gauss arrays
+    // where that has the ice strength
     NSDG_NEED_GRID(ctx);
-    const int ny = ctx->ny;
-    NSDG_CHECK_ARG(0 <= k0 && k0 <= j0 && j0 <= j1 && j1 <= ny, "need 0 <= k0 <= j0 <= j1 <= ny");
-    NSDG_CHECK_ARG(k0 == j0 - 1 || (k0 == 0 && j0 == 0), "need k0 == j0 - 1 (one ghost row below) or k0 == j0 == 0");
-    NSDG_CHECK_ARG(s11_in && s12_in && s22_in && s11_out && s12_out && s22_out && D_in && D_out && u_old && v_old && u_new && v_new && packed && hg
-            && eg && pm,
-        "null field pointer");
-    NSDG_CHECK_ARG(bbm_aligned16({ s11_in, s12_in, s22_in, s11_out, s12_out, s22_out, hg, eg, pm }), "tiled arrays (stress, Gauss arrays) must be 16-byte aligned");
-    NSDG_CHECK_ARG(u_new != u_old && v_new != v_old, "u_new/v_new must not alias u_old/v_old");
-    NSDG_CHECK_ARG(s11_out != s11_in && s12_out != s12_in && s22_out != s22_in, "the output stress must not alias the input stress");
+    NSDG_CHECK_ARG(D_in && D_out, "null field pointer");
     NSDG_CHECK_ARG(D_out != D_in, "the output damage must not alias the input damage");
-    if (k0 == j1)
-        return NSDG_OK;
-    if (!(ctx->pack_dt > 0)) {
-        nsdg_set_error("nsdg_bbm_iterate: nsdg_mevp_prepare / nsdg_mevp_pack_nodal was not called on this context");
-        return NSDG_ERR_STATE;
-    }
-    NSDG_CHECK_HIP(hipSetDevice(ctx->device));
+    bool run;
+    const int checked = nsdg_pass_check(ctx, __func__, 1, k0, j0, j1, false, 0, 0,
+        { s11_in, s12_in, s22_in, s11_out, s12_out, s22_out, u_old, v_old, u_new, v_new, packed, /* pg: none */ nullptr }, { hg, eg, pm }, &run);
+    if (!run)
+        return checked;
     const int ncw = nsdg_div_up(ctx->nx, 63); // 63 owned columns per wave
-    int R = ctx->strip_rows;
-    if (R <= 0) {
-        // the automatic strip height of the mEVP kernel (mevp_fused.hip: rounds of resident waves times R + 1 rows each) at this kernel's
-        // 1 wave per SIMD
-        const long slots = 4L * ctx->num_cus;
-        const int rows = j1 - k0;
-        double best = 1e30;
-        R = 4;
-        for (int r = 2; r <= 64; ++r) {
-            const long waves = (long)nsdg_div_up(rows, r) * ncw;
-            const long rounds = (waves + slots - 1) / slots;
-            const double cost = rounds * (r + 1.0) + (rounds == 1 ? 1.5 : 0.0);
-            if (cost < best) {
-                best = cost;
-                R = r;
-            }
-        }
-    }
+    const int R = nsdg_march_strip_rows(ctx, j1 - k0, ncw, 1);
     const long nwaves = (long)ncw * nsdg_div_up(j1 - k0, R);
     const StressPtrs S = { s11_in, s12_in, s22_in, s11_out, s12_out, s22_out };
     // the BBM momentum step: the mEVP node update with K1 = K2 = rho_i / dt_s (and u0 = v0 = 0 in the packing)
@@ -269,7 +185,7 @@ int nsdg_bbm_iterate(nsdg_ctx* ctx, int32_t k0, int32_t j0, int32_t j1, const do
     const BbmConsts B = nsdg_bbm_consts(ctx);
     const dim3 grid(nsdg_div_up(nwaves, 4)), block(256);
     auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, K, B, ctx->nx, ny, k0, j0, j1, R, ncw, ctx->hx, ctx->hy, S, D_in, D_out, u_old, v_old, packed,
+        hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, K, B, ctx->nx, ctx->ny, k0, j0, j1, R, ncw, ctx->hx, ctx->hy, S, D_in, D_out, u_old, v_old, packed,
             hg, eg, pm, u_new, v_new);
     };
     // masked or not: the instantiation goes with the packing the pass reads, as in nsdg_mevp_pass

@@ -332,22 +332,14 @@ __global__ __launch_bounds__(256) void ice_strength_kernel(int nx, int ny, int j
     const long e = (long)iy * nx + ix;
     const long tp = tile_off(ix, iy, tiles_per_row(nx), 9);
     double hc[6], ac[6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        hc[c] = H[c * N + e];
-        ac[c] = A[c * N + e];
-    }
+    plane_load6(H, N, e, hc);
+    plane_load6(A, N, e, ac);
     double pq[9];
 #pragma unroll
     for (int q = 0; q < 9; ++q) {
-        double h = 0., a = 0.;
-#pragma unroll
-        for (int c = 0; c < 6; ++c) {
-            FMA_TAB(h, PSI_G3[q][c], hc[c]);
-            FMA_TAB(a, PSI_G3[q][c], ac[c]);
-        }
-        h = fmax(h, 0.);
-        a = fmin(fmax(a, 0.), 1.);
+        double h, a;
+        gauss_thickness_conc(q, hc, ac, h, a);
+        clamp_thickness_conc(h, a);
         pq[q] = pstar * h * exp(-compaction * (1. - a));
     }
     tile_store9(pg, tp, ix & 63, pq);
@@ -366,18 +358,8 @@ __global__ __launch_bounds__(256) void wind_stress_kernel(long n, double f_atm, 
 
 using namespace nsdg_mevp_detail;
 
-// the tiled arrays are accessed 16 bytes at a time
-static inline bool aligned16(std::initializer_list<const void*> ptrs)
-{
-    for (const void* p : ptrs)
-        if ((uintptr_t)p & 15)
-            return false;
-    return true;
-}
-#define NSDG_CHECK_TILED_IN(fn, ...) NSDG_CHECK_ARG_IN(fn, aligned16({ __VA_ARGS__ }), "tiled arrays (stress, ice strength) must be 16-byte aligned")
-#define NSDG_CHECK_TILED(...) NSDG_CHECK_TILED_IN(__func__, __VA_ARGS__)
-
-static NodalConsts nodal_consts(const nsdg_ctx* ctx) { return nsdg_nodal_consts(ctx); }
+#define NSDG_TILED_MSG "tiled arrays (stress, ice strength) must be 16-byte aligned"
+#define NSDG_CHECK_TILED(...) NSDG_CHECK_ARG(nsdg_aligned16({ __VA_ARGS__ }), NSDG_TILED_MSG)
 
 // the adaptive form of alpha, beta (mevp_common.h) exists in the marching kernels only
 #define NSDG_NOT_ADAPTIVE(ctx)                                                                                                  \
@@ -517,7 +499,7 @@ int nsdg_mevp_velocity(nsdg_ctx* ctx, int32_t j0, int32_t j1, const double* s11,
         nsdg_set_error("nsdg_mevp_velocity: nsdg_mevp_pack_nodal was not called on this context");
         return NSDG_ERR_STATE;
     }
-    hipLaunchKernelGGL(ctx->pack_land ? mevp_velocity_land_kernel : mevp_velocity_kernel, grid, block, 0, ctx->stream, nodal_consts(ctx), ctx->nx, ctx->ny, j0, j1,
+    hipLaunchKernelGGL(ctx->pack_land ? mevp_velocity_land_kernel : mevp_velocity_kernel, grid, block, 0, ctx->stream, nsdg_nodal_consts(ctx), ctx->nx, ctx->ny, j0, j1,
         ctx->hx, ctx->hy, s11, s12, s22, u_old, v_old, packed, u_new, v_new);
     NSDG_CHECK_LAUNCH();
     return NSDG_OK;
@@ -525,14 +507,13 @@ int nsdg_mevp_velocity(nsdg_ctx* ctx, int32_t j0, int32_t j1, const double* s11,
 
 } // extern "C"
 
-int nsdg_mevp_pass(nsdg_ctx* ctx, int v, int k0, int j0, int j1, bool pair, int j0b, int j1b, const nsdg_mevp_bufs& b)
+int nsdg_pass_check(nsdg_ctx* ctx, const char* fn, int v, int k0, int j0, int j1, bool pair, int j0b, int j1b, const nsdg_mevp_bufs& b,
+    std::initializer_list<const void*> gauss, bool* run)
 {
-    static const char* const names[2][5] = { { "", "nsdg_mevp_iterate", "nsdg_mevp_iterate2", "nsdg_mevp_iterate3", "nsdg_mevp_iterate4" },
-        { "", "", "", "nsdg_mevp_iterate3_pair", "nsdg_mevp_iterate4_pair" } };
     static const char* const count[] = { "", "one", "two", "three", "four" };
     static const char* const variants[] = { "", "", "2, 3 or 4 (nsdg_mevp_variant_set) or call nsdg_mevp_iterate twice",
         "3 or 4 (nsdg_mevp_variant_set)", "4 (nsdg_mevp_variant_set)" };
-    const char* fn = names[pair][v];
+    *run = false;
     NSDG_CHECK_ARG_IN(fn, ctx != nullptr, "null context");
     if (ctx->nx <= 0) {
         nsdg_set_error("%s: nsdg_grid_set was not called", fn);
@@ -553,9 +534,10 @@ int nsdg_mevp_pass(nsdg_ctx* ctx, int v, int k0, int j0, int j1, bool pair, int 
         }
         NSDG_CHECK_ARG_IN(fn, !pair || j1 <= j0b || j1b <= j0, "the two row ranges must be disjoint");
     }
-    NSDG_CHECK_ARG_IN(fn, b.s11i && b.s12i && b.s22i && b.s11 && b.s12 && b.s22 && b.u_old && b.v_old && b.u_new && b.v_new && b.packed && b.pg,
+    NSDG_CHECK_ARG_IN(fn, b.s11i && b.s12i && b.s22i && b.s11 && b.s12 && b.s22 && b.u_old && b.v_old && b.u_new && b.v_new && b.packed
+            && std::find(gauss.begin(), gauss.end(), nullptr) == gauss.end(),
         "null field pointer");
-    NSDG_CHECK_TILED_IN(fn, b.s11i, b.s12i, b.s22i, b.s11, b.s12, b.s22, b.pg);
+    NSDG_CHECK_ARG_IN(fn, nsdg_aligned16({ b.s11i, b.s12i, b.s22i, b.s11, b.s12, b.s22 }) && nsdg_aligned16(gauss), NSDG_TILED_MSG);
     NSDG_CHECK_ARG_IN(fn, b.u_new != b.u_old && b.v_new != b.v_old, "u_new/v_new must not alias u_old/v_old");
     NSDG_CHECK_ARG_IN(fn, b.s11 != b.s11i && b.s12 != b.s12i && b.s22 != b.s22i, "the output stress must not alias the input stress");
     // nothing to do: v = 1 without a stress row, checked before the packing (j0 == j1 > k0 still updates the stress row k0); v >= 2
@@ -577,6 +559,18 @@ int nsdg_mevp_pass(nsdg_ctx* ctx, int v, int k0, int j0, int j1, bool pair, int 
         nsdg_set_error("%s: hipSetDevice(ctx->device) failed: %s", fn, hipGetErrorString(e));
         return NSDG_ERR_HIP;
     }
+    *run = true;
+    return NSDG_OK;
+}
+
+int nsdg_mevp_pass(nsdg_ctx* ctx, int v, int k0, int j0, int j1, bool pair, int j0b, int j1b, const nsdg_mevp_bufs& b)
+{
+    static const char* const names[2][5] = { { "", "nsdg_mevp_iterate", "nsdg_mevp_iterate2", "nsdg_mevp_iterate3", "nsdg_mevp_iterate4" },
+        { "", "", "", "nsdg_mevp_iterate3_pair", "nsdg_mevp_iterate4_pair" } };
+    bool run;
+    const int checked = nsdg_pass_check(ctx, names[pair][v], v, k0, j0, j1, pair, j0b, j1b, b, { b.pg }, &run);
+    if (!run)
+        return checked;
     // masked or not: the instantiation goes with the packing the pass reads (nsdg_mevp_pack_nodal / nsdg_mevp_prepare remembered whether
     // they flagged land nodes); the two-kernel form's velocity kernel (nsdg_mevp_velocity) reads the same flag
     const bool land = ctx->pack_land;

@@ -1,6 +1,7 @@
 // mevp_common.h -- the element and node arithmetic of the mEVP sub-cycle, each formula stated ONCE and inlined by every kernel that
 // needs it: the two-kernel form (mevp.hip), the single-iteration marching kernel (mevp_fused.hip) and the stage-per-wave pipeline
-// (mevp_fused4.hip).  The tiled layout of the element arrays and the packed layout of the nodal coefficients; the sum-factorised
+// (mevp_fused4.hip).  The tiled layout of the element arrays, the plane layout of the DG2 fields and the packed layout of the nodal
+// coefficients; thickness and concentration at the Gauss points with their clamps; the sum-factorised
 // element operators; the projected stress and its relaxation, uniform and adaptive; the nodal contributions; the node update
 // node_update<AD, LAND>; the land-node rule.  -ffp-contract=on fuses per source expression, so one statement of a formula is also what
 // makes the marching kernels agree bit for bit: an expression that is regrouped rounds differently.
@@ -61,6 +62,20 @@ __device__ __forceinline__ void tile_store9(double* __restrict__ a, long t, int 
     a[t + 512 - l] = c[8];
 }
 
+// DG2 field in plane layout (H, A, the damage: what the transport advects): the 6 coefficients of element e, N elements per plane
+__device__ __forceinline__ void plane_load6(const double* __restrict__ f, long N, long e, double (&c)[6])
+{
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+        c[k] = f[k * N + e];
+}
+__device__ __forceinline__ void plane_store6(double* __restrict__ f, long N, long e, const double (&c)[6])
+{
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+        f[k * N + e] = c[k];
+}
+
 // Workgroups are dealt round-robin to the 8 XCDs of the chip, each with its own L2.  The three-iteration kernel
 // gives every XCD a CONTIGUOUS range of (strip, column-wave) indices, so that the waves that share halo columns and
 // strip-boundary rows -- neighbours in that index -- read them through the same L2 (34.0-35.2 -> 33.0-33.3 ms per
@@ -79,6 +94,24 @@ __device__ __forceinline__ int xcd_contiguous_block(int b, int nblocks)
         if (t_ != 0.0)           \
             acc += t_ * (val);   \
     } while (0)
+
+// Mean thickness and concentration at Gauss point q of the 3x3 rule from the six DG2 coefficients of H and A of an element: the raw
+// values (nsdg_concentration_max tests them for finiteness: fmax(NaN, 0) is 0), and the clamps every consumer applies -- no negative
+// ice, a concentration in [0, 1] (ice strength, the Gauss arrays of the brittle rheology, the largest concentration of a state)
+__device__ __forceinline__ void gauss_thickness_conc(int q, const double (&hc)[6], const double (&ac)[6], double& h, double& a)
+{
+    h = 0., a = 0.;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+        FMA_TAB(h, PSI_G3[q][c], hc[c]);
+        FMA_TAB(a, PSI_G3[q][c], ac[c]);
+    }
+}
+__device__ __forceinline__ void clamp_thickness_conc(double& h, double& a)
+{
+    h = fmax(h, 0.);
+    a = fmin(fmax(a, 0.), 1.);
+}
 
 // ---------------------------------------------------------------------------------------------
 // Sum-factorised element operators.  Every 2-D basis function is a product of 1-D ones,

@@ -23,9 +23,12 @@
 // its owner has already overwritten.  No barrier, no atomics, no inter-workgroup communication: every
 // wave is independent and runs to completion.
 //
-// The march itself -- the carried contributions, the update of the four owned nodes, their store -- is the one of mevp_pipeline.h,
-// shared with the stage-per-wave pipeline (mevp_fused4.hip): a pass of n sub-iterations there is bit-identical to n launches of this
-// kernel.  What is this kernel's own is where its inputs come from (memory, every row) and the order of its loads.
+// The march itself is the one of mevp_pipeline.h: the frame of a wave (march_frame, shared with the stage-per-wave pipeline,
+// mevp_fused4.hip: a pass of n sub-iterations there is bit-identical to n launches of this kernel) and the row loop with the prologue
+// row, the velocity gather, the carried contributions, the update of the four owned nodes and their store (march_strip, shared with the
+// brittle rheology's kernel, bbm.hip).  What is this file's own is the mEVP element step handed to that loop -- where its inputs come from
+// (memory, every row) and the order of its loads per register budget -- and the strip height of a single-iteration march
+// (nsdg_march_strip_rows, which bbm.hip calls at its one wave per SIMD).
 #include "mevp_pipeline.h"
 
 namespace nsdg_mevp_detail {
@@ -45,89 +48,53 @@ __global__ __launch_bounds__(256, MINW) void mevp_fused_kernel(NodalConsts K, Ad
     if (M.y0 >= j1)
         return; // wave-uniform
     M.y1 = min(M.y0 + R, j1);
-    const int ixr = cw * 63 - 1 + lane;
-    const bool valid = ixr >= 0 && ixr < nx; // lanes outside the array load a clamped column and store nothing
-    M.K = K, M.AC = AC;
-    M.nx = nx, M.ny = ny, M.lane = lane;
-    M.own = valid && lane > 0;
-    M.ix = min(max(ixr, 0), nx - 1);
-    M.hasL = M.ix > 0, M.lastcol = M.ix == nx - 1;
-    M.ntx = tiles_per_row(nx);
-    M.nn = 2 * nx + 1;
-    M.nplane = nodal_plane((long)M.nn * (2 * ny + 1));
-    M.hx = hx, M.hy = hy, M.ihx = 1. / hx, M.ihy = 1. / hy, M.iarea = M.ihx * M.ihy;
-    M.ialpha = ialpha, M.dmin2 = dmin2;
-    const int ix = M.ix, nn = M.nn;
+    march_frame<63, 1>(M, K, AC, nx, ny, lane, cw, hx, hy, ialpha, dmin2); // 63 owned columns, lane 0 recomputes the column left of them
 
-    TopCarry carry; // zero by its member initialisers: the first row of the march adds nothing from a row below
-
-    for (int iy = (M.y0 > k0 ? M.y0 - 1 : M.y0); iy < M.y1; ++iy) {
-        const bool prologue = iy < M.y0; // recomputed row owned by the strip below: nothing is stored
-        const long ts = tile_off(ix, iy, M.ntx, 8), tp = tile_off(ix, iy, M.ntx, 9);
-        const long nV = (long)(2 * iy) * nn + 2 * ix;
-        double ul[9], vl[9], Pq[9], s11[8], s12[8], s22[8];
-#pragma unroll
-        for (int a = 0; a < 9; ++a) {
-            const long n = nV + (a / 3) * nn + a % 3;
-            ul[a] = u_old[n];
-            vl[a] = v_old[n];
-        }
-        tile_load9(pg, tp, ix & 63, Pq);
-        double qe = 0.; // adaptive form: this element's offer q_e = alpha_e h'_c of this sub-iteration (mevp_common.h)
-        if constexpr (AD) {
-            // local, solution-adaptive alpha (mevp_common.h); h' of the element's centre node is its packed coefficient [0]
-            const double hc = packed[nodal_off(nV + nn + 1)];
-            double r11[8], r12[8], r22[8], ialpha_e;
-            stress_projected_adaptive(ul, vl, Pq, M.ihx, M.ihy, dmin2, hc, AC, r11, r12, r22, qe, ialpha_e);
-            tile_load8(S.i11, ts, s11);
-            tile_load8(S.i12, ts, s12);
-            tile_load8(S.i22, ts, s22);
-            stress_relax(ialpha_e, r11, r12, r22, s11, s12, s22);
-        } else if constexpr (MINW >= 2) {
-            // 2 waves/SIMD build: stage the loads so that the live set stays under 256 registers -- the old
-            // stress is fetched only after the projected stress is formed, the partner wave covers the latency
-            double r11[8], r12[8], r22[8];
-            stress_projected(ul, vl, Pq, M.ihx, M.ihy, ialpha, dmin2, r11, r12, r22);
-            asm volatile("" ::: "memory");
-            tile_load8(S.i11, ts, s11);
-            tile_load8(S.i12, ts, s12);
-            tile_load8(S.i22, ts, s22);
-            stress_relax(ialpha, r11, r12, r22, s11, s12, s22);
-        } else {
-            tile_load8(S.i11, ts, s11);
-            tile_load8(S.i12, ts, s12);
-            tile_load8(S.i22, ts, s22);
-            stress_update(ul, vl, Pq, M.ihx, M.ihy, ialpha, dmin2, s11, s12, s22);
-        }
-        if (!prologue && M.own) {
-            tile_store8(S.o11, ts, s11);
-            tile_store8(S.o12, ts, s12);
-            tile_store8(S.o22, ts, s22);
-        }
-        double cx[9], cy[9];
-        node_contrib_all(s11, s12, s22, hx, hy, cx, cy);
-        if constexpr (MINW >= 2)
-            asm volatile("" ::: "memory"); // keep the nodal-coefficient loads below this point
-
-        if (!prologue && iy >= j0) { // wave-uniform
-            double c[4][6], un[4], vn[4];
-            load_owned_nodal(M, iy, c, packed);
-            const double uu[4] = { ul[0], ul[1], ul[3], ul[4] }, vv[4] = { vl[0], vl[1], vl[3], vl[4] };
-            owned_node_updates<AD, LAND>(M, iy > 0, c, uu, vv, carry, cx, cy, un, vn, qe);
-            if (M.own)
-                store_owned_nodes(nV, nn, M.lastcol, iy == ny - 1, un, vn, u_new, v_new);
-        }
-        carry_top<AD>(carry, cx, cy, qe); // the top-row contributions go to the next row of the march
-    }
+    // the element step of the mEVP rheology: the stress is relaxed in registers, stored, and is itself what the momentum equation takes
+    march_strip<AD, LAND, MINW >= 2>(M, k0, j0, u_old, v_old, packed, u_new, v_new,
+        [&](int iy, bool store, long nV, const double (&ul)[9], const double (&vl)[9], double (&s11)[8], double (&s12)[8], double (&s22)[8], double& qe) {
+            const long ts = tile_off(M.ix, iy, M.ntx, 8), tp = tile_off(M.ix, iy, M.ntx, 9);
+            double Pq[9];
+            tile_load9(pg, tp, M.ix & 63, Pq);
+            if constexpr (AD) {
+                // local, solution-adaptive alpha (mevp_common.h); h' of the element's centre node is its packed coefficient [0]
+                const double hc = packed[nodal_off(nV + M.nn + 1)];
+                double r11[8], r12[8], r22[8], ialpha_e;
+                stress_projected_adaptive(ul, vl, Pq, M.ihx, M.ihy, dmin2, hc, AC, r11, r12, r22, qe, ialpha_e);
+                tile_load8(S.i11, ts, s11);
+                tile_load8(S.i12, ts, s12);
+                tile_load8(S.i22, ts, s22);
+                stress_relax(ialpha_e, r11, r12, r22, s11, s12, s22);
+            } else if constexpr (MINW >= 2) {
+                // 2 waves/SIMD build: stage the loads so that the live set stays under 256 registers -- the old
+                // stress is fetched only after the projected stress is formed, the partner wave covers the latency
+                double r11[8], r12[8], r22[8];
+                stress_projected(ul, vl, Pq, M.ihx, M.ihy, ialpha, dmin2, r11, r12, r22);
+                asm volatile("" ::: "memory");
+                tile_load8(S.i11, ts, s11);
+                tile_load8(S.i12, ts, s12);
+                tile_load8(S.i22, ts, s22);
+                stress_relax(ialpha, r11, r12, r22, s11, s12, s22);
+            } else {
+                tile_load8(S.i11, ts, s11);
+                tile_load8(S.i12, ts, s12);
+                tile_load8(S.i22, ts, s22);
+                stress_update(ul, vl, Pq, M.ihx, M.ihy, ialpha, dmin2, s11, s12, s22);
+            }
+            if (store) {
+                tile_store8(S.o11, ts, s11);
+                tile_store8(S.o12, ts, s12);
+                tile_store8(S.o22, ts, s22);
+            }
+        });
 }
 
 } // namespace nsdg_mevp_detail
 
 using namespace nsdg_mevp_detail;
 
-int nsdg_launch_mevp_fused(nsdg_ctx* ctx, bool land, int k0, int j0, int j1, const nsdg_mevp_bufs& b)
+int nsdg_march_strip_rows(const nsdg_ctx* ctx, int rows, int ncw, int waves_per_simd)
 {
-    const int ncw = nsdg_div_up(ctx->nx, 63); // 63 owned columns per wave
     int R = ctx->strip_rows;
     if (R <= 0) {
         // Automatic strip height.  Every wave marches R+1 rows (one redundant), and the launch runs in
@@ -135,8 +102,7 @@ int nsdg_launch_mevp_fused(nsdg_ctx* ctx, bool land, int k0, int j0, int j1, con
         // that minimises it (measured on 2048^2: R = 17 -> 2 full rounds, 8 % faster than R = 4 with its
         // 8.25 rounds and 25 % redundant rows).  A single round is charged 1.5 row-times because one
         // straggling wave then ends the launch alone.
-        const long slots = 2L * 4 * ctx->num_cus; // 2 waves per SIMD at ~204 VGPRs
-        const int rows = j1 - k0;
+        const long slots = (long)waves_per_simd * 4 * ctx->num_cus;
         double best = 1e30;
         R = 4;
         for (int r = 2; r <= 64; ++r) {
@@ -149,6 +115,13 @@ int nsdg_launch_mevp_fused(nsdg_ctx* ctx, bool land, int k0, int j0, int j1, con
             }
         }
     }
+    return R;
+}
+
+int nsdg_launch_mevp_fused(nsdg_ctx* ctx, bool land, int k0, int j0, int j1, const nsdg_mevp_bufs& b)
+{
+    const int ncw = nsdg_div_up(ctx->nx, 63); // 63 owned columns per wave
+    const int R = nsdg_march_strip_rows(ctx, j1 - k0, ncw, 2); // 2 waves per SIMD at ~204 VGPRs
     const int nstrips = nsdg_div_up(j1 - k0, R);
     const long nwaves = (long)ncw * nstrips;
     const StressPtrs S = { b.s11i, b.s12i, b.s22i, b.s11, b.s12, b.s22 };

@@ -286,19 +286,7 @@ __global__ __launch_bounds__(256) void mevp_fused4_kernel(NodalConsts K, AdaptCo
     if (M.y0 >= j1)
         return; // workgroup-uniform: no wave of this workgroup reaches the barrier or a counter
     M.y1 = min(M.y0 + R, j1);
-    const int ixr = cw * P4_OWNED - P4_LEFT + lane;
-    const bool valid = ixr >= 0 && ixr < nx;
-    M.K = K;
-    M.nx = nx, M.ny = ny, M.lane = lane;
-    M.own = valid && lane >= P4_LEFT && lane < P4_LEFT + P4_OWNED;
-    M.ix = min(max(ixr, 0), nx - 1);
-    M.hasL = M.ix > 0, M.lastcol = M.ix == nx - 1;
-    M.ntx = tiles_per_row(nx);
-    M.nn = 2 * nx + 1;
-    M.nplane = nodal_plane((long)M.nn * (2 * ny + 1));
-    M.hx = hx, M.hy = hy, M.ihx = 1. / hx, M.ihy = 1. / hy, M.iarea = M.ihx * M.ihy;
-    M.ialpha = ialpha, M.dmin2 = dmin2;
-    M.AC = AC;
+    march_frame<P4_OWNED, P4_LEFT>(M, K, AC, nx, ny, lane, cw, hx, hy, ialpha, dmin2);
 
     // a pass of nst sub-iterations (2 <= nst <= 4): stage s works on the rows y0 - nst + s .. y1 + nst - 2 - s, the last one (nst - 1)
     // on y0 - 1 .. y1 - 1; the waves s >= nst have nothing to do

@@ -1,10 +1,17 @@
-// mevp_pipeline.h -- the march that the marching mEVP kernels share: the single-iteration kernel (mevp_fused.hip: one wave, one
-// sub-iteration) and the stage-per-wave pipeline (mevp_fused4.hip: one sub-iteration per wave of a workgroup).  A wave marches through
-// its strip bottom to top, one element per lane per row.  Here are the per-lane constants of a march, the stress pointers of a pass,
-// the contributions a row carries to the row above it, the packed coefficients and the update of the four nodes an element owns
-// (vertex, bottom edge-mid, left edge-mid, centre), the gather of an element's nine nodal velocities from owned nodes, and the store of
-// the owned nodes with the boundary zeros -- which the two-kernel form (mevp.hip) shares.  The same inlined functions in every kernel
-// keep the marching kernels bit-identical to each other.
+// mevp_pipeline.h -- the march that the marching kernels share: the single-iteration mEVP kernel (mevp_fused.hip) and its brittle sibling
+// (bbm.hip) -- one wave, one sub-iteration -- and the stage-per-wave pipeline (mevp_fused4.hip: one sub-iteration per wave of a
+// workgroup).  A wave marches through its strip bottom to top, one element per lane per row.  Who owns what:
+//   here             the per-lane constants of a march and the ONE function that fills them (march_frame), the stress pointers of a pass,
+//                    the contributions a row carries to the row above it, the packed coefficients and the update of the four nodes an
+//                    element owns (vertex, bottom edge-mid, left edge-mid, centre), the gather of an element's nine nodal velocities from
+//                    owned nodes, the store of the owned nodes with the boundary zeros -- which the two-kernel form (mevp.hip) shares --
+//                    and the row loop of a single-iteration march (march_strip): prologue row, velocity gather, contributions, node
+//                    update, store, carry;
+//   mevp_fused.hip   the mEVP element step inside march_strip, with its load orders per register budget, and the strip height of a
+//                    single-iteration march (nsdg_march_strip_rows);
+//   bbm.hip          the brittle element step inside march_strip;
+//   mevp_fused4.hip  its own march (p2p_row: inputs from LDS, one stage per wave) on the same frame and the same node functions.
+// The same inlined functions in every kernel keep the marching kernels bit-identical to each other.
 #pragma once
 #include "mevp_common.h"
 
@@ -112,6 +119,71 @@ __device__ __forceinline__ void store_owned_nodes(long nV, int nn, bool lastcol,
         u_new[nV + 2 * nn + 1] = 0., v_new[nV + 2 * nn + 1] = 0.;
         if (lastcol)
             u_new[nV + 2 * nn + 2] = 0., v_new[nV + 2 * nn + 2] = 0.;
+    }
+}
+
+// Everything of a march's per-lane constants but the strip's rows y0, y1, for column-wave `cw` of waves that own OWNED columns from lane
+// LEFT on: lane l works on column cw * OWNED - LEFT + l.  The lanes left and right of the owned ones recompute their neighbours'
+// columns; lanes outside the array load a clamped column and store nothing.
+template <int OWNED, int LEFT>
+__device__ __forceinline__ void march_frame(MarchConst& M, const NodalConsts& K, const AdaptConsts& AC, int nx, int ny, int lane, int cw,
+    double hx, double hy, double ialpha, double dmin2)
+{
+    const int ixr = cw * OWNED - LEFT + lane;
+    const bool valid = ixr >= 0 && ixr < nx;
+    M.K = K, M.AC = AC;
+    M.nx = nx, M.ny = ny, M.lane = lane;
+    M.own = valid && lane >= LEFT && lane < LEFT + OWNED;
+    M.ix = min(max(ixr, 0), nx - 1);
+    M.hasL = M.ix > 0, M.lastcol = M.ix == nx - 1;
+    M.ntx = tiles_per_row(nx);
+    M.nn = 2 * nx + 1;
+    M.nplane = nodal_plane((long)M.nn * (2 * ny + 1));
+    M.hx = hx, M.hy = hy, M.ihx = 1. / hx, M.ihy = 1. / hy, M.iarea = M.ihx * M.ihy;
+    M.ialpha = ialpha, M.dmin2 = dmin2;
+}
+
+// The row loop of a single-iteration march over the strip [M.y0, M.y1) of a launch whose stress rows start at k0 and whose velocity rows
+// start at j0: a strip above the first recomputes the row below it as a prologue (nothing of it is stored), every row gathers its nine
+// nodal velocities from memory, takes the stress that enters the momentum equation from the rheology, updates and stores its four owned
+// nodes and carries its top-row contributions to the next row.
+// element(iy, store, nV, ul, vl, m11, m12, m22, qe), an inlined callable, is the rheology's element step of row iy: it loads what it
+// needs, updates its state and stores it where `store` is true, and returns the coefficients of the stress of the momentum equation in
+// m?? and, in the adaptive form, the element's offer in qe.
+// FENCE: a compiler fence between the contributions and the nodal-coefficient loads (the 2-waves-per-SIMD build of mevp_fused.hip)
+template <bool AD, bool LAND, bool FENCE, class Element>
+__device__ __forceinline__ void march_strip(const MarchConst& M, int k0, int j0, const double* __restrict__ u_old, const double* __restrict__ v_old,
+    const double* __restrict__ packed, double* __restrict__ u_new, double* __restrict__ v_new, Element&& element)
+{
+    const int ix = M.ix, nn = M.nn;
+    TopCarry carry; // zero by its member initialisers: the first row of the march adds nothing from a row below
+
+    for (int iy = (M.y0 > k0 ? M.y0 - 1 : M.y0); iy < M.y1; ++iy) {
+        const bool prologue = iy < M.y0; // recomputed row owned by the strip below: nothing is stored
+        const long nV = (long)(2 * iy) * nn + 2 * ix;
+        double ul[9], vl[9], m11[8], m12[8], m22[8];
+#pragma unroll
+        for (int a = 0; a < 9; ++a) {
+            const long n = nV + (a / 3) * nn + a % 3;
+            ul[a] = u_old[n];
+            vl[a] = v_old[n];
+        }
+        double qe = 0.; // adaptive form: this element's offer q_e = alpha_e h'_c of this sub-iteration (mevp_common.h)
+        element(iy, !prologue && M.own, nV, ul, vl, m11, m12, m22, qe);
+        double cx[9], cy[9];
+        node_contrib_all(m11, m12, m22, M.hx, M.hy, cx, cy);
+        if constexpr (FENCE)
+            asm volatile("" ::: "memory"); // keep the nodal-coefficient loads below this point
+
+        if (!prologue && iy >= j0) { // wave-uniform
+            double c[4][6], un[4], vn[4];
+            load_owned_nodal(M, iy, c, packed);
+            const double uu[4] = { ul[0], ul[1], ul[3], ul[4] }, vv[4] = { vl[0], vl[1], vl[3], vl[4] };
+            owned_node_updates<AD, LAND>(M, iy > 0, c, uu, vv, carry, cx, cy, un, vn, qe);
+            if (M.own)
+                store_owned_nodes(nV, nn, M.lastcol, iy == M.ny - 1, un, vn, u_new, v_new);
+        }
+        carry_top<AD>(carry, cx, cy, qe); // the top-row contributions go to the next row of the march
     }
 }
 

@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <functional>
+#include <initializer_list>
 #include <type_traits>
 
 #include "../../include/nsdg.h"
@@ -95,6 +96,15 @@ void nsdg_phase_timer_free(nsdg_ctx* ctx); // phase_timer.hip: the event ring of
 
 static inline int nsdg_div_up(long a, long b) { return (int)((a + b - 1) / b); }
 
+// the tiled arrays are accessed 16 bytes at a time
+static inline bool nsdg_aligned16(std::initializer_list<const void*> ptrs)
+{
+    for (const void* p : ptrs)
+        if ((uintptr_t)p & 15)
+            return false;
+    return true;
+}
+
 // coefficients per element of a DG field of the order 0, 1 or 2
 constexpr int nsdg_nc(int order) { return order == 0 ? 1 : (order == 1 ? 3 : 6); }
 
@@ -120,6 +130,16 @@ struct nsdg_mevp_bufs {
     const double *packed, *pg;
 };
 
+// The checks of one marching pass of v sub-iterations, reported under the name `fn` of the entry point it works for: v = 1 on the stress
+// rows [k0, j1) and the velocity rows [j0, j1) -- the single-iteration pass of either rheology (nsdg_mevp_iterate, nsdg_bbm_iterate) --,
+// v = 2, 3, 4 on the rows [j0, j1) and, for the pair forms, on the disjoint rows [j0b, j1b) as well.  Context and grid, the row ranges,
+// nulls, 16-byte alignment of the tiled arrays and aliasing of the stress, the velocity and the packed coefficients of `b` (b.pg is not
+// looked at) and of `gauss`, the tiled Gauss-point arrays of the rheology; then, in this order: nothing to do for v = 1 without a stress
+// row, the packing's state, nothing to do for v >= 2 on an empty range, the variant, hipSetDevice.  *run: all is well and there is
+// something to launch; the result is the caller's either way
+int nsdg_pass_check(nsdg_ctx* ctx, const char* fn, int v, int k0, int j0, int j1, bool pair, int j0b, int j1b, const nsdg_mevp_bufs& b,
+    std::initializer_list<const void*> gauss, bool* run);
+
 // One checked pass of v sub-iterations, the work of every nsdg_mevp_iterate* entry point and reported under its name: v = 1 on the
 // stress rows [k0, j1) and the velocity rows [j0, j1) (nsdg_mevp_iterate); v = 2, 3, 4 on the rows [j0, j1) (nsdg_mevp_iterate2 / 3 / 4)
 // and, for the pair forms, on the disjoint rows [j0b, j1b) as well (nsdg_mevp_iterate3_pair / 4_pair)
@@ -130,6 +150,10 @@ int nsdg_mevp_pass(nsdg_ctx* ctx, int v, int k0, int j0, int j1, bool pair, int 
 // land: run the instantiation that holds land nodes at 0 -- chosen in ONE place, nsdg_mevp_pass, from what the packing saw
 int nsdg_launch_mevp_fused(nsdg_ctx* ctx, bool land, int k0, int j0, int j1, const nsdg_mevp_bufs& b);
 int nsdg_launch_mevp_fused4_ranges(nsdg_ctx* ctx, bool land, int nst, int j0, int j1, int j0b, int j1b, const nsdg_mevp_bufs& b);
+
+// rows per strip of a single-iteration march over `rows` element rows with ncw column-waves, in a kernel built for `waves_per_simd`
+// resident waves: the context's strip_rows, or the automatic height (mevp_fused.hip)
+int nsdg_march_strip_rows(const nsdg_ctx* ctx, int rows, int ncw, int waves_per_simd);
 
 // ---- transport (transport.hip) --------------------------------------------------------------------------------------------------
 // One checked transport step on the rows [j0, j1) as stage launches, reported under the name `fn` of the entry point it works for:

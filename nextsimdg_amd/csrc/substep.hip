@@ -25,8 +25,8 @@ using namespace nsdg_mevp_detail;
 constexpr unsigned long long BAD_MARK = 0xFFF8000000000000ull;
 constexpr unsigned long long BAD_INDEX_MASK = (1ull << 51) - 1;
 
-// one lane per element of the owned rows (grid-stride); the clamped concentration of ice_strength_kernel (csrc/mevp.hip) at the 9
-// Gauss points, counted where the clamped thickness there is > 0
+// one lane per element of the owned rows (grid-stride); the clamped concentration at the 9 Gauss points (mevp_common.h:
+// gauss_thickness_conc, clamp_thickness_conc: what ice_strength_kernel sees), counted where the clamped thickness there is > 0
 __global__ __launch_bounds__(256) void concentration_max_kernel(long e0, long e1, long N, const double* __restrict__ H,
     const double* __restrict__ A, unsigned long long* __restrict__ out)
 {
@@ -34,26 +34,20 @@ __global__ __launch_bounds__(256) void concentration_max_kernel(long e0, long e1
     const long stride = (long)gridDim.x * blockDim.x;
     for (long e = e0 + (long)blockIdx.x * blockDim.x + threadIdx.x; e < e1; e += stride) {
         double hc[6], ac[6];
+        plane_load6(H, N, e, hc);
+        plane_load6(A, N, e, ac);
         bool finite = true;
 #pragma unroll
-        for (int c = 0; c < 6; ++c) {
-            hc[c] = H[c * N + e];
-            ac[c] = A[c * N + e];
+        for (int c = 0; c < 6; ++c)
             finite = finite && std::isfinite(hc[c]) && std::isfinite(ac[c]);
-        }
         double amax = 0.;
 #pragma unroll
         for (int q = 0; q < 9; ++q) {
-            double h = 0., a = 0.;
-#pragma unroll
-            for (int c = 0; c < 6; ++c) {
-                FMA_TAB(h, PSI_G3[q][c], hc[c]);
-                FMA_TAB(a, PSI_G3[q][c], ac[c]);
-            }
+            double h, a;
+            gauss_thickness_conc(q, hc, ac, h, a);
             // the raw values are checked BEFORE the clamp: fmax(NaN, 0) is 0
             finite = finite && std::isfinite(h) && std::isfinite(a);
-            h = fmax(h, 0.);
-            a = fmin(fmax(a, 0.), 1.);
+            clamp_thickness_conc(h, a);
             if (h > 0. && a > amax) // only positive values enter: the pattern of -0 would be read as a bad mark
                 amax = a;
         }

@@ -539,9 +539,7 @@ class DynamicsCore:
                             if pending is None:
                                 pending = self._ghost_exchange_start()
                             self._ghost_exchange_finish(pending)
-                        self.u, self.ub = self.ub, self.u
-                        self.v, self.vb = self.vb, self.v
-                        self.s, self.sb = self.sb, self.s
+                        self._swap()
                         it += v
         split = self.overlap and b.world > 1 and (b.j1 - b.j0) >= 4 and not self.two_per_pass
         for _ in range(self.nsub - it):
@@ -562,15 +560,27 @@ class DynamicsCore:
                 reqs = self.halo.nodal_start(uvn)
                 calls[-1]()
                 self.halo.finish(reqs)
-            self.u, self.ub = self.ub, self.u
-            self.v, self.vb = self.vb, self.v
-            self.s, self.sb = self.sb, self.s
-            if self.rheology == "bbm":
-                self.D, self.Db = self.Db, self.D
+            self._swap()
         if self.rheology == "bbm" and b.world > 1 and self.nsub > 0:
             # inside the sub-cycle the damage of the ghost row below is recomputed and the ghost row above is never read: one exchange
             # hands the transport its ghost rows
             self.halo.element([self.D])
+
+    def _swap(self):
+        """a pass has written the other half of the ping-pong: the velocity, the stress and, for the brittle rheology, the damage"""
+        self.u, self.ub = self.ub, self.u
+        self.v, self.vb = self.vb, self.v
+        self.s, self.sb = self.sb, self.s
+        if self.rheology == "bbm":
+            self.D, self.Db = self.Db, self.D
+
+    def _bind(self, name):
+        """a call of ops.<name> with its arguments bound once: the binding fast path of the C ABI, or a closure"""
+        ops = self.ops
+        bind = getattr(ops, "bind_" + name, None)
+        if bind is None:  # ops without a binding fast path (the CPU test stand-in)
+            bind = lambda *a: (lambda: getattr(ops, name)(*a))
+        return bind
 
     def _ghost_exchange_start(self):
         """ghost zones of the multi-iteration passes, depth (d, d-1) with d = v k: velocity node rows (2d up, 2d-1
@@ -592,12 +602,9 @@ class DynamicsCore:
         calls = self._calls.get(key)
         if calls is not None:
             return calls
-        ops, b = self.ops, self.blk
+        b = self.blk
         uv, uvn = (self.u, self.v), (self.ub, self.vb)
-        name = "mevp_iterate%d" % v
-        bind = getattr(ops, "bind_" + name, None)
-        if bind is None:  # ops without a binding fast path (the CPU test stand-in)
-            bind = lambda *a: (lambda: getattr(ops, name)(*a))
+        bind = self._bind("mevp_iterate%d" % v)
         rng = []
         lo, hi = max(b.j0 - v * ext, 0), min(b.j1 + v * ext, b.ny)
         if split and ext == 0:
@@ -619,12 +626,9 @@ class DynamicsCore:
         calls = self._calls.get(key)
         if calls is not None:
             return calls
-        ops, b = self.ops, self.blk
+        b = self.blk
         uv, uvn = (self.u, self.v), (self.ub, self.vb)
-        name = "bbm_iterate" if bbm else "mevp_iterate"
-        bind = getattr(ops, "bind_" + name, None)
-        if bind is None:  # ops without a binding fast path (the CPU test stand-in)
-            bind = lambda *a: (lambda: getattr(ops, name)(*a))
+        bind = self._bind("bbm_iterate" if bbm else "mevp_iterate")
         rng = []
         if not split:
             rng.append((b.k0, b.j0, b.j1))  # k0 = j0 - 1: the ghost row just below is updated redundantly

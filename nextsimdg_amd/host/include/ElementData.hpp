@@ -17,7 +17,7 @@ namespace Nextsim {
 //! What a dynamics run carries from one step to the next beyond the cell means hice / cice of the FieldStore: the higher DG2 coefficients of
 //! the advected thickness and concentration, the CG2 velocity and the 24 stress coefficients.  The reference writes every prognostic field
 //! it has into its restart file (core/src/DevGridIO.cpp:169-201, read back at :101-138); its snapshot has no dynamics, so these are
-//! additional variables of the same group (names and dimensions: RectGrid.hpp).  x = the slow index of the file, y the fast one.
+//! additional variables of the same group (DYNAMICS_VARIABLES below).  x = the slow index of the file, y the fast one.
 struct DynamicsState {
     bool present = false; //!< false: a run starts from rest with piecewise-constant fields (a file of the reference, or of a column-only run)
     std::vector<double> hdg, adg; //!< coefficients 1..5 of H and A: [5][x][y]
@@ -26,18 +26,8 @@ struct DynamicsState {
     //! coefficients 1..5 of the snow S of dynamics.advect_column_state: [5][x][y]; EMPTY without that mode (nothing of it is written)
     //! and after reading a file that does not hold it (the higher coefficients then start at zero)
     std::vector<double> sdg;
-    void resize(std::size_t nx, std::size_t ny)
-    {
-        hdg.assign(5 * nx * ny, 0.), adg.assign(5 * nx * ny, 0.);
-        u.assign((2 * nx + 1) * (2 * ny + 1), 0.), v.assign((2 * nx + 1) * (2 * ny + 1), 0.);
-        s11.assign(8 * nx * ny, 0.), s12.assign(8 * nx * ny, 0.), s22.assign(8 * nx * ny, 0.);
-    }
-    void clear()
-    {
-        present = false;
-        for (auto* a : { &hdg, &adg, &u, &v, &s11, &s12, &s22, &sdg })
-            a->clear();
-    }
+    inline void resize(std::size_t nx, std::size_t ny); //!< every variable that is not optional: zeros of its shape
+    inline void clear();
 };
 
 //! Struct-of-arrays field container: every plane has n = nx*ny doubles, element index i*ny' ... see IStructure.
@@ -56,6 +46,53 @@ struct FieldStore {
 
     void resize(std::size_t nElements, int nIceLayers);
 };
+
+//! One variable a restart file holds for a dynamics run beyond the reference's own hice .. tice.  The table below states them ONCE, in file
+//! order: DynamicsState::resize / clear, both file formats (RectGrid::dump / init) and the ranks' payload (DynamicsStep::packRows) walk it.
+struct DynamicsVariable {
+    //! for x * y elements: DG2 coefficients 1..5 of an advected field (dg2 = 5, x, y) | the 8-function stress space (stress8 = 8, x, y) |
+    //! a plane (x, y) | the CG2 lattice (xnode = 2x+1, ynode = 2y+1); in brackets the named dimensions of an HDF5 file
+    enum Shape { DG5, STRESS8, PLANE, NODAL };
+    const char* name; //!< the dataset in group `data` of an HDF5 file = the entry of the sidecar's variables= line
+    Shape shape;
+    //! where it lives: in FieldStore::dyn, or (state == nullptr) in a plane of the FieldStore itself, which the files list here but which
+    //! is not DynamicsState's -- between the ranks it travels with the cell means (DynamicsStep::packRows), never again with the state
+    std::vector<double> DynamicsState::*state;
+    std::vector<double> FieldStore::*plane;
+    //! nullptr: every file with the state holds it.  Otherwise it is OPTIONAL -- written when it is not empty, empty after a file without
+    //! it -- and this sidecar header key announces it (an HDF5 file shows it by the dataset itself)
+    const char* sidecarFlag;
+
+    template <class Store> auto& in(Store& f) const { return state ? f.dyn.*state : f.*plane; } //!< its array in a (const) FieldStore
+    bool optional() const { return sidecarFlag != nullptr; }
+    int elementPlanes() const { return shape == DG5 ? 5 : shape == STRESS8 ? 8 : shape == PLANE ? 1 : 0; } //!< planes of x * y values
+    std::size_t size(std::size_t nx, std::size_t ny) const { return shape == NODAL ? (2 * nx + 1) * (2 * ny + 1) : elementPlanes() * nx * ny; }
+};
+inline constexpr DynamicsVariable DYNAMICS_VARIABLES[] = {
+    { "hice_dg", DynamicsVariable::DG5, &DynamicsState::hdg, nullptr, nullptr }, // the advected thickness (coefficient 0 = hice)
+    { "cice_dg", DynamicsVariable::DG5, &DynamicsState::adg, nullptr, nullptr }, // the advected concentration (coefficient 0 = cice)
+    { "u", DynamicsVariable::NODAL, &DynamicsState::u, nullptr, nullptr },
+    { "v", DynamicsVariable::NODAL, &DynamicsState::v, nullptr, nullptr },
+    { "s11", DynamicsVariable::STRESS8, &DynamicsState::s11, nullptr, nullptr },
+    { "s12", DynamicsVariable::STRESS8, &DynamicsState::s12, nullptr, nullptr },
+    { "s22", DynamicsVariable::STRESS8, &DynamicsState::s22, nullptr, nullptr },
+    { "newice", DynamicsVariable::PLANE, nullptr, &FieldStore::newice, nullptr }, // the column model's new-ice volume (NextsimPhysics::m_newice)
+    { "hsnow_dg", DynamicsVariable::DG5, &DynamicsState::sdg, nullptr, "data.snow_dg" }, // dynamics.advect_column_state: the advected snow (coefficient 0 = hsnow)
+};
+
+void DynamicsState::resize(std::size_t nx, std::size_t ny)
+{
+    for (const DynamicsVariable& v : DYNAMICS_VARIABLES)
+        if (v.state && !v.optional())
+            (this->*v.state).assign(v.size(nx, ny), 0.);
+}
+void DynamicsState::clear()
+{
+    present = false;
+    for (const DynamicsVariable& v : DYNAMICS_VARIABLES)
+        if (v.state)
+            (this->*v.state).clear();
+}
 
 //! Builder with the reference's method names (core/src/include/PrognosticGenerator.hpp:17-90).
 class PrognosticGenerator {

@@ -69,9 +69,27 @@ void tileRows(const double* planes, std::size_t planeStride, std::size_t srcRow0
                 t[tiledIndex(nx, ix, r, c)] = planes[c * planeStride + (srcRow0 + r) * nx + ix];
 }
 
-// device arrays of a block; the advected fields, the stress and the velocity exist twice (ping-pong)
-// (S0 .. T2Q: the snow and the weighted surface temperature of dynamics.advect_column_state; empty without it)
-enum Arr { H0, A0, H1, A1, T2H, T2A, S0, Q0, S1, Q1, T2S, T2Q, S11a, S12a, S22a, S11b, S12b, S22b, PG, VXDG, VYDG, UNX, UNY, Ua, Va, Ub, Vb, UA, VA, UO, VO, PACKED, COL, NARR };
+// The fields the DG2 transport advects, stated ONCE: the device buffers, the uploads and land clears of start(), the transport plan with
+// its bounds and the downloads of stop() walk this table.  What one field alone needs is said where it happens, by the row's index.
+struct AdvectedField {
+    const char* name;
+    nsdg_field_bounds bounds; // the closure of the transport step (include/nsdg.h "INPUT DOMAIN AND CLOSURE")
+    std::vector<double> FieldStore::*mean; // the host's plane of coefficient 0 ...
+    std::vector<double> DynamicsState::*higher; // ... and of coefficients 1..5 (both nullptr: no host storage -- never uploaded, cleared or downloaded)
+    bool columnState; // present only with dynamics.advect_column_state (such rows last: the fields of a run are the first `nfields`)
+};
+enum Field { FH, FA, FS, FQ, NFIELD };
+const AdvectedField ADVECTED[NFIELD] = {
+    { "H", { 0., HUGE_VAL, 0, 0 }, &FieldStore::hice, &DynamicsState::hdg, false }, // mean thickness: H >= 0
+    { "A", { 0., 1., 1, 0 }, &FieldStore::cice, &DynamicsState::adg, false }, // concentration in [0, 1], the cell mean capped at 1
+    { "S", { 0., HUGE_VAL, 0, 0 }, &FieldStore::hsnow, &DynamicsState::sdg, true }, // snow volume: S >= 0; plane 0 IS the column's hsnow
+    { "Q", { -HUGE_VAL, HUGE_VAL, 0, 0 }, nullptr, nullptr, true }, // = H tice0, unbounded: rebuilt at every step (nsdg_tracer_weight)
+};
+static_assert(NFIELD <= NSDG_RB_MAX_FIELDS, "the transport plan holds every advected field");
+
+// further device arrays of a block; the stress (its components in the order of STRESS) and the velocity exist twice (ping-pong)
+std::vector<double> DynamicsState::*const STRESS[3] = { &DynamicsState::s11, &DynamicsState::s12, &DynamicsState::s22 };
+enum Arr { S11a, S12a, S22a, S11b, S12b, S22b, PG, VXDG, VYDG, UNX, UNY, Ua, Va, Ub, Vb, UA, VA, UO, VO, PACKED, COL, NARR };
 // column planes inside COL
 enum Col { C_HSNOW, C_TICE, C_SST, C_SSS, C_TAIR, C_TDEW, C_SLP, C_QSW, C_QLW, C_MLD, C_SNOWFALL, C_WIND, C_NEWICE, NCOL };
 } // namespace
@@ -87,6 +105,7 @@ public:
     nsdg_ctx* ctx = nullptr;
     double* block = nullptr;
     std::vector<double*> d;
+    int nfields = 0; // rows of ADVECTED this run advects
     nsdg_rb_mevp* mevp = nullptr;
     nsdg_rb_transport* transport = nullptr;
     int par = 0, tpar = 0; // which buffers hold the velocity/stress iterate and the advected state
@@ -118,10 +137,9 @@ public:
         land = nullptr;
         ctx = nullptr;
     }
-    double* curH() const { return d[tpar == 0 ? H0 : H1]; }
-    double* curA() const { return d[tpar == 0 ? A0 : A1]; }
-    double* curS() const { return d[tpar == 0 ? S0 : S1]; }
-    double* curQ() const { return d[tpar == 0 ? Q0 : Q1]; }
+    // per advected field, after the arrays of Arr: the two halves of the ping-pong (h = 0, 1; tpar says which is current), the stage buffer (2)
+    double* adv(int k, int h) const { return d[NARR + 3 * k + h]; }
+    double* cur(int k) const { return adv(k, tpar); }
     double* curU() const { return d[par == 0 ? Ua : Ub]; }
     double* curV() const { return d[par == 0 ? Va : Vb]; }
     double* col(int k) const { return d[COL] + (long)k * N; }
@@ -392,14 +410,9 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
         b.NN = (long)(2 * b.nx + 1) * (2 * b.ny + 1);
         const long N = b.N, NN = b.NN;
         const long TS = nsdg_tiled_len(b.nx, b.ny, 8), TP = nsdg_tiled_len(b.nx, b.ny, 9);
-        long sizes[NARR];
-        for (int a = 0; a < NARR; ++a)
-            sizes[a] = 0;
-        for (int a : { H0, A0, H1, A1, T2H, T2A, VXDG, VYDG })
-            sizes[a] = 6 * N;
-        if (advectColumn)
-            for (int a : { S0, Q0, S1, Q1, T2S, T2Q })
-                sizes[a] = 6 * N;
+        b.nfields = (int)std::count_if(std::begin(ADVECTED), std::end(ADVECTED), [&](const AdvectedField& a) { return advectColumn || !a.columnState; });
+        // [6][ny][nx] unless set below: VXDG, VYDG and, after the arrays of Arr, the three buffers of every advected field (DynamicsBlock::adv)
+        std::vector<long> sizes(NARR + 3 * b.nfields, 6 * N);
         for (int a : { S11a, S12a, S22a, S11b, S12b, S22b })
             sizes[a] = TS;
         sizes[PG] = TP;
@@ -413,11 +426,11 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
             total += (s + 1) & ~1L; // keep every sub-array 16-byte aligned
         checkHip(hipMalloc(reinterpret_cast<void**>(&b.block), total * sizeof(double)), "DynamicsStep: hipMalloc");
         checkHip(hipMemset(b.block, 0, total * sizeof(double)), "DynamicsStep: hipMemset");
-        b.d.assign(NARR, nullptr);
+        b.d.clear();
         long off = 0;
-        for (int a = 0; a < NARR; ++a) {
-            b.d[a] = b.block + off;
-            off += (sizes[a] + 1) & ~1L;
+        for (long s : sizes) {
+            b.d.push_back(b.block + off);
+            off += (s + 1) & ~1L;
         }
         check(nsdg_grid_set(b.ctx, b.nx, b.ny, hx, hy), "nsdg_grid_set");
         check(nsdg_block_set(b.ctx, b.lo, b.nyGlobal), "nsdg_block_set");
@@ -427,29 +440,28 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
             check(nsdg_land_mask_set(b.ctx, b.land), "nsdg_land_mask_set");
         }
         // cell means -> DG coefficient 0 (the local rows, ghost rows included, are one contiguous slice)
-        const std::size_t first = (std::size_t)b.lo * b.nx;
-        checkHip(hipMemcpy(b.d[H0], f.hice.data() + first, N * sizeof(double), hipMemcpyHostToDevice), "upload H");
-        checkHip(hipMemcpy(b.d[A0], f.cice.data() + first, N * sizeof(double), hipMemcpyHostToDevice), "upload A");
-        if (f.dyn.present) {
-            // a restart: the state a dynamics run left (FieldStore::dyn) -- higher DG2 coefficients, velocity, stress -- for the local
-            // rows, ghost rows included (they hold what an exchange would deliver: the neighbours' own values)
-            const DynamicsState& dy = f.dyn;
-            const std::size_t NG = (std::size_t)nxf * nyf;
-            for (int c = 1; c < 6; ++c) {
-                checkHip(hipMemcpy(b.d[H0] + (long)c * N, dy.hdg.data() + (std::size_t)(c - 1) * NG + first, N * sizeof(double), hipMemcpyHostToDevice), "upload H (DG)");
-                checkHip(hipMemcpy(b.d[A0] + (long)c * N, dy.adg.data() + (std::size_t)(c - 1) * NG + first, N * sizeof(double), hipMemcpyHostToDevice), "upload A (DG)");
-                if (advectColumn && dy.sdg.size() == 5 * NG) // a file without hsnow_dg: the higher coefficients of the snow start at zero
-                    checkHip(hipMemcpy(b.d[S0] + (long)c * N, dy.sdg.data() + (std::size_t)(c - 1) * NG + first, N * sizeof(double), hipMemcpyHostToDevice), "upload S (DG)");
-            }
+        const std::size_t first = (std::size_t)b.lo * b.nx, NG = (std::size_t)nxf * nyf;
+        // a restart: the state a dynamics run left (FieldStore::dyn) -- higher DG2 coefficients, velocity, stress -- for the local
+        // rows, ghost rows included (they hold what an exchange would deliver: the neighbours' own values)
+        const DynamicsState& dy = f.dyn;
+        for (int k = 0; k < b.nfields; ++k) {
+            const AdvectedField& a = ADVECTED[k];
+            if (!a.mean)
+                continue;
+            checkHip(hipMemcpy(b.adv(k, 0), (f.*a.mean).data() + first, N * sizeof(double), hipMemcpyHostToDevice), "upload cell means");
+            if (!dy.present || (dy.*a.higher).size() != 5 * NG) // (a file without hsnow_dg: the higher coefficients of the snow start at zero)
+                continue;
+            for (int c = 1; c < 6; ++c)
+                checkHip(hipMemcpy(b.adv(k, 0) + (long)c * N, (dy.*a.higher).data() + (std::size_t)(c - 1) * NG + first, N * sizeof(double), hipMemcpyHostToDevice), "upload DG coefficients");
+        }
+        if (dy.present) {
             const std::size_t nn = 2 * (std::size_t)b.nx + 1, nfirst = 2 * (std::size_t)b.lo * nn;
             checkHip(hipMemcpy(b.d[Ua], dy.u.data() + nfirst, NN * sizeof(double), hipMemcpyHostToDevice), "upload u");
             checkHip(hipMemcpy(b.d[Va], dy.v.data() + nfirst, NN * sizeof(double), hipMemcpyHostToDevice), "upload v");
             std::vector<double> t((std::size_t)TS, 0.);
-            const std::vector<double>* comps[3] = { &dy.s11, &dy.s12, &dy.s22 };
-            const int dst[3] = { S11a, S12a, S22a };
             for (int k = 0; k < 3; ++k) {
-                tileRows(comps[k]->data(), NG, (std::size_t)b.lo, b.nx, b.ny, t);
-                checkHip(hipMemcpy(b.d[dst[k]], t.data(), (std::size_t)TS * sizeof(double), hipMemcpyHostToDevice), "upload stress");
+                tileRows((dy.*STRESS[k]).data(), NG, (std::size_t)b.lo, b.nx, b.ny, t);
+                checkHip(hipMemcpy(b.d[S11a + k], t.data(), (std::size_t)TS * sizeof(double), hipMemcpyHostToDevice), "upload stress");
             }
         }
         // analytic box-test forcing, evaluated on the device (ocean once, wind at the current model time every step); a forcing file's
@@ -465,14 +477,11 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
                 &f.snowfall, &f.wind, &f.newice };
             for (int c = 0; c < NCOL; ++c)
                 checkHip(hipMemcpy(b.col(c), planes[c]->data() + first, N * sizeof(double), hipMemcpyHostToDevice), "upload column fields");
-            if (advectColumn) // plane 0 of the snow field IS the column's hsnow (C_HSNOW stays unused)
-                checkHip(hipMemcpy(b.d[S0], f.hsnow.data() + first, N * sizeof(double), hipMemcpyHostToDevice), "upload S");
         }
         if (m_landMask) { // no ice on land, no motion at land nodes, whatever the initial state or the restart file held there
-            check(nsdg_land_clear(b.ctx, 0, b.ny, 6, b.d[H0]), "nsdg_land_clear");
-            check(nsdg_land_clear(b.ctx, 0, b.ny, 6, b.d[A0]), "nsdg_land_clear");
-            if (advectColumn)
-                check(nsdg_land_clear(b.ctx, 0, b.ny, 6, b.d[S0]), "nsdg_land_clear");
+            for (int k = 0; k < b.nfields; ++k)
+                if (ADVECTED[k].mean)
+                    check(nsdg_land_clear(b.ctx, 0, b.ny, 6, b.adv(k, 0)), "nsdg_land_clear");
             if (thermo) {
                 check(nsdg_land_clear(b.ctx, 0, b.ny, 1, b.col(C_HSNOW)), "nsdg_land_clear");
                 check(nsdg_land_clear(b.ctx, 0, b.ny, 1, b.col(C_NEWICE)), "nsdg_land_clear");
@@ -493,17 +502,11 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
         std::memset(&t, 0, sizeof t);
         t.nx = b.nx, t.ny = b.ny, t.j0 = b.j0, t.j1 = b.j1, t.depth_below = b.depthBelow, t.depth_above = b.depthAbove;
         t.rank_below = b.peerBelow, t.rank_above = b.peerAbove;
-        t.order = 2, t.nfields = advectColumn ? 4 : 2;
-        t.phi[0] = b.d[H0], t.phi[1] = b.d[A0], t.t1[0] = b.d[H1], t.t1[1] = b.d[A1], t.t2[0] = b.d[T2H], t.t2[1] = b.d[T2A];
-        if (advectColumn) // the snow S and the weighted surface temperature Q = H tice0
-            t.phi[2] = b.d[S0], t.phi[3] = b.d[Q0], t.t1[2] = b.d[S1], t.t1[3] = b.d[Q1], t.t2[2] = b.d[T2S], t.t2[3] = b.d[T2Q];
+        t.order = 2, t.nfields = b.nfields;
         t.vx_dg = b.d[VXDG], t.vy_dg = b.d[VYDG], t.un_x = b.d[UNX], t.un_y = b.d[UNY];
-        // the closure travels with the plan (its own bounds, not the context's): mean thickness H >= 0; concentration in [0, 1] with the
-        // cell mean capped at 1
-        // cell mean capped at 1; the snow volume S >= 0; Q unbounded
-        t.own_bounds = 1, t.nbounds = closure ? t.nfields : 0;
-        t.bounds[0] = nsdg_field_bounds { 0., HUGE_VAL, 0, 0 }, t.bounds[1] = nsdg_field_bounds { 0., 1., 1, 0 };
-        t.bounds[2] = nsdg_field_bounds { 0., HUGE_VAL, 0, 0 }, t.bounds[3] = nsdg_field_bounds { -HUGE_VAL, HUGE_VAL, 0, 0 };
+        t.own_bounds = 1, t.nbounds = closure ? t.nfields : 0; // the closure travels with the plan (its own bounds, not the context's)
+        for (int k = 0; k < b.nfields; ++k)
+            t.phi[k] = b.adv(k, 0), t.t1[k] = b.adv(k, 1), t.t2[k] = b.adv(k, 2), t.bounds[k] = ADVECTED[k].bounds;
         check(nsdg_rb_transport_create(b.ctx, &t, &b.transport), "nsdg_rb_transport_create");
         b.par = b.tpar = 0;
     });
@@ -524,7 +527,7 @@ void DynamicsStep::iterate(const Iterator::Duration& dtSeconds)
         forEachBlock([&](DynamicsBlock& b) {
             checkHip(hipSetDevice(b.device), "hipSetDevice");
             check(nsdg_phase_mark(b.ctx, NSDG_PHASE_REDUCTION), "nsdg_phase_mark"); // (the marks do nothing unless model.phase_timing is on)
-            check(nsdg_concentration_max(b.ctx, b.j0, b.j1, b.curH(), b.curA(), &b.amax), "nsdg_concentration_max");
+            check(nsdg_concentration_max(b.ctx, b.j0, b.j1, b.cur(FH), b.cur(FA), &b.amax), "nsdg_concentration_max");
         });
         double amax = 0.; // the blocks of this process are its threads: their maximum is taken here ...
         for (auto& b : m_blocks)
@@ -582,22 +585,20 @@ void DynamicsStep::subStep(double dt, bool last)
             }
             check(nsdg_phase_mark(ctx, NSDG_PHASE_COLUMN), "nsdg_phase_mark");
             // the column physics needs no exchange: it runs on the ghost rows too, redundantly
-            check(nsdg_column_step(ctx, b.N, dt, b.curH(), b.curA(), advectColumn ? b.curS() : b.col(C_HSNOW), b.col(C_TICE), b.col(C_SST), b.col(C_SSS), b.col(C_TAIR),
+            check(nsdg_column_step(ctx, b.N, dt, b.cur(FH), b.cur(FA), advectColumn ? b.cur(FS) : b.col(C_HSNOW), b.col(C_TICE), b.col(C_SST), b.col(C_SSS), b.col(C_TAIR),
                       b.col(C_TDEW), b.col(C_SLP), b.col(C_QSW), b.col(C_QLW), b.col(C_MLD), b.col(C_SNOWFALL), b.col(C_WIND), b.col(C_NEWICE),
                       nullptr),
                 "nsdg_column_step");
             if (b.land) {
                 // the column step computes on land elements too and its result there is discarded: the cell means of H, A (and S), the
                 // snow and the new ice (still the column phase)
-                check(nsdg_land_clear(ctx, 0, b.ny, 1, b.curH()), "nsdg_land_clear");
-                check(nsdg_land_clear(ctx, 0, b.ny, 1, b.curA()), "nsdg_land_clear");
-                check(nsdg_land_clear(ctx, 0, b.ny, 1, advectColumn ? b.curS() : b.col(C_HSNOW)), "nsdg_land_clear");
-                check(nsdg_land_clear(ctx, 0, b.ny, 1, b.col(C_NEWICE)), "nsdg_land_clear");
+                for (double* plane : { b.cur(FH), b.cur(FA), advectColumn ? b.cur(FS) : b.col(C_HSNOW), b.col(C_NEWICE) })
+                    check(nsdg_land_clear(ctx, 0, b.ny, 1, plane), "nsdg_land_clear");
             }
         }
         check(nsdg_phase_mark(ctx, NSDG_PHASE_PREPARE), "nsdg_phase_mark");
-        check(nsdg_ice_strength(ctx, 0, b.ny, b.curH(), b.curA(), b.d[PG]), "nsdg_ice_strength");
-        check(nsdg_mevp_prepare(ctx, dt, b.curH(), b.curA(), b.d[UA], b.d[VA], b.d[UO], b.d[VO], b.curU(), b.curV(), b.d[PACKED]), "nsdg_mevp_prepare");
+        check(nsdg_ice_strength(ctx, 0, b.ny, b.cur(FH), b.cur(FA), b.d[PG]), "nsdg_ice_strength");
+        check(nsdg_mevp_prepare(ctx, dt, b.cur(FH), b.cur(FA), b.d[UA], b.d[VA], b.d[UO], b.d[VO], b.curU(), b.curV(), b.d[PACKED]), "nsdg_mevp_prepare");
         int32_t out = 0;
         check(nsdg_phase_mark(ctx, NSDG_PHASE_SUBCYCLE), "nsdg_phase_mark");
         check(nsdg_rb_mevp_run(ctx, b.mevp, b.par, &out), "nsdg_rb_mevp_run");
@@ -606,11 +607,11 @@ void DynamicsStep::subStep(double dt, bool last)
         check(nsdg_prepare_advection(ctx, 2, b.curU(), b.curV(), b.d[VXDG], b.d[VYDG], b.d[UNX], b.d[UNY]), "nsdg_prepare_advection");
         // the surface temperature travels as Q = H tice0 (every local row: element-local, the ghost rows stay equal to their owners)
         if (advectColumn)
-            check(nsdg_tracer_weight(ctx, 2, 0, b.ny, b.curH(), b.col(C_TICE), b.curQ()), "nsdg_tracer_weight");
+            check(nsdg_tracer_weight(ctx, 2, 0, b.ny, b.cur(FH), b.col(C_TICE), b.cur(FQ)), "nsdg_tracer_weight");
         check(nsdg_rb_transport_run(ctx, b.transport, dt, b.tpar, &out), "nsdg_rb_transport_run");
         b.tpar = out;
         if (advectColumn)
-            check(nsdg_tracer_recover(ctx, 2, 0, b.ny, b.curH(), b.curA(), b.curQ(), p.min_conc, p.min_thick, b.col(C_TICE)), "nsdg_tracer_recover");
+            check(nsdg_tracer_recover(ctx, 2, 0, b.ny, b.cur(FH), b.cur(FA), b.cur(FQ), p.min_conc, p.min_thick, b.col(C_TICE)), "nsdg_tracer_recover");
         if (last) // the model step ends here: what follows until its next mark belongs to no phase
             check(nsdg_phase_mark(ctx, NSDG_PHASE_END), "nsdg_phase_mark");
     });
@@ -715,10 +716,9 @@ void DynamicsStep::stop(const Iterator::TimePoint&)
         if (gaveUp)
             throw std::runtime_error("DynamicsStep: " + std::to_string(gaveUp) + " wait(s) of the mEVP pipeline gave up: the fields are not to be trusted");
         const std::size_t first = (std::size_t)b.r0 * b.nx, count = (std::size_t)(b.r1 - b.r0) * b.nx, skip = (std::size_t)b.j0 * b.nx;
-        checkHip(hipMemcpy(f.hice.data() + first, b.curH() + skip, count * sizeof(double), hipMemcpyDeviceToHost), "download H");
-        checkHip(hipMemcpy(f.cice.data() + first, b.curA() + skip, count * sizeof(double), hipMemcpyDeviceToHost), "download A");
         if (thermo) {
-            checkHip(hipMemcpy(f.hsnow.data() + first, (advectColumn ? b.curS() : b.col(C_HSNOW)) + skip, count * sizeof(double), hipMemcpyDeviceToHost), "download hsnow");
+            if (!advectColumn) // (otherwise f.hsnow receives the mean of S below: S is advected only under thermodynamics)
+                checkHip(hipMemcpy(f.hsnow.data() + first, b.col(C_HSNOW) + skip, count * sizeof(double), hipMemcpyDeviceToHost), "download hsnow");
             checkHip(hipMemcpy(f.tice.data() + first, b.col(C_TICE) + skip, count * sizeof(double), hipMemcpyDeviceToHost), "download tice");
             checkHip(hipMemcpy(f.newice.data() + first, b.col(C_NEWICE) + skip, count * sizeof(double), hipMemcpyDeviceToHost), "download newice");
         }
@@ -730,28 +730,24 @@ void DynamicsStep::stop(const Iterator::TimePoint&)
         const std::size_t NG = (std::size_t)nxf * nyf;
         if (dy.hdg.size() != 5 * NG)
             dy.resize((std::size_t)nyf, (std::size_t)nxf);
-        // the higher coefficients of the snow exist only in this mode: without it nothing of them is written
-        if (!advectColumn)
-            dy.sdg.clear();
-        else if (dy.sdg.size() != 5 * NG)
-            dy.sdg.assign(5 * NG, 0.);
-        for (int c = 1; c < 6; ++c) {
-            if (advectColumn)
-                checkHip(hipMemcpy(dy.sdg.data() + (std::size_t)(c - 1) * NG + first, b.curS() + (long)c * b.N + skip, count * sizeof(double), hipMemcpyDeviceToHost), "download S (DG)");
-            checkHip(hipMemcpy(dy.hdg.data() + (std::size_t)(c - 1) * NG + first, b.curH() + (long)c * b.N + skip, count * sizeof(double), hipMemcpyDeviceToHost), "download H (DG)");
-            checkHip(hipMemcpy(dy.adg.data() + (std::size_t)(c - 1) * NG + first, b.curA() + (long)c * b.N + skip, count * sizeof(double), hipMemcpyDeviceToHost), "download A (DG)");
+        for (int k = 0; k < NFIELD; ++k) {
+            const AdvectedField& a = ADVECTED[k];
+            if (!a.mean)
+                continue;
+            // the higher coefficients of a field exist only while it is advected: otherwise nothing of them is written
+            (dy.*a.higher).resize(k < b.nfields ? 5 * NG : 0, 0.);
+            if (k >= b.nfields)
+                continue;
+            checkHip(hipMemcpy((f.*a.mean).data() + first, b.cur(k) + skip, count * sizeof(double), hipMemcpyDeviceToHost), "download cell means");
+            for (int c = 1; c < 6; ++c)
+                checkHip(hipMemcpy((dy.*a.higher).data() + (std::size_t)(c - 1) * NG + first, b.cur(k) + (long)c * b.N + skip, count * sizeof(double), hipMemcpyDeviceToHost), "download DG coefficients");
         }
         checkHip(hipMemcpy(dy.u.data() + 2L * b.r0 * nn, b.curU() + 2L * b.j0 * nn, rows * nn * sizeof(double), hipMemcpyDeviceToHost), "download u");
         checkHip(hipMemcpy(dy.v.data() + 2L * b.r0 * nn, b.curV() + 2L * b.j0 * nn, rows * nn * sizeof(double), hipMemcpyDeviceToHost), "download v");
-        {
-            const std::size_t TS = (std::size_t)nsdg_tiled_len(b.nx, b.ny, 8);
-            std::vector<double> t(TS);
-            std::vector<double>* comps[3] = { &dy.s11, &dy.s12, &dy.s22 };
-            const int src[3] = { b.par == 0 ? S11a : S11b, b.par == 0 ? S12a : S12b, b.par == 0 ? S22a : S22b };
-            for (int k = 0; k < 3; ++k) {
-                checkHip(hipMemcpy(t.data(), b.d[src[k]], TS * sizeof(double), hipMemcpyDeviceToHost), "download stress");
-                untileRows(t, b.nx, b.j0, b.j1 - b.j0, comps[k]->data(), NG, (std::size_t)b.r0);
-            }
+        std::vector<double> t((std::size_t)nsdg_tiled_len(b.nx, b.ny, 8));
+        for (int k = 0; k < 3; ++k) {
+            checkHip(hipMemcpy(t.data(), b.d[(b.par == 0 ? S11a : S11b) + k], t.size() * sizeof(double), hipMemcpyDeviceToHost), "download stress");
+            untileRows(t, b.nx, b.j0, b.j1 - b.j0, (dy.*STRESS[k]).data(), NG, (std::size_t)b.r0);
         }
         for (long k = 2L * b.r0 * nn; k < (2L * b.r0 + rows) * nn; ++k) {
             umax[idx] = std::max(umax[idx], std::max(std::fabs(dy.u[k]), std::fabs(dy.v[k])));
@@ -827,84 +823,64 @@ void DynamicsStep::writeRestartFile(const std::string& filePath)
         });
 }
 
-std::vector<std::vector<double>*> DynamicsStep::restartPlanes(FieldStore& f, bool thermodynamics)
-{
-    std::vector<std::vector<double>*> planes = { &f.hice, &f.cice };
-    if (thermodynamics)
-        for (auto* p : { &f.hsnow, &f.tice, &f.newice })
-            planes.push_back(p);
-    return planes;
-}
-
 namespace {
-// the element planes of the dynamics state (FieldStore::dyn): 5 + 5 + 3 x 8 planes of n values
-std::vector<double*> dynamicsPlanes(FieldStore& f)
+// What a rank sends for its rows [r0, r1), in order: fn(array, offset, length) for the rows of every prognostic plane a run changes; then,
+// unless state < 0, of what DynamicsState owns of DYNAMICS_VARIABLES with its first `state` optional ones -- the rows of every element
+// plane, and of a nodal array the node rows the block owns: [2 r0, 2 r1) and the top boundary row on the last block
+template <class F> void forPayload(FieldStore& f, bool thermodynamics, int nx, int r0, int r1, int state, F&& fn)
 {
-    std::vector<double*> p;
-    DynamicsState& d = f.dyn;
-    for (auto* v : { &d.hdg, &d.adg })
-        for (int c = 0; c < 5; ++c)
-            p.push_back(v->data() + (std::size_t)c * f.n);
-    for (auto* v : { &d.s11, &d.s12, &d.s22 })
-        for (int c = 0; c < 8; ++c)
-            p.push_back(v->data() + (std::size_t)c * f.n);
-    return p;
+    const std::size_t first = (std::size_t)r0 * nx, rows = (std::size_t)(r1 - r0) * nx, nn = 2 * (std::size_t)nx + 1;
+    for (auto* p : { &f.hice, &f.cice, &f.hsnow, &f.tice, &f.newice })
+        if (thermodynamics || p == &f.hice || p == &f.cice) // (the column model's planes change only with it)
+            fn(*p, first, rows);
+    for (const DynamicsVariable& v : DYNAMICS_VARIABLES) {
+        if (state < 0 || (v.optional() && state-- == 0))
+            break;
+        if (!v.state)
+            continue; // a plane of the FieldStore: it has travelled above, or does not travel
+        if (v.shape == DynamicsVariable::NODAL)
+            fn(v.in(f), 2 * (std::size_t)r0 * nn, (2 * (std::size_t)(r1 - r0) + ((std::size_t)r1 * nx == f.n ? 1 : 0)) * nn);
+        for (int c = 0; c < v.elementPlanes(); ++c)
+            fn(v.in(f), (std::size_t)c * f.n + first, rows);
+    }
 }
-// node rows a block of element rows [r0, r1) owns: [2 r0, 2 r1), and the top boundary row on the last block
-std::size_t ownedNodeRows(int r0, int r1, int ny) { return 2 * (std::size_t)(r1 - r0) + (r1 == ny ? 1 : 0); }
 } // namespace
 
 std::vector<double> DynamicsStep::packRows(FieldStore& f, bool thermodynamics, int nx, int r0, int r1)
 {
+    int state = f.dyn.present ? 0 : -1; // the state of the dynamics travels with the rows, with the optional variables it holds
+    for (const DynamicsVariable& v : DYNAMICS_VARIABLES)
+        state += f.dyn.present && v.optional() && !v.in(f).empty();
     std::vector<double> out;
-    const std::size_t first = (std::size_t)r0 * nx, count = (std::size_t)(r1 - r0) * nx;
-    for (auto* p : restartPlanes(f, thermodynamics))
-        out.insert(out.end(), p->begin() + first, p->begin() + first + count);
-    if (f.dyn.present) { // the state of the dynamics travels with the rows: element planes, then the owned node rows of u and v
-        for (double* p : dynamicsPlanes(f))
-            out.insert(out.end(), p + first, p + first + count);
-        const std::size_t nn = 2 * (std::size_t)nx + 1, nfirst = 2 * (std::size_t)r0 * nn, ncount = ownedNodeRows(r0, r1, (int)(f.n / nx)) * nn;
-        for (auto* v : { &f.dyn.u, &f.dyn.v })
-            out.insert(out.end(), v->begin() + nfirst, v->begin() + nfirst + ncount);
-        if (f.dyn.sdg.size() == 5 * f.n) // dynamics.advect_column_state: the higher coefficients of the snow last
-            for (int c = 0; c < 5; ++c)
-                out.insert(out.end(), f.dyn.sdg.begin() + (std::size_t)c * f.n + first, f.dyn.sdg.begin() + (std::size_t)c * f.n + first + count);
-    }
+    forPayload(f, thermodynamics, nx, r0, r1, state, [&](std::vector<double>& a, std::size_t at, std::size_t length) { out.insert(out.end(), a.begin() + at, a.begin() + at + length); });
     return out;
 }
 
 void DynamicsStep::placeRows(FieldStore& f, bool thermodynamics, int nx, int r0, int r1, const double* data, std::size_t count)
 {
-    const auto planes = restartPlanes(f, thermodynamics);
-    const std::size_t first = (std::size_t)r0 * nx, rows = (std::size_t)(r1 - r0) * nx;
-    const std::size_t nn = 2 * (std::size_t)nx + 1, ny = f.n / nx, nrows = ownedNodeRows(r0, r1, (int)ny) * nn;
-    const std::size_t plain = rows * planes.size(), full = plain + rows * (5 + 5 + 24) + 2 * nrows, snow = full + rows * 5;
-    if (count != plain && count != full && count != snow)
-        throw std::runtime_error("DynamicsStep: a rank delivered " + std::to_string(count) + " values for its rows, expected "
-            + std::to_string(plain) + " (or " + std::to_string(full) + " with the state of the dynamics, " + std::to_string(snow)
-            + " with the snow of dynamics.advect_column_state as well)");
-    for (std::size_t k = 0; k < planes.size(); ++k)
-        std::copy(data + k * rows, data + (k + 1) * rows, planes[k]->begin() + first);
-    if (count == full || count == snow) {
-        if (f.dyn.hdg.size() != 5 * f.n)
-            f.dyn.resize(ny, (std::size_t)nx);
-        const double* p = data + plain;
-        for (double* dst : dynamicsPlanes(f)) {
-            std::copy(p, p + rows, dst + first);
-            p += rows;
-        }
-        for (auto* v : { &f.dyn.u, &f.dyn.v }) {
-            std::copy(p, p + nrows, v->begin() + 2 * (std::size_t)r0 * nn);
-            p += nrows;
-        }
-        if (count == snow) {
-            if (f.dyn.sdg.size() != 5 * f.n)
-                f.dyn.sdg.assign(5 * f.n, 0.);
-            for (int c = 0; c < 5; ++c, p += rows)
-                std::copy(p, p + rows, f.dyn.sdg.begin() + (std::size_t)c * f.n + first);
-        }
-        f.dyn.present = true;
+    // what a rank sent shows in the size alone: its planes, or also the state of the dynamics with none, one, ... of its optional variables
+    const int optional = (int)std::count_if(std::begin(DYNAMICS_VARIABLES), std::end(DYNAMICS_VARIABLES), [](const DynamicsVariable& v) { return v.optional(); });
+    std::string sizes;
+    int state = -2; // as forPayload reads it, once found
+    for (int k = -1; k <= optional && state < -1; ++k) {
+        std::size_t size = 0;
+        forPayload(f, thermodynamics, nx, r0, r1, k, [&](std::vector<double>&, std::size_t, std::size_t length) { size += length; });
+        if (size == count)
+            state = k;
+        sizes += " " + std::to_string(size);
     }
+    if (state < -1)
+        throw std::runtime_error("DynamicsStep: a rank delivered " + std::to_string(count) + " values for its rows, expected one of" + sizes
+            + " (its planes alone, with the state of the dynamics, with each optional variable of that as well)");
+    int optionals = state;
+    for (const DynamicsVariable& v : DYNAMICS_VARIABLES) // whatever of the delivered state nothing has filled yet starts at zero
+        if (state >= 0 && v.state && (!v.optional() || optionals-- > 0) && v.in(f).size() != v.size(f.n / nx, (std::size_t)nx))
+            v.in(f).assign(v.size(f.n / nx, (std::size_t)nx), 0.);
+    f.dyn.present = f.dyn.present || state >= 0;
+    forPayload(f, thermodynamics, nx, r0, r1, state, [&](std::vector<double>& a, std::size_t at, std::size_t length) {
+        std::copy(data, data + length, a.begin() + at);
+        data += length;
+    });
 }
 
 } // namespace Nextsim

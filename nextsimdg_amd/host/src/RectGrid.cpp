@@ -1,8 +1,11 @@
 #include "RectGrid.hpp"
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <fstream>
+#include <map>
+#include <set>
 #include <sstream>
 #include <stdexcept>
 
@@ -91,17 +94,14 @@ void RectGrid::incrCursor()
 
 namespace {
 const char* MAGIC = "NSDG-RESTART 1";
-bool readHeader(std::istream& f, std::string& type, int& nx, int& ny, int& nl, bool* dynamics = nullptr, bool* snowDg = nullptr)
+//! `on`: receives every other key of the header whose value is 1 (data.dynamics and the flags of the optional variables)
+bool readHeader(std::istream& f, std::string& type, int& nx, int& ny, int& nl, std::set<std::string>* on = nullptr)
 {
     std::string line;
     if (!std::getline(f, line) || line != MAGIC)
         return false;
     type.clear();
     nx = ny = nl = 0;
-    if (dynamics)
-        *dynamics = false;
-    if (snowDg)
-        *snowDg = false;
     while (std::getline(f, line) && line != "END-HEADER") {
         const auto eq = line.find('=');
         if (eq == std::string::npos)
@@ -115,10 +115,8 @@ bool readHeader(std::istream& f, std::string& type, int& nx, int& ny, int& nl, b
             ny = std::stoi(v);
         else if (k == "data.nLayers")
             nl = std::stoi(v);
-        else if (k == "data.dynamics" && dynamics)
-            *dynamics = v == "1";
-        else if (k == "data.snow_dg" && snowDg)
-            *snowDg = v == "1";
+        else if (on && v == "1")
+            on->insert(k);
     }
     return nx > 0 && ny > 0 && nl > 0;
 }
@@ -152,6 +150,11 @@ bool wantsHdf5(const std::string& path)
     return false;
 }
 const char* const PLANE_NAMES[5] = { "hice", "cice", "hsnow", "sst", "sss" }; // core/src/DevGridIO.cpp:35-40
+const char* const DYNAMICS_FLAG = "data.dynamics"; // sidecar header: the variables of DYNAMICS_VARIABLES follow tice
+// the named dimensions of each DynamicsVariable::Shape in an HDF5 file, slowest first (x, y: the grid's own)
+const std::vector<const char*> SHAPE_DIMENSIONS[] = { { "dg2", "x", "y" }, { "stress8", "x", "y" }, { "x", "y" }, { "xnode", "ynode" } };
+// the variables of the dynamics state a file of `f` holds: all of them, the optional ones when they are not empty
+bool written(const DynamicsVariable& v, const FieldStore& f) { return !v.optional() || !v.in(f).empty(); }
 } // namespace
 
 void RectGrid::dump(const std::string& filePath) const
@@ -178,30 +181,21 @@ void RectGrid::dump(const std::string& filePath) const
         }
         w.dataset(data + "/tice", { (std::uint64_t)m_nx, (std::uint64_t)m_ny, (std::uint64_t)m_store.nLayers }, t);
         w.attachDimensions(data + "/tice", { data + "/x", data + "/y", data + "/nLayers" }); // DevGridIO.cpp:192-201
-        if (m_store.dyn.present) { // the state of the dynamics: further variables of the same group (RectGrid.hpp)
-            const DynamicsState& d = m_store.dyn;
+        if (m_store.dyn.present) { // the state of the dynamics: further variables of the same group (DYNAMICS_VARIABLES)
             const std::uint64_t X = (std::uint64_t)m_nx, Y = (std::uint64_t)m_ny;
-            w.dimension(data, "dg2", 5, 3);
-            w.dimension(data, "stress8", 8, 4);
-            w.dimension(data, "xnode", 2 * X + 1, 5);
-            w.dimension(data, "ynode", 2 * Y + 1, 6);
-            for (const auto& v : { std::make_pair("hice_dg", &d.hdg), std::make_pair("cice_dg", &d.adg) }) {
-                w.dataset(data + "/" + v.first, { 5, X, Y }, *v.second);
-                w.attachDimensions(data + "/" + v.first, { data + "/dg2", data + "/x", data + "/y" });
-            }
-            for (const auto& v : { std::make_pair("u", &d.u), std::make_pair("v", &d.v) }) {
-                w.dataset(data + "/" + v.first, { 2 * X + 1, 2 * Y + 1 }, *v.second);
-                w.attachDimensions(data + "/" + v.first, { data + "/xnode", data + "/ynode" });
-            }
-            for (const auto& v : { std::make_pair("s11", &d.s11), std::make_pair("s12", &d.s12), std::make_pair("s22", &d.s22) }) {
-                w.dataset(data + "/" + v.first, { 8, X, Y }, *v.second);
-                w.attachDimensions(data + "/" + v.first, { data + "/stress8", data + "/x", data + "/y" });
-            }
-            w.dataset(data + "/newice", { X, Y }, m_store.newice);
-            w.attachDimensions(data + "/newice", { data + "/x", data + "/y" });
-            if (!d.sdg.empty()) { // dynamics.advect_column_state: the higher coefficients of the snow, as hice_dg
-                w.dataset(data + "/hsnow_dg", { 5, X, Y }, d.sdg);
-                w.attachDimensions(data + "/hsnow_dg", { data + "/dg2", data + "/x", data + "/y" });
+            const std::map<std::string, std::uint64_t> length = { { "x", X }, { "y", Y }, { "dg2", 5 }, { "stress8", 8 }, { "xnode", 2 * X + 1 }, { "ynode", 2 * Y + 1 } };
+            int dimid = 3; // the further dimensions follow x, y, nLayers
+            for (const char* d : { "dg2", "stress8", "xnode", "ynode" })
+                w.dimension(data, d, length.at(d), dimid++);
+            for (const DynamicsVariable& v : DYNAMICS_VARIABLES) {
+                if (!written(v, m_store))
+                    continue;
+                std::vector<std::uint64_t> dims;
+                std::vector<std::string> scales;
+                for (const char* d : SHAPE_DIMENSIONS[v.shape])
+                    dims.push_back(length.at(d)), scales.push_back(data + "/" + d);
+                w.dataset(data + "/" + v.name, dims, v.in(m_store));
+                w.attachDimensions(data + "/" + v.name, scales);
             }
         }
         w.write(filePath);
@@ -214,21 +208,25 @@ void RectGrid::dump(const std::string& filePath) const
       << metadataNodeName() << "." << typeNodeName() << "=" << structureType() << "\n"
       << dataNodeName() << ".x=" << m_nx << "\n"
       << dataNodeName() << ".y=" << m_ny << "\n"
-      << dataNodeName() << ".nLayers=" << m_store.nLayers << "\n"
-      << (!m_store.dyn.present ? "variables=hice,cice,hsnow,sst,sss,tice\nEND-HEADER\n"
-              : m_store.dyn.sdg.empty()
-              ? "data.dynamics=1\nvariables=hice,cice,hsnow,sst,sss,tice,hice_dg,cice_dg,u,v,s11,s12,s22,newice\nEND-HEADER\n"
-              : "data.dynamics=1\ndata.snow_dg=1\nvariables=hice,cice,hsnow,sst,sss,tice,hice_dg,cice_dg,u,v,s11,s12,s22,newice,hsnow_dg\nEND-HEADER\n");
+      << dataNodeName() << ".nLayers=" << m_store.nLayers << "\n";
+    std::string variables = "variables=hice,cice,hsnow,sst,sss,tice";
+    if (m_store.dyn.present) { // its flag, the flags of its optional variables, and every name in the order the arrays follow
+        f << DYNAMICS_FLAG << "=1\n";
+        for (const DynamicsVariable& v : DYNAMICS_VARIABLES)
+            if (written(v, m_store)) {
+                if (v.optional())
+                    f << v.sidecarFlag << "=1\n";
+                variables += std::string(",") + v.name;
+            }
+    }
+    f << variables << "\nEND-HEADER\n";
     for (const auto* v : { &m_store.hice, &m_store.cice, &m_store.hsnow, &m_store.sst, &m_store.sss })
         f.write(reinterpret_cast<const char*>(v->data()), (std::streamsize)(v->size() * sizeof(double)));
     f.write(reinterpret_cast<const char*>(t.data()), (std::streamsize)(t.size() * sizeof(double)));
-    if (m_store.dyn.present) {
-        const DynamicsState& d = m_store.dyn;
-        for (const auto* v : { &d.hdg, &d.adg, &d.u, &d.v, &d.s11, &d.s12, &d.s22, &m_store.newice })
-            f.write(reinterpret_cast<const char*>(v->data()), (std::streamsize)(v->size() * sizeof(double)));
-        if (!d.sdg.empty())
-            f.write(reinterpret_cast<const char*>(d.sdg.data()), (std::streamsize)(d.sdg.size() * sizeof(double)));
-    }
+    if (m_store.dyn.present)
+        for (const DynamicsVariable& v : DYNAMICS_VARIABLES)
+            if (written(v, m_store))
+                f.write(reinterpret_cast<const char*>(v.in(m_store).data()), (std::streamsize)(v.in(m_store).size() * sizeof(double)));
 }
 
 void RectGrid::init(const std::string& filePath)
@@ -266,23 +264,19 @@ void RectGrid::init(const std::string& filePath)
         for (std::size_t e = 0; e < m_store.n; ++e)
             for (int l = 0; l < m_store.nLayers; ++l)
                 m_store.tice[(std::size_t)l * m_store.n + e] = t[e * m_store.nLayers + l];
-        if (h.exists(g + "s11")) { // the state of a dynamics run (all of it or none of it)
-            DynamicsState& dy = m_store.dyn;
-            dy.resize((std::size_t)m_nx, (std::size_t)m_ny);
-            for (const auto& v : { std::make_pair("hice_dg", &dy.hdg), std::make_pair("cice_dg", &dy.adg), std::make_pair("u", &dy.u), std::make_pair("v", &dy.v),
-                     std::make_pair("s11", &dy.s11), std::make_pair("s12", &dy.s12), std::make_pair("s22", &dy.s22), std::make_pair("newice", &m_store.newice) }) {
-                std::vector<double> a = h.readDoubles(g + v.first);
-                if (a.size() != v.second->size())
-                    throw std::runtime_error("restart file " + filePath + ": " + v.first + " does not have the size the grid asks for");
-                v.second->swap(a);
+        const auto held = [&](const DynamicsVariable& v) { return h.exists(g + v.name); };
+        if (std::any_of(std::begin(DYNAMICS_VARIABLES), std::end(DYNAMICS_VARIABLES), [&](const DynamicsVariable& v) { return !v.optional() && held(v); })) {
+            // the state of a dynamics run (all of it or none of it); an optional variable the file does not hold stays empty
+            m_store.dyn.resize((std::size_t)m_nx, (std::size_t)m_ny);
+            for (const DynamicsVariable& v : DYNAMICS_VARIABLES) {
+                if (v.optional() && !held(v))
+                    continue;
+                std::vector<double> a = h.readDoubles(g + v.name);
+                if (a.size() != v.size((std::size_t)m_nx, (std::size_t)m_ny))
+                    throw std::runtime_error("restart file " + filePath + ": " + v.name + " does not have the size the grid asks for");
+                v.in(m_store).swap(a);
             }
-            if (h.exists(g + "hsnow_dg")) { // the snow of dynamics.advect_column_state (optional: absent, its higher coefficients start at zero)
-                std::vector<double> a = h.readDoubles(g + "hsnow_dg");
-                if (a.size() != dy.hdg.size())
-                    throw std::runtime_error("restart file " + filePath + ": hsnow_dg does not have the size the grid asks for");
-                dy.sdg.swap(a);
-            }
-            dy.present = true;
+            m_store.dyn.present = true;
         }
         resetCursor();
         return;
@@ -290,8 +284,8 @@ void RectGrid::init(const std::string& filePath)
     std::ifstream f(filePath, std::ios::binary);
     std::string type;
     int nx, ny, nl;
-    bool dynamics = false, snowDg = false;
-    if (!f || !readHeader(f, type, nx, ny, nl, &dynamics, &snowDg))
+    std::set<std::string> on;
+    if (!f || !readHeader(f, type, nx, ny, nl, &on))
         throw std::runtime_error("cannot read restart file " + filePath);
     if (structureType() == "devgrid" && (nx != 10 || ny != 10))
         throw std::runtime_error("devgrid restart files must be 10x10");
@@ -300,16 +294,15 @@ void RectGrid::init(const std::string& filePath)
         f.read(reinterpret_cast<char*>(v->data()), (std::streamsize)(v->size() * sizeof(double)));
     std::vector<double> t(m_store.tice.size());
     f.read(reinterpret_cast<char*>(t.data()), (std::streamsize)(t.size() * sizeof(double)));
-    if (dynamics) {
-        DynamicsState& d = m_store.dyn;
-        d.resize((std::size_t)nx, (std::size_t)ny);
-        for (auto* v : { &d.hdg, &d.adg, &d.u, &d.v, &d.s11, &d.s12, &d.s22, &m_store.newice })
-            f.read(reinterpret_cast<char*>(v->data()), (std::streamsize)(v->size() * sizeof(double)));
-        if (snowDg) {
-            d.sdg.assign(d.hdg.size(), 0.);
-            f.read(reinterpret_cast<char*>(d.sdg.data()), (std::streamsize)(d.sdg.size() * sizeof(double)));
+    if (on.count(DYNAMICS_FLAG)) {
+        m_store.dyn.resize((std::size_t)nx, (std::size_t)ny);
+        for (const DynamicsVariable& v : DYNAMICS_VARIABLES) {
+            if (v.optional() && !on.count(v.sidecarFlag))
+                continue; // stays empty
+            v.in(m_store).resize(v.size((std::size_t)nx, (std::size_t)ny));
+            f.read(reinterpret_cast<char*>(v.in(m_store).data()), (std::streamsize)(v.in(m_store).size() * sizeof(double)));
         }
-        d.present = true;
+        m_store.dyn.present = true;
     }
     if (!f)
         throw std::runtime_error("restart file " + filePath + " is truncated");

@@ -839,71 +839,90 @@ static void test_restart_gather()
     CHECK_THROWS_AS(gatherToRankZero(orphan, &x, sizeof x, nullptr, 1), std::runtime_error);
 }
 
-static void fillDynamicsState(FieldStore& f, int nx, int ny, double salt)
-{ // nx = slow ("x" of the file), ny = fast
+static std::vector<char> fileBytes(const std::string& path)
+{
+    std::ifstream f(path, std::ios::binary);
+    return std::vector<char>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+}
+
+static void fillDynamicsState(FieldStore& f, int nx, int ny, double salt, bool snow = false)
+{ // nx = slow ("x" of the file), ny = fast; snow: with the higher coefficients of the snow of dynamics.advect_column_state (hsnow_dg)
     f.dyn.resize((std::size_t)nx, (std::size_t)ny);
+    f.dyn.sdg.assign(snow ? f.dyn.hdg.size() : 0, 0.);
     auto fill = [&](std::vector<double>& v, double base) {
         for (std::size_t k = 0; k < v.size(); ++k)
             v[k] = base + salt + 1e-3 * (double)k;
     };
     fill(f.dyn.hdg, 1.), fill(f.dyn.adg, 2.), fill(f.dyn.u, 3.), fill(f.dyn.v, 4.), fill(f.dyn.s11, 5.), fill(f.dyn.s12, 6.), fill(f.dyn.s22, 7.);
+    fill(f.dyn.sdg, 8.);
     f.dyn.present = true;
 }
 
 static void test_restart_with_dynamics_state()
-{ // what a dynamics run carries between steps travels in the restart file, in both formats (RectGrid.hpp), and between the ranks
-    for (const char* path : { "/tmp/nsdg_host_test_dyn_restart.nc", "/tmp/nsdg_host_test_dyn_restart.nsdg" }) {
-        RectGrid g;
-        g.resize(5, 7, 2);
-        FieldStore& f = g.fields();
-        for (std::size_t e = 0; e < f.n; ++e)
-            f.hice[e] = 0.1 * e, f.cice[e] = 0.5, f.newice[e] = 1e-5 * e;
-        fillDynamicsState(f, 5, 7, 0.25);
-        g.dump(path);
-        auto again = StructureFactory::generateFromFile(path);
-        again->init(path);
-        const FieldStore& r = again->fields();
-        CHECK(r.dyn.present && r.dyn.hdg == f.dyn.hdg && r.dyn.adg == f.dyn.adg && r.dyn.u == f.dyn.u && r.dyn.v == f.dyn.v);
-        CHECK(r.dyn.s11 == f.dyn.s11 && r.dyn.s12 == f.dyn.s12 && r.dyn.s22 == f.dyn.s22 && r.newice == f.newice && r.hice == f.hice);
-        if (Hdf5File::isHdf5(path)) { // named dimensions as the reference names its own (core/src/DevGridIO.cpp:169-172)
-            const Hdf5File h(path);
-            CHECK(h.dims("/data/hice_dg") == (std::vector<std::uint64_t> { 5, 5, 7 }) && h.dims("/data/u") == (std::vector<std::uint64_t> { 11, 15 }));
-            CHECK(h.dims("/data/s12") == (std::vector<std::uint64_t> { 8, 5, 7 }) && h.exists("/data/stress8") && h.exists("/data/xnode"));
+{ // what a dynamics run carries between steps travels in the restart file, in both formats (RectGrid.hpp), and between the ranks;
+  // with and without the optional hsnow_dg
+    const char* keep = std::getenv("NSDG_KEEP_DYN_RESTART"); // a directory: lets the Python test pin the bytes of the four files
+    for (const bool snow : { false, true })
+        for (const char* ext : { ".nc", ".nsdg" }) {
+            const std::string path = std::string("/tmp/nsdg_host_test_dyn_restart") + ext;
+            RectGrid g;
+            g.resize(5, 7, 2);
+            FieldStore& f = g.fields();
+            for (std::size_t e = 0; e < f.n; ++e)
+                f.hice[e] = 0.1 * e, f.cice[e] = 0.5, f.newice[e] = 1e-5 * e;
+            fillDynamicsState(f, 5, 7, 0.25, snow);
+            g.dump(path);
+            if (keep) {
+                const std::vector<char> bytes = fileBytes(path);
+                std::ofstream(std::string(keep) + (snow ? "/dyn_restart_snow" : "/dyn_restart") + ext, std::ios::binary).write(bytes.data(), (std::streamsize)bytes.size());
+            }
+            auto again = StructureFactory::generateFromFile(path);
+            again->init(path);
+            const FieldStore& r = again->fields();
+            CHECK(r.dyn.present && r.dyn.hdg == f.dyn.hdg && r.dyn.adg == f.dyn.adg && r.dyn.u == f.dyn.u && r.dyn.v == f.dyn.v);
+            CHECK(r.dyn.s11 == f.dyn.s11 && r.dyn.s12 == f.dyn.s12 && r.dyn.s22 == f.dyn.s22 && r.newice == f.newice && r.hice == f.hice);
+            CHECK(r.dyn.sdg == f.dyn.sdg && r.dyn.sdg.size() == (snow ? 5 * f.n : 0)); // a file without hsnow_dg leaves it empty
+            if (Hdf5File::isHdf5(path)) { // named dimensions as the reference names its own (core/src/DevGridIO.cpp:169-172)
+                const Hdf5File h(path);
+                CHECK(h.dims("/data/hice_dg") == (std::vector<std::uint64_t> { 5, 5, 7 }) && h.dims("/data/u") == (std::vector<std::uint64_t> { 11, 15 }));
+                CHECK(h.dims("/data/s12") == (std::vector<std::uint64_t> { 8, 5, 7 }) && h.exists("/data/stress8") && h.exists("/data/xnode"));
+                CHECK(h.exists("/data/hsnow_dg") == snow && (!snow || h.dims("/data/hsnow_dg") == (std::vector<std::uint64_t> { 5, 5, 7 })));
+            }
+            // a file without the state (the reference's, a column-only run's): the dynamics start from rest
+            RectGrid plain;
+            plain.resize(5, 7, 2);
+            plain.dump(path);
+            again->init(path);
+            CHECK(!again->fields().dyn.present && again->fields().dyn.sdg.empty());
+            std::remove(path.c_str());
         }
-        // a file without the state (the reference's, a column-only run's): the dynamics start from rest
-        RectGrid plain;
-        plain.resize(5, 7, 2);
-        plain.dump(path);
-        again->init(path);
-        CHECK(!again->fields().dyn.present);
-        std::remove(path);
-    }
     // the rows of a rank travel with their share of the state
     const int nx = 7, ny = 10; // here nx = the fast dimension of the dynamics (row length), ny = rows
-    FieldStore a, b;
-    a.resize((std::size_t)nx * ny, 1), b.resize((std::size_t)nx * ny, 1);
-    fillDynamicsState(a, ny, nx, 0.5);
-    for (const auto& rows : { std::make_pair(3, 6), std::make_pair(6, 10) }) { // an interior block and the last one (which owns the top node row)
-        const std::vector<double> packed = DynamicsStep::packRows(a, false, nx, rows.first, rows.second);
-        const std::size_t nodeRows = 2 * (std::size_t)(rows.second - rows.first) + (rows.second == ny ? 1 : 0);
-        CHECK(packed.size() == (std::size_t)(rows.second - rows.first) * nx * (2 + 34) + 2 * nodeRows * (2 * nx + 1));
-        DynamicsStep::placeRows(b, false, nx, rows.first, rows.second, packed.data(), packed.size());
-        bool ok = b.dyn.present;
-        for (int c = 0; c < 8 && ok; ++c)
-            for (int e = rows.first * nx; e < rows.second * nx; ++e)
-                ok = ok && b.dyn.s12[(std::size_t)c * a.n + e] == a.dyn.s12[(std::size_t)c * a.n + e] && (c >= 5 || b.dyn.adg[(std::size_t)c * a.n + e] == a.dyn.adg[(std::size_t)c * a.n + e]);
-        for (std::size_t k = 2 * (std::size_t)rows.first * (2 * nx + 1); k < (2 * (std::size_t)rows.first + nodeRows) * (2 * nx + 1) && ok; ++k)
-            ok = ok && b.dyn.u[k] == a.dyn.u[k] && b.dyn.v[k] == a.dyn.v[k];
-        CHECK(ok);
-        CHECK(b.dyn.u[0] == 0. && b.dyn.s11[0] == 0.); // rows nobody delivered stay as they were
-        CHECK_THROWS_AS(DynamicsStep::placeRows(b, false, nx, rows.first, rows.second, packed.data(), packed.size() - 1), std::runtime_error);
+    for (const bool snow : { false, true }) {
+        FieldStore a, b;
+        a.resize((std::size_t)nx * ny, 1), b.resize((std::size_t)nx * ny, 1);
+        fillDynamicsState(a, ny, nx, 0.5, snow);
+        for (const auto& rows : { std::make_pair(3, 6), std::make_pair(6, 10) }) { // an interior block and the last one (which owns the top node row)
+            const std::vector<double> packed = DynamicsStep::packRows(a, false, nx, rows.first, rows.second);
+            const std::size_t nodeRows = 2 * (std::size_t)(rows.second - rows.first) + (rows.second == ny ? 1 : 0);
+            CHECK(packed.size() == (std::size_t)(rows.second - rows.first) * nx * (2 + 34 + (snow ? 5 : 0)) + 2 * nodeRows * (2 * nx + 1));
+            DynamicsStep::placeRows(b, false, nx, rows.first, rows.second, packed.data(), packed.size());
+            bool ok = b.dyn.present;
+            for (int c = 0; c < 8 && ok; ++c)
+                for (int e = rows.first * nx; e < rows.second * nx; ++e)
+                    ok = ok && b.dyn.s12[(std::size_t)c * a.n + e] == a.dyn.s12[(std::size_t)c * a.n + e] && (c >= 5 || b.dyn.adg[(std::size_t)c * a.n + e] == a.dyn.adg[(std::size_t)c * a.n + e]);
+            for (std::size_t k = 2 * (std::size_t)rows.first * (2 * nx + 1); k < (2 * (std::size_t)rows.first + nodeRows) * (2 * nx + 1) && ok; ++k)
+                ok = ok && b.dyn.u[k] == a.dyn.u[k] && b.dyn.v[k] == a.dyn.v[k];
+            CHECK(ok);
+            CHECK(b.dyn.u[0] == 0. && b.dyn.s11[0] == 0.); // rows nobody delivered stay as they were
+            bool snowOk = b.dyn.sdg.size() == (snow ? 5 * a.n : 0) && (!snow || b.dyn.sdg[0] == 0.); // the snow's coefficients travel when the sender holds them
+            for (int c = 0; c < 5 && snow && snowOk; ++c)
+                for (int e = rows.first * nx; e < rows.second * nx; ++e)
+                    snowOk = snowOk && b.dyn.sdg[(std::size_t)c * a.n + e] == a.dyn.sdg[(std::size_t)c * a.n + e];
+            CHECK(snowOk);
+            CHECK_THROWS_AS(DynamicsStep::placeRows(b, false, nx, rows.first, rows.second, packed.data(), packed.size() - 1), std::runtime_error);
+        }
     }
-}
-
-static std::vector<char> fileBytes(const std::string& path)
-{
-    std::ifstream f(path, std::ios::binary);
-    return std::vector<char>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
 }
 
 static void run_dynamics_to_file(const std::string& model, const std::string& extra, const std::string& finalFile)
@@ -1007,7 +1026,9 @@ int main(int argc, char** argv)
 {
     const bool gpu = argc > 1 && std::strcmp(argv[1], "--gpu") == 0;
     try {
-        if (!gpu) {
+        if (argc > 1 && std::strcmp(argv[1], "--restart-files") == 0) { // that case alone: for the Python test that pins its files' bytes
+            test_restart_with_dynamics_state();
+        } else if (!gpu) {
             test_module_loader();
             test_configured_module();
             test_configurator();

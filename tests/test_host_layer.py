@@ -85,6 +85,30 @@ def test_written_restart_file_is_read_by_the_hdf5_library(host_build, tmp_path):
     assert row4 and "1.0403" in row4[0], data  # element (4, 3) of the pattern 1 + 0.01 i + 0.0001 j
 
 
+RESTART_SHA256 = {  # recorded from the commit before the variable table, with this keep hook added to its test program
+    "dyn_restart.nc": "13bbe136805c5e048f76c76c7318b1108bd80b84df38002c33c079ebcc6f3f3a",
+    "dyn_restart.nsdg": "7ec362ba7240af6b7606d3c6768b304390c39566a99d6f3545a2d0077f6e5d9c",
+    "dyn_restart_snow.nc": "be98ff1146642aab2bbdebae812a7e6ff129e2192816f72f9a13b6501e1ef4f7",
+    "dyn_restart_snow.nsdg": "27070e9fbc1369c0d851dbf516f8717b4683681bb72fac215c7a07826f584391",
+}
+
+
+def test_restart_file_bytes_are_pinned(host_build, tmp_path):
+    """the round trips of host_tests cannot see a writer and a reader that change together: the restart files of its
+    test_restart_with_dynamics_state (5 x 7 grid, 2 layers; both formats, with and without hsnow_dg) are kept and
+    compared byte for byte, through their SHA-256, with what the code wrote when the formats were laid down"""
+    import hashlib
+
+    env = dict(os.environ, NSDG_GOLDEN_DIR=GOLDEN, NSDG_KEEP_DYN_RESTART=str(tmp_path))
+    p = subprocess.run([os.path.join(host_build, "host_tests"), "--restart-files"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=env, timeout=300)
+    assert p.returncode == 0 and re.search(r"[1-9]\d* checks, 0 failures", p.stdout.decode()), p.stdout.decode()
+    got = {}
+    for name in RESTART_SHA256:
+        with open(os.path.join(str(tmp_path), name), "rb") as f:
+            got[name] = hashlib.sha256(f.read()).hexdigest()
+    assert got == RESTART_SHA256
+
+
 def test_help_lists_the_reference_options(host_build):
     rc, out = run([os.path.join(host_build, "nextsim_amd"), "--help"])
     assert rc == 0

@@ -123,6 +123,65 @@ def test_reference_keeps_the_damage_in_range_under_random_input():
     assert all(np.all(np.isfinite(x)) for x in So + [Do, un, vn])
 
 
+# ---- the cases of the device tests hold their conditions on the reference alone -----------------------------------------------------------
+import bbm_cases as B  # noqa: E402
+
+FIVE = ("compressive", "envelope", "intact", "d_below_0", "d_above_dmax")
+# kind: the branches that hold >= 5 % of the Gauss points at 70 x 9.  dmax runs dt_s = 1 s and t_heal = 1e30: r <= 0.5 and nothing heals to
+# 0 there, its own branch is the output clamp.  icefree is random_case around its patches: no compressive failure, damage inside (0, d_max).
+SHARES = {k: FIVE + ("r_is_1", "healed_to_0") for k in ("branches", "exponent1", "exponent2", "params")}
+SHARES["dmax"] = FIVE + ("out_at_dmax",)
+SHARES["icefree"] = ("envelope", "intact", "ice_free")
+
+
+@pytest.mark.parametrize("key", B.ALL_CASES, ids=B.case_id)
+def test_device_case_holds_its_margins_branches_and_conditioning(key):
+    """every (kind, shape) of tests/test_gpu_bbm_branches.py, on the reference alone: (a) no Gauss point within 1e3 Pa of sigma_n = 0 (old
+    stress) or within 1e-6 N of sigma_n = -N (new stress), the scheme's two discontinuities; (b) at 70 x 9 every branch the kind is
+    there for holds its share of the Gauss points; (c) the float64 reference agrees with its own evaluation in longdouble within a
+    quarter of the tolerance the device is held to, so an error above that tolerance is the kernel's"""
+    case, ref = B.built(key)
+    B.assert_margins(case, ref, B.case_id(key))
+    kind, nx, ny = key[:3]
+    if (nx, ny) == (70, 9):
+        s = B.shares(case, ref)
+        print({k: round(v, 3) for k, v in s.items()})
+        for k in SHARES[kind]:
+            assert s[k] >= 0.05, (k, s[k])
+        assert s["pt_clamped"] > 0.0 and s["pt_zero"] >= 0.2
+        if kind == "icefree":
+            assert s["hg_zero"] >= 0.02
+        else:
+            assert s["ice_free"] == 0.0
+    wide = B.case_reference(case, np.longdouble)
+    assert wide["u"].dtype == np.longdouble and wide["S"][0].dtype == np.longdouble and wide["D"].dtype == np.longdouble
+    worst = {}
+    for name, got, want in [(n, ref["S"][i], wide["S"][i]) for i, n in enumerate(("s11", "s12", "s22"))] + [(k, ref[k], wide[k]) for k in ("D", "u", "v")]:
+        worst[name] = float(np.max(np.abs(got - want) / B.tolerance(got)))
+    if kind == "icefree":  # the second comparison of the device test: the nodes with ice under the floor of their own maximum
+        ice = ~B.ice_free_nodes(case, ref)
+        for k in ("u", "v"):
+            worst[k + " (ice)"] = float(np.max(np.abs(ref[k] - wide[k])[ice] / B.tolerance(ref[k], ref[k][ice])[ice]))
+    print("float64 against longdouble, worst |difference| / tolerance: " + ", ".join("%s %.3f" % kv for kv in worst.items()))
+    assert max(worst.values()) <= 0.25, worst
+
+
+def test_a_slab_of_whole_rows_reproduces_the_full_reference_bitwise():
+    """what the 2048 x 2048 device test relies on: the reference on a slab of whole rows, as a local array of its own, equals the
+    reference on the full array bit for bit once one margin row is dropped on every side that is not the physical boundary"""
+    nx, ny = 20, 30
+    case = B.build(nx, ny, B.SEED, "branches")
+    full = B.case_reference(case)
+    for r0, r1 in ((0, 8), (9, 19), (ny - 8, ny)):
+        part = B.case_reference(dict(case, c=B.slab(case["c"], r0, r1)))
+        e0, e1, n0, n1 = B.slab_interior(r0, r1, ny)
+        assert (e1 - e0, n1 - n0) == ((7, 15) if r0 == 0 or r1 == ny else (8, 17))
+        for a, b in zip(part["S"] + [part["D"]], full["S"] + [full["D"]]):
+            assert np.array_equal(a[:, e0:e1], b[:, r0 + e0:r0 + e1])
+        for k in ("u", "v"):
+            assert np.array_equal(part[k][n0:n1], full[k][2 * r0 + n0:2 * r0 + n1]) and np.any(part[k][n0:n1] != 0.0)
+
+
 # ---- the row-block driver on the reference ops -----------------------------------------------------------------------------------------
 NX, NY, NSUB, NSTEPS, DT = 12, 18, 8, 3, 8.0
 

@@ -19,6 +19,7 @@ for p in (ROOT, HERE):
         sys.path.insert(0, p)
 
 import bbm_ref as R  # noqa: E402
+from bbm_cases import dg2, random_case, reference  # noqa: E402,F401 -- the inputs and their reference, shared with the CPU conditions
 from nextsimdg_amd import abi, rowblock  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -37,7 +38,7 @@ def ctx(gpu):
 
 
 def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    return a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a)).cuda()  # a field already on the device stays there
 
 
 def tdev(a):
@@ -58,47 +59,6 @@ def assert_close(got, want, rtol, atol, what):
     assert np.all(err <= lim), "%s: %d of %d entries differ, worst err / limit %.3g" % (what, (err > lim).sum(), err.size, (err / lim).max())
 
 
-def dg2(rng, lo, hi, ny, nx, wiggle):
-    """a DG2 field with cell means in [lo, hi] and small higher coefficients"""
-    f = wiggle * rng.uniform(-1.0, 1.0, (6, ny, nx))
-    f[0] = rng.uniform(lo, hi, (ny, nx))
-    return f
-
-
-def random_case(nx, ny, seed=11, land=None):
-    """the inputs of one sub-iteration: |sigma_n| in [1.5e3, 3e4] Pa with both signs (+- 350 Pa from the higher coefficients), the
-    deviatoric part +- 2e4 Pa, nodal velocities of +- 5e-5 m/s on 500 m node spacing, H in [0.3, 2], A in [0.7, 1], D in [0, 0.9]"""
-    rng = np.random.default_rng(seed)
-    sn = rng.uniform(1.5e3, 3.0e4, (ny, nx)) * rng.choice([-1.0, 1.0], (ny, nx))
-    d1, d2 = rng.uniform(-2e4, 2e4, (2, ny, nx))
-    S = [50.0 * rng.uniform(-1.0, 1.0, (8, ny, nx)) for _ in range(3)]
-    S[0][0], S[1][0], S[2][0] = sn + d1, d2, sn - d1
-    shape = (2 * ny + 1, 2 * nx + 1)
-    u, v = 5e-5 * rng.uniform(-1.0, 1.0, (2,) + shape)
-    for a in (u, v):
-        a[0] = a[-1] = 0.0
-        a[:, 0] = a[:, -1] = 0.0
-    c = dict(nx=nx, ny=ny, S=S, u=u, v=v, H=dg2(rng, 0.35, 1.9, ny, nx, 0.01), A=dg2(rng, 0.72, 0.98, ny, nx, 0.004), D=dg2(rng, 0.05, 0.85, ny, nx, 0.01),
-             ua=rng.uniform(-10.0, 10.0, shape), va=rng.uniform(-10.0, 10.0, shape), uo=rng.uniform(-0.05, 0.05, shape),
-             vo=rng.uniform(-0.05, 0.05, shape), land=land)
-    if land is not None:  # no ice, no stress, no motion on land -- and a wind that must never enter
-        for f in [c["H"], c["A"], c["D"]] + S:
-            f[:, land] = 0.0
-        ln = R.land_nodes(land)
-        u[ln] = v[ln] = 0.0
-        c["ua"][ln] = c["va"][ln] = np.nan
-    return c
-
-
-def reference(c, bp=None, dts=DTS, hx=HX, hy=HY):
-    mpar, bp, diag = R.mevp_par(), bp or R.bbm_par(), {}
-    gauss = R.prepare(mpar, bp, c["H"], c["A"])
-    nod = R.nodal_fields(mpar, c["H"], c["A"], c["ua"], c["va"], c["uo"], c["vo"])
-    ln = R.land_nodes(c["land"]) if c.get("land") is not None else None
-    So, Do, un, vn = R.iterate(mpar, bp, hx, hy, dts, c["S"], c["D"], c["u"], c["v"], gauss, nod, land=ln, diag=diag)
-    return dict(S=So, D=Do, u=un, v=vn, gauss=gauss, diag=diag)
-
-
 def assert_branch_margins(diag, first=True):
     """the reference stays clear of the scheme's two discontinuities (Pt at sigma_n = 0, d_c at sigma_n = -N), no Gauss point excluded"""
     N = R.bbm_par()["compr_strength"]
@@ -113,10 +73,10 @@ def assert_branch_margins(diag, first=True):
 class Device:
     """the device arrays of a case and one sub-iteration on them through the C ABI"""
 
-    def __init__(self, ctx, c, bp=None, dts=DTS, hx=HX, hy=HY, land_mask=None):
+    def __init__(self, ctx, c, bp=None, dts=DTS, hx=HX, hy=HY, land_mask=None, mp=None):
         nx, ny = c["nx"], c["ny"]
         self.ctx, self.nx, self.ny = ctx, nx, ny
-        ctx.set_mevp_params(ctx.mevp_default_params())
+        ctx.set_mevp_params(mp or ctx.mevp_default_params())
         ctx.set_bbm_params(bp or ctx.bbm_default_params())
         ctx.set_grid(nx, ny, hx, hy)
         self.mask = None if land_mask is None else torch.from_numpy(np.ascontiguousarray(land_mask).astype(np.uint8)).cuda()

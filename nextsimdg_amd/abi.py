@@ -625,6 +625,12 @@ class Context:
         ts = [state[k] for k in STATE] + [forcing[k] for k in FORCING] + [newice]
         _check_f64(*ts, diag)
         n = ts[0].numel()
+        # the ABI takes bare pointers and one n: a shorter plane would be read and written past its end on the device
+        for name, t in zip(STATE + FORCING + ["newice"], ts):
+            if t.numel() != n:
+                raise NsdgError("column_step: %s has %d elements, hice has %d" % (name, t.numel(), n))
+        if diag is not None and diag.numel() != NDIAG * n:
+            raise NsdgError("column_step: diag has %d elements, expected NDIAG * n = %d" % (diag.numel(), NDIAG * n))
         self._call(self.lib.nsdg_column_step(self.h, n, float(dt), *[_ptr(t) for t in ts], _ptr(diag)))
 
     # ---- dynamics

@@ -56,7 +56,8 @@ extern "C" {
  * nsdg_substep_count and nsdg_comm_max_f64 (sub-stepping of the model time step), nsdg_forcing_sample (forcing from a file) and
  * nsdg_tracer_weight / nsdg_tracer_recover (column state transport) and nsdg_phase_timing_set / nsdg_phase_mark / nsdg_phase_times (per-phase
  * device timing) and nsdg_land_mask_set / nsdg_land_clear / nsdg_land_clear_nodes (land mask) and nsdg_bbm_default_params / nsdg_bbm_params_set /
- * nsdg_bbm_prepare / nsdg_bbm_iterate / nsdg_bbm_substep_count (brittle rheology) are additions; nothing that existed changed. */
+ * nsdg_bbm_prepare / nsdg_bbm_iterate / nsdg_bbm_substep_count (brittle rheology) and nsdg_history_accumulate / nsdg_history_field_name /
+ * nsdg_history_field_id (history output) are additions; nothing that existed changed. */
 #define NSDG_ABI_VERSION 6
 
 typedef enum {
@@ -630,6 +631,56 @@ int nsdg_bbm_iterate(nsdg_ctx* ctx, int32_t k0, int32_t j0, int32_t j1, const do
     double* s11_out, double* s12_out, double* s22_out, const double* D_in, double* D_out, const double* u_old, const double* v_old,
     double* u_new, double* v_new, const double* packed, const double* hg, const double* eg, const double* pm);
 int nsdg_bbm_substep_count(const nsdg_bbm_params* p, double rho_ice, double h, double dt, double courant, int32_t max_nsub, int32_t* nsub);
+
+/* ---- history output: time means and snapshots accumulated on the device (csrc/history.hip) ----------------------------
+ * No counterpart in the reference snapshot, which writes its restart file and nothing else.  The fields below are element-local functions of
+ * arrays that sit on the device at the end of every model step, so a host samples them with ONE streaming launch per step into accumulator
+ * planes it owns, downloads those once per output window and divides by the number of samples.
+ *
+ * nsdg_history_accumulate: for every element (iy, ix) of the local rows [j0, j1) and every k < nfields
+ *     acc[k * plane_stride + (iy - row0) * nx + ix]  (store ? = : +=)  x_fields[k](e)
+ *   One launch on the context's stream, one lane per element; every source value is loaded at most once per element, whatever the list.
+ *   The accumulation over time is sequential per element: the result depends on nothing but the samples -- not on the row range, the strip
+ *   or the decomposition.  store != 0 OVERWRITES (it does not add to zero): a NaN left in acc is dropped and no memset is needed.  acc is
+ *   nfields planes of plane_stride doubles each; row0 is the local row that plane row 0 stands for (a row block passes its first owned
+ *   row and keeps planes of its owned rows only).  Rows outside [j0, j1) are not written.
+ *
+ * The samples x_f(e), normative:
+ *   hice, cice, hsnow, tice, damage   H[e], A[e], hsnow[e], tice[e], D[e]: plane 0 of the field -- the cell mean --, unclamped
+ *   u, v                              the velocity at the CG2 centre node of the element, n = (2 iy + 1) (2 nx + 1) + 2 ix + 1
+ *   speed                             sqrt(u u + v v) at that node
+ *   divergence, shear                 with E / W = the nodes (2 iy + 1, 2 ix + 2) / (2 iy + 1, 2 ix) and N / S = (2 iy + 2, 2 ix + 1) / (2 iy, 2 ix + 1):
+ *                                         e11 = (uE - uW) / hx,   e22 = (vN - vS) / hy,   g = (uN - uS) / hy + (vE - vW) / hx
+ *                                     -- the exact derivatives of the biquadratic velocity at the element centre --
+ *                                         divergence = e11 + e22,   shear = sqrt((e11 - e22)^2 + g g)      [1/s]
+ *   sigma_n, sigma_s                  (s11_0 + s22_0) / 2  and  sqrt((s11_0 - s22_0)^2 / 4 + s12_0^2)  from coefficient 0 of the tiled stress,
+ *                                     a[T + 2 l] in "Data layout": the cell mean, because the other seven basis functions have zero mean.
+ *                                     The unit is whatever the rheology stores: the thickness-integrated stress [N/m] of the mEVP
+ *                                     sub-cycle, the stress [Pa] of the BBM sub-cycle.
+ *   Every operation is one fp64 operation (IEEE add, multiply, divide; the device's square root); the device may contract a product and a
+ *   sum into an FMA.
+ *
+ * Checks, as for nsdg_tracer_*: grid set (else NSDG_ERR_STATE); 0 <= j0 <= j1 <= ny; 1 <= nfields <= NSDG_HISTORY_MAX_FIELDS; known ids, no
+ *   id twice; a field whose source pointer is NULL is refused with a message that names the field (sources no listed field reads may be
+ *   NULL); 0 <= row0 <= j0 and plane_stride >= (j1 - row0) nx: NSDG_ERR_ARG.  j0 == j1 does nothing.
+ * nsdg_history_field_name: the name of an id (NULL for an unknown id); nsdg_history_field_id: the id of a name, -1 if unknown.  Host only.
+ * The call belongs to no phase of the phase table: the hosts make it after their NSDG_PHASE_END mark. */
+#define NSDG_HISTORY_MAX_FIELDS 16
+enum {
+    NSDG_HIST_HICE = 0, NSDG_HIST_CICE, NSDG_HIST_U, NSDG_HIST_V, NSDG_HIST_SPEED, NSDG_HIST_DIVERGENCE, NSDG_HIST_SHEAR, NSDG_HIST_SIGMA_N,
+    NSDG_HIST_SIGMA_S, NSDG_HIST_HSNOW, NSDG_HIST_TICE, NSDG_HIST_DAMAGE, NSDG_HIST_COUNT
+};
+typedef struct {
+    const double *H, *A; /* DG fields: plane 0 is read */
+    const double *u, *v; /* CG2 velocity */
+    const double *s11, *s12, *s22; /* tiled stress */
+    const double *hsnow, *tice; /* one plane each (plane 0 of the snow field S under column state transport) */
+    const double* D; /* damage of the brittle rheology: plane 0 is read */
+} nsdg_history_sources;
+int nsdg_history_accumulate(nsdg_ctx* ctx, int32_t j0, int32_t j1, int32_t nfields, const int32_t* fields, const nsdg_history_sources* src,
+    int32_t store, int32_t row0, int64_t plane_stride, double* acc);
+const char* nsdg_history_field_name(int32_t field);
+int nsdg_history_field_id(const char* name);
 
 /* ---- row-block decomposition: ghost-row exchange (SURVEY.md section 8(b) "nsdg_halo_exchange", 8(e)) ----------
  * The reference is a single-process, single-thread program; these entry points have no

@@ -75,6 +75,16 @@ class PhaseTable(C.Structure):
     _fields_ = [("ms", C.c_double * PHASE_MAX), ("count", C.c_int64 * PHASE_MAX), ("total_ms", C.c_double), ("spans", C.c_int64)]
 
 
+# NSDG_HIST_*: the history fields in id order (include/nsdg.h "history output"); the library answers the same names (nsdg_history_field_name)
+HISTORY_FIELDS = ("hice", "cice", "u", "v", "speed", "divergence", "shear", "sigma_n", "sigma_s", "hsnow", "tice", "damage")
+HISTORY_SOURCES = ("H", "A", "u", "v", "s11", "s12", "s22", "hsnow", "tice", "D")
+
+
+class HistorySources(C.Structure):
+    """nsdg_history_sources: the device arrays a sample is taken from (a field no listed field reads may stay NULL)"""
+    _fields_ = [(n, C.c_void_p) for n in HISTORY_SOURCES]
+
+
 COMM_ID_BYTES = 128
 RB_MAX_FIELDS = 4
 
@@ -144,6 +154,9 @@ SYMBOLS = {
     "nsdg_ice_strength": (C.c_int, [VP, I32, I32, VP, VP, VP]),
     "nsdg_tracer_weight": (C.c_int, [VP, I32, I32, I32, VP, VP, VP]),
     "nsdg_tracer_recover": (C.c_int, [VP, I32, I32, I32, VP, VP, VP, D, D, VP]),
+    "nsdg_history_accumulate": (C.c_int, [VP, I32, I32, I32, C.POINTER(I32), C.POINTER(HistorySources), I32, I32, I64, VP]),
+    "nsdg_history_field_name": (C.c_char_p, [I32]),
+    "nsdg_history_field_id": (C.c_int, [C.c_char_p]),
     "nsdg_boxtest_forcing": (C.c_int, [VP, D, D, VP, VP, VP, VP]),
     "nsdg_block_set": (C.c_int, [VP, I32, I32]),
     "nsdg_column_forcing": (C.c_int, [VP, I32, D] + [VP] * 7),
@@ -769,6 +782,31 @@ class Context:
         H[0] >= min_thick A[0]); T keeps its value elsewhere"""
         _check_f64(H, A, Q, T)
         self._call(self.lib.nsdg_tracer_recover(self.h, order, j0, j1, _ptr(H), _ptr(A), _ptr(Q), float(min_conc), float(min_thick), _ptr(T)))
+
+    # ---- history output (include/nsdg.h "history output"; csrc/history.hip)
+    def history_accumulate(self, j0, j1, fields, sources, store, row0, acc):
+        """nsdg_history_accumulate: one sample of every field of `fields` (names of HISTORY_FIELDS) at the elements of the local rows
+        [j0, j1), stored into (store) or added to acc[k, iy - row0, ix]; acc: [len(fields), rows, nx] with rows >= j1 - row0.  sources:
+        name -> tensor for the names of HISTORY_SOURCES the fields read (H, A, D: DG planes [nc, ny, nx], plane 0 is read; u, v: the CG2
+        lattice; s11, s12, s22: tiled; hsnow, tice: one plane)"""
+        ids = (I32 * max(len(fields), 1))()
+        for k, name in enumerate(fields):
+            if name not in HISTORY_FIELDS:
+                raise NsdgError("unknown history field %r (known: %s)" % (name, " ".join(HISTORY_FIELDS)))
+            ids[k] = HISTORY_FIELDS.index(name)
+        ts = {n: sources.get(n) for n in HISTORY_SOURCES}
+        _check_f64(acc, *ts.values())
+        n_el, n_node = self.nx * self.ny, (2 * self.nx + 1) * (2 * self.ny + 1)
+        need = {"H": n_el, "A": n_el, "D": n_el, "hsnow": n_el, "tice": n_el, "u": n_node, "v": n_node}
+        need.update({n: (self.ny * ((self.nx + TILE - 1) // TILE) * 8 * TILE) for n in ("s11", "s12", "s22")})
+        for n, t in ts.items():  # the ABI takes bare pointers: a shorter array would be read past its end on the device
+            if t is not None and t.numel() < need[n]:
+                raise NsdgError("history_accumulate: source %s has %d values, the grid needs %d" % (n, t.numel(), need[n]))
+        if acc.dim() != 3 or acc.shape[0] != len(fields) or acc.shape[2] != self.nx or acc.shape[1] < j1 - row0:
+            raise NsdgError("history_accumulate: acc has shape %s, expected [%d, >= %d, %d]" % (tuple(acc.shape), len(fields), j1 - row0, self.nx))
+        src = HistorySources(*[None if ts[n] is None else ts[n].data_ptr() for n in HISTORY_SOURCES])
+        self._call(self.lib.nsdg_history_accumulate(self.h, j0, j1, len(fields), ids, C.byref(src), int(bool(store)), row0,
+                                                    acc.shape[1] * acc.shape[2], _ptr(acc)))
 
     def concentration_max(self, H, A, j0=0, j1=None):
         """nsdg_concentration_max: largest clamped concentration at the Gauss points of rows [j0, j1) where there is ice (waits for the

@@ -52,6 +52,9 @@
 //     dynamics.substep_courant  cells the strength wave may cross per sub-step under auto (1.5)
 //     dynamics.max_substeps  the largest n auto may choose (16); a state that needs more stops the run with the needed n
 //     model.phase_timing, model.phase_timing_file   per-phase device time of the step (include/PhaseTiming.hpp)
+//     model.output_period, model.output_file, model.output_fields, model.output_kind   history output: time means or snapshots of element
+//                            fields, accumulated on the device after every model step and written once per window
+//                            (include/HistoryOutput.hpp; include/nsdg.h "history output"); period 0 (default): off, nothing changes
 //     dynamics.row_blocks, dynamics.devices, dynamics.passes_per_exchange (2), dynamics.overlap (true),
 //     dynamics.graph (false), dynamics.loopback_world (0: off; N: rehearse an interior block of N on one GPU with
 //     real RCCL send/recv to the rank itself -- values wrap around, for timing and call-path checks only)
@@ -72,6 +75,7 @@ struct nsdg_ctx;
 namespace Nextsim {
 
 class ForcingFile;
+class HistoryOutput;
 class LandMaskFile;
 
 class DynamicsBlock; // one row block: context, device arrays, driver plans (DynamicsStep.cpp)
@@ -119,6 +123,9 @@ private:
     //! forcing at m_time, column step, ice strength, prepare, sub-cycle and transport with dt, each opened by its phase mark; `last`: the
     //! model step ends with this sub-step (NSDG_PHASE_END)
     void subStep(double dt, bool last);
+    //! model.output_period: after a model step of dt seconds -- one sample on every block if the window asks for one, the flush if it ends
+    void sampleHistory(long dt);
+    void flushHistory(); //!< the window's record: every block's owned rows into one host array, divided by the count, one file
     void resolvePhaseTimes(); //!< model.phase_timing: every block's table -> the timer tree and model.phase_timing_file (PhaseTiming.hpp)
     //! dynamics.forcing = file: records k0, k1 resident on the block's device, sampled with time weight w into the block's wind / ocean
     //! (the pairs the file holds) and, with thermodynamics, its column forcing planes
@@ -138,6 +145,7 @@ private:
     std::string forcing = "host", devices;
     std::shared_ptr<const ForcingFile> m_forcingFile; // dynamics.forcing = file: the records, read and checked in configure()
     std::shared_ptr<const LandMaskFile> m_landMask; // dynamics.land_mask_file: the element mask, read and checked in configure()
+    std::unique_ptr<HistoryOutput> m_history; // model.output_period > 0: keys, windows and record files (null: off)
     int substeps = 1; // dynamics.substeps; 0 = auto
     double substepCourant = 1.5; // dynamics.substep_courant (NSDG_SUBSTEP_COURANT)
     int maxSubsteps = 16; // dynamics.max_substeps

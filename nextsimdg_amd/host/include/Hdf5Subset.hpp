@@ -42,6 +42,8 @@ class Hdf5File {
 public:
     //! true if the file starts with the HDF5 signature
     static bool isHdf5(const std::string& filePath);
+    //! true if the name ends in .nc, .h5 or .hdf5: the files the host writes through Hdf5Writer (restart files, history records)
+    static bool hasHdf5Extension(const std::string& filePath);
 
     //! Reads the whole file into memory and parses the superblock.  Throws Hdf5Error.
     explicit Hdf5File(const std::string& filePath);

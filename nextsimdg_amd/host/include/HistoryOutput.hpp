@@ -1,0 +1,81 @@
+// HistoryOutput.hpp -- gridded output at a chosen period: time means and snapshots of element fields that the device accumulates
+// (include/nsdg.h "history output").  This class is the part that needs no device: the keys, the window
+// arithmetic and the record files.  DynamicsStep owns the accumulators, samples after every model step and downloads at a window end.
+//
+// Configuration keys (all optional; the period 0 -- the default -- turns the output off and nothing of a run changes):
+//     model.output_period   whole seconds, a multiple of model.time_step
+//     model.output_file     the name the record files are made from: ice.nsdg gives ice.<time_end, 10 digits>.nsdg, one per window; a
+//                           process of a multi-process run appends .rank<r> and writes its own rows
+//     model.output_fields   comma list of the names of nsdg_history_field_name (default hice,cice,u,v)
+//     model.output_kind     mean (default): the mean of the samples taken at the end of every model step of the window;
+//                           snapshot: the sample of the window's last step alone
+// Windows are aligned to absolute model time: a window ends after the model step in which the integer model clock reaches (or passes) a
+// multiple of the period.  A run that starts or stops inside a window writes that window with the samples it has, so a restart at a
+// window boundary needs no state of the output in the restart file.
+//
+// Record file.  The extension picks the format, as in RectGrid::dump: .nc / .h5 / .hdf5 are written through Hdf5Writer -- one float64
+// dataset /data/<field> of shape (rows, y) per field and the string attributes time_start, time_end, samples, kind, fields, x, y, row0,
+// rows of the group /history --, anything else is the plain form: the line "NSDG-HISTORY 1", the same keys as key=value lines,
+// END-HEADER and the planes as float64 in the order of `fields`.  A plane has the orientation of the restart file's hice: element
+// (i, j) of the structure at i * y + j, rows [row0, row0 + rows) of the x rows.
+#pragma once
+#include <string>
+#include <vector>
+
+namespace Nextsim {
+
+class HistoryOutput {
+public:
+    struct Config {
+        long period = 0; //!< seconds; 0: off
+        std::string file;
+        std::vector<std::string> fields; //!< names, in the order of the record's planes
+        std::vector<int> ids; //!< their NSDG_HIST_* ids
+        bool snapshot = false;
+        bool on() const { return period > 0; }
+    };
+    //! model.output_*, read and checked against model.time_step and what the step can sample; throws std::invalid_argument naming the
+    //! key.  thermodynamics: the column model runs (hsnow, tice exist).  Touches no device.
+    static Config fromConfiguration(bool thermodynamics);
+    //! for a step that cannot write history (HipStep): throws std::invalid_argument if any model.output_* key is given
+    static void refuseFor(const std::string& stepName);
+
+    //! what to do after a model step
+    struct Action {
+        bool sample = false; //!< take a sample of the state the step left ...
+        bool store = false; //!< ... as the first of its window: overwrite the accumulator
+        bool flush = false; //!< the window ends with this step: download and write (if it holds a sample)
+    };
+
+    explicit HistoryOutput(const Config& c);
+    const Config& config() const { return m_c; }
+    //! the integer model clock at the start of the run
+    void start(long time);
+    //! a model step of dt seconds has run: advances the clock and says what follows; counts the sample it asks for
+    Action step(long dt);
+    //! the window was written (or dropped): the next sample opens a new one
+    void closeWindow();
+    long clock() const { return m_clock; }
+    long samples() const { return m_samples; }
+    long windowStart() const { return m_windowStart; } //!< the clock at the start of the first sampled step of the window
+    long windowEnd() const { return m_windowEnd; } //!< the clock after the last sampled step
+
+    struct Record {
+        long timeStart = 0, timeEnd = 0, samples = 0;
+        std::string kind;
+        std::vector<std::string> fields;
+        long x = 0, y = 0, row0 = 0, rows = 0; //!< the structure's shape and the rows this file holds
+        std::vector<double> data; //!< fields.size() planes of rows * y
+    };
+    //! ice.nsdg, 480 -> ice.0000000480.nsdg (world > 1: ... .rank<r>)
+    static std::string recordPath(const std::string& file, long timeEnd, int rank = 0, int world = 1);
+    //! writes `r` in the format the extension of `formatOf` (the configured model.output_file) asks for
+    static void write(const std::string& path, const std::string& formatOf, const Record& r);
+    static Record read(const std::string& path);
+
+private:
+    Config m_c;
+    long m_clock = 0, m_samples = 0, m_windowStart = 0, m_windowEnd = 0;
+};
+
+} // namespace Nextsim

@@ -15,6 +15,7 @@
 
 #include "../../../include/nsdg.h"
 #include "ForcingFile.hpp"
+#include "HistoryOutput.hpp"
 #include "LandMaskFile.hpp"
 #include "ModuleLoader.hpp"
 #include "PhaseTiming.hpp"
@@ -115,6 +116,7 @@ public:
     double* records = nullptr;
     long recordOf[2] = { -1, -1 };
     std::uint8_t* land = nullptr; // dynamics.land_mask_file: the mask of the local rows, ghost rows included (set on the context)
+    double* hist = nullptr; // model.output_period: the history accumulator, one plane of the OWNED rows per output field (null: off)
 
     ~DynamicsBlock() { release(); }
     void release()
@@ -130,6 +132,9 @@ public:
         if (records)
             (void)hipFree(records);
         records = nullptr;
+        if (hist)
+            (void)hipFree(hist);
+        hist = nullptr;
         if (ctx)
             nsdg_ctx_destroy(ctx); // finalises the communicator too
         if (land) // after the context, which held the pointer
@@ -264,6 +269,11 @@ void DynamicsStep::configure()
     if (advectColumn && !thermo)
         throw std::invalid_argument("dynamics.advect_column_state needs dynamics.thermodynamics = true: without the column model there is no "
                                     "snow or surface temperature to carry");
+    // history output (include/HistoryOutput.hpp): the keys are read and checked here, before any device is touched; period 0 = off
+    m_history.reset();
+    const HistoryOutput::Config hc = HistoryOutput::fromConfiguration(thermo);
+    if (hc.on())
+        m_history = std::make_unique<HistoryOutput>(hc);
 }
 
 void DynamicsStep::init()
@@ -321,6 +331,8 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
     nxf = pStructure->ny(); // fast dimension of the x-major index i*ny + j
     nyf = pStructure->nx();
     m_time = (double)startTime;
+    if (m_history)
+        m_history->start((long)startTime); // the integer clock the output windows are aligned to (m_time is a double under sub-stepping)
     if (m_landMask) {
         m_landMask->checkShape((std::size_t)nyf, (std::size_t)nxf);
         if (m_rank == 0)
@@ -488,6 +500,10 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
             }
             check(nsdg_land_clear_nodes(b.ctx, b.d[Ua], b.d[Va]), "nsdg_land_clear_nodes");
         }
+        if (m_history) { // one plane of the owned rows per output field; the first sample of a window stores: no memset
+            const std::size_t n = m_history->config().ids.size() * (std::size_t)(b.j1 - b.j0) * b.nx;
+            checkHip(hipMalloc(reinterpret_cast<void**>(&b.hist), n * sizeof(double)), "DynamicsStep: hipMalloc (history accumulator)");
+        }
         // driver plans
         nsdg_rb_mevp_desc m;
         std::memset(&m, 0, sizeof m);
@@ -549,6 +565,65 @@ void DynamicsStep::iterate(const Iterator::Duration& dtSeconds)
     }
     m_substepsRun += n;
     ++m_steps;
+    if (m_history)
+        sampleHistory((long)dtSeconds);
+}
+
+void DynamicsStep::sampleHistory(long dt)
+{
+    // after the NSDG_PHASE_END mark of the step: the sample belongs to no phase, and it is never part of a captured graph
+    const HistoryOutput::Action a = m_history->step(dt);
+    if (a.sample) {
+        const std::vector<int>& ids = m_history->config().ids;
+        forEachBlock([&](DynamicsBlock& b) {
+            checkHip(hipSetDevice(b.device), "hipSetDevice");
+            nsdg_history_sources src;
+            std::memset(&src, 0, sizeof src);
+            src.H = b.cur(FH), src.A = b.cur(FA), src.u = b.curU(), src.v = b.curV();
+            const int s = b.par == 0 ? S11a : S11b;
+            src.s11 = b.d[s], src.s12 = b.d[s + 1], src.s22 = b.d[s + 2];
+            if (thermo) // the snow plane the column step actually uses: plane 0 of S under dynamics.advect_column_state
+                src.hsnow = advectColumn ? b.cur(FS) : b.col(C_HSNOW), src.tice = b.col(C_TICE);
+            check(nsdg_history_accumulate(b.ctx, b.j0, b.j1, (int32_t)ids.size(), ids.data(), &src, a.store ? 1 : 0, b.j0, (int64_t)(b.j1 - b.j0) * b.nx, b.hist),
+                "nsdg_history_accumulate");
+        });
+    }
+    if (a.flush)
+        flushHistory();
+}
+
+void DynamicsStep::flushHistory()
+{
+    // the window ends: the owned rows of every block of this process into ONE host array, divided by the count, one record file
+    const long samples = m_history->samples();
+    if (samples > 0) {
+        ScopedTimer timer("history flush");
+        const HistoryOutput::Config& c = m_history->config();
+        int row0 = m_blocks[0]->r0, row1 = m_blocks[0]->r1;
+        for (auto& bp : m_blocks)
+            row0 = std::min(row0, bp->r0), row1 = std::max(row1, bp->r1);
+        HistoryOutput::Record r;
+        r.timeStart = m_history->windowStart(), r.timeEnd = m_history->windowEnd(), r.samples = samples;
+        r.kind = c.snapshot ? "snapshot" : "mean";
+        r.fields = c.fields;
+        r.x = nyf, r.y = nxf, r.row0 = row0, r.rows = row1 - row0;
+        const std::size_t plane = (std::size_t)r.rows * nxf;
+        r.data.assign(c.fields.size() * plane, 0.);
+        for (auto& bp : m_blocks) { // sequential: the blocks fill disjoint row ranges
+            DynamicsBlock& b = *bp;
+            checkHip(hipSetDevice(b.device), "hipSetDevice");
+            check(nsdg_ctx_synchronize(b.ctx), "DynamicsStep: history flush");
+            const std::size_t count = (std::size_t)(b.r1 - b.r0) * b.nx;
+            for (std::size_t k = 0; k < c.fields.size(); ++k)
+                checkHip(hipMemcpy(r.data.data() + k * plane + (std::size_t)(b.r0 - row0) * b.nx, b.hist + k * count, count * sizeof(double), hipMemcpyDeviceToHost),
+                    "download history");
+        }
+        const double n = (double)samples;
+        for (double& x : r.data)
+            x /= n;
+        HistoryOutput::write(HistoryOutput::recordPath(c.file, r.timeEnd, m_rank, m_world), c.file, r);
+    }
+    m_history->closeWindow();
 }
 
 void DynamicsStep::subStep(double dt, bool last)
@@ -703,6 +778,8 @@ void DynamicsStep::stop(const Iterator::TimePoint&)
     ScopedTimer timer("stop (download)");
     if (m_blocks.empty())
         return;
+    if (m_history) // a run that stops inside a window writes it with the samples it has; an empty window (a second stop()) writes nothing
+        flushHistory();
     FieldStore& f = pStructure->fields();
     std::vector<double> umax(m_blocks.size(), 0.);
     bool finite = true;

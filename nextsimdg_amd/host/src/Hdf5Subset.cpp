@@ -87,6 +87,16 @@ bool Hdf5File::isHdf5(const std::string& filePath)
     return f && f.read(reinterpret_cast<char*>(sig), 8) && std::memcmp(sig, SIGNATURE, 8) == 0;
 }
 
+bool Hdf5File::hasHdf5Extension(const std::string& path)
+{
+    for (const char* ext : { ".nc", ".h5", ".hdf5" }) {
+        const std::size_t n = std::strlen(ext);
+        if (path.size() > n && path.compare(path.size() - n, n, ext) == 0)
+            return true;
+    }
+    return false;
+}
+
 void Hdf5File::need(std::size_t off, std::size_t n, const char* what) const
 {
     if (off > m_data.size() || n > m_data.size() - off)

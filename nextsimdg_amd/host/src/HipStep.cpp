@@ -6,6 +6,7 @@
 #include <string>
 
 #include "../../../include/nsdg.h"
+#include "HistoryOutput.hpp"
 #include "ModuleLoader.hpp"
 #include "PhaseTiming.hpp"
 #include "Timer.hpp"
@@ -45,6 +46,7 @@ void HipStep::release()
 
 void HipStep::init()
 {
+    HistoryOutput::refuseFor("Nextsim::HipStep"); // before a device is touched: the column step alone writes no history output
     if (!ctx)
         check(nsdg_ctx_create(0, nullptr, &ctx), "HipStep::init");
     phaseTiming = PhaseTiming::enabled();

@@ -140,15 +140,6 @@ std::string RectGrid::typeInFile(const std::string& filePath, bool throwOnError)
 }
 
 namespace {
-bool wantsHdf5(const std::string& path)
-{
-    for (const char* ext : { ".nc", ".h5", ".hdf5" }) {
-        const std::size_t n = std::strlen(ext);
-        if (path.size() > n && path.compare(path.size() - n, n, ext) == 0)
-            return true;
-    }
-    return false;
-}
 const char* const PLANE_NAMES[5] = { "hice", "cice", "hsnow", "sst", "sss" }; // core/src/DevGridIO.cpp:35-40
 const char* const DYNAMICS_FLAG = "data.dynamics"; // sidecar header: the variables of DYNAMICS_VARIABLES follow tice
 // the named dimensions of each DynamicsVariable::Shape in an HDF5 file, slowest first (x, y: the grid's own)
@@ -164,7 +155,7 @@ void RectGrid::dump(const std::string& filePath) const
     for (std::size_t e = 0; e < m_store.n; ++e)
         for (int l = 0; l < m_store.nLayers; ++l)
             t[e * m_store.nLayers + l] = m_store.tice[(std::size_t)l * m_store.n + e];
-    if (wantsHdf5(filePath)) { // groups, names and dimensions of core/src/DevGridIO.cpp:150-201
+    if (Hdf5File::hasHdf5Extension(filePath)) { // groups, names and dimensions of core/src/DevGridIO.cpp:150-201
         Hdf5Writer w;
         w.group("/" + metadataNodeName());
         w.stringAttribute("/" + metadataNodeName(), typeNodeName(), structureType());

@@ -275,10 +275,17 @@ class DynamicsCore:
     LAND_OPS = ("set_land_mask", "land_clear", "land_clear_nodes")
     BBM_OPS = ("bbm_prepare", "bbm_iterate")
     DAMAGE_BOUNDS = (0.0, 1.0, False)  # the damage D of the brittle rheology: in [0, 1], no cap of the cell mean
+    # history output (include/nsdg.h "history output"; the names: abi.HISTORY_FIELDS): the fields of the column
+    # state exist in a CoupledCore only
+    HISTORY_COLUMN_FIELDS = ("hsnow", "tice")
+    HAS_COLUMN_STATE = False
 
     def __init__(self, ops, blk, hx, hy, dt, nsub, device, exchanger=None, overlap=True, native=False, use_graph=False, closure=True,
-                 phase_timing=False, land=None, rheology="mevp", bbm=None):
+                 phase_timing=False, land=None, rheology="mevp", bbm=None, history=None):
         self.ops, self.blk, self.hx, self.hy, self.dt, self.nsub = ops, blk, hx, hy, dt, nsub
+        # history: names of abi.HISTORY_FIELDS sampled once per model step (step(), or advance() with all its sub-steps) into one accumulator
+        # on the device, read as time means by history_read().  None: nothing is asked of `ops` and nothing is allocated
+        self.history = self._check_history(history, rheology, ops)
         # rheology: "mevp", or "bbm" -- the brittle Bingham-Maxwell sub-cycle (include/nsdg.h "brittle rheology"):
         # nsub explicit sub-iterations of dt / nsub, a damage field D updated in the sub-cycle and advected with H and A.  bbm: an
         # abi.BbmParams set on the ops object (None: whatever the ops object holds, the library's defaults on a new context)
@@ -380,8 +387,86 @@ class DynamicsCore:
             self.Db = z(6, ny, nx)
             self.hg, self.eg, self.pm = (ops.private_zeros(9, ny, nx, device) for _ in range(3))
             self._zero_nodal = z(*nodal)
+        if self.history is not None:
+            self._hist_acc = z(len(self.history), blk.j1 - blk.j0, nx)  # the owned rows only: a sample is element-local
+            self._hist_count = 0
         if native:
             self._init_native()
+
+    def _check_history(self, history, rheology, ops):
+        """the field list of history= as a tuple, or None; ValueError for a list this core cannot sample"""
+        if history is None:
+            return None
+        from nextsimdg_amd import abi
+
+        if isinstance(history, str):
+            history = (history,)
+        history = tuple(history)
+        if not history:
+            raise ValueError("history= needs at least one field (None turns it off)")
+        unknown = [n for n in history if n not in abi.HISTORY_FIELDS]
+        if unknown:
+            raise ValueError("unknown history field %s (known: %s)" % (", ".join(repr(n) for n in unknown), " ".join(abi.HISTORY_FIELDS)))
+        twice = sorted({n for n in history if history.count(n) > 1})
+        if twice:
+            raise ValueError("history field %s is listed twice" % ", ".join(repr(n) for n in twice))
+        if "damage" in history and rheology != "bbm":
+            raise ValueError("the history field 'damage' needs rheology='bbm': the mEVP sub-cycle has no damage")
+        column = [n for n in history if n in self.HISTORY_COLUMN_FIELDS]
+        if column and not self.HAS_COLUMN_STATE:
+            raise ValueError("the history field %s is column state: it needs a CoupledCore" % ", ".join(repr(n) for n in column))
+        if not callable(getattr(ops, "history_accumulate", None)):
+            raise ValueError("history= needs an ops object with the history call of the C ABI (abi.Context); %s has no history_accumulate"
+                             % type(ops).__name__)
+        return history
+
+    def _history_sources(self):
+        """the current ping-pong side of everything a sample reads"""
+        src = {"H": self.H, "A": self.A, "u": self.u, "v": self.v, "s11": self.s[0], "s12": self.s[1], "s22": self.s[2]}
+        if self.rheology == "bbm":
+            src["D"] = self.D
+        return src
+
+    def _history_sample(self):
+        """one sample of the owned rows at the end of a model step: one launch, after the step's last phase mark and outside every
+        captured graph; the first sample of a window stores, the others add"""
+        if self.history is None:
+            return
+        b = self.blk
+        self.ops.history_accumulate(b.j0, b.j1, self.history, self._history_sources(), self._hist_count == 0, b.j0, self._hist_acc)
+        self._hist_count += 1
+
+    def history_read(self, reset=True):
+        """{"rows": (r0, r1), "count": n, name: float64 [rows, nx] = the mean of the n samples since the last reset} for the rows this rank
+        owns (one download; waits for the last sample).  reset: the next sample opens a new window.  merge_history() joins the ranks"""
+        if self.history is None:
+            raise ValueError("history_read() needs a core constructed with history=")
+        if self._hist_count == 0:
+            raise ValueError("history_read(): no sample since the last reset")
+        b, n = self.blk, self._hist_count
+        acc = self._hist_acc.detach().cpu().numpy()
+        out = {"rows": (b.r0, b.r1), "count": n}
+        for k, name in enumerate(self.history):
+            out[name] = acc[k] / n
+        if reset:
+            self._hist_count = 0
+        return out
+
+    @staticmethod
+    def merge_history(parts):
+        """the ranks' history_read()s (any order) -> the record of the whole domain"""
+        import numpy as np
+
+        parts = sorted(parts, key=lambda p: p["rows"][0])
+        if any(p["count"] != parts[0]["count"] for p in parts):
+            raise ValueError("the ranks hold different numbers of samples: %s" % [p["count"] for p in parts])
+        if any(a["rows"][1] != c["rows"][0] for a, c in zip(parts, parts[1:])):
+            raise ValueError("the ranks' rows do not join: %s" % [p["rows"] for p in parts])
+        out = {"rows": (parts[0]["rows"][0], parts[-1]["rows"][1]), "count": parts[0]["count"]}
+        for k in parts[0]:
+            if k not in ("rows", "count"):
+                out[k] = np.concatenate([p[k] for p in parts], axis=0)
+        return out
 
     def _init_native(self):
         b = self.blk
@@ -685,6 +770,7 @@ class DynamicsCore:
         self.transport()
         if not self._in_advance:
             self._mark(PHASE_END)
+            self._history_sample()
 
     # ---- sub-stepping (include/nsdg.h "sub-stepping"): a model step of model_dt run as n steps of model_dt / n
     def substep_count(self, model_dt, courant=None, max_substeps=16, params=None):
@@ -730,6 +816,7 @@ class DynamicsCore:
             self.dt = dt
             self._in_advance = False
             self._mark(PHASE_END)
+        self._history_sample()  # one sample per model step, after its last sub-step
         return n
 
     def owned(self, f):
@@ -873,6 +960,7 @@ class CoupledCore(DynamicsCore):
     # closure of the column state transport's extra fields: snow volume S >= 0, the product Q = H T unbounded (include/nsdg.h)
     COLUMN_STATE_BOUNDS = ((0.0, float("inf"), False), (-float("inf"), float("inf"), False))
     COLUMN_FORCING = ("sst", "sss", "tair", "tdew", "slp", "qsw", "qlw", "mld", "snowfall", "wind")
+    HAS_COLUMN_STATE = True
 
     def __init__(self, ops, blk, hx, hy, dt, nsub, device, forcing=None, advect_column_state=False, min_conc=1e-12, min_thick=0.01, **kw):
         """forcing: None = the forcing planes are whatever load_column() put there (constant in time);
@@ -909,6 +997,12 @@ class CoupledCore(DynamicsCore):
             self._records, self._device = {}, device
         elif forcing not in (None, "dummy", "winter"):
             raise ValueError("forcing must be None, 'dummy', 'winter' or a ForcingSeries, got %r" % (forcing,))
+
+    def _history_sources(self):
+        """and the column state: the snow plane the column step actually uses (plane 0 of S under advect_column_state) and tice0"""
+        src = super()._history_sources()
+        src["hsnow"], src["tice"] = self.col["hsnow"], self.col["tice0"]
+        return src
 
     def load_column(self, fields):
         """fields: dict name -> global [ny, nx] numpy array for hsnow, tice0 and the 10 forcing fields"""
@@ -988,3 +1082,4 @@ class CoupledCore(DynamicsCore):
         self.time += self.dt
         if not self._in_advance:
             self._mark(PHASE_END)
+            self._history_sample()

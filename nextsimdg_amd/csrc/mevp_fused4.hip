@@ -21,6 +21,10 @@
 //     them used to re-read.  The other two pairs (128 B) are still re-read from memory -- a ring for them needs another 2 x 28 KB
 //     and the LDS is full: 96 + 31.5 + 28 = 155.5 of 160 KB (profiles/r05_fused4_p2p.md: what fits, what was measured).
 //   * no barrier after the prologue: the waves run as far apart as their dependencies allow, idle steps do not exist.
+//   * the last stage issues the 12 streaming stores of a row's stress right after the relaxation, under the contributions and node
+//     updates that only read those registers (NSDG_P2P_EARLY bit 2, mevp_p2p.h; -1.7 ... -1.9 % per step).  The same move for the
+//     hand-over between the stages (bit 1: slot wait and the 12 LDS writes right after the relaxation) is built and off: it asks for
+//     the slot before the consumer has freed it and costs 6.9 % (profiles/r15_early_stress_writes.md).
 //
 // Memory ordering of the hand-over, the bounded wait and how a wait that gave up becomes an error status: mevp_p2p.h.  Every wait is
 // on an event that is strictly earlier in the dependency graph of the march (row r of stage k + 1 waits for row r + 1 of stage k; row r
@@ -119,6 +123,22 @@ __device__ __forceinline__ void load_owned_nodal2(const MarchConst& M, int nrow,
     load_nodal2(packed, M.nplane, nVn + 1, c[1]);
     load_nodal2(packed, M.nplane, nVn + M.nn, c[2]);
     load_nodal2(packed, M.nplane, nVn + M.nn + 1, c[3]);
+}
+// the 24 stress coefficients of a row into its hand-over slot (pairs 0 .. 11) / to memory (the last stage)
+__device__ __forceinline__ void hand_stress(double* out, const double (&s11)[8], const double (&s12)[8], const double (&s22)[8])
+{
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        lds_pair(out, k, s11[2 * k], s11[2 * k + 1]);
+        lds_pair(out, 4 + k, s12[2 * k], s12[2 * k + 1]);
+        lds_pair(out, 8 + k, s22[2 * k], s22[2 * k + 1]);
+    }
+}
+__device__ __forceinline__ void store_stress(const StressPtrs& S, long ts, const double (&s11)[8], const double (&s12)[8], const double (&s22)[8])
+{
+    tile_store8_nt<(NSDG_P2P_NT & 2) != 0>(S.o11, ts, s11);
+    tile_store8_nt<(NSDG_P2P_NT & 2) != 0>(S.o12, ts, s12);
+    tile_store8_nt<(NSDG_P2P_NT & 2) != 0>(S.o22, ts, s22);
 }
 // One row of one stage.  FIRST: the loader (stage 0): inputs from memory, ice strength into the ring.
 template <bool FIRST, bool AD, bool LAND>
@@ -220,7 +240,19 @@ __device__ __forceinline__ void p2p_row(const MarchConst& M, const Stage& G, int
         tile_load8_nt<(NSDG_P2P_NT & 1) != 0>(S.i12, ts, f.s12);
         tile_load8_nt<(NSDG_P2P_NT & 1) != 0>(S.i22, ts, f.s22);
     }
-    NSDG_PHASE(3); // relaxation, (loader) stress request
+    // the 24 stress coefficients are final here: with NSDG_P2P_EARLY (mevp_p2p.h) they leave now, under the node arithmetic below
+    constexpr bool EARLY_HAND = (NSDG_P2P_EARLY & 1) != 0, EARLY_STORE = (NSDG_P2P_EARLY & 2) != 0;
+    if constexpr (EARLY_HAND) {
+        if (FIRST || stage < G.nst - 1) { // the same condition as at the end of the row (read[stage] >= row - 2), tested earlier
+            NSDG_SPIN_COUNT(1, flag_wait(flags, 3 + stage, row - P4_HSLOTS, rep));
+            hand_stress(lds + (stage * P4_HSLOTS + (row & 1)) * P4_SLOT + 2 * M.lane, s11, s12, s22);
+        }
+    }
+    if constexpr (EARLY_STORE) {
+        if (!(FIRST || stage < G.nst - 1) && M.own && row >= M.y0)
+            store_stress(S, tile_off(ix, row, M.ntx, 8), s11, s12, s22);
+    }
+    NSDG_PHASE(3); // relaxation, (loader) stress request; NSDG_P2P_EARLY: slot wait and stress hand-over (bit 1), stress stores (bit 2)
     // ------------------------------------------------------------------------------------------ contributions, node updates
     {
         double cx[9], cy[9];
@@ -239,29 +271,25 @@ __device__ __forceinline__ void p2p_row(const MarchConst& M, const Stage& G, int
     NSDG_PHASE(5); // request of the coefficients
     // ------------------------------------------------------------------------------------------ outputs
     if (FIRST || stage < G.nst - 1) {
-        NSDG_SPIN_COUNT(1, flag_wait(flags, 3 + stage, row - P4_HSLOTS, rep)); // the consumer has taken the row this slot held
+        if constexpr (!EARLY_HAND)
+            NSDG_SPIN_COUNT(1, flag_wait(flags, 3 + stage, row - P4_HSLOTS, rep)); // the consumer has taken the row this slot held
         double* out = lds + (stage * P4_HSLOTS + (row & 1)) * P4_SLOT + 2 * M.lane;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            lds_pair(out, k, s11[2 * k], s11[2 * k + 1]);
-            lds_pair(out, 4 + k, s12[2 * k], s12[2 * k + 1]);
-            lds_pair(out, 8 + k, s22[2 * k], s22[2 * k + 1]);
-        }
+        if constexpr (!EARLY_HAND)
+            hand_stress(out, s11, s12, s22);
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             lds_pair(out, 12 + k, un[2 * k], un[2 * k + 1]);
             lds_pair(out, 14 + k, vn[2 * k], vn[2 * k + 1]);
         }
-        flag_publish(flags, stage, row);
+        flag_publish(flags, stage, row); // its lgkmcnt(0) covers the early writes of the row too
     } else if (M.own && row >= M.y0) { // the last stage runs on rows y0-1 .. y1-1
         const long ts = tile_off(ix, row, M.ntx, 8);
         const long nV = (long)(2 * row) * nn + 2 * ix;
-        tile_store8_nt<(NSDG_P2P_NT & 2) != 0>(S.o11, ts, s11);
-        tile_store8_nt<(NSDG_P2P_NT & 2) != 0>(S.o12, ts, s12);
-        tile_store8_nt<(NSDG_P2P_NT & 2) != 0>(S.o22, ts, s22);
+        if constexpr (!EARLY_STORE)
+            store_stress(S, ts, s11, s12, s22);
         store_owned_nodes(nV, nn, M.lastcol, row == M.ny - 1, un, vn, u_new, v_new);
     }
-    NSDG_PHASE(6); // outputs: slot wait, LDS writes, done[] published / global stores
+    NSDG_PHASE(6); // outputs: slot wait, LDS writes, done[] published / global stores (what NSDG_P2P_EARLY has not moved to phase 3)
 }
 
 // LAND: the instantiation that holds land nodes at 0 (mevp_common.h: node_update), launched after a packing that saw a land mask

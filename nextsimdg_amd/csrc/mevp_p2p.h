@@ -74,6 +74,17 @@ __device__ __forceinline__ void lds_pair(double* slot, int k, double a, double b
 #ifndef NSDG_P2P_NT
 #define NSDG_P2P_NT 3
 #endif
+// When the stress of a row leaves its stage (NSDG_P2P_EARLY bits: 1 the stages that hand over wait for their free slot and write the 12
+// stress pairs into it right after the relaxation, 2 the last stage issues its stress stores there).  The stress registers are final
+// after stress_relax; the contributions and node updates that follow only read them, so the writes can issue under that arithmetic.
+// 0: everything leaves at the end of the row.  Measured against the parent on one box, five alternations in both orders
+// (profiles/r15_early_stress_writes.md): 2 28.21-28.37 -> 27.71-27.88 ms per step at 2048^2 (-1.7 ... -1.9 %, the parent's own spread
+// 0.03-0.07 ms), 7.66-7.80 -> 7.54-7.70 at 1024^2; 1 +6.9 % and 3 +8.0 %: the slot is asked for ~2000 cycles sooner, before the consumer
+// has freed it, so the loader -- which never waits for a slot at the end of the row -- polls 4.8 times per row and paces the pipeline.
+// 2 is the default.
+#ifndef NSDG_P2P_EARLY
+#define NSDG_P2P_EARLY 2
+#endif
 typedef double nsdg_pair16 __attribute__((ext_vector_type(2)));
 template <bool NT>
 __device__ __forceinline__ void tile_load8_nt(const double* __restrict__ a, long t, double (&c)[8])

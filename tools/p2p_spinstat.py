@@ -43,7 +43,7 @@ for s in range(4):
     v = [out[4 * s + k] for k in range(4)]
     rows = max(v[3], 1)
     print("  %d    %10.1f      %8.3f  %8.3f  %8.3f" % (s, v[3] / passes, v[0] / rows, v[1] / rows, v[2] / rows))
-names = ("inputs (wait for the previous stage, LDS reads)", "projected stress", "ring / stress hand-over, requests of P, u, v", "relaxation, stress request",
+names = ("inputs (wait for the previous stage, LDS reads)", "projected stress", "ring / stress hand-over, requests of P, u, v", "relaxation, stress request, early stress writes",
          "contributions, node updates (wait for c)", "request of c", "outputs (slot wait, LDS writes / stores)")
 print("shader cycles per row (s_memtime stamps, fenced: the stamped build is slower than the product):")
 print("phase                                                       " + "".join("  stage %d" % s for s in range(4)))

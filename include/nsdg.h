@@ -57,7 +57,8 @@ extern "C" {
  * nsdg_tracer_weight / nsdg_tracer_recover (column state transport) and nsdg_phase_timing_set / nsdg_phase_mark / nsdg_phase_times (per-phase
  * device timing) and nsdg_land_mask_set / nsdg_land_clear / nsdg_land_clear_nodes (land mask) and nsdg_bbm_default_params / nsdg_bbm_params_set /
  * nsdg_bbm_prepare / nsdg_bbm_iterate / nsdg_bbm_substep_count (brittle rheology) and nsdg_history_accumulate / nsdg_history_field_name /
- * nsdg_history_field_id (history output) are additions; nothing that existed changed. */
+ * nsdg_history_field_id, nsdg_history_accumulate_stats / nsdg_history_row_totals / nsdg_history_stat_* / nsdg_history_series_* (history
+ * output) are additions; nothing that existed changed. */
 #define NSDG_ABI_VERSION 6
 
 typedef enum {
@@ -681,6 +682,49 @@ int nsdg_history_accumulate(nsdg_ctx* ctx, int32_t j0, int32_t j1, int32_t nfiel
     int32_t store, int32_t row0, int64_t plane_stride, double* acc);
 const char* nsdg_history_field_name(int32_t field);
 int nsdg_history_field_id(const char* name);
+
+/* nsdg_history_accumulate_stats: nsdg_history_accumulate -- the same single launch, the same samples, every source value still loaded at
+ * most once per element -- with a statistic per plane.  For every pair (fields[k], stats[k]), x = x_fields[k](e), p = the element's slot of
+ * plane k:
+ *   NSDG_STAT_MEAN       p (store ? = : +=) x.  A list of nothing but MEAN equals nsdg_history_accumulate bit for bit.
+ *   NSDG_STAT_ICE_MEAN   w = min(max(A[e], 0), 1) from plane 0 of src.A (a NaN stays a NaN);  t = w x, rounded as a statement of its own and
+ *                        never fused into the sum;  p (store ? = : +=) t.  The ONE weight plane takes
+ *                            wacc[(iy - row0) nx + ix] (store ? = : +=) w
+ *                        once per element if any pair of the list is ICE_MEAN, and is not touched otherwise.
+ *   NSDG_STAT_MIN / MAX  store: p = x; else MIN: p = (x < p || x != x) ? x : p, MAX: p = (x > p || x != x) ? x : p.  A NaN sample makes the
+ *                        extreme NaN and it stays NaN, as the sums keep a NaN.
+ * The host finishes a window of n samples: MEAN acc / n; ICE_MEAN acc / wacc where wacc > 0 and NaN elsewhere (no ice in the window);
+ * MIN / MAX as stored.  A field may be listed with several statistics; the same pair twice is refused by name.
+ * Checks: those of nsdg_history_accumulate, and NSDG_ERR_ARG for an unknown stat id, for ICE_MEAN with src->A == NULL (the message names the
+ * field and A) and for ICE_MEAN with wacc == NULL.  wacc may be NULL when no pair is ICE_MEAN.
+ *
+ * nsdg_history_row_totals: the scalars of a time series, one value per ROW and quantity:
+ *     out[k * q_stride + (iy - row0)] = R_quantities[k](iy)   for iy in [j0, j1); always overwrites; no other slot is written.
+ *   With w as above and speed = the sample of NSDG_HIST_SPEED, the row terms x(iy, ix) -- each formed in a statement of its own before it
+ *   enters the reduction, all dimensionless: the host multiplies by hx hy once -- and their reductions are
+ *     area  w, sum      extent  A[e] >= extent_conc ? 1 : 0, sum      volume  max(H[e], 0), sum      snow_volume  max(hsnow[e], 0), sum
+ *     drift  w speed, sum      speed_max  speed, max      hice_max  H[e], max         (max: the NaN-propagating rule of NSDG_STAT_MAX)
+ *   The order of a row's reduction is normative: lane l of 64 folds ix = l, l + 64, l + 128, ... in ascending order, starting from the
+ *   identity (0 for a sum, -inf for a max); then for s = 32, 16, 8, 4, 2, 1: p_l = op(p_l, p_(l + s)) for l < s; R = p_0.  One wave64 per
+ *   row, no atomics, no shared memory: R depends on the values of the row alone -- not on the row range, the grid or the decomposition --,
+ *   so a host that adds the rows in global row order gets the same total from one block as from N.
+ * Checks: grid set; 0 <= j0 <= j1 <= ny; 1 <= nq <= NSDG_SERIES_COUNT; known ids, none twice; a quantity whose source is NULL is refused by
+ *   name; extent_conc finite; 0 <= row0 <= j0; q_stride >= j1 - row0: NSDG_ERR_ARG.  j0 == j1 does nothing.
+ * nsdg_history_stat_name / _id ("mean" "ice_mean" "min" "max") and nsdg_history_series_name / _id ("area" "extent" "volume" "snow_volume"
+ * "drift" "speed_max" "hice_max"): as nsdg_history_field_name / _id.  Host only. */
+enum { NSDG_STAT_MEAN = 0, NSDG_STAT_ICE_MEAN, NSDG_STAT_MIN, NSDG_STAT_MAX, NSDG_STAT_COUNT };
+enum {
+    NSDG_SERIES_AREA = 0, NSDG_SERIES_EXTENT, NSDG_SERIES_VOLUME, NSDG_SERIES_SNOW_VOLUME, NSDG_SERIES_DRIFT, NSDG_SERIES_SPEED_MAX,
+    NSDG_SERIES_HICE_MAX, NSDG_SERIES_COUNT
+};
+int nsdg_history_accumulate_stats(nsdg_ctx* ctx, int32_t j0, int32_t j1, int32_t nfields, const int32_t* fields, const int32_t* stats,
+    const nsdg_history_sources* src, int32_t store, int32_t row0, int64_t plane_stride, double* acc, double* wacc);
+int nsdg_history_row_totals(nsdg_ctx* ctx, int32_t j0, int32_t j1, int32_t nq, const int32_t* quantities, const nsdg_history_sources* src,
+    double extent_conc, int32_t row0, int64_t q_stride, double* out);
+const char* nsdg_history_stat_name(int32_t stat);
+int nsdg_history_stat_id(const char* name);
+const char* nsdg_history_series_name(int32_t quantity);
+int nsdg_history_series_id(const char* name);
 
 /* ---- row-block decomposition: ghost-row exchange (SURVEY.md section 8(b) "nsdg_halo_exchange", 8(e)) ----------
  * The reference is a single-process, single-thread program; these entry points have no

@@ -78,6 +78,11 @@ class PhaseTable(C.Structure):
 # NSDG_HIST_*: the history fields in id order (include/nsdg.h "history output"); the library answers the same names (nsdg_history_field_name)
 HISTORY_FIELDS = ("hice", "cice", "u", "v", "speed", "divergence", "shear", "sigma_n", "sigma_s", "hsnow", "tice", "damage")
 HISTORY_SOURCES = ("H", "A", "u", "v", "s11", "s12", "s22", "hsnow", "tice", "D")
+# NSDG_STAT_* and NSDG_SERIES_*, in id order; SERIES_SOURCES: what a quantity of nsdg_history_row_totals reads
+HISTORY_STATS = ("mean", "ice_mean", "min", "max")
+SERIES_QUANTITIES = ("area", "extent", "volume", "snow_volume", "drift", "speed_max", "hice_max")
+SERIES_SOURCES = {"area": ("A",), "extent": ("A",), "volume": ("H",), "snow_volume": ("hsnow",), "drift": ("A", "u", "v"),
+                  "speed_max": ("u", "v"), "hice_max": ("H",)}
 
 
 class HistorySources(C.Structure):
@@ -157,6 +162,12 @@ SYMBOLS = {
     "nsdg_history_accumulate": (C.c_int, [VP, I32, I32, I32, C.POINTER(I32), C.POINTER(HistorySources), I32, I32, I64, VP]),
     "nsdg_history_field_name": (C.c_char_p, [I32]),
     "nsdg_history_field_id": (C.c_int, [C.c_char_p]),
+    "nsdg_history_accumulate_stats": (C.c_int, [VP, I32, I32, I32, C.POINTER(I32), C.POINTER(I32), C.POINTER(HistorySources), I32, I32, I64, VP, VP]),
+    "nsdg_history_row_totals": (C.c_int, [VP, I32, I32, I32, C.POINTER(I32), C.POINTER(HistorySources), D, I32, I64, VP]),
+    "nsdg_history_stat_name": (C.c_char_p, [I32]),
+    "nsdg_history_stat_id": (C.c_int, [C.c_char_p]),
+    "nsdg_history_series_name": (C.c_char_p, [I32]),
+    "nsdg_history_series_id": (C.c_int, [C.c_char_p]),
     "nsdg_boxtest_forcing": (C.c_int, [VP, D, D, VP, VP, VP, VP]),
     "nsdg_block_set": (C.c_int, [VP, I32, I32]),
     "nsdg_column_forcing": (C.c_int, [VP, I32, D] + [VP] * 7),
@@ -789,24 +800,63 @@ class Context:
         [j0, j1), stored into (store) or added to acc[k, iy - row0, ix]; acc: [len(fields), rows, nx] with rows >= j1 - row0.  sources:
         name -> tensor for the names of HISTORY_SOURCES the fields read (H, A, D: DG planes [nc, ny, nx], plane 0 is read; u, v: the CG2
         lattice; s11, s12, s22: tiled; hsnow, tice: one plane)"""
-        ids = (I32 * max(len(fields), 1))()
-        for k, name in enumerate(fields):
-            if name not in HISTORY_FIELDS:
-                raise NsdgError("unknown history field %r (known: %s)" % (name, " ".join(HISTORY_FIELDS)))
-            ids[k] = HISTORY_FIELDS.index(name)
+        ids = self._history_ids(fields, HISTORY_FIELDS, "history field")
+        src = self._history_sources("history_accumulate", sources, acc)
+        self._history_check_acc("history_accumulate", acc, len(fields), j1, row0)
+        self._call(self.lib.nsdg_history_accumulate(self.h, j0, j1, len(fields), ids, C.byref(src), int(bool(store)), row0,
+                                                    acc.shape[1] * acc.shape[2], _ptr(acc)))
+
+    def history_accumulate_stats(self, j0, j1, pairs, sources, store, row0, acc, wacc=None):
+        """nsdg_history_accumulate_stats: history_accumulate with a statistic per plane.  pairs: (field, stat) with stat a name of
+        HISTORY_STATS; wacc: the weight plane [rows, nx] of the "ice_mean" pairs (None when there is none)"""
+        pairs = [tuple(p) for p in pairs]
+        ids = self._history_ids([f for f, _ in pairs], HISTORY_FIELDS, "history field")
+        stats = self._history_ids([s for _, s in pairs], HISTORY_STATS, "history statistic")
+        src = self._history_sources("history_accumulate_stats", sources, acc, wacc)
+        self._history_check_acc("history_accumulate_stats", acc, len(pairs), j1, row0)
+        if wacc is not None and tuple(wacc.shape) != tuple(acc.shape[1:]):
+            raise NsdgError("history_accumulate_stats: wacc has shape %s, expected %s" % (tuple(wacc.shape), tuple(acc.shape[1:])))
+        self._call(self.lib.nsdg_history_accumulate_stats(self.h, j0, j1, len(pairs), ids, stats, C.byref(src), int(bool(store)), row0,
+                                                          acc.shape[1] * acc.shape[2], _ptr(acc), _ptr(wacc)))
+
+    def history_row_totals(self, j0, j1, quantities, sources, extent_conc, row0, out):
+        """nsdg_history_row_totals: out[k, iy - row0] = the total of quantity k (names of SERIES_QUANTITIES) over row iy, for the local rows
+        [j0, j1); out: [len(quantities), rows] with rows >= j1 - row0 and unit stride along the rows (a slot of a larger buffer is fine)"""
+        ids = self._history_ids(quantities, SERIES_QUANTITIES, "series quantity")
+        import torch
+
+        src = self._history_sources("history_row_totals", sources)
+        if out.dtype != torch.float64 or not out.is_cuda:
+            raise NsdgError("expected a float64 CUDA tensor")
+        if out.dim() != 2 or out.shape[0] != len(quantities) or out.shape[1] < j1 - row0 or out.stride(1) != 1 or out.stride(0) < out.shape[1]:
+            raise NsdgError("history_row_totals: out has shape %s and strides %s, expected [%d, >= %d] with unit stride along the rows"
+                            % (tuple(out.shape), tuple(out.stride()), len(quantities), j1 - row0))
+        self._call(self.lib.nsdg_history_row_totals(self.h, j0, j1, len(quantities), ids, C.byref(src), float(extent_conc), row0,
+                                                    out.stride(0), out.data_ptr()))
+
+    @staticmethod
+    def _history_ids(names, known, what):
+        ids = (I32 * max(len(names), 1))()
+        for k, name in enumerate(names):
+            if name not in known:
+                raise NsdgError("unknown %s %r (known: %s)" % (what, name, " ".join(known)))
+            ids[k] = known.index(name)
+        return ids
+
+    def _history_sources(self, call, sources, *outputs):
         ts = {n: sources.get(n) for n in HISTORY_SOURCES}
-        _check_f64(acc, *ts.values())
+        _check_f64(*[t for t in outputs if t is not None], *ts.values())
         n_el, n_node = self.nx * self.ny, (2 * self.nx + 1) * (2 * self.ny + 1)
         need = {"H": n_el, "A": n_el, "D": n_el, "hsnow": n_el, "tice": n_el, "u": n_node, "v": n_node}
         need.update({n: (self.ny * ((self.nx + TILE - 1) // TILE) * 8 * TILE) for n in ("s11", "s12", "s22")})
         for n, t in ts.items():  # the ABI takes bare pointers: a shorter array would be read past its end on the device
             if t is not None and t.numel() < need[n]:
-                raise NsdgError("history_accumulate: source %s has %d values, the grid needs %d" % (n, t.numel(), need[n]))
-        if acc.dim() != 3 or acc.shape[0] != len(fields) or acc.shape[2] != self.nx or acc.shape[1] < j1 - row0:
-            raise NsdgError("history_accumulate: acc has shape %s, expected [%d, >= %d, %d]" % (tuple(acc.shape), len(fields), j1 - row0, self.nx))
-        src = HistorySources(*[None if ts[n] is None else ts[n].data_ptr() for n in HISTORY_SOURCES])
-        self._call(self.lib.nsdg_history_accumulate(self.h, j0, j1, len(fields), ids, C.byref(src), int(bool(store)), row0,
-                                                    acc.shape[1] * acc.shape[2], _ptr(acc)))
+                raise NsdgError("%s: source %s has %d values, the grid needs %d" % (call, n, t.numel(), need[n]))
+        return HistorySources(*[None if ts[n] is None else ts[n].data_ptr() for n in HISTORY_SOURCES])
+
+    def _history_check_acc(self, call, acc, nplanes, j1, row0):
+        if acc.dim() != 3 or acc.shape[0] != nplanes or acc.shape[2] != self.nx or acc.shape[1] < j1 - row0:
+            raise NsdgError("%s: acc has shape %s, expected [%d, >= %d, %d]" % (call, tuple(acc.shape), nplanes, j1 - row0, self.nx))
 
     def concentration_max(self, H, A, j0=0, j1=None):
         """nsdg_concentration_max: largest clamped concentration at the Gauss points of rows [j0, j1) where there is ice (waits for the

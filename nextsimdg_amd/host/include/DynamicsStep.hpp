@@ -76,6 +76,7 @@ namespace Nextsim {
 
 class ForcingFile;
 class HistoryOutput;
+class SeriesOutput;
 class LandMaskFile;
 
 class DynamicsBlock; // one row block: context, device arrays, driver plans (DynamicsStep.cpp)
@@ -125,7 +126,10 @@ private:
     void subStep(double dt, bool last);
     //! model.output_period: after a model step of dt seconds -- one sample on every block if the window asks for one, the flush if it ends
     void sampleHistory(long dt);
-    void flushHistory(); //!< the window's record: every block's owned rows into one host array, divided by the count, one file
+    void flushHistory(); //!< the window's record: every block's owned rows into one host array, finished per statistic, one file
+    //! model.series_file: after a model step -- one row-totals launch on every block into the next slot of its buffer, the flush if full
+    void sampleSeries(long dt);
+    void flushSeries(); //!< synchronises every block, downloads its slots, adds the rows in global row order and appends the lines
     void resolvePhaseTimes(); //!< model.phase_timing: every block's table -> the timer tree and model.phase_timing_file (PhaseTiming.hpp)
     //! dynamics.forcing = file: records k0, k1 resident on the block's device, sampled with time weight w into the block's wind / ocean
     //! (the pairs the file holds) and, with thermodynamics, its column forcing planes
@@ -146,6 +150,7 @@ private:
     std::shared_ptr<const ForcingFile> m_forcingFile; // dynamics.forcing = file: the records, read and checked in configure()
     std::shared_ptr<const LandMaskFile> m_landMask; // dynamics.land_mask_file: the element mask, read and checked in configure()
     std::unique_ptr<HistoryOutput> m_history; // model.output_period > 0: keys, windows and record files (null: off)
+    std::unique_ptr<SeriesOutput> m_series; // model.series_file: the time series of the domain totals (null: off)
     int substeps = 1; // dynamics.substeps; 0 = auto
     double substepCourant = 1.5; // dynamics.substep_courant (NSDG_SUBSTEP_COURANT)
     int maxSubsteps = 16; // dynamics.max_substeps

@@ -117,6 +117,8 @@ public:
     long recordOf[2] = { -1, -1 };
     std::uint8_t* land = nullptr; // dynamics.land_mask_file: the mask of the local rows, ghost rows included (set on the context)
     double* hist = nullptr; // model.output_period: the history accumulator, one plane of the OWNED rows per output field (null: off)
+    double* histWeight = nullptr; // ... and the summed weights of its ice-weighted means, one plane (null: none is asked for)
+    double* series = nullptr; // model.series_file: [model.series_buffer][quantities][owned rows] row totals (null: off)
 
     ~DynamicsBlock() { release(); }
     void release()
@@ -135,6 +137,12 @@ public:
         if (hist)
             (void)hipFree(hist);
         hist = nullptr;
+        if (histWeight)
+            (void)hipFree(histWeight);
+        histWeight = nullptr;
+        if (series)
+            (void)hipFree(series);
+        series = nullptr;
         if (ctx)
             nsdg_ctx_destroy(ctx); // finalises the communicator too
         if (land) // after the context, which held the pointer
@@ -274,6 +282,11 @@ void DynamicsStep::configure()
     const HistoryOutput::Config hc = HistoryOutput::fromConfiguration(thermo);
     if (hc.on())
         m_history = std::make_unique<HistoryOutput>(hc);
+    // the time series of the domain totals (SeriesOutput): the same; a multi-process run is refused here, nothing gathers its rows
+    m_series.reset();
+    const SeriesOutput::Config sc = SeriesOutput::fromConfiguration(thermo, RankEnvironment::fromEnv().world);
+    if (sc.on())
+        m_series = std::make_unique<SeriesOutput>(sc);
 }
 
 void DynamicsStep::init()
@@ -333,6 +346,8 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
     m_time = (double)startTime;
     if (m_history)
         m_history->start((long)startTime); // the integer clock the output windows are aligned to (m_time is a double under sub-stepping)
+    if (m_series)
+        m_series->start((long)startTime);
     if (m_landMask) {
         m_landMask->checkShape((std::size_t)nyf, (std::size_t)nxf);
         if (m_rank == 0)
@@ -503,7 +518,14 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
         if (m_history) { // one plane of the owned rows per output field; the first sample of a window stores: no memset
             const std::size_t n = m_history->config().ids.size() * (std::size_t)(b.j1 - b.j0) * b.nx;
             checkHip(hipMalloc(reinterpret_cast<void**>(&b.hist), n * sizeof(double)), "DynamicsStep: hipMalloc (history accumulator)");
+            if (m_history->config().weighted())
+                checkHip(hipMalloc(reinterpret_cast<void**>(&b.histWeight), (std::size_t)(b.j1 - b.j0) * b.nx * sizeof(double)),
+                    "DynamicsStep: hipMalloc (history weights)");
         }
+        if (m_series) // every slot is written before it is read: no memset
+            checkHip(hipMalloc(reinterpret_cast<void**>(&b.series),
+                         (std::size_t)m_series->config().buffer * m_series->config().ids.size() * (b.j1 - b.j0) * sizeof(double)),
+                "DynamicsStep: hipMalloc (series buffer)");
         // driver plans
         nsdg_rb_mevp_desc m;
         std::memset(&m, 0, sizeof m);
@@ -565,8 +587,23 @@ void DynamicsStep::iterate(const Iterator::Duration& dtSeconds)
     }
     m_substepsRun += n;
     ++m_steps;
+    if (m_series)
+        sampleSeries((long)dtSeconds);
     if (m_history)
         sampleHistory((long)dtSeconds);
+}
+
+// what a history sample and the row totals read: the current side of every ping-pong
+static nsdg_history_sources historySources(const DynamicsBlock& b, bool thermo, bool advectColumn)
+{
+    nsdg_history_sources src;
+    std::memset(&src, 0, sizeof src);
+    src.H = b.cur(FH), src.A = b.cur(FA), src.u = b.curU(), src.v = b.curV();
+    const int s = b.par == 0 ? S11a : S11b;
+    src.s11 = b.d[s], src.s12 = b.d[s + 1], src.s22 = b.d[s + 2];
+    if (thermo) // the snow plane the column step actually uses: plane 0 of S under dynamics.advect_column_state
+        src.hsnow = advectColumn ? b.cur(FS) : b.col(C_HSNOW), src.tice = b.col(C_TICE);
+    return src;
 }
 
 void DynamicsStep::sampleHistory(long dt)
@@ -574,22 +611,70 @@ void DynamicsStep::sampleHistory(long dt)
     // after the NSDG_PHASE_END mark of the step: the sample belongs to no phase, and it is never part of a captured graph
     const HistoryOutput::Action a = m_history->step(dt);
     if (a.sample) {
-        const std::vector<int>& ids = m_history->config().ids;
+        const HistoryOutput::Config& c = m_history->config();
+        const std::vector<int>& ids = c.ids;
+        const bool stats = c.hasStats(); // bare names: the plain call, as ever
         forEachBlock([&](DynamicsBlock& b) {
             checkHip(hipSetDevice(b.device), "hipSetDevice");
-            nsdg_history_sources src;
-            std::memset(&src, 0, sizeof src);
-            src.H = b.cur(FH), src.A = b.cur(FA), src.u = b.curU(), src.v = b.curV();
-            const int s = b.par == 0 ? S11a : S11b;
-            src.s11 = b.d[s], src.s12 = b.d[s + 1], src.s22 = b.d[s + 2];
-            if (thermo) // the snow plane the column step actually uses: plane 0 of S under dynamics.advect_column_state
-                src.hsnow = advectColumn ? b.cur(FS) : b.col(C_HSNOW), src.tice = b.col(C_TICE);
-            check(nsdg_history_accumulate(b.ctx, b.j0, b.j1, (int32_t)ids.size(), ids.data(), &src, a.store ? 1 : 0, b.j0, (int64_t)(b.j1 - b.j0) * b.nx, b.hist),
-                "nsdg_history_accumulate");
+            const nsdg_history_sources src = historySources(b, thermo, advectColumn);
+            const int64_t stride = (int64_t)(b.j1 - b.j0) * b.nx;
+            if (stats)
+                check(nsdg_history_accumulate_stats(b.ctx, b.j0, b.j1, (int32_t)ids.size(), ids.data(), c.stats.data(), &src, a.store ? 1 : 0, b.j0, stride,
+                          b.hist, b.histWeight),
+                    "nsdg_history_accumulate_stats");
+            else
+                check(nsdg_history_accumulate(b.ctx, b.j0, b.j1, (int32_t)ids.size(), ids.data(), &src, a.store ? 1 : 0, b.j0, stride, b.hist),
+                    "nsdg_history_accumulate");
         });
     }
     if (a.flush)
         flushHistory();
+}
+
+void DynamicsStep::sampleSeries(long dt)
+{
+    // like the history sample: after the step's last phase mark, outside every captured graph; the host counts the slots
+    const std::vector<int>& ids = m_series->config().ids;
+    const std::size_t slot = m_series->step(dt);
+    forEachBlock([&](DynamicsBlock& b) {
+        checkHip(hipSetDevice(b.device), "hipSetDevice");
+        const nsdg_history_sources src = historySources(b, thermo, advectColumn);
+        const int64_t rows = b.j1 - b.j0;
+        check(nsdg_history_row_totals(b.ctx, b.j0, b.j1, (int32_t)ids.size(), ids.data(), &src, SeriesOutput::EXTENT_CONC, b.j0, rows,
+                  b.series + slot * ids.size() * rows),
+            "nsdg_history_row_totals");
+    });
+    if (m_series->full())
+        flushSeries();
+}
+
+void DynamicsStep::flushSeries()
+{
+    const SeriesOutput::Config& c = m_series->config();
+    const std::size_t count = m_series->pending().size(), nq = c.ids.size();
+    if (count == 0) // (a second stop())
+        return;
+    ScopedTimer timer("series flush");
+    int row0 = m_blocks[0]->r0, row1 = m_blocks[0]->r1;
+    for (auto& bp : m_blocks)
+        row0 = std::min(row0, bp->r0), row1 = std::max(row1, bp->r1);
+    const std::size_t nrows = (std::size_t)(row1 - row0);
+    std::vector<double> rows(count * nq * nrows), part;
+    for (auto& bp : m_blocks) { // sequential: the blocks fill disjoint row ranges
+        DynamicsBlock& b = *bp;
+        checkHip(hipSetDevice(b.device), "hipSetDevice");
+        check(nsdg_ctx_synchronize(b.ctx), "DynamicsStep: series flush");
+        const std::size_t own = (std::size_t)(b.r1 - b.r0);
+        part.resize(count * nq * own);
+        checkHip(hipMemcpy(part.data(), b.series, part.size() * sizeof(double), hipMemcpyDeviceToHost), "download series");
+        for (std::size_t s = 0; s < count * nq; ++s)
+            std::copy(part.begin() + s * own, part.begin() + (s + 1) * own, rows.begin() + s * nrows + (b.r0 - row0));
+    }
+    std::vector<std::string> lines;
+    for (std::size_t s = 0; s < count; ++s)
+        lines.push_back(SeriesOutput::formatLine(m_series->pending()[s], SeriesOutput::totals(c.ids, rows.data() + s * nq * nrows, nrows, L / nxf, L / nyf)));
+    SeriesOutput::append(c, lines);
+    m_series->flushed();
 }
 
 void DynamicsStep::flushHistory()
@@ -618,9 +703,18 @@ void DynamicsStep::flushHistory()
                 checkHip(hipMemcpy(r.data.data() + k * plane + (std::size_t)(b.r0 - row0) * b.nx, b.hist + k * count, count * sizeof(double), hipMemcpyDeviceToHost),
                     "download history");
         }
-        const double n = (double)samples;
-        for (double& x : r.data)
-            x /= n;
+        std::vector<double> weights;
+        if (c.weighted()) { // the summed weights of the ice-weighted means, the same rows
+            weights.assign(plane, 0.);
+            for (auto& bp : m_blocks) {
+                DynamicsBlock& b = *bp;
+                checkHip(hipSetDevice(b.device), "hipSetDevice");
+                checkHip(hipMemcpy(weights.data() + (std::size_t)(b.r0 - row0) * b.nx, b.histWeight, (std::size_t)(b.r1 - b.r0) * b.nx * sizeof(double),
+                             hipMemcpyDeviceToHost),
+                    "download history weights");
+            }
+        }
+        HistoryOutput::finish(c.stats, samples, plane, weights.empty() ? nullptr : weights.data(), r.data);
         HistoryOutput::write(HistoryOutput::recordPath(c.file, r.timeEnd, m_rank, m_world), c.file, r);
     }
     m_history->closeWindow();
@@ -780,6 +874,8 @@ void DynamicsStep::stop(const Iterator::TimePoint&)
         return;
     if (m_history) // a run that stops inside a window writes it with the samples it has; an empty window (a second stop()) writes nothing
         flushHistory();
+    if (m_series)
+        flushSeries();
     FieldStore& f = pStructure->fields();
     std::vector<double> umax(m_blocks.size(), 0.);
     bool finite = true;

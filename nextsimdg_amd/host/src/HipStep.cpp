@@ -46,7 +46,8 @@ void HipStep::release()
 
 void HipStep::init()
 {
-    HistoryOutput::refuseFor("Nextsim::HipStep"); // before a device is touched: the column step alone writes no history output
+    HistoryOutput::refuseFor("Nextsim::HipStep"); // before a device is touched: the column step alone writes no history output ...
+    SeriesOutput::refuseFor("Nextsim::HipStep"); // ... and no time series
     if (!ctx)
         check(nsdg_ctx_create(0, nullptr, &ctx), "HipStep::init");
     phaseTiming = PhaseTiming::enabled();

@@ -279,13 +279,19 @@ class DynamicsCore:
     # state exist in a CoupledCore only
     HISTORY_COLUMN_FIELDS = ("hsnow", "tice")
     HAS_COLUMN_STATE = False
+    series = None  # series=: off unless the constructor says otherwise
 
     def __init__(self, ops, blk, hx, hy, dt, nsub, device, exchanger=None, overlap=True, native=False, use_graph=False, closure=True,
-                 phase_timing=False, land=None, rheology="mevp", bbm=None, history=None):
+                 phase_timing=False, land=None, rheology="mevp", bbm=None, history=None, series=None, series_capacity=1024, extent_conc=0.15):
         self.ops, self.blk, self.hx, self.hy, self.dt, self.nsub = ops, blk, hx, hy, dt, nsub
         # history: names of abi.HISTORY_FIELDS sampled once per model step (step(), or advance() with all its sub-steps) into one accumulator
-        # on the device, read as time means by history_read().  None: nothing is asked of `ops` and nothing is allocated
+        # on the device, read as time means by history_read().  None: nothing is asked of `ops` and nothing is allocated.  An entry may be
+        # "name:stat" with a statistic of abi.HISTORY_STATS ("name" alone is the mean): ice-weighted means and the extremes of the window
         self.history = self._check_history(history, rheology, ops)
+        # series: names of abi.SERIES_QUANTITIES; every model step leaves their row totals in the next of series_capacity slots of a device
+        # buffer, read by series_read() and made domain totals by merge_series().  extent_conc: the concentration the ice extent counts from
+        self.series = self._check_series(series, series_capacity, extent_conc, ops)
+        self.series_capacity, self.extent_conc = int(series_capacity), float(extent_conc)
         # rheology: "mevp", or "bbm" -- the brittle Bingham-Maxwell sub-cycle (include/nsdg.h "brittle rheology"):
         # nsub explicit sub-iterations of dt / nsub, a damage field D updated in the sub-cycle and advected with H and A.  bbm: an
         # abi.BbmParams set on the ops object (None: whatever the ops object holds, the library's defaults on a new context)
@@ -390,11 +396,18 @@ class DynamicsCore:
         if self.history is not None:
             self._hist_acc = z(len(self.history), blk.j1 - blk.j0, nx)  # the owned rows only: a sample is element-local
             self._hist_count = 0
+            if any(st == "ice_mean" for _, st in self._hist_pairs or ()):
+                self._hist_wacc = z(blk.j1 - blk.j0, nx)  # the summed weights of the window, one plane for every ice-weighted mean
+        if self.series is not None:
+            self._series_buf = z(self.series_capacity, len(self.series), blk.j1 - blk.j0)
+            self._series_count = 0
         if native:
             self._init_native()
 
     def _check_history(self, history, rheology, ops):
-        """the field list of history= as a tuple, or None; ValueError for a list this core cannot sample"""
+        """the entries of history= as a tuple, or None; ValueError for a list this core cannot sample.  Sets self._hist_pairs: None for a
+        list of bare names -- sampled by ops.history_accumulate, as ever --, else the (field, stat) of every entry"""
+        self._hist_pairs = None
         if history is None:
             return None
         from nextsimdg_amd import abi
@@ -404,21 +417,64 @@ class DynamicsCore:
         history = tuple(history)
         if not history:
             raise ValueError("history= needs at least one field (None turns it off)")
-        unknown = [n for n in history if n not in abi.HISTORY_FIELDS]
+        pairs = [tuple(e.split(":", 1)) if ":" in e else (e, "mean") for e in history]
+        names = [n for n, _ in pairs]
+        unknown = [n for n in names if n not in abi.HISTORY_FIELDS]
         if unknown:
             raise ValueError("unknown history field %s (known: %s)" % (", ".join(repr(n) for n in unknown), " ".join(abi.HISTORY_FIELDS)))
-        twice = sorted({n for n in history if history.count(n) > 1})
+        unknown = [e for e, (_, st) in zip(history, pairs) if st not in abi.HISTORY_STATS]
+        if unknown:
+            raise ValueError("unknown history statistic in %s (known: %s)" % (", ".join(repr(e) for e in unknown), " ".join(abi.HISTORY_STATS)))
+        twice = sorted({e for e, p in zip(history, pairs) if pairs.count(p) > 1})
         if twice:
             raise ValueError("history field %s is listed twice" % ", ".join(repr(n) for n in twice))
-        if "damage" in history and rheology != "bbm":
+        if "damage" in names and rheology != "bbm":
             raise ValueError("the history field 'damage' needs rheology='bbm': the mEVP sub-cycle has no damage")
-        column = [n for n in history if n in self.HISTORY_COLUMN_FIELDS]
+        column = [n for n in names if n in self.HISTORY_COLUMN_FIELDS]
         if column and not self.HAS_COLUMN_STATE:
             raise ValueError("the history field %s is column state: it needs a CoupledCore" % ", ".join(repr(n) for n in column))
-        if not callable(getattr(ops, "history_accumulate", None)):
-            raise ValueError("history= needs an ops object with the history call of the C ABI (abi.Context); %s has no history_accumulate"
-                             % type(ops).__name__)
+        weighted = [e for e, (_, st) in zip(history, pairs) if st == "ice_mean"]
+        if weighted and "A" not in self.TRANSPORTED:
+            raise ValueError("the history entry %s weights by the concentration: this core has no A" % ", ".join(repr(e) for e in weighted))
+        call = "history_accumulate_stats" if any(":" in e for e in history) else "history_accumulate"
+        if not callable(getattr(ops, call, None)):
+            raise ValueError("history= needs an ops object with the history call of the C ABI (abi.Context); %s has no %s"
+                             % (type(ops).__name__, call))
+        if call == "history_accumulate_stats":
+            self._hist_pairs = pairs
         return history
+
+    def _check_series(self, series, capacity, extent_conc, ops):
+        """the quantities of series= as a tuple, or None; ValueError for a list this core cannot total"""
+        if series is None:
+            return None
+        import math
+
+        from nextsimdg_amd import abi
+
+        if isinstance(series, str):
+            series = (series,)
+        series = tuple(series)
+        if not series:
+            raise ValueError("series= needs at least one quantity (None turns it off)")
+        unknown = [n for n in series if n not in abi.SERIES_QUANTITIES]
+        if unknown:
+            raise ValueError("unknown series quantity %s (known: %s)" % (", ".join(repr(n) for n in unknown), " ".join(abi.SERIES_QUANTITIES)))
+        twice = sorted({n for n in series if series.count(n) > 1})
+        if twice:
+            raise ValueError("series quantity %s is listed twice" % ", ".join(repr(n) for n in twice))
+        if "drift" in series and "area" not in series:
+            raise ValueError("the series quantity 'drift' is the ice-weighted mean speed: it needs 'area', the sum of the weights, in the list")
+        if "snow_volume" in series and not self.HAS_COLUMN_STATE:
+            raise ValueError("the series quantity 'snow_volume' is column state: it needs a CoupledCore")
+        if int(capacity) < 1:
+            raise ValueError("series_capacity must be at least 1, got %r" % (capacity,))
+        if not math.isfinite(extent_conc):
+            raise ValueError("extent_conc must be finite, got %r" % (extent_conc,))
+        if not callable(getattr(ops, "history_row_totals", None)):
+            raise ValueError("series= needs an ops object with the row totals of the C ABI (abi.Context); %s has no history_row_totals"
+                             % type(ops).__name__)
+        return series
 
     def _history_sources(self):
         """the current ping-pong side of everything a sample reads"""
@@ -430,11 +486,29 @@ class DynamicsCore:
     def _history_sample(self):
         """one sample of the owned rows at the end of a model step: one launch, after the step's last phase mark and outside every
         captured graph; the first sample of a window stores, the others add"""
+        if self.series is not None:
+            self._series_sample()
         if self.history is None:
             return
         b = self.blk
-        self.ops.history_accumulate(b.j0, b.j1, self.history, self._history_sources(), self._hist_count == 0, b.j0, self._hist_acc)
+        if self._hist_pairs is None:
+            self.ops.history_accumulate(b.j0, b.j1, self.history, self._history_sources(), self._hist_count == 0, b.j0, self._hist_acc)
+        else:
+            self.ops.history_accumulate_stats(b.j0, b.j1, self._hist_pairs, self._history_sources(), self._hist_count == 0, b.j0, self._hist_acc,
+                                              getattr(self, "_hist_wacc", None))
         self._hist_count += 1
+
+    def _series_room(self):
+        """a model step begins: ValueError if its row totals would find no free slot.  The host counts the slots; nothing is synchronised"""
+        if self.series is not None and not self._in_advance and self._series_count >= self.series_capacity:
+            raise ValueError("the series buffer is full (series_capacity = %d samples): call series_read() before the next step"
+                             % self.series_capacity)
+
+    def _series_sample(self):
+        """the row totals of the owned rows at the end of a model step: one launch into the next free slot"""
+        b = self.blk
+        self.ops.history_row_totals(b.j0, b.j1, self.series, self._history_sources(), self.extent_conc, b.j0, self._series_buf[self._series_count])
+        self._series_count += 1
 
     def history_read(self, reset=True):
         """{"rows": (r0, r1), "count": n, name: float64 [rows, nx] = the mean of the n samples since the last reset} for the rows this rank
@@ -446,10 +520,74 @@ class DynamicsCore:
         b, n = self.blk, self._hist_count
         acc = self._hist_acc.detach().cpu().numpy()
         out = {"rows": (b.r0, b.r1), "count": n}
-        for k, name in enumerate(self.history):
-            out[name] = acc[k] / n
+        if self._hist_pairs is None:
+            for k, name in enumerate(self.history):
+                out[name] = acc[k] / n
+        else:
+            import numpy as np
+
+            wacc = self._hist_wacc.detach().cpu().numpy() if hasattr(self, "_hist_wacc") else None
+            for k, (entry, (_, stat)) in enumerate(zip(self.history, self._hist_pairs)):
+                if stat == "mean":
+                    out[entry] = acc[k] / n
+                elif stat == "ice_mean":  # NaN where the window saw no ice
+                    iced = wacc > 0
+                    out[entry] = np.where(iced, acc[k] / np.where(iced, wacc, 1.0), np.nan)
+                else:
+                    out[entry] = acc[k].copy()
         if reset:
             self._hist_count = 0
+        return out
+
+    def series_read(self, reset=True):
+        """{"rows": (r0, r1), "count": n, name: float64 [n, rows] = the row totals of the n steps since the last reset} for the rows this
+        rank owns, as the device left them (one download; waits for the last step).  reset: the next step writes slot 0 again.
+        merge_series() makes the totals of the whole domain"""
+        if self.series is None:
+            raise ValueError("series_read() needs a core constructed with series=")
+        b, n = self.blk, self._series_count
+        buf = self._series_buf[:n].detach().cpu().numpy()
+        out = {"rows": (b.r0, b.r1), "count": n}
+        for k, name in enumerate(self.series):
+            out[name] = buf[:, k].copy()
+        if reset:
+            self._series_count = 0
+        return out
+
+    @staticmethod
+    def merge_series(parts, hx, hy):
+        """the ranks' series_read()s (any order) -> {"count": n, name: float64 [n]}: area and extent in m^2, volume and snow_volume in
+        m^3, drift = sum(w speed) / sum(w) in m/s (NaN where there is no ice), speed_max, hice_max.  The rows of a sample are added one
+        after the other in global row order, whatever the decomposition, so one block and N blocks give the same bits"""
+        import numpy as np
+
+        parts = sorted(parts, key=lambda p: p["rows"][0])
+        if any(p["count"] != parts[0]["count"] for p in parts):
+            raise ValueError("the ranks hold different numbers of samples: %s" % [p["count"] for p in parts])
+        if any(a["rows"][1] != c["rows"][0] for a, c in zip(parts, parts[1:])):
+            raise ValueError("the ranks' rows do not join: %s" % [p["rows"] for p in parts])
+        n = parts[0]["count"]
+        out = {"rows": (parts[0]["rows"][0], parts[-1]["rows"][1]), "count": n}
+        raw = {}
+        for k in parts[0]:
+            if k in ("rows", "count"):
+                continue
+            rows = np.concatenate([p[k] for p in parts], axis=1)
+            if k in ("speed_max", "hice_max"):  # np.maximum keeps a NaN, as the rows do
+                raw[k] = np.maximum.accumulate(rows, axis=1)[:, -1] if n else np.zeros(0)
+            else:  # sequential in row order: np.sum would add pairwise
+                raw[k] = np.add.accumulate(rows, axis=1)[:, -1] if n else np.zeros(0)
+        cell = hx * hy
+        for k, v in raw.items():
+            if k == "drift":
+                if "area" not in raw:
+                    raise ValueError("'drift' needs 'area' in the series")
+                iced = raw["area"] > 0
+                out[k] = np.where(iced, v / np.where(iced, raw["area"], 1.0), np.nan)
+            elif k in ("area", "extent", "volume", "snow_volume"):
+                out[k] = v * cell
+            else:
+                out[k] = v
         return out
 
     @staticmethod
@@ -765,6 +903,7 @@ class DynamicsCore:
         self._set_fields(new)
 
     def step(self):
+        self._series_room()
         self._set_grid()
         self.momentum()
         self.transport()
@@ -799,6 +938,7 @@ class DynamicsCore:
     def advance(self, model_dt, substeps=1, courant=None, max_substeps=16, params=None):
         """one model step of model_dt as n calls of step() with self.dt = model_dt / n (restored afterwards); substeps: an int >= 1, or
         "auto" (n from the state at the start of the step, substep_count).  Returns n; substeps = 1 is step() at model_dt, bit for bit"""
+        self._series_room()
         if substeps == "auto":
             self._mark(PHASE_REDUCTION)
             n = self.substep_count(model_dt, courant, max_substeps, params)[0]
@@ -1074,6 +1214,7 @@ class CoupledCore(DynamicsCore):
             self.ops.column_wind(self.ua, self.va, self.col["wind"])
 
     def step(self):
+        self._series_room()
         self._set_grid()
         self.external_forcing()
         self.thermodynamics()

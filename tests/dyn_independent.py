@@ -25,6 +25,12 @@ different routes wherever the mathematics allows one:
 
 It does NOT make parity "green" (nothing can, without a reference implementation); it says that two independently written
 statements of DESIGN.md section 3 agree to round-off.  Pure-Python loops: small grids only.
+
+Of the TRANSPORT this file states one DG2 Runge-Kutta stage and the DG2 closure on the 6 x 5 case, with a velocity that is zero on the
+boundary.  That is no longer the whole independent hold of the transport: tests/transport_independent.py restates it at the orders
+0, 1 and 2 -- advecting velocity, stage, full step in Butcher form, closure, row ranges, open boundary -- vectorised for grids of any
+size, and the oracle (tests/test_transport_independent_cpu.py) and every transport kernel and entry point
+(tests/test_gpu_transport_independent.py) are held to it.
 """
 import numpy as np
 from numpy.polynomial import Polynomial as Poly

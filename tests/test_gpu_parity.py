@@ -1094,7 +1094,10 @@ def test_hip_path_matches_the_independent_restatement(ctx, variant):
     """the HIP path against tests/golden/dyn_independent_v3.npz -- the outputs of the independent dense numpy restatement of
     DESIGN.md section 3 (tests/dyn_independent.py), which the oracle is held to on the CPU: ice strength, nodal means, wind
     stress, ONE mEVP sub-iteration and ONE DG2 transport stage on the 6 x 5 case, through the C ABI.  Not reference parity
-    (the snapshot has no dynamics code, /root/reference/CMakeLists.txt:43-46): it removes the common mode of oracle and kernels."""
+    (the snapshot has no dynamics code, /root/reference/CMakeLists.txt:43-46): it removes the common mode of oracle and kernels.
+    The one DG2 stage here reaches the default stage kernel on a closed box only; the transport as a whole -- every order, kernel and
+    entry point, the open boundary, the march and its closure -- is held to its own restatement in
+    tests/test_gpu_transport_independent.py."""
     import dyn_independent as D
 
     fix = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dyn_independent_v3.npz"))

@@ -58,7 +58,7 @@ extern "C" {
  * device timing) and nsdg_land_mask_set / nsdg_land_clear / nsdg_land_clear_nodes (land mask) and nsdg_bbm_default_params / nsdg_bbm_params_set /
  * nsdg_bbm_prepare / nsdg_bbm_iterate / nsdg_bbm_substep_count (brittle rheology) and nsdg_history_accumulate / nsdg_history_field_name /
  * nsdg_history_field_id, nsdg_history_accumulate_stats / nsdg_history_row_totals / nsdg_history_stat_* / nsdg_history_series_* (history
- * output) are additions; nothing that existed changed. */
+ * output) and nsdg_drifters_advance / nsdg_comm_max_f64_array (drifters) are additions; nothing that existed changed. */
 #define NSDG_ABI_VERSION 6
 
 typedef enum {
@@ -726,6 +726,41 @@ int nsdg_history_stat_id(const char* name);
 const char* nsdg_history_series_name(int32_t quantity);
 int nsdg_history_series_id(const char* name);
 
+/* ---- drifters: Lagrangian points advected by the ice velocity (csrc/drifters.hip) -----------------------------------
+ * No counterpart in the reference snapshot.  The state of n drifters is ONE device array d[3][n] of doubles: plane 0 = x [m], plane 1 = y [m],
+ * plane 2 = the status as a double.  x and y are GLOBAL domain coordinates: the domain is [0, Lx] x [0, Ly], Lx = nx hx, Ly = ny_global hy
+ * (nsdg_block_set; a single domain: ny_global = ny).  Status: 0 active, 1 left the domain, 2 lost its ice, 3 on land.  A drifter whose
+ * status is not 0 never moves again.
+ *
+ * nsdg_drifters_advance: ONE launch on the context's stream, one lane per drifter, no atomics, out of place.  u, v: the CG2 velocity of the
+ * local array; A: the concentration, plane 0 (the cell mean) is read.  For every drifter (x, y, s) of d_in, in THIS order:
+ *   1. element     ix = min(nx - 1, (int)floor(x / hx)),  iyg = min(ny_global - 1, (int)floor(y / hy))  -- IEEE divisions, never a reciprocal:
+ *                  who owns a drifter must be the same decision on every rank; the local row is iy = iyg - row0.  (An index is also never
+ *                  below 0: a coordinate below 0 or a NaN, which the hosts refuse, never becomes an address.)
+ *   2. ownership   iy outside [j0, j1): the drifter is not this launch's -- all three planes of d_out get -inf.  Every case below writes all
+ *                  three planes, so the elementwise maximum over the launches of a decomposition is the whole list.
+ *   3. stopped     s != 0: (x, y, s) is copied through.
+ *   4. status      the element is land in the context's mask (nsdg_land_mask_set), if one is set: (x, y, 3); else A[iy nx + ix] < min_conc:
+ *                  (x, y, 2) -- a NaN concentration is not "<".
+ *   5. velocity    (u1, v1) = V(x, y), the biquadratic CG2 velocity of element (ix, iy) from its 3 x 3 nodes (2 ix + c, 2 iy + r): with the local
+ *                  coordinates xi = x / hx - ix - 1/2, eta = y / hy - iyg - 1/2 and the weights of the nodes at -1/2, 0, +1/2
+ *                      L-(t) = 2 t^2 - t,   L0(t) = 1 - 4 t^2,   L+(t) = 2 t^2 + t,
+ *                  V = sum over the rows r bottom to top of L_r(eta) (L-(xi) w_r0 + L0(xi) w_r1 + L+(xi) w_r2), a row west to east.
+ *   6. predictor   xp = x + dt u1, yp = y + dt v1, xp clamped to [max(ix - 1, 0) hx, min(ix + 2, nx) hx] and yp to [max(iyg - 1, 0) hy,
+ *                  min(iyg + 2, ny_global) hy]: the 3 x 3 elements around the drifter's own.  The clamp is stated in the drifter's own
+ *                  element indices: it does not depend on the decomposition, and at any sane Courant number it is never active.
+ *   7. velocity    the element of (xp, yp) by rule 1, its indices limited to [max(ix - 1, 0), min(ix + 1, nx - 1)] and [max(iyg - 1, 0),
+ *                  min(iyg + 1, ny_global - 1)] (a predictor ON the upper limit of the clamp is on the closed edge of the last of those
+ *                  elements, where the continuous velocity has the same value); (u2, v2) = V(xp, yp) there.
+ *   8. Heun        xn = x + (0.5 dt) (u1 + u2), yn likewise.  !(0 <= xn <= Lx && 0 <= yn <= Ly) -- a NaN too --: (x, y, 1); else (xn, yn, 0).
+ *   Every operation is one fp64 operation; the device may contract a product and a sum into an FMA.
+ * Checks, as for the history calls: grid set (else NSDG_ERR_STATE); 0 <= j0 <= j1 <= ny; n >= 0 (n == 0 does nothing); dt and min_conc finite;
+ *   non-null pointers; d_out != d_in; every row of [j0, j1) has its neighbour rows inside the local array or at the physical boundary --
+ *   j0 >= 1 unless row0 + j0 == 0, j1 <= ny - 1 unless row0 + j1 == ny_global --, else NSDG_ERR_ARG with a message that names the missing ghost
+ *   row.  The velocity must be valid on those rows (node rows 2 (j0 - 1) .. 2 (j1 + 1)).  The call belongs to no phase of the phase table. */
+int nsdg_drifters_advance(nsdg_ctx* ctx, int32_t j0, int32_t j1, double dt, double min_conc, int64_t n, const double* u, const double* v,
+    const double* A, const double* d_in, double* d_out);
+
 /* ---- row-block decomposition: ghost-row exchange (SURVEY.md section 8(b) "nsdg_halo_exchange", 8(e)) ----------
  * The reference is a single-process, single-thread program; these entry points have no
  * counterpart in it.  They sit behind the same seam as everything else, the batched model step
@@ -753,6 +788,15 @@ int nsdg_comm_deadline_set(nsdg_ctx* ctx, double seconds);
  * collective calls.  RCCL: ncclAllReduce(ncclMax) on a device scalar on the communication stream, the wait bounded by the deadline; local
  * transport: on the host, under the same deadline.  NSDG_ERR_COMM when a rank does not arrive in time. */
 int nsdg_comm_max_f64(nsdg_ctx* ctx, double* value);
+/* The elementwise maximum, in place, of the DEVICE array dev[0 .. n) over the ranks of the context's communicator (the NaN rule of
+ * nsdg_comm_max_f64); without a communicator, with a world of one or with n == 0 nothing happens.  Collective, every rank with the same n.
+ * After nsdg_drifters_advance exactly one rank holds a finite triple per drifter and the others -inf: this merge gives every rank the whole
+ * list.  RCCL: ncclAllReduce(ncclMax) in place on the communication stream, ordered behind the context's stream by an event, and the
+ * context's stream waits for it; the host does not wait (a dead peer shows at the next bounded wait).  This path has never run: no machine
+ * with two GPUs was at hand, as for every RCCL path of this library.  Local transport: staged on the host under the group's mutex, as
+ * nsdg_comm_max_f64 with a vector in place of the scalar -- this transport SYNCHRONISES the context's streams (within the deadline) on
+ * every rank; NSDG_ERR_COMM when a rank does not arrive in time or brings another n. */
+int nsdg_comm_max_f64_array(nsdg_ctx* ctx, double* dev, int64_t n);
 
 /* Rehearsal aid for a box with ONE GPU (tools/rank_share_timing.py, bench.py's loopback rehearsal): a loopback exchange
  * has no wire time, so a kernel that spins for delay_us + bytes of the larger direction / gbs (GB/s per direction) is put on

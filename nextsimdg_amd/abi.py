@@ -90,6 +90,10 @@ class HistorySources(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in HISTORY_SOURCES]
 
 
+# drifters (include/nsdg.h "drifters"): the status values of plane 2, and the lanes per workgroup of the launch (csrc/drifters.hip)
+DRIFTER_ACTIVE, DRIFTER_LEFT, DRIFTER_NO_ICE, DRIFTER_LAND = 0, 1, 2, 3
+DRIFTERS_BLOCK = 256
+
 COMM_ID_BYTES = 128
 RB_MAX_FIELDS = 4
 
@@ -168,6 +172,7 @@ SYMBOLS = {
     "nsdg_history_stat_id": (C.c_int, [C.c_char_p]),
     "nsdg_history_series_name": (C.c_char_p, [I32]),
     "nsdg_history_series_id": (C.c_int, [C.c_char_p]),
+    "nsdg_drifters_advance": (C.c_int, [VP, I32, I32, D, D, I64] + [VP] * 5),
     "nsdg_boxtest_forcing": (C.c_int, [VP, D, D, VP, VP, VP, VP]),
     "nsdg_block_set": (C.c_int, [VP, I32, I32]),
     "nsdg_column_forcing": (C.c_int, [VP, I32, D] + [VP] * 7),
@@ -195,6 +200,7 @@ SYMBOLS = {
     "nsdg_comm_rank": (C.c_int, [VP, C.POINTER(I32), C.POINTER(I32)]),
     "nsdg_comm_deadline_set": (C.c_int, [VP, D]),
     "nsdg_comm_max_f64": (C.c_int, [VP, C.POINTER(D)]),
+    "nsdg_comm_max_f64_array": (C.c_int, [VP, VP, I64]),
     "nsdg_comm_simulate_wire": (C.c_int, [VP, D, D]),
     "nsdg_halo_plan_create": (C.c_int, [VP, I32, I32, I32, C.POINTER(HaloSeg), I32, C.POINTER(HaloSeg), I32, C.POINTER(HaloSeg), I32,
                                         C.POINTER(HaloSeg), C.POINTER(VP)]),
@@ -871,6 +877,28 @@ class Context:
         v = D(float(value))
         self._call(self.lib.nsdg_comm_max_f64(self.h, C.byref(v)))
         return float(v.value)
+
+    def comm_max_f64_array(self, t):
+        """nsdg_comm_max_f64_array: the elementwise maximum of the device tensor t over the ranks of the context's communicator, in place
+        (collective; the local transport synchronises)"""
+        _check_f64(t)
+        self._call(self.lib.nsdg_comm_max_f64_array(self.h, _ptr(t), t.numel()))
+
+    # ---- drifters (include/nsdg.h "drifters"; csrc/drifters.hip)
+    def drifters_advance(self, j0, j1, dt, min_conc, u, v, A, d_in, d_out):
+        """nsdg_drifters_advance: one Heun step of the drifters d_in ([3, n]: x, y, status) whose element lies in the local rows [j0, j1),
+        written to d_out; every other drifter of d_out is -inf in all three planes.  u, v: the CG2 velocity; A: the concentration ([nc, ny,
+        nx], plane 0 is read)"""
+        _check_f64(u, v, A, d_in, d_out)
+        if d_in.dim() != 2 or d_in.shape[0] != 3 or tuple(d_out.shape) != tuple(d_in.shape):
+            raise NsdgError("drifters_advance: d_in and d_out must be [3, n] arrays of one shape, got %s and %s" % (tuple(d_in.shape), tuple(d_out.shape)))
+        n_node = (2 * self.nx + 1) * (2 * self.ny + 1)
+        if u.numel() != n_node or v.numel() != n_node:  # the ABI takes bare pointers
+            raise NsdgError("drifters_advance: the nodal arrays of the grid hold %d values" % n_node)
+        if A.numel() < self.nx * self.ny:
+            raise NsdgError("drifters_advance: A has %d values, the grid needs %d" % (A.numel(), self.nx * self.ny))
+        self._call(self.lib.nsdg_drifters_advance(self.h, j0, j1, float(dt), float(min_conc), d_in.shape[1], _ptr(u), _ptr(v), _ptr(A),
+                                                  _ptr(d_in), _ptr(d_out)))
 
     def boxtest_forcing(self, domain_size, t, wind=None, ocean=None):
         ts = list(wind or (None, None)) + list(ocean or (None, None))

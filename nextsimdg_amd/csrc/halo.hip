@@ -132,6 +132,10 @@ struct LocalGroup {
     int red_arrived = 0;
     long red_generation = 0;
     double red_acc = 0., red_result = 0.;
+    // nsdg_comm_max_f64_array: the same hand-shake with a vector in place of the scalar, and state of its own
+    int vec_arrived = 0;
+    long vec_generation = 0;
+    std::vector<double> vec_acc, vec_result;
 };
 
 std::mutex g_groups_mutex;
@@ -168,6 +172,8 @@ struct nsdg_comm {
     hipStream_t stream = nullptr; // communication stream
     int nplans = 0; // plans created so far (their indices match across the ranks of a group)
     bool broken = false; // a wait ran into the deadline: the streams may never drain, abort instead of draining
+    hipEvent_t ev_red[2] = { nullptr, nullptr }; // nsdg_comm_max_f64_array on RCCL: "the array is ready" / "the array is reduced" (created on first use)
+    std::vector<double> red_stage; // nsdg_comm_max_f64_array on the local transport: this rank's host copy of the array
     // rehearsal aid (nsdg_comm_simulate_wire): simulated transfer time per exchange, fixed part and bandwidth per direction
     double sim_delay_us = 0., sim_gbs = 0.;
 };
@@ -435,6 +441,9 @@ int nsdg_comm_finalize(nsdg_ctx* ctx)
     }
     if (!c->broken) // hipStreamDestroy waits for the stream's work: a broken communicator's stream is left to the process exit
         (void)hipStreamDestroy(c->stream);
+    for (hipEvent_t e : c->ev_red)
+        if (e)
+            (void)hipEventDestroy(e);
     delete c;
     ctx->comm = nullptr;
     return NSDG_OK;
@@ -778,6 +787,89 @@ int nsdg_comm_max_f64(nsdg_ctx* ctx, double* value)
         }
     }
     *value = g->red_result;
+    return NSDG_OK;
+}
+
+int nsdg_comm_max_f64_array(nsdg_ctx* ctx, double* dev, int64_t n)
+{
+    NSDG_CHECK_ARG(ctx != nullptr, "null context");
+    NSDG_CHECK_ARG(n >= 0, "n must be >= 0");
+    NSDG_CHECK_ARG(dev != nullptr || n == 0, "null pointer");
+    nsdg_comm* c = ctx->comm;
+    if (!c || c->world == 1 || n == 0)
+        return NSDG_OK;
+    if (c->broken) {
+        nsdg_set_error("nsdg_comm_max_f64_array: the communicator is broken (an earlier wait ran into the deadline)");
+        return NSDG_ERR_COMM;
+    }
+    NSDG_CHECK_HIP(hipSetDevice(ctx->device));
+    if (c->nccl) {
+        // in place on the communication stream, behind what the compute stream has enqueued so far; the compute stream waits for the result.
+        // Nothing here blocks the host: a dead peer shows at the next bounded drain (nsdg_ctx_synchronize)
+        for (hipEvent_t& e : c->ev_red)
+            if (!e)
+                NSDG_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        NSDG_CHECK_HIP(hipEventRecord(c->ev_red[0], ctx->stream));
+        NSDG_CHECK_HIP(hipStreamWaitEvent(c->stream, c->ev_red[0], 0));
+        NSDG_CHECK_RCCL(g_rccl.AllReduce(dev, dev, (size_t)n, ncclDouble, ncclMax, c->nccl, c->stream));
+        NSDG_CHECK_HIP(hipEventRecord(c->ev_red[1], c->stream));
+        NSDG_CHECK_HIP(hipStreamWaitEvent(ctx->stream, c->ev_red[1], 0));
+        return NSDG_OK;
+    }
+    // local transport: the ranks are threads of this process -- every rank brings its array to the host (this SYNCHRONISES its streams,
+    // within the deadline), the maximum is taken there under the group's mutex, and every rank takes the result back to its device
+    int rc = nsdg_comm_bounded_drain(ctx);
+    if (rc != NSDG_OK)
+        return rc;
+    std::vector<double>& mine = c->red_stage;
+    mine.resize((size_t)n);
+    NSDG_CHECK_HIP(hipMemcpy(mine.data(), dev, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    LocalGroup* g = c->local;
+    {
+        std::unique_lock<std::mutex> lock(g->m);
+        if (g->failed) {
+            nsdg_set_error("nsdg_comm_max_f64_array: a rank of the local group failed");
+            return NSDG_ERR_COMM;
+        }
+        const long generation = g->vec_generation;
+        if (g->vec_arrived == 0)
+            g->vec_acc = mine;
+        else if (g->vec_acc.size() != mine.size()) {
+            g->failed = true;
+            g->cv.notify_all();
+            nsdg_set_error("nsdg_comm_max_f64_array: the ranks of the local group pass arrays of different lengths (%ld and %ld)", (long)g->vec_acc.size(),
+                (long)mine.size());
+            return NSDG_ERR_COMM;
+        } else {
+            for (size_t k = 0; k < mine.size(); ++k) {
+                const double a = g->vec_acc[k], b = mine[k];
+                g->vec_acc[k] = (std::isnan(a) || std::isnan(b)) ? NAN : std::max(a, b);
+            }
+        }
+        if (++g->vec_arrived == g->world) {
+            g->vec_result.swap(g->vec_acc);
+            g->vec_arrived = 0;
+            ++g->vec_generation;
+            g->cv.notify_all();
+        } else {
+            const auto done = [&] { return g->failed || g->vec_generation != generation; };
+            bool ok = true;
+            if (ctx->comm_deadline_s > 0.)
+                ok = g->cv.wait_for(lock, std::chrono::duration<double>(ctx->comm_deadline_s), done);
+            else
+                g->cv.wait(lock, done);
+            if (!ok || g->failed) {
+                g->failed = true;
+                g->cv.notify_all();
+                nsdg_set_error("nsdg_comm_max_f64_array: a rank of the local group failed or did not arrive within %g s", ctx->comm_deadline_s);
+                return NSDG_ERR_COMM;
+            }
+        }
+        // the next reduction cannot complete -- and replace the result -- before every rank, this one included, has arrived at it
+        mine = g->vec_result;
+    }
+    NSDG_CHECK_HIP(hipMemcpyAsync(dev, mine.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    NSDG_CHECK_HIP(hipStreamSynchronize(ctx->stream)); // `mine` is pageable and reused by the next call
     return NSDG_OK;
 }
 

@@ -55,6 +55,10 @@
 //     model.output_period, model.output_file, model.output_fields, model.output_kind   history output: time means or snapshots of element
 //                            fields, accumulated on the device after every model step and written once per window
 //                            (include/HistoryOutput.hpp; include/nsdg.h "history output"); period 0 (default): off, nothing changes
+//     model.drifters_file, model.drifters_output, model.drifters_period, model.drifters_min_conc   Lagrangian drifters moved by the ice
+//                            velocity after every transport step and written as text blocks (include/Drifters.hpp; include/nsdg.h
+//                            "drifters"); works with dynamics.row_blocks (block 0 writes), refused in a multi-process run; no file
+//                            (default): off, nothing changes
 //     dynamics.row_blocks, dynamics.devices, dynamics.passes_per_exchange (2), dynamics.overlap (true),
 //     dynamics.graph (false), dynamics.loopback_world (0: off; N: rehearse an interior block of N on one GPU with
 //     real RCCL send/recv to the rank itself -- values wrap around, for timing and call-path checks only)
@@ -77,6 +81,7 @@ namespace Nextsim {
 class ForcingFile;
 class HistoryOutput;
 class SeriesOutput;
+class DriftersOutput;
 class LandMaskFile;
 
 class DynamicsBlock; // one row block: context, device arrays, driver plans (DynamicsStep.cpp)
@@ -130,6 +135,7 @@ private:
     //! model.series_file: after a model step -- one row-totals launch on every block into the next slot of its buffer, the flush if full
     void sampleSeries(long dt);
     void flushSeries(); //!< synchronises every block, downloads its slots, adds the rows in global row order and appends the lines
+    void writeDrifters(); //!< model.drifters_output: block 0's list (every block holds the same) as the block of the current clock
     void resolvePhaseTimes(); //!< model.phase_timing: every block's table -> the timer tree and model.phase_timing_file (PhaseTiming.hpp)
     //! dynamics.forcing = file: records k0, k1 resident on the block's device, sampled with time weight w into the block's wind / ocean
     //! (the pairs the file holds) and, with thermodynamics, its column forcing planes
@@ -151,6 +157,8 @@ private:
     std::shared_ptr<const LandMaskFile> m_landMask; // dynamics.land_mask_file: the element mask, read and checked in configure()
     std::unique_ptr<HistoryOutput> m_history; // model.output_period > 0: keys, windows and record files (null: off)
     std::unique_ptr<SeriesOutput> m_series; // model.series_file: the time series of the domain totals (null: off)
+    std::unique_ptr<DriftersOutput> m_drifters; // model.drifters_file: keys, clock and text files of the drifters (null: off)
+    std::vector<double> m_drifterStart; // ... and the list the input file holds, [3][n], read and checked in configure()
     int substeps = 1; // dynamics.substeps; 0 = auto
     double substepCourant = 1.5; // dynamics.substep_courant (NSDG_SUBSTEP_COURANT)
     int maxSubsteps = 16; // dynamics.max_substeps

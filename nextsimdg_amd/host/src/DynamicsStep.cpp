@@ -14,6 +14,7 @@
 #include <thread>
 
 #include "../../../include/nsdg.h"
+#include "Drifters.hpp"
 #include "ForcingFile.hpp"
 #include "HistoryOutput.hpp"
 #include "LandMaskFile.hpp"
@@ -119,6 +120,9 @@ public:
     double* hist = nullptr; // model.output_period: the history accumulator, one plane of the OWNED rows per output field (null: off)
     double* histWeight = nullptr; // ... and the summed weights of its ice-weighted means, one plane (null: none is asked for)
     double* series = nullptr; // model.series_file: [model.series_buffer][quantities][owned rows] row totals (null: off)
+    // model.drifters_file: the whole list [3][n] on every block, twice -- a step is out of place; dpar says which half is current (null: off)
+    double* drift[2] = { nullptr, nullptr };
+    int dpar = 0;
 
     ~DynamicsBlock() { release(); }
     void release()
@@ -143,6 +147,11 @@ public:
         if (series)
             (void)hipFree(series);
         series = nullptr;
+        for (double*& p : drift) {
+            if (p)
+                (void)hipFree(p);
+            p = nullptr;
+        }
         if (ctx)
             nsdg_ctx_destroy(ctx); // finalises the communicator too
         if (land) // after the context, which held the pointer
@@ -287,6 +296,15 @@ void DynamicsStep::configure()
     const SeriesOutput::Config sc = SeriesOutput::fromConfiguration(thermo, RankEnvironment::fromEnv().world);
     if (sc.on())
         m_series = std::make_unique<SeriesOutput>(sc);
+    // drifters (include/Drifters.hpp): the keys and the input file are read and checked here, before any device is touched; a
+    // multi-process run is refused here
+    m_drifters.reset();
+    m_drifterStart.clear();
+    const DriftersOutput::Config dc = DriftersOutput::fromConfiguration(RankEnvironment::fromEnv().world, loopbackWorld != 0);
+    if (dc.on()) {
+        m_drifterStart = DriftersOutput::read(dc.file, L, L);
+        m_drifters = std::make_unique<DriftersOutput>(dc);
+    }
 }
 
 void DynamicsStep::init()
@@ -348,6 +366,8 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
         m_history->start((long)startTime); // the integer clock the output windows are aligned to (m_time is a double under sub-stepping)
     if (m_series)
         m_series->start((long)startTime);
+    if (m_drifters)
+        m_drifters->start((long)startTime);
     if (m_landMask) {
         m_landMask->checkShape((std::size_t)nyf, (std::size_t)nxf);
         if (m_rank == 0)
@@ -526,6 +546,13 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
             checkHip(hipMalloc(reinterpret_cast<void**>(&b.series),
                          (std::size_t)m_series->config().buffer * m_series->config().ids.size() * (b.j1 - b.j0) * sizeof(double)),
                 "DynamicsStep: hipMalloc (series buffer)");
+        if (m_drifters && !m_drifterStart.empty()) { // every block holds the whole list; the partner is written before it is read
+            const std::size_t bytes = m_drifterStart.size() * sizeof(double);
+            for (double*& p : b.drift)
+                checkHip(hipMalloc(reinterpret_cast<void**>(&p), bytes), "DynamicsStep: hipMalloc (drifters)");
+            checkHip(hipMemcpy(b.drift[0], m_drifterStart.data(), bytes, hipMemcpyHostToDevice), "upload drifters");
+            b.dpar = 0;
+        }
         // driver plans
         nsdg_rb_mevp_desc m;
         std::memset(&m, 0, sizeof m);
@@ -591,6 +618,21 @@ void DynamicsStep::iterate(const Iterator::Duration& dtSeconds)
         sampleSeries((long)dtSeconds);
     if (m_history)
         sampleHistory((long)dtSeconds);
+    if (m_drifters && m_drifters->step((long)dtSeconds))
+        writeDrifters();
+}
+
+void DynamicsStep::writeDrifters()
+{
+    // every block holds the same list after the merge: row block 0 writes
+    std::vector<double> planes(m_drifterStart.size());
+    if (!planes.empty()) {
+        DynamicsBlock& b = *m_blocks[0];
+        checkHip(hipSetDevice(b.device), "hipSetDevice");
+        check(nsdg_ctx_synchronize(b.ctx), "DynamicsStep: drifters output");
+        checkHip(hipMemcpy(planes.data(), b.drift[b.dpar], planes.size() * sizeof(double), hipMemcpyDeviceToHost), "download drifters");
+    }
+    m_drifters->write(planes);
 }
 
 // what a history sample and the row totals read: the current side of every ping-pong
@@ -781,6 +823,17 @@ void DynamicsStep::subStep(double dt, bool last)
         b.tpar = out;
         if (advectColumn)
             check(nsdg_tracer_recover(ctx, 2, 0, b.ny, b.cur(FH), b.cur(FA), b.cur(FQ), p.min_conc, p.min_thick, b.col(C_TICE)), "nsdg_tracer_recover");
+        if (b.drift[0]) {
+            // the drifters of the owned rows move with the velocity the sub-cycle left (its ghost node rows are complete: the plan's ghost
+            // zones are (v k, v k - 1) deep) and the concentration the transport left; then the blocks' lists are merged.  No phase of
+            // its own: inside the span, before its end mark
+            const int64_t n = (int64_t)(m_drifterStart.size() / 3);
+            check(nsdg_drifters_advance(ctx, b.j0, b.j1, dt, m_drifters->config().minConc, n, b.curU(), b.curV(), b.cur(FA), b.drift[b.dpar], b.drift[1 - b.dpar]),
+                "nsdg_drifters_advance");
+            b.dpar = 1 - b.dpar;
+            if (b.world > 1)
+                check(nsdg_comm_max_f64_array(ctx, b.drift[b.dpar], 3 * n), "nsdg_comm_max_f64_array");
+        }
         if (last) // the model step ends here: what follows until its next mark belongs to no phase
             check(nsdg_phase_mark(ctx, NSDG_PHASE_END), "nsdg_phase_mark");
     });
@@ -876,6 +929,8 @@ void DynamicsStep::stop(const Iterator::TimePoint&)
         flushHistory();
     if (m_series)
         flushSeries();
+    if (m_drifters && m_drifters->dueAtStop()) // the block of the last time, once (stop() comes twice: the iterator's, the restart file's)
+        writeDrifters();
     FieldStore& f = pStructure->fields();
     std::vector<double> umax(m_blocks.size(), 0.);
     bool finite = true;

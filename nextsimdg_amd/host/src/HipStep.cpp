@@ -6,6 +6,7 @@
 #include <string>
 
 #include "../../../include/nsdg.h"
+#include "Drifters.hpp"
 #include "HistoryOutput.hpp"
 #include "ModuleLoader.hpp"
 #include "PhaseTiming.hpp"
@@ -48,6 +49,7 @@ void HipStep::init()
 {
     HistoryOutput::refuseFor("Nextsim::HipStep"); // before a device is touched: the column step alone writes no history output ...
     SeriesOutput::refuseFor("Nextsim::HipStep"); // ... and no time series
+    DriftersOutput::refuseFor("Nextsim::HipStep"); // ... and has no velocity to move drifters with
     if (!ctx)
         check(nsdg_ctx_create(0, nullptr, &ctx), "HipStep::init");
     phaseTiming = PhaseTiming::enabled();

@@ -274,6 +274,7 @@ class DynamicsCore:
 
     LAND_OPS = ("set_land_mask", "land_clear", "land_clear_nodes")
     BBM_OPS = ("bbm_prepare", "bbm_iterate")
+    DRIFTER_OPS = ("drifters_advance",)
     DAMAGE_BOUNDS = (0.0, 1.0, False)  # the damage D of the brittle rheology: in [0, 1], no cap of the cell mean
     # history output (include/nsdg.h "history output"; the names: abi.HISTORY_FIELDS): the fields of the column
     # state exist in a CoupledCore only
@@ -282,7 +283,8 @@ class DynamicsCore:
     series = None  # series=: off unless the constructor says otherwise
 
     def __init__(self, ops, blk, hx, hy, dt, nsub, device, exchanger=None, overlap=True, native=False, use_graph=False, closure=True,
-                 phase_timing=False, land=None, rheology="mevp", bbm=None, history=None, series=None, series_capacity=1024, extent_conc=0.15):
+                 phase_timing=False, land=None, rheology="mevp", bbm=None, history=None, series=None, series_capacity=1024, extent_conc=0.15,
+                 drifters=None, drifter_min_conc=0.15):
         self.ops, self.blk, self.hx, self.hy, self.dt, self.nsub = ops, blk, hx, hy, dt, nsub
         # history: names of abi.HISTORY_FIELDS sampled once per model step (step(), or advance() with all its sub-steps) into one accumulator
         # on the device, read as time means by history_read().  None: nothing is asked of `ops` and nothing is allocated.  An entry may be
@@ -292,6 +294,12 @@ class DynamicsCore:
         # buffer, read by series_read() and made domain totals by merge_series().  extent_conc: the concentration the ice extent counts from
         self.series = self._check_series(series, series_capacity, extent_conc, ops)
         self.series_capacity, self.extent_conc = int(series_capacity), float(extent_conc)
+        # drifters: [n, 2] positions (x, y) in metres of the GLOBAL domain [0, nx hx] x [0, ny_global hy], or [n, 3] with the status (0 active,
+        # 1 left the domain, 2 lost its ice, 3 on land) as a third column: Lagrangian points moved once per step() by the velocity the sub-cycle
+        # left (include/nsdg.h "drifters").  Every rank keeps the whole list.  drifter_min_conc: the cell-mean
+        # concentration below which a drifter has lost its ice.  None: nothing is asked of `ops` and nothing is allocated
+        drift0 = self._check_drifters(drifters, drifter_min_conc, ops, exchanger)
+        self.drifter_min_conc = float(drifter_min_conc)
         # rheology: "mevp", or "bbm" -- the brittle Bingham-Maxwell sub-cycle (include/nsdg.h "brittle rheology"):
         # nsub explicit sub-iterations of dt / nsub, a damage field D updated in the sub-cycle and advected with H and A.  bbm: an
         # abi.BbmParams set on the ops object (None: whatever the ops object holds, the library's defaults on a new context)
@@ -401,8 +409,78 @@ class DynamicsCore:
         if self.series is not None:
             self._series_buf = z(self.series_capacity, len(self.series), blk.j1 - blk.j0)
             self._series_count = 0
+        self._drift = self._drift_b = None
+        if drift0 is not None:  # the whole list on every rank, and the partner an out-of-place step writes
+            self._drift = torch.from_numpy(drift0).to(device)
+            self._drift_b = torch.empty_like(self._drift)
         if native:
             self._init_native()
+
+    def _check_drifters(self, drifters, min_conc, ops, exchanger):
+        """drifters= as a float64 [3, n] array (x, y, status), or None; ValueError for a list this core cannot carry"""
+        if drifters is None:
+            return None
+        import math
+
+        import numpy as np
+
+        b = self.blk
+        missing = [m for m in self.DRIFTER_OPS if not callable(getattr(ops, m, None))]
+        if missing:
+            raise ValueError("drifters= needs an ops object with the drifter call of the C ABI (abi.Context); %s has no %s"
+                             % (type(ops).__name__, ", ".join(missing)))
+        if not math.isfinite(min_conc):
+            raise ValueError("drifter_min_conc must be finite, got %r" % (min_conc,))
+        xy = np.array(drifters, dtype=np.float64)
+        if xy.ndim != 2 or xy.shape[1] not in (2, 3):
+            raise ValueError("drifters must be an [n, 2] array of positions or an [n, 3] array with the status, got shape %s" % (xy.shape,))
+        if not np.all(np.isfinite(xy)):
+            raise ValueError("drifter %d has a non-finite value" % int(np.argwhere(~np.isfinite(xy))[0][0]))
+        Lx, Ly = b.nx * self.hx, b.ny_glob * self.hy
+        outside = ~((xy[:, 0] >= 0) & (xy[:, 0] <= Lx) & (xy[:, 1] >= 0) & (xy[:, 1] <= Ly))
+        if outside.any():
+            k = int(np.argwhere(outside)[0][0])
+            raise ValueError("drifter %d at (%r, %r) m is outside the domain [0, %r] x [0, %r] m" % (k, float(xy[k, 0]), float(xy[k, 1]), Lx, Ly))
+        d = np.zeros((3, xy.shape[0]))
+        d[:xy.shape[1]] = xy.T
+        bad = ~np.isin(d[2], (0.0, 1.0, 2.0, 3.0))
+        if bad.any():
+            k = int(np.argwhere(bad)[0][0])
+            raise ValueError("drifter %d has the status %r; known: 0 active, 1 left the domain, 2 lost its ice, 3 on land" % (k, float(d[2, k])))
+        if b.world > 1 and not isinstance(exchanger, NativeHaloExchanger) and not (dist.is_available() and dist.is_initialized()):
+            raise ValueError("drifters= on %d row blocks merges the ranks' lists after every step: it needs a NativeHaloExchanger "
+                             "(comm_max_f64_array) or an initialised torch.distributed process group (all_reduce); %s has neither"
+                             % (b.world, "HaloExchanger" if exchanger is None else type(exchanger).__name__))
+        return d
+
+    def _drifters_step(self):
+        """the drifters of the owned rows move by one Heun step of self.dt with the velocity the sub-cycle left and the concentration the
+        transport left, then the ranks' lists are merged: a rank writes -inf for what it does not own, so the elementwise maximum is the
+        whole list.  Out of place: the two arrays swap.  No phase of its own; inside the span, before its end mark"""
+        if self._drift is None or self._drift.shape[1] == 0:
+            return
+        b = self.blk
+        if b.world > 1 and not self.two_per_pass:
+            # a predictor may sit in the ghost row above, whose upper node rows a single-iteration sub-cycle never receives (it needs
+            # the lowest only): one exchange of the velocity with the ghost rows complete
+            self.halo.nodal((self.u, self.v), rows_down=2 * b.depth_above + 1)
+        self.ops.drifters_advance(b.j0, b.j1, self.dt, self.drifter_min_conc, self.u, self.v, self.A, self._drift, self._drift_b)
+        self._drift, self._drift_b = self._drift_b, self._drift
+        if b.world > 1:
+            if isinstance(self.halo, NativeHaloExchanger):
+                self.halo.ctx.comm_max_f64_array(self._drift)
+            else:
+                dist.all_reduce(self._drift, op=dist.ReduceOp.MAX, group=self.halo.group)
+
+    def drifters_read(self):
+        """{"x", "y": float64 [n] in metres of the global domain, "status": int64 [n]} -- the whole list, identical on every rank (one
+        download; waits for the last step)"""
+        if self._drift is None:
+            raise ValueError("drifters_read() needs a core constructed with drifters=")
+        import numpy as np
+
+        d = self._drift.detach().cpu().numpy()
+        return {"x": d[0].copy(), "y": d[1].copy(), "status": d[2].astype(np.int64)}
 
     def _check_history(self, history, rheology, ops):
         """the entries of history= as a tuple, or None; ValueError for a list this core cannot sample.  Sets self._hist_pairs: None for a
@@ -907,6 +985,7 @@ class DynamicsCore:
         self._set_grid()
         self.momentum()
         self.transport()
+        self._drifters_step()
         if not self._in_advance:
             self._mark(PHASE_END)
             self._history_sample()
@@ -986,6 +1065,8 @@ class DynamicsCore:
             out[name] = self.ops.private_to_planes(f, nx)[:, b.j0:b.j1].detach().cpu().numpy().copy()
         if self.rheology == "bbm":
             out["D"] = self.owned(self.D).detach().cpu().numpy().copy()
+        if self._drift is not None:  # the whole list, not row-sliced: every rank holds the same
+            out["drifters"] = self._drift.detach().cpu().numpy().copy()
         return out
 
     def load_state_dict(self, state):
@@ -1008,6 +1089,10 @@ class DynamicsCore:
             if "D" not in state:
                 raise ValueError("a core with rheology='bbm' needs the damage D in the state")
             put(self.D, state["D"][:, es])
+        if self._drift is not None:
+            if "drifters" not in state or tuple(state["drifters"].shape) != tuple(self._drift.shape):
+                raise ValueError("a core with drifters= needs the [3, %d] array 'drifters' in the state" % self._drift.shape[1])
+            put(self._drift, state["drifters"])
         self._clear_land()
 
     @staticmethod
@@ -1022,6 +1107,9 @@ class DynamicsCore:
                 out[k] = np.concatenate([s[k] for s in states], axis=1)
         for k in ("u", "v"):
             out[k] = np.concatenate([s[k] for s in states], axis=0)
+        if "drifters" in states[0]:  # every rank holds the whole list
+            assert all(np.array_equal(s["drifters"], states[0]["drifters"]) for s in states), "the ranks' drifter lists differ"
+            out["drifters"] = states[0]["drifters"].copy()
         return out
 
 
@@ -1220,6 +1308,7 @@ class CoupledCore(DynamicsCore):
         self.thermodynamics()
         self.momentum()
         self.transport()
+        self._drifters_step()
         self.time += self.dt
         if not self._in_advance:
             self._mark(PHASE_END)

@@ -25,11 +25,15 @@ arrays) is packed into one buffer and sent with one P2P op (HaloExchanger).
 
 The numerical kernels are reached through an `ops` object with the method names of
 nextsimdg_amd.abi.Context (the C-ABI binding).  Nothing here computes on the host.
-"""
-import os
 
+A model step is ONE frame, DynamicsCore.step(); a subclass adds its phases in _phases().  History means, series and drifters are objects of
+nextsimdg_amd/outputs.py that the frame calls once each; the reductions over the ranks belong to the exchanger, which owns the group.
+"""
+import numpy as np
 import torch
 import torch.distributed as dist
+
+from nextsimdg_amd import abi, outputs
 
 # NSDG_PHASE_* of include/nsdg.h: the ids of step()'s phase marks (names: abi.PHASES)
 PHASE_FORCING, PHASE_COLUMN, PHASE_PREPARE, PHASE_SUBCYCLE, PHASE_TRANSPORT, PHASE_REDUCTION, PHASE_END = 0, 1, 2, 3, 4, 5, -1
@@ -37,6 +41,11 @@ PHASE_FORCING, PHASE_COLUMN, PHASE_PREPARE, PHASE_SUBCYCLE, PHASE_TRANSPORT, PHA
 
 def split_rows(ny, world, rank):
     return (rank * ny) // world, ((rank + 1) * ny) // world
+
+
+def _put(dst, array):
+    """a numpy array (any view) into a device tensor of its shape"""
+    dst.copy_(torch.from_numpy(np.ascontiguousarray(array)).to(dst.device))
 
 
 class RowBlock:
@@ -76,6 +85,7 @@ class HaloPlan:
         self.up_send, self.down_send, self.from_above, self.from_below = [], [], [], []
         self.buffers = None  # transport-private (packed send / receive buffers)
         self.ops = self.flat_up = self.flat_down = None  # transport-private (P2P ops and flattened views, built once)
+        self.native = None  # transport-private (NativeHaloExchanger: the plan behind the C ABI)
 
 
 class HaloExchanger:
@@ -102,7 +112,11 @@ class HaloExchanger:
             plan = self._cache[key] = HaloPlan()
             if self.blk.world > 1:
                 build(plan)
+                self._prepare(plan)
         return plan
+
+    def _prepare(self, plan):
+        """a new plan knows what travels: a transport that builds something per plan does it here"""
 
     def _add_nodal(self, plan, fields, rows_down):
         """CG2 nodal arrays [2ny+1, 2nx+1]: 2*depth_below node rows travel upwards, `rows_down` rows (1 for the
@@ -198,16 +212,29 @@ class HaloExchanger:
             self._add_rows(p, fields, rows_of)
             self._add_nodal(p, nodal_fields, rows_down)
 
-        return self._start(self._plan(key, build)), ()
-
-    def rows_exchange_finish(self, handle, unused=()):
-        self._finish(handle)
+        return self._start(self._plan(key, build))
 
     def element(self, fields):
         """refresh the ghost element rows of DG arrays [nc, ny, nx] (after a transport stage)"""
         key = ("e",) + tuple(f.data_ptr() for f in fields)
         plan = self._plan(key, lambda p: self._add_rows(p, fields, lambda f, a, c: f[:, a:c, :]))
-        self._finish(self._start(plan))
+        self.finish(self._start(plan))
+
+    # ------------------------------------------------------------------ reductions over the ranks of the group
+    def can_reduce(self):
+        return dist.is_available() and dist.is_initialized()
+
+    def max_scalar(self, value):
+        """the maximum of a host float over the ranks (one block: the value itself, nothing is called)"""
+        if self.blk.world == 1:
+            return value
+        t = torch.tensor([value], dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
+        return float(t.item())
+
+    def max_array(self, tensor):
+        """the elementwise maximum over the ranks, in place"""
+        dist.all_reduce(tensor, op=dist.ReduceOp.MAX, group=self.group)
 
 
 class NativeHaloExchanger(HaloExchanger):
@@ -218,43 +245,36 @@ class NativeHaloExchanger(HaloExchanger):
     def __init__(self, ctx, blk, device=None, group=None, loopback=False, local_group=None):
         super().__init__(blk, group, loopback)
         self.ctx = ctx
-        if loopback:
-            # rehearsal of an interior block on one GPU: a communicator of ONE rank, both neighbours are that rank
-            # (what goes up arrives from below); the values wrap around, the calls and sizes are the real ones
-            if local_group is not None:
-                ctx.comm_init_local(local_group, 0, 1)
-            else:
-                ctx.comm_init_rccl(0, 1)
-            self.peer_below = 0 if blk.below is not None else None
-            self.peer_above = 0 if blk.above is not None else None
+        # loopback: rehearsal of an interior block on one GPU: a communicator of ONE rank, both neighbours are that rank
+        # (what goes up arrives from below); the values wrap around, the calls and sizes are the real ones
+        rank, world = (0, 1) if loopback else (blk.rank, blk.world)
+        if local_group is not None:
+            ctx.comm_init_local(local_group, rank, world)
         else:
-            if local_group is not None:
-                ctx.comm_init_local(local_group, blk.rank, blk.world)
-            else:
-                ctx.comm_init_rccl(blk.rank, blk.world, group)
-            self.peer_below, self.peer_above = blk.below, blk.above
+            ctx.comm_init_rccl(rank, world, group)  # (one rank: the group is not asked)
+        self.peer_below, self.peer_above = (None if p is None else 0 if loopback else p for p in (blk.below, blk.above))
 
-    def _plan(self, key, build):
-        plan = self._cache.get(key)
-        if plan is None:
-            plan = self._cache[key] = HaloPlan()
-            if self.blk.world > 1:
-                build(plan)
-                if plan.up_send or plan.down_send or plan.from_above or plan.from_below:
-                    plan.native = self.ctx.halo_plan(self.peer_below, self.peer_above, plan.up_send, plan.down_send,
-                                                     plan.from_above, plan.from_below)
-        return plan
+    def _prepare(self, plan):
+        if plan.up_send or plan.down_send or plan.from_above or plan.from_below:
+            plan.native = self.ctx.halo_plan(self.peer_below, self.peer_above, plan.up_send, plan.down_send, plan.from_above, plan.from_below)
 
     def _start(self, plan):
-        native = getattr(plan, "native", None)
-        if native is None:
-            return None
-        native.start()
-        return native
+        if plan.native is not None:
+            plan.native.start()
+        return plan.native
 
     def _finish(self, handle):
         if handle is not None:
             handle.finish()
+
+    def can_reduce(self):
+        return True
+
+    def max_scalar(self, value):
+        return self.ctx.comm_max_f64(value)  # (also on one block: the communicator decides)
+
+    def max_array(self, tensor):
+        self.ctx.comm_max_f64_array(tensor)
 
 
 class DynamicsCore:
@@ -268,119 +288,80 @@ class DynamicsCore:
     # closure of the transported fields (include/nsdg.h "INPUT DOMAIN AND CLOSURE"): mean thickness H >= 0; concentration
     # 0 <= A <= 1 at the quadrature points with the cell mean capped at 1 (ridging) -- (lo, hi, cap_mean) per field
     BOUNDS = ((0.0, float("inf"), False), (0.0, 1.0, True))
-    # the advected DG2 fields (attribute names), in the order of the step calls' field lists and of BOUNDS; CoupledCore with
-    # advect_column_state adds the snow S and the weighted surface temperature Q
+    # the advected DG2 fields (attribute names), in the order of the step calls' field lists and of BOUNDS.  A subclass may state its own;
+    # the constructor appends what _more_transported() returns (CoupledCore with advect_column_state: the snow S and the weighted surface
+    # temperature Q) and the damage D of rheology="bbm", and leaves the complete lists on the instance
     TRANSPORTED = ("H", "A")
 
     LAND_OPS = ("set_land_mask", "land_clear", "land_clear_nodes")
     BBM_OPS = ("bbm_prepare", "bbm_iterate")
-    DRIFTER_OPS = ("drifters_advance",)
     DAMAGE_BOUNDS = (0.0, 1.0, False)  # the damage D of the brittle rheology: in [0, 1], no cap of the cell mean
-    # history output (include/nsdg.h "history output"; the names: abi.HISTORY_FIELDS): the fields of the column
-    # state exist in a CoupledCore only
-    HISTORY_COLUMN_FIELDS = ("hsnow", "tice")
+    HISTORY_COLUMN_FIELDS = outputs.History.COLUMN_FIELDS
     HAS_COLUMN_STATE = False
-    series = None  # series=: off unless the constructor says otherwise
+    merge_history, merge_series = staticmethod(outputs.merge_history), staticmethod(outputs.merge_series)
 
     def __init__(self, ops, blk, hx, hy, dt, nsub, device, exchanger=None, overlap=True, native=False, use_graph=False, closure=True,
                  phase_timing=False, land=None, rheology="mevp", bbm=None, history=None, series=None, series_capacity=1024, extent_conc=0.15,
                  drifters=None, drifter_min_conc=0.15):
-        self.ops, self.blk, self.hx, self.hy, self.dt, self.nsub = ops, blk, hx, hy, dt, nsub
-        # history: names of abi.HISTORY_FIELDS sampled once per model step (step(), or advance() with all its sub-steps) into one accumulator
-        # on the device, read as time means by history_read().  None: nothing is asked of `ops` and nothing is allocated.  An entry may be
-        # "name:stat" with a statistic of abi.HISTORY_STATS ("name" alone is the mean): ice-weighted means and the extremes of the window
-        self.history = self._check_history(history, rheology, ops)
-        # series: names of abi.SERIES_QUANTITIES; every model step leaves their row totals in the next of series_capacity slots of a device
-        # buffer, read by series_read() and made domain totals by merge_series().  extent_conc: the concentration the ice extent counts from
-        self.series = self._check_series(series, series_capacity, extent_conc, ops)
-        self.series_capacity, self.extent_conc = int(series_capacity), float(extent_conc)
-        # drifters: [n, 2] positions (x, y) in metres of the GLOBAL domain [0, nx hx] x [0, ny_global hy], or [n, 3] with the status (0 active,
-        # 1 left the domain, 2 lost its ice, 3 on land) as a third column: Lagrangian points moved once per step() by the velocity the sub-cycle
-        # left (include/nsdg.h "drifters").  Every rank keeps the whole list.  drifter_min_conc: the cell-mean
-        # concentration below which a drifter has lost its ice.  None: nothing is asked of `ops` and nothing is allocated
-        drift0 = self._check_drifters(drifters, drifter_min_conc, ops, exchanger)
-        self.drifter_min_conc = float(drifter_min_conc)
-        # rheology: "mevp", or "bbm" -- the brittle Bingham-Maxwell sub-cycle (include/nsdg.h "brittle rheology"):
-        # nsub explicit sub-iterations of dt / nsub, a damage field D updated in the sub-cycle and advected with H and A.  bbm: an
-        # abi.BbmParams set on the ops object (None: whatever the ops object holds, the library's defaults on a new context)
-        if rheology not in ("mevp", "bbm"):
-            raise ValueError("rheology must be 'mevp' or 'bbm', got %r" % (rheology,))
-        self.rheology = rheology
-        if rheology == "bbm":
-            if native:
-                raise ValueError("rheology='bbm' is not built in the native row-block plan (nsdg_rb_mevp_*): use native=False")
-            if blk.world > 1 and (blk.depth_below, blk.depth_above) != (1, 1):
-                raise ValueError("rheology='bbm' runs one sub-iteration per pass: a row block needs the ghost depth (1, 1), got (%d, %d)"
-                                 % (blk.depth_below, blk.depth_above))
-            missing = [m for m in self.BBM_OPS if not callable(getattr(ops, m, None))]
-            if missing:
-                raise ValueError("rheology='bbm' needs an ops object with the BBM calls of the C ABI (abi.Context); %s has no %s"
-                                 % (type(ops).__name__, ", ".join(missing)))
-            if len(self.TRANSPORTED) + 1 > 4:  # NSDG_RB_MAX_FIELDS
-                raise ValueError("rheology='bbm' with advect_column_state=True would advect %d fields (%s and D); a transport step carries at most 4"
-                                 % (len(self.TRANSPORTED) + 1, ", ".join(self.TRANSPORTED)))
-            self.TRANSPORTED = self.TRANSPORTED + ("D",)
-            self.BOUNDS = self.BOUNDS + (self.DAMAGE_BOUNDS,)
-            if bbm is not None:
-                ops.set_bbm_params(bbm)
-        elif bbm is not None:
-            raise ValueError("bbm= parameters need rheology='bbm'")
+        self.ops, self.blk, self.hx, self.hy, self.dt, self.nsub, self.overlap = ops, blk, hx, hy, dt, nsub, overlap
+        # closure: cap + scaling limiter at the end of every transport step (the ice-free-node rule is a parameter of the
+        # sub-cycle, on by default).  False: the bare scheme of rounds 1-4 (frozen fixtures of that scheme)
+        self.closure = closure
+        # native: the sub-cycle and the transport of a step are ONE C call each (csrc/rowblock.hip runs the same
+        # sequence of passes and exchanges as subcycle() / transport() below); needs the C-ABI ops and, with
+        # neighbours, a NativeHaloExchanger (it owns the communicator).  use_graph: replay the launches between
+        # two exchanges as one hipGraph.
+        self.native, self.use_graph = native, use_graph
+        self.halo = exchanger if exchanger is not None else HaloExchanger(blk)
+        # Everything that can refuse comes first: a constructor that raises has changed nothing on `ops`
+        self._check_rheology(rheology, bbm)
+        self.TRANSPORTED, self.BOUNDS = self._transported()
         # land: bool array [ny_global, nx] of the WHOLE domain (True = land; include/nsdg.h "land mask"): the nodes of
         # land elements hold u = v = 0 like the array edge.  This rank keeps its rows, ghost rows included -- the mask is static, nothing
         # is exchanged -- and sets them on the ops object whenever it sets the grid
         self.land, self._land_on_ops = None, False
         if land is not None:
-            import numpy as np
-
-            missing = [m for m in self.LAND_OPS if not callable(getattr(ops, m, None))]
-            if missing:
-                raise ValueError("land= needs an ops object with the land-mask calls of the C ABI (abi.Context); %s has no %s"
-                                 % (type(ops).__name__, ", ".join(missing)))
+            outputs.require_ops(ops, self.LAND_OPS, "land=", "land-mask calls")
             land = np.asarray(land)
             if land.shape != (blk.ny_glob, blk.nx):
                 raise ValueError("land must be a [ny_global, nx] = [%d, %d] array, got shape %s" % (blk.ny_glob, blk.nx, land.shape))
             self.land = torch.from_numpy(np.ascontiguousarray(land[blk.elem_slice()] != 0).astype(np.uint8)).to(device)
         # phase_timing: step() brackets its parts with the library's phase marks (include/nsdg.h "per-phase device timing": one event per
         # mark on the ops' stream, read by phase_times()); off, nothing is asked of `ops` beyond the kernels
-        self._phase_timing = bool(phase_timing)
-        self._in_advance, self._phase_open = False, PHASE_END
+        self._phase_timing, self._phase_open = bool(phase_timing), PHASE_END
         if self._phase_timing:
-            missing = [m for m in ("phase_timing", "phase_mark", "phase_times") if not callable(getattr(ops, m, None))]
-            if missing:
-                raise ValueError("phase_timing=True needs an ops object with the phase calls of the C ABI (abi.Context); %s has no %s"
-                                 % (type(ops).__name__, ", ".join(missing)))
-            ops.phase_timing(True)
-        self.overlap = overlap
-        # closure: cap + scaling limiter at the end of every transport step (the ice-free-node rule is a parameter of the
-        # sub-cycle, on by default).  False: the bare scheme of rounds 1-4 (frozen fixtures of that scheme)
-        self.closure = closure
-        # the native driver's plan carries the bounds itself (nsdg_rb_transport_desc.own_bounds); the Python sequence of step calls reads
-        # them from the context: stated here, put back by close() (they apply to EVERY later step call on the context: include/nsdg.h)
-        self._bounds_before = getattr(ops, "transport_bounds", ())
-        ops.set_transport_bounds(self.BOUNDS if closure else ())
-        nf = len(self.TRANSPORTED)
-        # native: the sub-cycle and the transport of a step are ONE C call each (csrc/rowblock.hip runs the same
-        # sequence of passes and exchanges as subcycle() / transport() below); needs the C-ABI ops and, with
-        # neighbours, a NativeHaloExchanger (it owns the communicator).  use_graph: replay the launches between
-        # two exchanges as one hipGraph.
-        self.native, self.use_graph = native, use_graph
-        self._calls = {}
+            outputs.require_ops(ops, ("phase_timing", "phase_mark", "phase_times"), "phase_timing=True", "phase calls")
         # v sub-iterations per kernel pass (v = 4: variant 4, v = 3: variant 3, v = 2: variant 2) need a (v k, v k - 1) ghost depth
         # for k passes between two exchanges; a single domain has no ghosts at all.  All variants produce
         # bit-identical results, so a variant-3 context on a (2k, 2k-1) block simply uses the two-iteration kernel.
+        # per_pass >= 2: the ghost zones hold stress rows as well as velocity rows
         variant = getattr(ops, "mevp_variant", None)
         self.per_pass = 1
         for v in (4, 3, 2):
             deep = blk.depth_below >= v and blk.depth_below % v == 0 and blk.depth_above == blk.depth_below - 1
-            if variant is not None and variant >= v and (blk.world == 1 or deep):
+            if variant is not None and variant >= v and (blk.world == 1 or deep) and rheology != "bbm":  # (no multi-iteration brittle passes)
                 self.per_pass = v
                 break
-        if rheology == "bbm":  # multi-iteration passes of the brittle sub-cycle are not built
-            self.per_pass = 1
-        self.two_per_pass = self.per_pass >= 2  # the ghost zones hold stress rows as well as velocity rows
         self.group_passes = blk.depth_below // self.per_pass if (self.per_pass >= 2 and blk.world > 1) else 1  # passes between two exchanges
-        self.halo = exchanger if exchanger is not None else HaloExchanger(blk)
-        nx, ny = blk.nx, blk.ny
+        # the outputs (nextsimdg_amd/outputs.py), each an object or None; history and series: the names, as given
+        self._history = None if history is None else outputs.History(history, ops, blk, device, rheology, self.TRANSPORTED, self.HAS_COLUMN_STATE)
+        self._series = None if series is None else outputs.Series(series, series_capacity, extent_conc, ops, blk, device, self.HAS_COLUMN_STATE)
+        self._drifters = None if drifters is None else outputs.Drifters(drifters, drifter_min_conc, ops, blk, hx, hy, self.halo, device,
+                                                                         complete_ghosts=self.per_pass == 1)
+        self.history = self._history.entries if self._history is not None else None
+        self.series = self._series.names if self._series is not None else None
+        self.series_capacity, self.extent_conc, self.drifter_min_conc = int(series_capacity), float(extent_conc), float(drifter_min_conc)
+        # from here on `ops` is changed; close() puts it back
+        if bbm is not None:
+            ops.set_bbm_params(bbm)
+        if self._phase_timing:
+            ops.phase_timing(True)
+        # the native driver's plan carries the bounds itself (nsdg_rb_transport_desc.own_bounds); the Python sequence of step calls reads
+        # them from the context: stated here, put back by close() (they apply to EVERY later step call on the context: include/nsdg.h)
+        self._bounds_before = getattr(ops, "transport_bounds", ())
+        ops.set_transport_bounds(self.BOUNDS if closure else ())
+        self._calls = {}
+        nx, ny, nf = blk.nx, blk.ny, len(self.TRANSPORTED)
         z = lambda *s: torch.zeros(*s, dtype=torch.float64, device=device)
         nodal = (2 * ny + 1, 2 * nx + 1)
         for name in self.TRANSPORTED:
@@ -401,158 +382,42 @@ class DynamicsCore:
             self.Db = z(6, ny, nx)
             self.hg, self.eg, self.pm = (ops.private_zeros(9, ny, nx, device) for _ in range(3))
             self._zero_nodal = z(*nodal)
-        if self.history is not None:
-            self._hist_acc = z(len(self.history), blk.j1 - blk.j0, nx)  # the owned rows only: a sample is element-local
-            self._hist_count = 0
-            if any(st == "ice_mean" for _, st in self._hist_pairs or ()):
-                self._hist_wacc = z(blk.j1 - blk.j0, nx)  # the summed weights of the window, one plane for every ice-weighted mean
-        if self.series is not None:
-            self._series_buf = z(self.series_capacity, len(self.series), blk.j1 - blk.j0)
-            self._series_count = 0
-        self._drift = self._drift_b = None
-        if drift0 is not None:  # the whole list on every rank, and the partner an out-of-place step writes
-            self._drift = torch.from_numpy(drift0).to(device)
-            self._drift_b = torch.empty_like(self._drift)
         if native:
             self._init_native()
 
-    def _check_drifters(self, drifters, min_conc, ops, exchanger):
-        """drifters= as a float64 [3, n] array (x, y, status), or None; ValueError for a list this core cannot carry"""
-        if drifters is None:
-            return None
-        import math
+    def _check_rheology(self, rheology, bbm):
+        """rheology: "mevp", or "bbm" -- the brittle Bingham-Maxwell sub-cycle (include/nsdg.h "brittle rheology"):
+        nsub explicit sub-iterations of dt / nsub, a damage field D updated in the sub-cycle and advected with H and A.  bbm: an
+        abi.BbmParams set on the ops object (None: whatever the ops object holds, the library's defaults on a new context)"""
+        blk = self.blk
+        if rheology not in ("mevp", "bbm"):
+            raise ValueError("rheology must be 'mevp' or 'bbm', got %r" % (rheology,))
+        self.rheology = rheology
+        if rheology == "bbm":
+            if self.native:
+                raise ValueError("rheology='bbm' is not built in the native row-block plan (nsdg_rb_mevp_*): use native=False")
+            if blk.world > 1 and (blk.depth_below, blk.depth_above) != (1, 1):
+                raise ValueError("rheology='bbm' runs one sub-iteration per pass: a row block needs the ghost depth (1, 1), got (%d, %d)"
+                                 % (blk.depth_below, blk.depth_above))
+            outputs.require_ops(self.ops, self.BBM_OPS, "rheology='bbm'", "BBM calls")
+        elif bbm is not None:
+            raise ValueError("bbm= parameters need rheology='bbm'")
 
-        import numpy as np
+    def _more_transported(self):
+        """(names, bounds) of the fields a subclass advects besides the class's TRANSPORTED"""
+        return (), ()
 
-        b = self.blk
-        missing = [m for m in self.DRIFTER_OPS if not callable(getattr(ops, m, None))]
-        if missing:
-            raise ValueError("drifters= needs an ops object with the drifter call of the C ABI (abi.Context); %s has no %s"
-                             % (type(ops).__name__, ", ".join(missing)))
-        if not math.isfinite(min_conc):
-            raise ValueError("drifter_min_conc must be finite, got %r" % (min_conc,))
-        xy = np.array(drifters, dtype=np.float64)
-        if xy.ndim != 2 or xy.shape[1] not in (2, 3):
-            raise ValueError("drifters must be an [n, 2] array of positions or an [n, 3] array with the status, got shape %s" % (xy.shape,))
-        if not np.all(np.isfinite(xy)):
-            raise ValueError("drifter %d has a non-finite value" % int(np.argwhere(~np.isfinite(xy))[0][0]))
-        Lx, Ly = b.nx * self.hx, b.ny_glob * self.hy
-        outside = ~((xy[:, 0] >= 0) & (xy[:, 0] <= Lx) & (xy[:, 1] >= 0) & (xy[:, 1] <= Ly))
-        if outside.any():
-            k = int(np.argwhere(outside)[0][0])
-            raise ValueError("drifter %d at (%r, %r) m is outside the domain [0, %r] x [0, %r] m" % (k, float(xy[k, 0]), float(xy[k, 1]), Lx, Ly))
-        d = np.zeros((3, xy.shape[0]))
-        d[:xy.shape[1]] = xy.T
-        bad = ~np.isin(d[2], (0.0, 1.0, 2.0, 3.0))
-        if bad.any():
-            k = int(np.argwhere(bad)[0][0])
-            raise ValueError("drifter %d has the status %r; known: 0 active, 1 left the domain, 2 lost its ice, 3 on land" % (k, float(d[2, k])))
-        if b.world > 1 and not isinstance(exchanger, NativeHaloExchanger) and not (dist.is_available() and dist.is_initialized()):
-            raise ValueError("drifters= on %d row blocks merges the ranks' lists after every step: it needs a NativeHaloExchanger "
-                             "(comm_max_f64_array) or an initialised torch.distributed process group (all_reduce); %s has neither"
-                             % (b.world, "HaloExchanger" if exchanger is None else type(exchanger).__name__))
-        return d
-
-    def _drifters_step(self):
-        """the drifters of the owned rows move by one Heun step of self.dt with the velocity the sub-cycle left and the concentration the
-        transport left, then the ranks' lists are merged: a rank writes -inf for what it does not own, so the elementwise maximum is the
-        whole list.  Out of place: the two arrays swap.  No phase of its own; inside the span, before its end mark"""
-        if self._drift is None or self._drift.shape[1] == 0:
-            return
-        b = self.blk
-        if b.world > 1 and not self.two_per_pass:
-            # a predictor may sit in the ghost row above, whose upper node rows a single-iteration sub-cycle never receives (it needs
-            # the lowest only): one exchange of the velocity with the ghost rows complete
-            self.halo.nodal((self.u, self.v), rows_down=2 * b.depth_above + 1)
-        self.ops.drifters_advance(b.j0, b.j1, self.dt, self.drifter_min_conc, self.u, self.v, self.A, self._drift, self._drift_b)
-        self._drift, self._drift_b = self._drift_b, self._drift
-        if b.world > 1:
-            if isinstance(self.halo, NativeHaloExchanger):
-                self.halo.ctx.comm_max_f64_array(self._drift)
-            else:
-                dist.all_reduce(self._drift, op=dist.ReduceOp.MAX, group=self.halo.group)
-
-    def drifters_read(self):
-        """{"x", "y": float64 [n] in metres of the global domain, "status": int64 [n]} -- the whole list, identical on every rank (one
-        download; waits for the last step)"""
-        if self._drift is None:
-            raise ValueError("drifters_read() needs a core constructed with drifters=")
-        import numpy as np
-
-        d = self._drift.detach().cpu().numpy()
-        return {"x": d[0].copy(), "y": d[1].copy(), "status": d[2].astype(np.int64)}
-
-    def _check_history(self, history, rheology, ops):
-        """the entries of history= as a tuple, or None; ValueError for a list this core cannot sample.  Sets self._hist_pairs: None for a
-        list of bare names -- sampled by ops.history_accumulate, as ever --, else the (field, stat) of every entry"""
-        self._hist_pairs = None
-        if history is None:
-            return None
-        from nextsimdg_amd import abi
-
-        if isinstance(history, str):
-            history = (history,)
-        history = tuple(history)
-        if not history:
-            raise ValueError("history= needs at least one field (None turns it off)")
-        pairs = [tuple(e.split(":", 1)) if ":" in e else (e, "mean") for e in history]
-        names = [n for n, _ in pairs]
-        unknown = [n for n in names if n not in abi.HISTORY_FIELDS]
-        if unknown:
-            raise ValueError("unknown history field %s (known: %s)" % (", ".join(repr(n) for n in unknown), " ".join(abi.HISTORY_FIELDS)))
-        unknown = [e for e, (_, st) in zip(history, pairs) if st not in abi.HISTORY_STATS]
-        if unknown:
-            raise ValueError("unknown history statistic in %s (known: %s)" % (", ".join(repr(e) for e in unknown), " ".join(abi.HISTORY_STATS)))
-        twice = sorted({e for e, p in zip(history, pairs) if pairs.count(p) > 1})
-        if twice:
-            raise ValueError("history field %s is listed twice" % ", ".join(repr(n) for n in twice))
-        if "damage" in names and rheology != "bbm":
-            raise ValueError("the history field 'damage' needs rheology='bbm': the mEVP sub-cycle has no damage")
-        column = [n for n in names if n in self.HISTORY_COLUMN_FIELDS]
-        if column and not self.HAS_COLUMN_STATE:
-            raise ValueError("the history field %s is column state: it needs a CoupledCore" % ", ".join(repr(n) for n in column))
-        weighted = [e for e, (_, st) in zip(history, pairs) if st == "ice_mean"]
-        if weighted and "A" not in self.TRANSPORTED:
-            raise ValueError("the history entry %s weights by the concentration: this core has no A" % ", ".join(repr(e) for e in weighted))
-        call = "history_accumulate_stats" if any(":" in e for e in history) else "history_accumulate"
-        if not callable(getattr(ops, call, None)):
-            raise ValueError("history= needs an ops object with the history call of the C ABI (abi.Context); %s has no %s"
-                             % (type(ops).__name__, call))
-        if call == "history_accumulate_stats":
-            self._hist_pairs = pairs
-        return history
-
-    def _check_series(self, series, capacity, extent_conc, ops):
-        """the quantities of series= as a tuple, or None; ValueError for a list this core cannot total"""
-        if series is None:
-            return None
-        import math
-
-        from nextsimdg_amd import abi
-
-        if isinstance(series, str):
-            series = (series,)
-        series = tuple(series)
-        if not series:
-            raise ValueError("series= needs at least one quantity (None turns it off)")
-        unknown = [n for n in series if n not in abi.SERIES_QUANTITIES]
-        if unknown:
-            raise ValueError("unknown series quantity %s (known: %s)" % (", ".join(repr(n) for n in unknown), " ".join(abi.SERIES_QUANTITIES)))
-        twice = sorted({n for n in series if series.count(n) > 1})
-        if twice:
-            raise ValueError("series quantity %s is listed twice" % ", ".join(repr(n) for n in twice))
-        if "drift" in series and "area" not in series:
-            raise ValueError("the series quantity 'drift' is the ice-weighted mean speed: it needs 'area', the sum of the weights, in the list")
-        if "snow_volume" in series and not self.HAS_COLUMN_STATE:
-            raise ValueError("the series quantity 'snow_volume' is column state: it needs a CoupledCore")
-        if int(capacity) < 1:
-            raise ValueError("series_capacity must be at least 1, got %r" % (capacity,))
-        if not math.isfinite(extent_conc):
-            raise ValueError("extent_conc must be finite, got %r" % (extent_conc,))
-        if not callable(getattr(ops, "history_row_totals", None)):
-            raise ValueError("series= needs an ops object with the row totals of the C ABI (abi.Context); %s has no history_row_totals"
-                             % type(ops).__name__)
-        return series
+    def _transported(self):
+        """(names, bounds) of every advected field, stated once: the class's own, the subclass's additions, the damage of the brittle
+        rheology -- and the one rule on their number"""
+        more, more_bounds = self._more_transported()
+        names, bounds = tuple(self.TRANSPORTED) + tuple(more), tuple(self.BOUNDS) + tuple(more_bounds)
+        if self.rheology == "bbm":
+            if len(names) + 1 > 4:  # NSDG_RB_MAX_FIELDS
+                raise ValueError("rheology='bbm' with advect_column_state=True would advect %d fields (%s and D); a transport step carries at most 4"
+                                 % (len(names) + 1, ", ".join(names)))
+            names, bounds = names + ("D",), bounds + (self.DAMAGE_BOUNDS,)
+        return names, bounds
 
     def _history_sources(self):
         """the current ping-pong side of everything a sample reads"""
@@ -561,128 +426,23 @@ class DynamicsCore:
             src["D"] = self.D
         return src
 
-    def _history_sample(self):
-        """one sample of the owned rows at the end of a model step: one launch, after the step's last phase mark and outside every
-        captured graph; the first sample of a window stores, the others add"""
-        if self.series is not None:
-            self._series_sample()
-        if self.history is None:
-            return
-        b = self.blk
-        if self._hist_pairs is None:
-            self.ops.history_accumulate(b.j0, b.j1, self.history, self._history_sources(), self._hist_count == 0, b.j0, self._hist_acc)
-        else:
-            self.ops.history_accumulate_stats(b.j0, b.j1, self._hist_pairs, self._history_sources(), self._hist_count == 0, b.j0, self._hist_acc,
-                                              getattr(self, "_hist_wacc", None))
-        self._hist_count += 1
-
-    def _series_room(self):
-        """a model step begins: ValueError if its row totals would find no free slot.  The host counts the slots; nothing is synchronised"""
-        if self.series is not None and not self._in_advance and self._series_count >= self.series_capacity:
-            raise ValueError("the series buffer is full (series_capacity = %d samples): call series_read() before the next step"
-                             % self.series_capacity)
-
-    def _series_sample(self):
-        """the row totals of the owned rows at the end of a model step: one launch into the next free slot"""
-        b = self.blk
-        self.ops.history_row_totals(b.j0, b.j1, self.series, self._history_sources(), self.extent_conc, b.j0, self._series_buf[self._series_count])
-        self._series_count += 1
-
     def history_read(self, reset=True):
-        """{"rows": (r0, r1), "count": n, name: float64 [rows, nx] = the mean of the n samples since the last reset} for the rows this rank
-        owns (one download; waits for the last sample).  reset: the next sample opens a new window.  merge_history() joins the ranks"""
-        if self.history is None:
+        """outputs.History.read: the means (and statistics) of the window since the last reset, for the rows this rank owns"""
+        if self._history is None:
             raise ValueError("history_read() needs a core constructed with history=")
-        if self._hist_count == 0:
-            raise ValueError("history_read(): no sample since the last reset")
-        b, n = self.blk, self._hist_count
-        acc = self._hist_acc.detach().cpu().numpy()
-        out = {"rows": (b.r0, b.r1), "count": n}
-        if self._hist_pairs is None:
-            for k, name in enumerate(self.history):
-                out[name] = acc[k] / n
-        else:
-            import numpy as np
-
-            wacc = self._hist_wacc.detach().cpu().numpy() if hasattr(self, "_hist_wacc") else None
-            for k, (entry, (_, stat)) in enumerate(zip(self.history, self._hist_pairs)):
-                if stat == "mean":
-                    out[entry] = acc[k] / n
-                elif stat == "ice_mean":  # NaN where the window saw no ice
-                    iced = wacc > 0
-                    out[entry] = np.where(iced, acc[k] / np.where(iced, wacc, 1.0), np.nan)
-                else:
-                    out[entry] = acc[k].copy()
-        if reset:
-            self._hist_count = 0
-        return out
+        return self._history.read(reset)
 
     def series_read(self, reset=True):
-        """{"rows": (r0, r1), "count": n, name: float64 [n, rows] = the row totals of the n steps since the last reset} for the rows this
-        rank owns, as the device left them (one download; waits for the last step).  reset: the next step writes slot 0 again.
-        merge_series() makes the totals of the whole domain"""
-        if self.series is None:
+        """outputs.Series.read: the row totals of the steps since the last reset, for the rows this rank owns"""
+        if self._series is None:
             raise ValueError("series_read() needs a core constructed with series=")
-        b, n = self.blk, self._series_count
-        buf = self._series_buf[:n].detach().cpu().numpy()
-        out = {"rows": (b.r0, b.r1), "count": n}
-        for k, name in enumerate(self.series):
-            out[name] = buf[:, k].copy()
-        if reset:
-            self._series_count = 0
-        return out
+        return self._series.read(reset)
 
-    @staticmethod
-    def merge_series(parts, hx, hy):
-        """the ranks' series_read()s (any order) -> {"count": n, name: float64 [n]}: area and extent in m^2, volume and snow_volume in
-        m^3, drift = sum(w speed) / sum(w) in m/s (NaN where there is no ice), speed_max, hice_max.  The rows of a sample are added one
-        after the other in global row order, whatever the decomposition, so one block and N blocks give the same bits"""
-        import numpy as np
-
-        parts = sorted(parts, key=lambda p: p["rows"][0])
-        if any(p["count"] != parts[0]["count"] for p in parts):
-            raise ValueError("the ranks hold different numbers of samples: %s" % [p["count"] for p in parts])
-        if any(a["rows"][1] != c["rows"][0] for a, c in zip(parts, parts[1:])):
-            raise ValueError("the ranks' rows do not join: %s" % [p["rows"] for p in parts])
-        n = parts[0]["count"]
-        out = {"rows": (parts[0]["rows"][0], parts[-1]["rows"][1]), "count": n}
-        raw = {}
-        for k in parts[0]:
-            if k in ("rows", "count"):
-                continue
-            rows = np.concatenate([p[k] for p in parts], axis=1)
-            if k in ("speed_max", "hice_max"):  # np.maximum keeps a NaN, as the rows do
-                raw[k] = np.maximum.accumulate(rows, axis=1)[:, -1] if n else np.zeros(0)
-            else:  # sequential in row order: np.sum would add pairwise
-                raw[k] = np.add.accumulate(rows, axis=1)[:, -1] if n else np.zeros(0)
-        cell = hx * hy
-        for k, v in raw.items():
-            if k == "drift":
-                if "area" not in raw:
-                    raise ValueError("'drift' needs 'area' in the series")
-                iced = raw["area"] > 0
-                out[k] = np.where(iced, v / np.where(iced, raw["area"], 1.0), np.nan)
-            elif k in ("area", "extent", "volume", "snow_volume"):
-                out[k] = v * cell
-            else:
-                out[k] = v
-        return out
-
-    @staticmethod
-    def merge_history(parts):
-        """the ranks' history_read()s (any order) -> the record of the whole domain"""
-        import numpy as np
-
-        parts = sorted(parts, key=lambda p: p["rows"][0])
-        if any(p["count"] != parts[0]["count"] for p in parts):
-            raise ValueError("the ranks hold different numbers of samples: %s" % [p["count"] for p in parts])
-        if any(a["rows"][1] != c["rows"][0] for a, c in zip(parts, parts[1:])):
-            raise ValueError("the ranks' rows do not join: %s" % [p["rows"] for p in parts])
-        out = {"rows": (parts[0]["rows"][0], parts[-1]["rows"][1]), "count": parts[0]["count"]}
-        for k in parts[0]:
-            if k not in ("rows", "count"):
-                out[k] = np.concatenate([p[k] for p in parts], axis=0)
-        return out
+    def drifters_read(self):
+        """outputs.Drifters.read: positions and statuses of the whole list"""
+        if self._drifters is None:
+            raise ValueError("drifters_read() needs a core constructed with drifters=")
+        return self._drifters.read()
 
     def _init_native(self):
         b = self.blk
@@ -722,20 +482,17 @@ class DynamicsCore:
     def load_global(self, H, A, uo, vo, ua, va, u=None, v=None, D=None):
         """fill the local arrays (ghost rows included) from global numpy arrays; D: the damage of rheology="bbm" (None: left as it is)"""
         es, ns = self.blk.elem_slice(), self.blk.node_slice()
-        put = lambda dst, src: dst.copy_(torch.from_numpy(src).to(dst.device))
-        import numpy as np
-
-        put(self.H, np.ascontiguousarray(H[:, es]))
-        put(self.A, np.ascontiguousarray(A[:, es]))
+        _put(self.H, H[:, es])
+        _put(self.A, A[:, es])
         for dst, src in ((self.uo, uo), (self.vo, vo), (self.ua, ua), (self.va, va)):
-            put(dst, np.ascontiguousarray(src[ns]))
+            _put(dst, src[ns])
         if u is not None:
-            put(self.u, np.ascontiguousarray(u[ns]))
-            put(self.v, np.ascontiguousarray(v[ns]))
+            _put(self.u, u[ns])
+            _put(self.v, v[ns])
         if D is not None:
             if self.rheology != "bbm":
                 raise ValueError("a damage field needs rheology='bbm'")
-            put(self.D, np.ascontiguousarray(D[:, es]))
+            _put(self.D, D[:, es])
         self._clear_land()
 
     def _clear_land(self):
@@ -769,8 +526,6 @@ class DynamicsCore:
     def phase_times(self, reset=False):
         """{phase name: (device ms, closed intervals), "total": (ms, spans)} of the steps so far; waits for the last mark.  A span is one
         step() -- or one advance(), with all its sub-steps -- timed from its first mark to its end by its own pair of events"""
-        from nextsimdg_amd import abi
-
         if not self._phase_timing:
             raise ValueError("phase_times() needs a core constructed with phase_timing=True")
         phases, total = self.ops.phase_times(reset)
@@ -842,13 +597,14 @@ class DynamicsCore:
                             self._ghost_exchange_finish(pending)
                         self._swap()
                         it += v
-        split = self.overlap and b.world > 1 and (b.j1 - b.j0) >= 4 and not self.two_per_pass
+        deep = self.per_pass >= 2
+        split = self.overlap and b.world > 1 and (b.j1 - b.j0) >= 4 and not deep
         for _ in range(self.nsub - it):
             uvn = (self.ub, self.vb)
             calls = self._iterate_calls(split)
             if not split:
                 calls[0]()
-                if self.two_per_pass:  # keep the deeper ghost zones (stress as well as velocity) of the multi-iteration passes consistent
+                if deep:  # keep the deeper ghost zones (stress as well as velocity) of the multi-iteration passes consistent
                     self._ghost_exchange_finish(self._ghost_exchange_start())
                 else:
                     self.halo.nodal(uvn)
@@ -893,7 +649,7 @@ class DynamicsCore:
 
     def _ghost_exchange_finish(self, pending):
         if pending is not None:
-            self.halo.rows_exchange_finish(*pending)
+            self.halo.finish(pending)
 
     def _pass_calls(self, v, split, ext=0):
         """launches of one pass of v (2, 3 or 4) sub-iterations for the current ping-pong parity (bound once, cached).
@@ -916,8 +672,7 @@ class DynamicsCore:
                 rng.append((b.j0, b.j0 + b.depth_above + 1))
                 lo = b.j0 + b.depth_above + 1
         rng.append((lo, hi))
-        calls = [bind(j0, j1, self.s, self.sb, uv, uvn, self.packed, self.pg) for (j0, j1) in rng]
-        self._calls[key] = calls
+        calls = self._calls[key] = [bind(j0, j1, self.s, self.sb, uv, uvn, self.packed, self.pg) for (j0, j1) in rng]
         return calls
 
     def _iterate_calls(self, split):
@@ -980,33 +735,43 @@ class DynamicsCore:
         self.t1[:] = f
         self._set_fields(new)
 
+    # ---- the frame of a model step: begin, one or several sub-steps of the phases, end
     def step(self):
-        self._series_room()
+        self._begin_step()
+        self._substep()
+        self._end_step()
+
+    def _begin_step(self):
+        if self._series is not None:
+            self._series.room()
+
+    def _substep(self):
+        """the grid, the phases and the drifters at self.dt: step() runs it once, advance() n times"""
         self._set_grid()
+        self._phases()
+        if self._drifters is not None:
+            self._drifters.step(self.dt, self.u, self.v, self.A)
+
+    def _phases(self):
+        """what a step computes, in order; a subclass puts its own phases around these"""
         self.momentum()
         self.transport()
-        self._drifters_step()
-        if not self._in_advance:
-            self._mark(PHASE_END)
-            self._history_sample()
+
+    def _end_step(self):
+        """the end mark of the span and one sample per model step, after its last sub-step: the row totals, then the history"""
+        self._mark(PHASE_END)
+        for output in (self._series, self._history):
+            if output is not None:
+                output.sample(self._history_sources())
 
     # ---- sub-stepping (include/nsdg.h "sub-stepping"): a model step of model_dt run as n steps of model_dt / n
     def substep_count(self, model_dt, courant=None, max_substeps=16, params=None):
         """(n, amax, c): the number of sub-steps the state asks for (nsdg_substep_count) from the largest concentration of the owned rows
-        (ops.concentration_max), the same on every rank: the maximum over the ranks goes through nsdg_comm_max_f64 on a
-        NativeHaloExchanger's communicator and through torch.distributed (MAX on a CPU scalar) otherwise.  params: the MevpParams whose
+        (ops.concentration_max), the same on every rank: the maximum over the ranks is the exchanger's (nsdg_comm_max_f64 on a
+        NativeHaloExchanger's communicator, torch.distributed MAX on a CPU scalar otherwise).  params: the MevpParams whose
         pstar, compaction and rho_ice give the wave speed (default: nsdg_mevp_default_params)"""
-        from nextsimdg_amd import abi
-
-        b = self.blk
         self._set_grid()
-        amax = self.ops.concentration_max(self.H, self.A, b.j0, b.j1)
-        if isinstance(self.halo, NativeHaloExchanger):
-            amax = self.halo.ctx.comm_max_f64(amax)
-        elif b.world > 1:
-            t = torch.tensor([amax], dtype=torch.float64)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.halo.group)
-            amax = float(t.item())
+        amax = self.halo.max_scalar(self.ops.concentration_max(self.H, self.A, self.blk.j0, self.blk.j1))
         if params is None:
             params = abi.MevpParams()
             abi.load_library().nsdg_mevp_default_params(abi.C.byref(params))
@@ -1015,28 +780,24 @@ class DynamicsCore:
         return n, amax, c
 
     def advance(self, model_dt, substeps=1, courant=None, max_substeps=16, params=None):
-        """one model step of model_dt as n calls of step() with self.dt = model_dt / n (restored afterwards); substeps: an int >= 1, or
+        """one model step of model_dt as n sub-steps with self.dt = model_dt / n (restored afterwards); substeps: an int >= 1, or
         "auto" (n from the state at the start of the step, substep_count).  Returns n; substeps = 1 is step() at model_dt, bit for bit"""
-        self._series_room()
+        if substeps != "auto" and not (isinstance(substeps, int) and not isinstance(substeps, bool) and substeps >= 1):
+            raise ValueError("substeps must be an integer >= 1 or 'auto', got %r" % (substeps,))
+        self._begin_step()
         if substeps == "auto":
             self._mark(PHASE_REDUCTION)
-            n = self.substep_count(model_dt, courant, max_substeps, params)[0]
-        elif isinstance(substeps, int) and not isinstance(substeps, bool) and substeps >= 1:
-            n = substeps
-        else:
-            raise ValueError("substeps must be an integer >= 1 or 'auto', got %r" % (substeps,))
+            substeps = self.substep_count(model_dt, courant, max_substeps, params)[0]
         dt = self.dt
-        self.dt = model_dt / n
-        self._in_advance = True  # the span of the phase table is the model step: one end mark after the last sub-step
+        self.dt = model_dt / substeps
         try:
-            for _ in range(n):
-                self.step()
+            for _ in range(substeps):
+                self._substep()
         finally:
             self.dt = dt
-            self._in_advance = False
-            self._mark(PHASE_END)
-        self._history_sample()  # one sample per model step, after its last sub-step
-        return n
+            self._mark(PHASE_END)  # the span of the phase table is the model step, also one that failed
+        self._end_step()
+        return substeps
 
     def owned(self, f):
         """owned element rows of a DG array / owned node rows of a nodal array (for gathering)"""
@@ -1048,7 +809,6 @@ class DynamicsCore:
         top = 2 * b.j1 + (1 if b.above is None else 0)
         return f[2 * b.j0:top]
 
-
     # ---- checkpoint / resume (round 6).  The state a run carries from one step to the next: the DG2 fields H and A, the velocity and the
     # stress -- what the C++ host writes into its restart file (host/include/RectGrid.hpp: hice, cice, hice_dg, cice_dg, u, v, s11, s12,
     # s22), which the reference's restart files are the model for (core/src/DevGridIO.cpp:169-201: every prognostic field it has).
@@ -1059,47 +819,38 @@ class DynamicsCore:
         b = self.blk
         nx = b.nx
         out = {"rows": (b.r0, b.r1), "ny_global": b.ny_glob, "nx": nx}
-        for name, f in (("H", self.H), ("A", self.A), ("u", self.u), ("v", self.v)):
-            out[name] = self.owned(f).detach().cpu().numpy().copy()
+        for name in ("H", "A", "u", "v") + (("D",) if self.rheology == "bbm" else ()):
+            out[name] = self.owned(getattr(self, name)).detach().cpu().numpy().copy()
         for name, f in zip(("s11", "s12", "s22"), self.s):
             out[name] = self.ops.private_to_planes(f, nx)[:, b.j0:b.j1].detach().cpu().numpy().copy()
-        if self.rheology == "bbm":
-            out["D"] = self.owned(self.D).detach().cpu().numpy().copy()
-        if self._drift is not None:  # the whole list, not row-sliced: every rank holds the same
-            out["drifters"] = self._drift.detach().cpu().numpy().copy()
+        if self._drifters is not None:
+            out["drifters"] = self._drifters.state()
         return out
 
     def load_state_dict(self, state):
         """resume from a GLOBAL state (rows (0, ny_global): e.g. the ranks' state_dict()s concatenated): fills the local arrays, ghost rows
         included, and the current ping-pong buffers; forcing (load_global) and column fields are loaded as for a fresh run"""
-        import numpy as np
-
         b = self.blk
         if tuple(state["rows"]) != (0, b.ny_glob) or state["nx"] != b.nx:
             raise ValueError("load_state_dict needs the state of the whole domain (rows (0, %d)), got rows %s" % (b.ny_glob, (state["rows"],)))
         es, ns = b.elem_slice(), b.node_slice()
-        put = lambda dst, src: dst.copy_(torch.from_numpy(np.ascontiguousarray(src)).to(dst.device))
-        put(self.H, state["H"][:, es])
-        put(self.A, state["A"][:, es])
-        put(self.u, state["u"][ns])
-        put(self.v, state["v"][ns])
+        _put(self.H, state["H"][:, es])
+        _put(self.A, state["A"][:, es])
+        _put(self.u, state["u"][ns])
+        _put(self.v, state["v"][ns])
         for f, name in zip(self.s, ("s11", "s12", "s22")):
             f.copy_(self.ops.planes_to_private(torch.from_numpy(np.ascontiguousarray(state[name][:, es])).to(f.device)))
         if self.rheology == "bbm":
             if "D" not in state:
                 raise ValueError("a core with rheology='bbm' needs the damage D in the state")
-            put(self.D, state["D"][:, es])
-        if self._drift is not None:
-            if "drifters" not in state or tuple(state["drifters"].shape) != tuple(self._drift.shape):
-                raise ValueError("a core with drifters= needs the [3, %d] array 'drifters' in the state" % self._drift.shape[1])
-            put(self._drift, state["drifters"])
+            _put(self.D, state["D"][:, es])
+        if self._drifters is not None:
+            self._drifters.load_state(state)
         self._clear_land()
 
     @staticmethod
     def merge_states(states):
         """the ranks' state_dict()s (any order) -> the state of the whole domain"""
-        import numpy as np
-
         states = sorted(states, key=lambda s: s["rows"][0])
         out = {"rows": (states[0]["rows"][0], states[-1]["rows"][1]), "ny_global": states[0]["ny_global"], "nx": states[0]["nx"]}
         for k in ("H", "A", "S", "D", "s11", "s12", "s22"):
@@ -1125,8 +876,6 @@ class ForcingSeries:
     OCEAN = ("ocean_u", "ocean_v")
 
     def __init__(self, times, fields):
-        import numpy as np
-
         t = np.array(times, dtype=np.float64)
         if t.ndim != 1 or t.size < 1:
             raise ValueError("times must be a 1-d array of at least one record time")
@@ -1158,8 +907,6 @@ class ForcingSeries:
     def bracket(self, t):
         """(k0, k1, w): the records around model time t and the weight of k1 -- k0 is the last record with times[k0] <= t, k1 = k0 + 1,
         w = (t - times[k0]) / (times[k1] - times[k0]); at the last record itself k1 = k0 and w = 0"""
-        import numpy as np
-
         t0, t1 = float(self.times[0]), float(self.times[-1])
         if not (t0 <= t <= t1):
             raise ValueError("model time %r s is outside the forcing records [%r, %r] s" % (t, t0, t1))
@@ -1199,10 +946,7 @@ class CoupledCore(DynamicsCore):
         and the wind (ua, va) and the ocean current (uo, vo) where the series holds them; the column wind speed as above.
         advect_column_state: the snow and the surface temperature ride on the ice (class docstring); min_conc / min_thick: the ice test of
         nsdg_tracer_recover (the defaults of the ice-free-node rule, nsdg_mevp_default_params; 0 and 0 with closure = False, as the C++ host)"""
-        self.advect_column_state = bool(advect_column_state)
-        if self.advect_column_state:  # before the base class allocates the advected fields and builds the transport plan
-            self.TRANSPORTED = DynamicsCore.TRANSPORTED + ("S", "Q")
-            self.BOUNDS = DynamicsCore.BOUNDS + self.COLUMN_STATE_BOUNDS
+        self.advect_column_state = bool(advect_column_state)  # (read by _more_transported() while the base class constructs)
         super().__init__(ops, blk, hx, hy, dt, nsub, device, **kw)
         closure = kw.get("closure", True)
         self.min_conc, self.min_thick = (min_conc, min_thick) if closure else (0.0, 0.0)
@@ -1226,6 +970,9 @@ class CoupledCore(DynamicsCore):
         elif forcing not in (None, "dummy", "winter"):
             raise ValueError("forcing must be None, 'dummy', 'winter' or a ForcingSeries, got %r" % (forcing,))
 
+    def _more_transported(self):
+        return (("S", "Q"), self.COLUMN_STATE_BOUNDS) if self.advect_column_state else ((), ())
+
     def _history_sources(self):
         """and the column state: the snow plane the column step actually uses (plane 0 of S under advect_column_state) and tice0"""
         src = super()._history_sources()
@@ -1234,11 +981,9 @@ class CoupledCore(DynamicsCore):
 
     def load_column(self, fields):
         """fields: dict name -> global [ny, nx] numpy array for hsnow, tice0 and the 10 forcing fields"""
-        import numpy as np
-
         es = self.blk.elem_slice()
         for k, dst in self.col.items():
-            dst.copy_(torch.from_numpy(np.ascontiguousarray(fields[k][es])).to(dst.device))
+            _put(dst, fields[k][es])
 
     def transport(self):
         if not self.advect_column_state:
@@ -1260,13 +1005,11 @@ class CoupledCore(DynamicsCore):
 
     def load_state_dict(self, state):
         """DynamicsCore.load_state_dict and, with advect_column_state, the snow S (required: plane 0 is the column's hsnow)"""
-        import numpy as np
-
         if self.advect_column_state and "S" not in state:
             raise ValueError("a CoupledCore with advect_column_state needs the snow S in the state")
         super().load_state_dict(state)
         if self.advect_column_state:
-            self.S.copy_(torch.from_numpy(np.ascontiguousarray(state["S"][:, self.blk.elem_slice()])).to(self.S.device))
+            _put(self.S, state["S"][:, self.blk.elem_slice()])
             self._clear_land()
 
     def thermodynamics(self):
@@ -1301,15 +1044,8 @@ class CoupledCore(DynamicsCore):
             self.ops.column_forcing(self.forcing, self.time, self.col)
             self.ops.column_wind(self.ua, self.va, self.col["wind"])
 
-    def step(self):
-        self._series_room()
-        self._set_grid()
+    def _phases(self):
         self.external_forcing()
         self.thermodynamics()
-        self.momentum()
-        self.transport()
-        self._drifters_step()
+        super()._phases()
         self.time += self.dt
-        if not self._in_advance:
-            self._mark(PHASE_END)
-            self._history_sample()

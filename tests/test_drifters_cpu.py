@@ -282,7 +282,7 @@ def test_without_drifters_nothing_is_called_or_allocated(one_block):
 
     bt = synthetic.BoxTest(NX, NY)
     core = rowblock.DynamicsCore(OracleOps(alpha=200.0, beta=200.0), rowblock.RowBlock(NX, NY), bt.hx, bt.hy, 120.0, NSUB, torch.device("cpu"))
-    assert core._drift is None and core._drift_b is None and "drifters" not in core.state_dict()  # OracleOps has no drifters_advance to call
+    assert core._drifters is None and "drifters" not in core.state_dict()  # OracleOps has no drifters_advance to call
     with pytest.raises(ValueError, match="drifters="):
         core.drifters_read()
     plain = run_core(0, 1, drifters=None)  # the fields do not know about the drifters

@@ -330,7 +330,7 @@ def test_graphs_equal_no_graphs_and_passes_of_four_equal_single_sub_iterations(g
 
 def test_advance_samples_once_and_windows_reset(ctx):
     core, _ = make_core(ctx, ("hice", "speed", "sigma_n"))
-    core._hist_acc.fill_(float("nan"))
+    core._history.acc.fill_(float("nan"))
     assert core.advance(120.0, substeps=2) == 2
     rec = core.history_read()
     assert rec["count"] == 1 and np.array_equal(rec["hice"], core.H[0].cpu().numpy())

@@ -455,7 +455,7 @@ def test_graphs_equal_no_graphs_under_the_native_plan(gpu, one_block):
 
 def test_windows_reset_and_a_full_buffer_is_refused(ctx):
     core, _ = G.make_core(ctx, ("hice:max", "speed:ice_mean"), series=("volume",), series_capacity=2)
-    core._hist_acc.fill_(NAN), core._hist_wacc.fill_(NAN), core._series_buf.fill_(NAN)
+    core._history.acc.fill_(NAN), core._history.wacc.fill_(NAN), core._series.buf.fill_(NAN)
     assert core.advance(120.0, substeps=2) == 2
     rec = core.history_read()
     assert rec["count"] == 1 and np.array_equal(rec["hice:max"], core.H[0].cpu().numpy())  # the first sample stores: no NaN survives

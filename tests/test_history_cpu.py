@@ -208,7 +208,7 @@ def test_one_block_equals_gloo_worlds_bitwise(single, world, coupled, tmp_path):
 
 def test_history_none_leaves_the_run_unchanged(single):
     core, _ = make_core(0, 1, None)
-    assert core.history is None and not hasattr(core, "_hist_acc")
+    assert core.history is None and core._history is None
     for _ in range(NSTEPS):
         core.step()
     a, b = core.state_dict(), single[False][0].state_dict()
@@ -223,7 +223,7 @@ def test_windows_reset_and_advance_samples_once():
     core, _ = make_core(0, 1, ("hice", "speed"))
     with pytest.raises(ValueError, match="no sample"):
         core.history_read()
-    core._hist_acc.fill_(float("nan"))  # the first sample of a window stores: what the accumulator held is dropped
+    core._history.acc.fill_(float("nan"))  # the first sample of a window stores: what the accumulator held is dropped
     core.step()
     first = core.history_read()
     assert first["count"] == 1 and np.array_equal(first["hice"], core.H[0].numpy())

@@ -170,8 +170,8 @@ def test_bare_names_take_the_plain_call_and_need_nothing_new():
     ops = Recording(alpha=200.0, beta=200.0)
     core, _ = make_core(("hice", "speed"), ops=ops)
     core.step()
-    assert ops.calls == ["history_accumulate"] and core._hist_pairs is None and not hasattr(core, "_hist_wacc") and core.series is None
-    assert not hasattr(core, "_series_buf")
+    assert ops.calls == ["history_accumulate"] and core._history.with_stats is False and core._history.wacc is None and core.series is None
+    assert core._series is None
     assert sorted(core.history_read()) == ["count", "hice", "rows", "speed"]
     core, _ = make_core(("hice",), ops=R.HistoryOps(alpha=200.0, beta=200.0))  # a test double without the new methods keeps working
     core.step()

@@ -25,6 +25,10 @@
 //     updates that only read those registers (NSDG_P2P_EARLY bit 2, mevp_p2p.h; -1.7 ... -1.9 % per step).  The same move for the
 //     hand-over between the stages (bit 1: slot wait and the 12 LDS writes right after the relaxation) is built and off: it asks for
 //     the slot before the consumer has freed it and costs 6.9 % (profiles/r15_early_stress_writes.md).
+//   * the loader (stage 0) never polls, so it paces every row.  Where it requests its loads and where they land is stated by hand
+//     (NSDG_P2P_LAND, mevp_p2p.h; the table above p2p_row): the coefficient pair goes to its ring behind the projected stress, the
+//     next row's stress is requested at the very end of the row into the registers the row's own stress has just left (-3.7 ...
+//     -3.8 % per step, 68 fewer registers per wave; profiles/r16_loader_landing.md).
 //
 // Memory ordering of the hand-over, the bounded wait and how a wait that gave up becomes an error status: mevp_p2p.h.  Every wait is
 // on an event that is strictly earlier in the dependency graph of the march (row r of stage k + 1 waits for row r + 1 of stage k; row r
@@ -40,9 +44,13 @@ namespace nsdg_mevp_detail {
 // previous stage's hand-over, 1 a free hand-over slot, 2 a free ring slot -- and the rows the stage worked on in [3]
 __device__ unsigned long long nsdg_p2p_spin_dev[4][4];
 __device__ unsigned long long nsdg_p2p_phase_dev[4][8]; // shader cycles per stage and phase of a row (s_memtime, fenced)
-#define NSDG_SPIN_ARG , unsigned (&spins)[3], unsigned (&phase)[8], unsigned& stamp_last
-#define NSDG_SPIN_PASS , spins, phase, stamp_last
+__device__ unsigned long long nsdg_p2p_land_dev[4]; // shader cycles the loader spent at each of its landing points (s_memtime around the s_waitcnt, no fence)
+#define NSDG_SPIN_ARG , unsigned (&spins)[3], unsigned (&phase)[8], unsigned& stamp_last, unsigned (&landc)[4]
+#define NSDG_SPIN_PASS , spins, phase, stamp_last, landc
 #define NSDG_SPIN_COUNT(k, n) spins[k] += (n)
+#if NSDG_P2P_SPINSTAT + 0 == 2 // -DNSDG_P2P_SPINSTAT=2: the polls and the landing points only -- no phase stamps, whose fences change the schedule
+#define NSDG_PHASE(k)
+#else
 #define NSDG_PHASE(k)                                                   \
     do {                                                                \
         __builtin_amdgcn_sched_barrier(0);                              \
@@ -51,11 +59,27 @@ __device__ unsigned long long nsdg_p2p_phase_dev[4][8]; // shader cycles per sta
         stamp_last = now_;                                              \
         __builtin_amdgcn_sched_barrier(0);                              \
     } while (0)
+#endif
+// a landing point between two s_memtime: what is added to landc[k] is the stall at its s_waitcnt plus the two stamps' own ~12 cycles
+#define NSDG_LAND_TIMED(k, ...)                                                     \
+    do {                                                                            \
+        const unsigned land0_ = (unsigned)__builtin_amdgcn_s_memtime();             \
+        __VA_ARGS__;                                                                \
+        landc[k] += (unsigned)__builtin_amdgcn_s_memtime() - land0_;                \
+    } while (0)
 #else
 #define NSDG_PHASE(k)
 #define NSDG_SPIN_ARG
 #define NSDG_SPIN_PASS
 #define NSDG_SPIN_COUNT(k, n) (void)(n) /* the wait itself is the argument: it must stay */
+#define NSDG_LAND_TIMED(k, ...) __VA_ARGS__
+#endif
+// the stamped build with the switch at 0 has no landing point of its own to time: it waits, timed, where and for as many loads as the
+// compiler does in the product (the three s_waitcnt vmcnt of the loader's loop, table above p2p_row)
+#if defined(NSDG_P2P_SPINSTAT) && NSDG_P2P_LAND == 0
+#define NSDG_LAND_PROBE(k, n) NSDG_LAND_TIMED(k, p2p_wait_vm<n>())
+#else
+#define NSDG_LAND_PROBE(k, n)
 #endif
 
 constexpr int P4_OWNED = 57, P4_LEFT = 4; // lanes 4 .. 60 own a column (four sub-iterations reach four columns / rows)
@@ -140,6 +164,43 @@ __device__ __forceinline__ void store_stress(const StressPtrs& S, long ts, const
     tile_store8_nt<(NSDG_P2P_NT & 2) != 0>(S.o12, ts, s12);
     tile_store8_nt<(NSDG_P2P_NT & 2) != 0>(S.o22, ts, s22);
 }
+// The loader's loads and where they land (NSDG_P2P_LAND, mevp_p2p.h).  During row r the loader requests the inputs of row r + 1 in four
+// groups; vmcnt counts a wave's loads in the order of their issue, so a landing point is "at most N loads younger than the group":
+//
+//   group  loads                                   issued in row r                                      consumed in row r + 1
+//   A   5  ice strength P (4 x 16 B, 1 x 8 B)      ring block, after the ring write of P(r)             projected stress
+//   B   8  u, v, two node rows (4 x (16 + 8 B))    ring block, after A                                  projected stress
+//   C  12  stress (3 x 4 x 16 B)                   after the relaxation | bit 2: behind the hand-over   relaxation
+//   D  12  nodal coefficients (4 x 3 x 16 B)       request_c, after the node updates                    ring write of the pair, node updates
+//
+// Bit 2 requests C at the very end of the row, behind the hand-over of the row's own stress: the working registers are dead there, the
+// request can take them and the compiler has no copy to make (requested anywhere earlier the new stress needs a second register set,
+// and the copies between the two sets at the end of the row are what the compiler's waits stand in front of).  The lead of C shrinks
+// from a row to the top of the next row plus its projected stress.
+//
+//   issue order over the rows:   ... A B C D | A' B' C' D' ...        bit 2:   ... A B D C | A' B' D' C' ...
+//
+//   landing point                                     lands    younger loads in flight                        N
+//   L1  ring write of the pair (bit 1), behind the    D        A' B'                                         13
+//         projected stress                                     bit 2: C A' B'                                25
+//   the stress copy (bit 2: in front of the relaxation) and every other use: the compiler's own waits, which with bit 2 are 28 at the
+//   top of the row (A and 4 of B; the rest of B lands in the ring block) and 24 ... 13 in front of the relaxation (C, behind A' B')
+//
+// With the switch at 0 the compiler waits three times per row (adaptive form: vmcnt(12) at the top -- A, B and C; vmcnt(5) in the ring
+// block behind the issue of A' -- C, D; vmcnt(4) before request_c -- A', B' and 8 of the 12 loads of C', whose destination it copies
+// out of the accumulation registers there); the stamped build times those three (NSDG_LAND_PROBE).  With a bit set the prologue of the
+// march lets all its loads land before the first row, so the loop's waits are those of its own requests; in the last row of a stage
+// nrow == row and the same loads are issued once more.
+constexpr int P4_NA = 5, P4_NB = 8, P4_NC = 12;
+constexpr bool P4_LAND_COEFF = (NSDG_P2P_LAND & 1) != 0, P4_LAND_ORDER = (NSDG_P2P_LAND & 2) != 0;
+constexpr int P4_L1 = P4_LAND_ORDER ? P4_NC + P4_NA + P4_NB : P4_NA + P4_NB;
+// the loader's stress request (group C)
+__device__ __forceinline__ void request_stress(const StressPtrs& S, long ts, Fetch& f)
+{
+    tile_load8_nt<(NSDG_P2P_NT & 1) != 0>(S.i11, ts, f.s11);
+    tile_load8_nt<(NSDG_P2P_NT & 1) != 0>(S.i12, ts, f.s12);
+    tile_load8_nt<(NSDG_P2P_NT & 1) != 0>(S.i22, ts, f.s22);
+}
 // One row of one stage.  FIRST: the loader (stage 0): inputs from memory, ice strength into the ring.
 template <bool FIRST, bool AD, bool LAND>
 __device__ __forceinline__ void p2p_row(const MarchConst& M, const Stage& G, int row, Fetch& f, TopCarry& carry, double* __restrict__ lds,
@@ -164,6 +225,7 @@ __device__ __forceinline__ void p2p_row(const MarchConst& M, const Stage& G, int
     double s11[8], s12[8], s22[8], uu[4], vv[4], ul[9], vl[9], un[4], vn[4];
     // ------------------------------------------------------------------------------------------ inputs of the row
     if (FIRST) {
+        NSDG_LAND_PROBE(0, 12);
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             ul[a] = f.ub[a], ul[3 + a] = f.um[a], ul[6 + a] = f.ut[a];
@@ -206,8 +268,16 @@ __device__ __forceinline__ void p2p_row(const MarchConst& M, const Stage& G, int
         // register set takes the next row's; u, v of the next row
         NSDG_SPIN_COUNT(2, flag_wait(flags, 3 + G.nst - 2, min(row - P4_PRING, G.last_final), rep)); // read[] of the LAST link: the last stage has passed that row
         ring_write_P<P4_PRING>(ring, row, M.lane, f.P);
-        ring_write_c(cring, row, M.lane, f.c); // this row's coefficients were requested a step ago; the stages 1-3 take the pair from here
+#if defined(NSDG_P2P_SPINSTAT) && NSDG_P2P_LAND == 0
+        // the product's compiled order: the requests of P issue above the wait for the coefficients
         tile_load9_nt<(NSDG_P2P_NT & 4) != 0>(pg, tile_off(ix, nrow, M.ntx, 9), ix & 63, f.P);
+        NSDG_LAND_PROBE(1, P4_NA);
+        ring_write_c(cring, row, M.lane, f.c);
+#else
+        if constexpr (!P4_LAND_COEFF)
+            ring_write_c(cring, row, M.lane, f.c); // this row's coefficients were requested a step ago; the stages 1-3 take the pair from here
+        tile_load9_nt<(NSDG_P2P_NT & 4) != 0>(pg, tile_off(ix, nrow, M.ntx, 9), ix & 63, f.P);
+#endif
         if (nrow > row) { // wave-uniform: the top node row of this element row is the bottom one of the next
 #pragma unroll
             for (int a = 0; a < 3; ++a)
@@ -217,9 +287,11 @@ __device__ __forceinline__ void p2p_row(const MarchConst& M, const Stage& G, int
         fetch_nodes(v_old, nVn + nn, f.vm);
         fetch_nodes(u_old, nVn + 2 * nn, f.ut);
         fetch_nodes(v_old, nVn + 2 * nn, f.vt);
+        if constexpr (!P4_LAND_ORDER) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i)
-            s11[i] = f.s11[i], s12[i] = f.s12[i], s22[i] = f.s22[i];
+            for (int i = 0; i < 8; ++i)
+                s11[i] = f.s11[i], s12[i] = f.s12[i], s22[i] = f.s22[i];
+        }
     } else {
         ring_read_P<P4_PRING>(ring, nrow, M.lane, f.P); // written by the loader before it handed row nrow over: done[stage - 1] >= row + 1 implies done[0] >= nrow
         const double* in = lds + ((stage - 1) * P4_HSLOTS + (row & 1)) * P4_SLOT + 2 * M.lane;
@@ -232,9 +304,21 @@ __device__ __forceinline__ void p2p_row(const MarchConst& M, const Stage& G, int
         flag_publish(flags, 3 + stage - 1, row);
     }
     NSDG_PHASE(2); // loader: ring wait, ring writes, requests of P, u, v; stages: ring read, stress read, read[] published
+    if constexpr (FIRST && P4_LAND_COEFF) {
+        // L1: the projected stress is complete (its registers are named, so the arithmetic stays above), then this row's coefficients
+        // land and the pair goes to the ring -- its slot is free since the ring wait above
+        p2p_name(r11), p2p_name(r12), p2p_name(r22);
+        NSDG_LAND_TIMED(1, p2p_land<P4_L1>(f.c));
+        ring_write_c(cring, row, M.lane, f.c);
+    }
+    if constexpr (FIRST && P4_LAND_ORDER) { // the stress copy, in front of the relaxation that consumes it: its request is the youngest but A', B'
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            s11[i] = f.s11[i], s12[i] = f.s12[i], s22[i] = f.s22[i];
+    }
     stress_relax(ialpha, r11, r12, r22, s11, s12, s22); // AD: alpha_e of this element; else ialpha = M.ialpha
     __builtin_amdgcn_sched_barrier(0);
-    if (FIRST) { // stress of the next row
+    if (FIRST && !P4_LAND_ORDER) { // stress of the next row
         const long ts = tile_off(ix, nrow, M.ntx, 8);
         tile_load8_nt<(NSDG_P2P_NT & 1) != 0>(S.i11, ts, f.s11);
         tile_load8_nt<(NSDG_P2P_NT & 1) != 0>(S.i12, ts, f.s12);
@@ -267,6 +351,9 @@ __device__ __forceinline__ void p2p_row(const MarchConst& M, const Stage& G, int
     }
     __builtin_amdgcn_sched_barrier(0);
     NSDG_PHASE(4); // contributions, node updates (the wait for the nodal coefficients is here)
+    if (FIRST) {
+        NSDG_LAND_PROBE(3, 4);
+    }
     request_c(nrow); // nodal coefficients of the next row
     NSDG_PHASE(5); // request of the coefficients
     // ------------------------------------------------------------------------------------------ outputs
@@ -282,6 +369,8 @@ __device__ __forceinline__ void p2p_row(const MarchConst& M, const Stage& G, int
             lds_pair(out, 14 + k, vn[2 * k], vn[2 * k + 1]);
         }
         flag_publish(flags, stage, row); // its lgkmcnt(0) covers the early writes of the row too
+        if constexpr (FIRST && P4_LAND_ORDER) // the stress of the next row: this row's has left, the request may take its registers
+            request_stress(S, tile_off(ix, nrow, M.ntx, 8), f);
     } else if (M.own && row >= M.y0) { // the last stage runs on rows y0-1 .. y1-1
         const long ts = tile_off(ix, row, M.ntx, 8);
         const long nV = (long)(2 * row) * nn + 2 * ix;
@@ -346,6 +435,7 @@ __global__ __launch_bounds__(256) void mevp_fused4_kernel(NodalConsts K, AdaptCo
 #ifdef NSDG_P2P_SPINSTAT
     unsigned spins[3] = { 0, 0, 0 }, phase[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     unsigned stamp_last = (unsigned)__builtin_amdgcn_s_memtime();
+    unsigned landc[4] = { 0, 0, 0, 0 };
 #endif
     if (G.s == 0) {
         const int row = G.first;
@@ -361,6 +451,14 @@ __global__ __launch_bounds__(256) void mevp_fused4_kernel(NodalConsts K, AdaptCo
         tile_load8_nt<(NSDG_P2P_NT & 1) != 0>(S.i22, ts, f.s22);
         tile_load9_nt<(NSDG_P2P_NT & 4) != 0>(pg, tile_off(M.ix, row, M.ntx, 9), M.ix & 63, f.P);
         load_owned_nodal(M, row, f.c, packed);
+        if constexpr (NSDG_P2P_LAND != 0) {
+            // everything the prologue requested lands here, once per strip: a load still in flight at the head of the loop is one
+            // the compiler has to assume in flight in every row, and it waits for it wherever a later row reuses the register
+            p2p_land<0>(f.P, f.ub, f.vb, f.um, f.vm, f.ut, f.vt, f.s11, f.s12, f.s22, f.c);
+#pragma unroll
+            for (int n = 0; n < 4; ++n)
+                p2p_name(f.c[n][0], f.c[n][1], f.c[n][2], f.c[n][3]);
+        }
         for (int row = G.first; row <= G.last; ++row)
             p2p_row<true, AD, LAND>(M, G, row, f, carry, lds, flags, rep, S, u_old, v_old, packed, pg, u_new, v_new NSDG_SPIN_PASS);
     } else {
@@ -374,6 +472,9 @@ __global__ __launch_bounds__(256) void mevp_fused4_kernel(NodalConsts K, AdaptCo
         atomicAdd(&nsdg_p2p_spin_dev[G.s][3], (unsigned long long)(G.last - G.first + 1));
         for (int k = 0; k < 8; ++k)
             atomicAdd(&nsdg_p2p_phase_dev[G.s][k], (unsigned long long)phase[k]);
+        if (G.s == 0)
+            for (int k = 0; k < 4; ++k)
+                atomicAdd(&nsdg_p2p_land_dev[k], (unsigned long long)landc[k]);
     }
 #endif
 }
@@ -393,6 +494,14 @@ extern "C" int nsdg_debug_p2p_spinstat(unsigned long long* out48) // [16] polls,
         e = hipMemcpyToSymbol(HIP_SYMBOL(nsdg_p2p_spin_dev), zero, 16 * sizeof(unsigned long long));
     if (e == hipSuccess)
         e = hipMemcpyToSymbol(HIP_SYMBOL(nsdg_p2p_phase_dev), zero, 32 * sizeof(unsigned long long));
+    return (int)e;
+}
+extern "C" int nsdg_debug_p2p_landstat(unsigned long long* out4) // cycles at the loader's landing points: [1] L1; switch at 0: [0] the top of the row, [1] the ring write of the pair, [3] before request_c
+{
+    static const unsigned long long zero[4] = { 0 };
+    hipError_t e = hipMemcpyFromSymbol(out4, HIP_SYMBOL(nsdg_p2p_land_dev), 4 * sizeof(unsigned long long));
+    if (e == hipSuccess)
+        e = hipMemcpyToSymbol(HIP_SYMBOL(nsdg_p2p_land_dev), zero, 4 * sizeof(unsigned long long));
     return (int)e;
 }
 #endif

@@ -85,6 +85,50 @@ __device__ __forceinline__ void lds_pair(double* slot, int k, double a, double b
 #ifndef NSDG_P2P_EARLY
 #define NSDG_P2P_EARLY 2
 #endif
+// Where the loader's loads land (NSDG_P2P_LAND bits; the row's issue order and the counts: mevp_fused4.hip, above p2p_row).  The loader
+// (stage 0) never polls: the stages 1-3 wait for it, so a cycle it stalls at an s_waitcnt is a cycle of every wave.  With the switch at
+// 0 the compiler alone decides where a load has to have landed; a bit states one placement by hand:
+//   1 coefficients:  the ring write of the coefficient pair, and with it the landing point of the row's coefficients, moves behind
+//                    the projected-stress arithmetic (the loader itself needs them only at the node updates);
+//   2 request order: the stress of the next row is requested at the very end of the row, behind the hand-over of the row's own
+//                    stress, not after the relaxation: the request takes the working registers, 48 registers are free under the
+//                    node updates and no copy between two register sets is left; it lands in front of the relaxation.
+// Either bit also lets everything the prologue requested land before the first row.  No formula, wait between waves, counter, slot or
+// LDS layout changes.  With the switch at 0 the loader stalls ~45 + ~170 + ~160 shader cycles of its ~6600-cycle row at the compiler's
+// three waits; with 3 its one stated landing point costs nothing beyond the stamps.  Measured against the parent on one box, five
+// alternations in both orders (profiles/r16_loader_landing.md): 3 28.26-28.38 -> 27.19-27.36 ms per step at 2048^2 (-3.7 ... -3.8 %,
+// the parent's own spread 0.08-0.09 ms), 7.64-7.91 -> 7.31-7.56 at 1024^2; 1 alone -2.1 %, 2 alone -2.6 % at 2048^2.  Registers per
+// wave 364 / 346 -> 296 / 292 (adaptive / uniform).  3 is the default.
+#ifndef NSDG_P2P_LAND
+#define NSDG_P2P_LAND 3
+#endif
+// A landing point: at most N vector-memory loads of this wave are still in flight behind it, and the registers named after it are
+// opaque to the compiler there ("+v": consumed here), so their data is not used earlier.  The loads are ordinary ones the compiler
+// counts itself: its own s_waitcnt in front of the naming statement can only ask for the same or less, never for data that has not
+// landed.
+template <int N>
+__device__ __forceinline__ void p2p_wait_vm()
+{
+    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+__device__ __forceinline__ void p2p_name(double& a, double& b, double& c, double& d) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)); }
+__device__ __forceinline__ void p2p_name(double& a, double& b, double& c) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c)); }
+__device__ __forceinline__ void p2p_name(double& a) { asm volatile("" : "+v"(a)); }
+__device__ __forceinline__ void p2p_name(double (&x)[3]) { p2p_name(x[0], x[1], x[2]); }
+__device__ __forceinline__ void p2p_name(double (&x)[8]) { p2p_name(x[0], x[1], x[2], x[3]), p2p_name(x[4], x[5], x[6], x[7]); }
+__device__ __forceinline__ void p2p_name(double (&x)[9]) { p2p_name(x[0], x[1], x[2], x[3]), p2p_name(x[4], x[5], x[6], x[7]), p2p_name(x[8]); }
+__device__ __forceinline__ void p2p_name(double (&c)[4][6]) // the pair a ring takes: [n][4], [n][5]
+{
+    p2p_name(c[0][4], c[0][5], c[1][4], c[1][5]), p2p_name(c[2][4], c[2][5], c[3][4], c[3][5]);
+}
+template <int N, class... T>
+__device__ __forceinline__ void p2p_land(T&... x)
+{
+    p2p_wait_vm<N>();
+    (p2p_name(x), ...);
+}
+
 typedef double nsdg_pair16 __attribute__((ext_vector_type(2)));
 template <bool NT>
 __device__ __forceinline__ void tile_load8_nt(const double* __restrict__ a, long t, double (&c)[8])

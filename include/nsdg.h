@@ -58,7 +58,8 @@ extern "C" {
  * device timing) and nsdg_land_mask_set / nsdg_land_clear / nsdg_land_clear_nodes (land mask) and nsdg_bbm_default_params / nsdg_bbm_params_set /
  * nsdg_bbm_prepare / nsdg_bbm_iterate / nsdg_bbm_substep_count (brittle rheology) and nsdg_history_accumulate / nsdg_history_field_name /
  * nsdg_history_field_id, nsdg_history_accumulate_stats / nsdg_history_row_totals / nsdg_history_stat_* / nsdg_history_series_* (history
- * output) and nsdg_drifters_advance / nsdg_comm_max_f64_array (drifters) are additions; nothing that existed changed. */
+ * output) and nsdg_drifters_advance / nsdg_comm_max_f64_array (drifters) and nsdg_rb_bbm_create / nsdg_rb_bbm_destroy / nsdg_rb_bbm_run /
+ * nsdg_rb_bbm_stats (the brittle sub-cycle of a row block) and nsdg_bbm_params_check are additions; nothing that existed changed. */
 #define NSDG_ABI_VERSION 6
 
 typedef enum {
@@ -599,6 +600,7 @@ int nsdg_land_clear_nodes(nsdg_ctx* ctx, double* u, double* v);
  *
  * nsdg_bbm_params_set: NSDG_ERR_ARG for a non-finite member, relax_exponent < 1, d_max outside (0, 1) or a non-positive young, lambda0 or
  *   t_heal.
+ * nsdg_bbm_params_check: the same checks without a context (host only): a host validates its configuration before it touches a device.
  * nsdg_bbm_iterate: one sub-iteration, the stress and damage on element rows [k0, j1), the velocity of the nodes owned by rows [j0, j1);
  *   the row conventions of nsdg_mevp_iterate (k0 == j0 - 1 or k0 == j0 == 0).  Stress AND damage are out of place: a row may be updated
  *   redundantly by two owners with bit-identical results, so a row block needs no exchange of D inside the sub-cycle.  A null pointer, an
@@ -627,6 +629,7 @@ typedef struct {
 #define NSDG_BBM_COURANT 0.25
 void nsdg_bbm_default_params(nsdg_bbm_params* p);
 int nsdg_bbm_params_set(nsdg_ctx* ctx, const nsdg_bbm_params* p);
+int nsdg_bbm_params_check(const nsdg_bbm_params* p); /* host only, no context: NSDG_OK, or NSDG_ERR_ARG with nsdg_bbm_params_set's message */
 int nsdg_bbm_prepare(nsdg_ctx* ctx, int32_t j0, int32_t j1, const double* H, const double* A, double* hg, double* eg, double* pm);
 int nsdg_bbm_iterate(nsdg_ctx* ctx, int32_t k0, int32_t j0, int32_t j1, const double* s11_in, const double* s12_in, const double* s22_in,
     double* s11_out, double* s12_out, double* s22_out, const double* D_in, double* D_out, const double* u_old, const double* v_old,
@@ -876,6 +879,42 @@ int nsdg_rb_mevp_info(const nsdg_rb_mevp* plan, int32_t* per_pass, int32_t* grou
 int nsdg_rb_mevp_run(nsdg_ctx* ctx, nsdg_rb_mevp* plan, int32_t parity, int32_t* parity_out);
 /* exchange statistics summed over the plan's ghost exchanges (bytes: of its largest exchange) */
 int nsdg_rb_mevp_stats(nsdg_ctx* ctx, nsdg_rb_mevp* plan, nsdg_halo_stats* out, int32_t reset);
+
+/* The brittle sub-cycle of a row block ("brittle rheology" above; csrc/rowblock.hip): nsub sub-iterations of nsdg_bbm_iterate with the
+ * exchanges of the single-sub-iteration branch of nsdg_rb_mevp_run -- unsplit: one launch from k0 = max(j0 - 1, 0), then one velocity
+ * node row down and two up; with `overlap` and at least 4 owned rows: the top row, the bottom row, the exchange posted, the interior, the
+ * exchange finished.  No multi-iteration passes and no hipGraph replay.  A block with neighbours must have the ghost depth (1, 1)
+ * (NSDG_ERR_ARG otherwise) and a communicator (NSDG_ERR_STATE otherwise).
+ * The damage.  The transport plan holds fixed buffers phi[k] / t1[k] of D and alternates between them by its own parity; the sub-cycle
+ * ping-pongs D nsub times.  So the plan takes both transport buffers, D[0] = phi and D[1] = t1 of that field, and a work buffer of the
+ * same size (the transport's t2 of D is free between two transport steps).  nsdg_rb_bbm_run's damage_parity says which of D[] is current
+ * (the transport plan's parity): the sub-iterations alternate between D[damage_parity] and D_work, after an odd nsub nsdg_copy_f64 of all
+ * local rows puts the result back, and one exchange of the 6 coefficient planes hands the transport its ghost rows: D ends in
+ * D[damage_parity] for every nsub > 0.  nsub == 0 launches nothing, exchanges nothing and returns the parity it was given.
+ * complete_nodes != 0: the call ends (nsub > 0) with one more exchange of the final velocity with 2 depth_above + 1 node rows downwards, so
+ * that every ghost node row is current (the drifters' predictor may sit in the ghost row above).
+ * Before the call: nsdg_bbm_prepare into hg, eg, pm and nsdg_mevp_prepare(dt / nsub, ..., u0 = v0 = zeros) into packed. */
+typedef struct nsdg_rb_bbm nsdg_rb_bbm;
+typedef struct {
+    int32_t nx, ny, j0, j1;
+    int32_t depth_below, depth_above;
+    int32_t rank_below, rank_above;
+    int32_t nsub; /* sub-iterations per call */
+    int32_t overlap; /* launch the rows whose results travel first, post the exchange, then the interior */
+    int32_t complete_nodes; /* end with an exchange of every ghost node row of the final velocity */
+    int32_t reserved;
+    double *s11[2], *s12[2], *s22[2]; /* ping-pong: tiled stress */
+    double *u[2], *v[2]; /* ping-pong: CG2 velocity */
+    const double* packed; /* nsdg_mevp_prepare output of this step (dt / nsub, u0 = v0 = 0) */
+    const double *hg, *eg, *pm; /* nsdg_bbm_prepare output of this step */
+    double* D[2]; /* the transport's two buffers of the damage: [6][ny][nx] each */
+    double* D_work; /* same size: the partner of the current buffer inside the call */
+} nsdg_rb_bbm_desc;
+int nsdg_rb_bbm_create(nsdg_ctx* ctx, const nsdg_rb_bbm_desc* desc, nsdg_rb_bbm** out);
+int nsdg_rb_bbm_destroy(nsdg_rb_bbm* plan);
+/* `parity`: which ping-pong set of stress and velocity is current, *parity_out: which one holds the result; damage_parity: above */
+int nsdg_rb_bbm_run(nsdg_ctx* ctx, nsdg_rb_bbm* plan, int32_t parity, int32_t damage_parity, int32_t* parity_out);
+int nsdg_rb_bbm_stats(nsdg_ctx* ctx, nsdg_rb_bbm* plan, nsdg_halo_stats* out, int32_t reset);
 
 #define NSDG_RB_MAX_FIELDS 4
 typedef struct nsdg_rb_transport nsdg_rb_transport;

@@ -104,6 +104,14 @@ class RbMevpDesc(C.Structure):
         (n, C.c_void_p * 2) for n in ("s11", "s12", "s22", "u", "v")] + [("packed", C.c_void_p), ("pg", C.c_void_p)]
 
 
+class RbBbmDesc(C.Structure):
+    """nsdg_rb_bbm_desc"""
+    _fields_ = [(n, C.c_int32) for n in ("nx", "ny", "j0", "j1", "depth_below", "depth_above", "rank_below", "rank_above", "nsub",
+                                          "overlap", "complete_nodes", "reserved")] + [
+        (n, C.c_void_p * 2) for n in ("s11", "s12", "s22", "u", "v")] + [(n, C.c_void_p) for n in ("packed", "hg", "eg", "pm")] + [
+        ("D", C.c_void_p * 2), ("D_work", C.c_void_p)]
+
+
 class RbTransportDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("nx", "ny", "j0", "j1", "depth_below", "depth_above", "rank_below", "rank_above", "order",
                                           "nfields")] + [
@@ -147,6 +155,7 @@ SYMBOLS = {
     "nsdg_land_clear_nodes": (C.c_int, [VP, VP, VP]),
     "nsdg_bbm_default_params": (None, [C.POINTER(BbmParams)]),
     "nsdg_bbm_params_set": (C.c_int, [VP, C.POINTER(BbmParams)]),
+    "nsdg_bbm_params_check": (C.c_int, [C.POINTER(BbmParams)]),
     "nsdg_bbm_prepare": (C.c_int, [VP, I32, I32] + [VP] * 5),
     "nsdg_bbm_iterate": (C.c_int, [VP, I32, I32, I32] + [VP] * 16),
     "nsdg_bbm_substep_count": (C.c_int, [C.POINTER(BbmParams), D, D, D, D, I32, C.POINTER(I32)]),
@@ -214,6 +223,10 @@ SYMBOLS = {
     "nsdg_rb_mevp_info": (C.c_int, [VP, C.POINTER(I32), C.POINTER(I32)]),
     "nsdg_rb_mevp_run": (C.c_int, [VP, VP, I32, C.POINTER(I32)]),
     "nsdg_rb_mevp_stats": (C.c_int, [VP, VP, C.POINTER(HaloStats), I32]),
+    "nsdg_rb_bbm_create": (C.c_int, [VP, C.POINTER(RbBbmDesc), C.POINTER(VP)]),
+    "nsdg_rb_bbm_destroy": (C.c_int, [VP]),
+    "nsdg_rb_bbm_run": (C.c_int, [VP, VP, I32, I32, C.POINTER(I32)]),
+    "nsdg_rb_bbm_stats": (C.c_int, [VP, VP, C.POINTER(HaloStats), I32]),
     "nsdg_rb_transport_create": (C.c_int, [VP, C.POINTER(RbTransportDesc), C.POINTER(VP)]),
     "nsdg_rb_transport_destroy": (C.c_int, [VP]),
     "nsdg_rb_transport_run": (C.c_int, [VP, VP, D, I32, C.POINTER(I32)]),
@@ -571,6 +584,47 @@ class Context:
         run.stats = stats
         run.close = close
         return run, per_pass.value, group.value
+
+    def rb_bbm(self, blk, peers, nsub, overlap, s2, uv2, packed, gauss, damage, damage_work, complete_nodes=False):
+        """native brittle sub-cycle driver of a row block (nsdg_rb_bbm_*); s2, uv2: as rb_mevp; gauss = (hg, eg, pm) of bbm_prepare;
+        damage = the transport's two buffers of D (phi, t1), damage_work: the partner inside the call.  Returns
+        run(parity, damage_parity) -> parity of the result; D ends in damage[damage_parity]"""
+        d = RbBbmDesc()
+        self._geometry(d, blk, peers)
+        d.nsub, d.overlap, d.complete_nodes = nsub, int(bool(overlap)), int(bool(complete_nodes))
+        ts = list(s2[0]) + list(s2[1]) + list(uv2[0]) + list(uv2[1]) + [packed] + list(gauss) + list(damage) + [damage_work]
+        _check_f64(*ts)
+        for k in range(2):
+            d.s11[k], d.s12[k], d.s22[k] = (s2[k][i].data_ptr() for i in range(3))
+            d.u[k], d.v[k] = uv2[k][0].data_ptr(), uv2[k][1].data_ptr()
+            d.D[k] = damage[k].data_ptr()
+        d.packed, d.D_work = packed.data_ptr(), damage_work.data_ptr()
+        d.hg, d.eg, d.pm = (t.data_ptr() for t in gauss)
+        h = VP()
+        self._call(self.lib.nsdg_rb_bbm_create(self.h, C.byref(d), C.byref(h)))
+        out, fn, ch = I32(), self.lib.nsdg_rb_bbm_run, self.h
+
+        def run(parity, damage_parity):
+            rc = fn(ch, h, parity, damage_parity, C.byref(out))
+            if rc != 0:
+                self._call(rc)
+            return out.value
+
+        def stats(reset=False):
+            st = HaloStats()
+            self._call(self.lib.nsdg_rb_bbm_stats(ch, h, C.byref(st), int(reset)))
+            return st.as_dict()
+
+        def close():
+            if run.handle is not None and self.h:
+                self.lib.nsdg_rb_bbm_destroy(run.handle)
+            run.handle = None
+
+        run.keep = ts
+        run.handle = h
+        run.stats = stats
+        run.close = close
+        return run
 
     def rb_transport(self, blk, peers, phi, t1, t2, adv, bounds=None):
         """native SSP-RK3 transport driver of a row block; returns run(dt, parity) -> parity of the new state.  bounds: the closure of the

@@ -134,14 +134,23 @@ void nsdg_bbm_default_params(nsdg_bbm_params* p)
     p->reserved = 0;
 }
 
-int nsdg_bbm_params_set(nsdg_ctx* ctx, const nsdg_bbm_params* p)
-{
-    NSDG_CHECK_ARG(ctx && p, "null argument");
+int nsdg_bbm_params_check(const nsdg_bbm_params* p)
+{ // host only, no context: what nsdg_bbm_params_set refuses
+    NSDG_CHECK_ARG(p, "null argument");
     for (double x : { p->young, p->nu, p->p0, p->lambda0, p->tan_phi, p->cohesion_lab, p->compr_strength, p->t_heal, p->d_max })
         NSDG_CHECK_ARG(std::isfinite(x), "non-finite parameter");
     NSDG_CHECK_ARG(p->relax_exponent >= 1, "relax_exponent must be an integer >= 1");
     NSDG_CHECK_ARG(p->d_max > 0. && p->d_max < 1., "d_max must lie in (0, 1)");
     NSDG_CHECK_ARG(p->young > 0. && p->lambda0 > 0. && p->t_heal > 0., "young, lambda0 and t_heal must be positive");
+    return NSDG_OK;
+}
+
+int nsdg_bbm_params_set(nsdg_ctx* ctx, const nsdg_bbm_params* p)
+{
+    NSDG_CHECK_ARG(ctx && p, "null argument");
+    const int rc = nsdg_bbm_params_check(p);
+    if (rc != NSDG_OK)
+        return rc;
     ctx->bbm = *p;
     return NSDG_OK;
 }

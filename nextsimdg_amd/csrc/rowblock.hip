@@ -1,4 +1,4 @@
-// rowblock.hip -- the per-step driver of one rank's row block behind the C ABI: the mEVP sub-cycle and the
+// rowblock.hip -- the per-step driver of one rank's row block behind the C ABI: the mEVP sub-cycle, the BBM sub-cycle and the
 // SSP-RK3 transport with their ghost-row exchanges (halo.hip), one call each per model step.
 //
 // Why here and not in the callers: both hosts -- the C++ host layer (host/src/DynamicsStep.cpp, multi-rank) and the
@@ -474,6 +474,171 @@ int nsdg_rb_mevp_run(nsdg_ctx* ctx, nsdg_rb_mevp* p, int32_t parity, int32_t* pa
                 return rc;
         }
         par = 1 - par;
+    }
+    *parity_out = par;
+    return NSDG_OK;
+}
+
+} // extern "C"
+
+// =================================================================================================== BBM sub-cycle
+// The brittle sub-cycle of a row block: the single-sub-iteration branch of nsdg_rb_mevp_run with nsdg_bbm_iterate's launch in place of
+// the mEVP one (rowblock.py DynamicsCore.subcycle with rheology = "bbm" is the specification).  Stress, velocity and damage share one
+// parity inside the call; the damage alternates between the transport's CURRENT buffer of D and a work buffer and ends in the former.
+struct nsdg_rb_bbm {
+    nsdg_ctx* ctx;
+    Geometry g;
+    nsdg_rb_bbm_desc d;
+    nsdg_halo* node_plan[2] = { nullptr, nullptr }; // one velocity node row down, two up: after every sub-iteration, destination buffer 0 / 1
+    nsdg_halo* full_plan[2] = { nullptr, nullptr }; // complete_nodes: the final velocity with every ghost node row
+    nsdg_halo* damage_plan[2] = { nullptr, nullptr }; // the ghost rows of the transport's buffer 0 / 1 of D
+};
+
+namespace {
+
+int bbm_launch(nsdg_rb_bbm* p, int k0, int j0, int j1, int par, const double* d_in, double* d_out)
+{
+    const nsdg_rb_bbm_desc& d = p->d;
+    const int q = 1 - par;
+    return nsdg_bbm_iterate(p->ctx, k0, j0, j1, d.s11[par], d.s12[par], d.s22[par], d.s11[q], d.s12[q], d.s22[q], d_in, d_out, d.u[par], d.v[par],
+        d.u[q], d.v[q], d.packed, d.hg, d.eg, d.pm);
+}
+
+int exchange_now(nsdg_ctx* ctx, nsdg_halo* plan)
+{
+    if (!plan)
+        return NSDG_OK;
+    const int rc = nsdg_halo_start(ctx, plan);
+    return rc != NSDG_OK ? rc : nsdg_halo_finish(ctx, plan);
+}
+
+} // namespace
+
+extern "C" {
+
+int nsdg_rb_bbm_create(nsdg_ctx* ctx, const nsdg_rb_bbm_desc* desc, nsdg_rb_bbm** out)
+{
+    NSDG_CHECK_ARG(ctx && desc && out, "null argument");
+    *out = nullptr;
+    const nsdg_rb_bbm_desc& d = *desc;
+    Geometry g = { d.nx, d.ny, d.j0, d.j1, d.depth_below, d.depth_above, d.rank_below, d.rank_above };
+    int rc = check_geometry(g);
+    if (rc != NSDG_OK)
+        return rc;
+    NSDG_CHECK_ARG(!g.multi() || (g.depth_below == 1 && g.depth_above == 1),
+        "the brittle sub-cycle runs one sub-iteration per pass: a block with neighbours needs the ghost depth (1, 1)");
+    NSDG_CHECK_ARG(d.nsub >= 0, "negative sub-iteration count");
+    for (int k = 0; k < 2; ++k)
+        NSDG_CHECK_ARG(d.s11[k] && d.s12[k] && d.s22[k] && d.u[k] && d.v[k] && d.D[k], "null ping-pong buffer");
+    NSDG_CHECK_ARG(d.packed && d.hg && d.eg && d.pm && d.D_work, "null field pointer");
+    NSDG_CHECK_ARG(d.s11[0] != d.s11[1] && d.s12[0] != d.s12[1] && d.s22[0] != d.s22[1] && d.u[0] != d.u[1] && d.v[0] != d.v[1],
+        "the two halves of a ping-pong pair must not alias");
+    NSDG_CHECK_ARG(d.D[0] != d.D[1] && d.D_work != d.D[0] && d.D_work != d.D[1], "the damage buffers must not alias");
+    if (g.multi() && !ctx->comm) {
+        nsdg_set_error("nsdg_rb_bbm_create: a block with neighbours needs nsdg_comm_init* first");
+        return NSDG_ERR_STATE;
+    }
+    nsdg_rb_bbm* p = new nsdg_rb_bbm();
+    p->ctx = ctx;
+    p->g = g;
+    p->d = d;
+    if (g.multi()) {
+        for (int q = 0; q < 2 && rc == NSDG_OK; ++q) { // q: the buffer a sub-iteration has just written / the transport's buffer of D
+            SegList nodes, full, damage;
+            add_node_rows(g, d.u[q], 1, nodes);
+            add_node_rows(g, d.v[q], 1, nodes);
+            rc = make_plan(ctx, g, nodes, &p->node_plan[q]);
+            if (rc == NSDG_OK && d.complete_nodes) {
+                add_node_rows(g, d.u[q], 2 * g.depth_above + 1, full);
+                add_node_rows(g, d.v[q], 2 * g.depth_above + 1, full);
+                rc = make_plan(ctx, g, full, &p->full_plan[q]);
+            }
+            if (rc == NSDG_OK) {
+                add_plane_rows(g, d.D[q], 6, damage);
+                rc = make_plan(ctx, g, damage, &p->damage_plan[q]);
+            }
+        }
+    }
+    if (rc != NSDG_OK) {
+        nsdg_rb_bbm_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return NSDG_OK;
+}
+
+int nsdg_rb_bbm_destroy(nsdg_rb_bbm* p)
+{
+    if (!p)
+        return NSDG_OK;
+    for (int q = 0; q < 2; ++q) {
+        nsdg_halo_plan_destroy(p->node_plan[q]);
+        nsdg_halo_plan_destroy(p->full_plan[q]);
+        nsdg_halo_plan_destroy(p->damage_plan[q]);
+    }
+    delete p;
+    return NSDG_OK;
+}
+
+int nsdg_rb_bbm_stats(nsdg_ctx* ctx, nsdg_rb_bbm* p, nsdg_halo_stats* out, int32_t reset)
+{
+    NSDG_CHECK_ARG(ctx && p && p->ctx == ctx && out, "plan does not belong to this context");
+    return sum_stats(ctx, { p->node_plan[0], p->node_plan[1], p->full_plan[0], p->full_plan[1], p->damage_plan[0], p->damage_plan[1] }, out, reset);
+}
+
+int nsdg_rb_bbm_run(nsdg_ctx* ctx, nsdg_rb_bbm* p, int32_t parity, int32_t damage_parity, int32_t* parity_out)
+{
+    NSDG_CHECK_ARG(ctx && p && p->ctx == ctx && parity_out, "plan does not belong to this context");
+    NSDG_CHECK_ARG((parity == 0 || parity == 1) && (damage_parity == 0 || damage_parity == 1), "parity must be 0 or 1");
+    NSDG_NEED_GRID(ctx);
+    NSDG_CHECK_ARG(ctx->nx == p->g.nx && ctx->ny == p->g.ny, "nsdg_grid_set does not match the plan's local array");
+    const Geometry& g = p->g;
+    const nsdg_rb_bbm_desc& d = p->d;
+    int par = parity, rc;
+    // the damage: sub-iteration `it` reads the transport's current buffer (it even) or the work buffer (it odd) and writes the other
+    double* const dcur = d.D[damage_parity];
+    const bool split = d.overlap && g.multi() && (g.j1 - g.j0) >= 4;
+    for (int it = 0; it < d.nsub; ++it) {
+        const double* din = (it % 2 == 0) ? dcur : d.D_work;
+        double* dout = (it % 2 == 0) ? d.D_work : dcur;
+        nsdg_halo* plan = p->node_plan[1 - par];
+        if (!split) {
+            const int k0 = std::max(g.j0 - 1, 0);
+            if ((rc = bbm_launch(p, k0, g.j0, g.j1, par, din, dout)) != NSDG_OK)
+                return rc;
+            if ((rc = exchange_now(ctx, plan)) != NSDG_OK)
+                return rc;
+        } else {
+            int lo = g.j0, hi = g.j1;
+            if (g.has_above()) { // top owned element row -> the two node rows sent upwards
+                if ((rc = bbm_launch(p, g.j1 - 2, g.j1 - 1, g.j1, par, din, dout)) != NSDG_OK)
+                    return rc;
+                hi = g.j1 - 1;
+            }
+            if (g.has_below()) { // bottom owned element row (+ redundant ghost-row stress and damage) -> the node row sent downwards
+                if ((rc = bbm_launch(p, g.j0 - 1, g.j0, g.j0 + 1, par, din, dout)) != NSDG_OK)
+                    return rc;
+                lo = g.j0 + 1;
+            }
+            if (plan && (rc = nsdg_halo_start(ctx, plan)) != NSDG_OK)
+                return rc;
+            if ((rc = bbm_launch(p, lo > 0 ? lo - 1 : 0, lo, hi, par, din, dout)) != NSDG_OK)
+                return rc;
+            if (plan && (rc = nsdg_halo_finish(ctx, plan)) != NSDG_OK)
+                return rc;
+        }
+        par = 1 - par;
+    }
+    if (d.nsub > 0) {
+        // an odd count has left the result in the work buffer: every local row goes back to where the transport reads it
+        if (d.nsub % 2 == 1 && (rc = nsdg_copy_f64(ctx, dcur, d.D_work, 6L * g.nx * g.ny)) != NSDG_OK)
+            return rc;
+        // inside the sub-cycle the damage of the ghost row below is recomputed and the ghost row above is never read: one exchange
+        // hands the transport its ghost rows
+        if ((rc = exchange_now(ctx, p->damage_plan[damage_parity])) != NSDG_OK)
+            return rc;
+        if ((rc = exchange_now(ctx, p->full_plan[par])) != NSDG_OK)
+            return rc;
     }
     *parity_out = par;
     return NSDG_OK;

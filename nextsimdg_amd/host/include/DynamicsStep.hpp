@@ -59,6 +59,19 @@
 //                            velocity after every transport step and written as text blocks (include/Drifters.hpp; include/nsdg.h
 //                            "drifters"); works with dynamics.row_blocks (block 0 writes), refused in a multi-process run; no file
 //                            (default): off, nothing changes
+//     dynamics.rheology      mevp (default: every run without the key is byte for byte what it was) | bbm -- the brittle Bingham-Maxwell
+//                            sub-cycle (include/nsdg.h "brittle rheology") through the row-block plan nsdg_rb_bbm_*:
+//                            ghost depth (1, 1), one sub-iteration per pass, nsub explicit sub-iterations of dt / nsub; the damage D is a
+//                            third advected field (bounds 0, 1, no cap), cleared on land, written to the restart file as `damage` (six
+//                            planes; a file without it: the run starts undamaged) and offered to the history output as `damage`.
+//                            dynamics.passes_per_exchange, .alpha, .beta and .subcycle do not apply.  Refused with
+//                            dynamics.advect_column_state (five fields), dynamics.substeps = auto (that rule is the mEVP strength wave)
+//                            and dynamics.graph
+//     [bbm] young, nu, p0, lambda0, tan_phi, cohesion_lab, compr_strength, t_heal, d_max, relax_exponent   the members of
+//                            nsdg_bbm_params (defaults: nsdg_bbm_default_params), checked by nsdg_bbm_params_check when the step is configured
+//     dynamics.bbm_courant   cells the elastic wave may cross per sub-iteration (NSDG_BBM_COURANT = 0.25): without an explicit
+//                            dynamics.nsub the count is nsdg_bbm_substep_count for the (sub-)step's dt; an explicit dynamics.nsub is used
+//                            as given, with one warning line if it is below the rule's value
 //     dynamics.row_blocks, dynamics.devices, dynamics.passes_per_exchange (2), dynamics.overlap (true),
 //     dynamics.graph (false), dynamics.loopback_world (0: off; N: rehearse an interior block of N on one GPU with
 //     real RCCL send/recv to the rank itself -- values wrap around, for timing and call-path checks only)
@@ -123,6 +136,8 @@ public:
     static std::vector<double> packRows(FieldStore& f, bool thermodynamics, int nx, int r0, int r1);
     //! ... and how rank 0 puts it into its structure; throws std::runtime_error when the size is not that of the rows
     static void placeRows(FieldStore& f, bool thermodynamics, int nx, int r0, int r1, const double* data, std::size_t count);
+    //! the keys of the brittle rheology (dynamics.rheology, dynamics.bbm_courant, bbm.*): a step that does not run it refuses them
+    static const std::vector<std::string>& brittleKeys();
 
 private:
     void release();
@@ -159,6 +174,9 @@ private:
     std::unique_ptr<SeriesOutput> m_series; // model.series_file: the time series of the domain totals (null: off)
     std::unique_ptr<DriftersOutput> m_drifters; // model.drifters_file: keys, clock and text files of the drifters (null: off)
     std::vector<double> m_drifterStart; // ... and the list the input file holds, [3][n], read and checked in configure()
+    struct Brittle; // dynamics.rheology = bbm: the parameters and the sub-iteration rule (DynamicsStep.cpp); null: mEVP
+    std::unique_ptr<Brittle> m_brittle;
+    bool nsubGiven = false; // dynamics.nsub is in the configuration
     int substeps = 1; // dynamics.substeps; 0 = auto
     double substepCourant = 1.5; // dynamics.substep_courant (NSDG_SUBSTEP_COURANT)
     int maxSubsteps = 16; // dynamics.max_substeps

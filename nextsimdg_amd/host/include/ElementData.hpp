@@ -26,6 +26,9 @@ struct DynamicsState {
     //! coefficients 1..5 of the snow S of dynamics.advect_column_state: [5][x][y]; EMPTY without that mode (nothing of it is written)
     //! and after reading a file that does not hold it (the higher coefficients then start at zero)
     std::vector<double> sdg;
+    //! all six coefficients of the damage D of dynamics.rheology = bbm: [6][x][y] (no FieldStore plane holds its mean); EMPTY without that
+    //! rheology and after reading a file that does not hold it (a brittle run then starts undamaged)
+    std::vector<double> damage;
     inline void resize(std::size_t nx, std::size_t ny); //!< every variable that is not optional: zeros of its shape
     inline void clear();
 };
@@ -51,8 +54,9 @@ struct FieldStore {
 //! order: DynamicsState::resize / clear, both file formats (RectGrid::dump / init) and the ranks' payload (DynamicsStep::packRows) walk it.
 struct DynamicsVariable {
     //! for x * y elements: DG2 coefficients 1..5 of an advected field (dg2 = 5, x, y) | the 8-function stress space (stress8 = 8, x, y) |
-    //! a plane (x, y) | the CG2 lattice (xnode = 2x+1, ynode = 2y+1); in brackets the named dimensions of an HDF5 file
-    enum Shape { DG5, STRESS8, PLANE, NODAL };
+    //! a plane (x, y) | the CG2 lattice (xnode = 2x+1, ynode = 2y+1) | all six DG2 coefficients of a field without a mean plane (dg2full = 6, x, y); in
+    //! brackets the named dimensions of an HDF5 file
+    enum Shape { DG5, STRESS8, PLANE, NODAL, DG6 };
     const char* name; //!< the dataset in group `data` of an HDF5 file = the entry of the sidecar's variables= line
     Shape shape;
     //! where it lives: in FieldStore::dyn, or (state == nullptr) in a plane of the FieldStore itself, which the files list here but which
@@ -65,7 +69,7 @@ struct DynamicsVariable {
 
     template <class Store> auto& in(Store& f) const { return state ? f.dyn.*state : f.*plane; } //!< its array in a (const) FieldStore
     bool optional() const { return sidecarFlag != nullptr; }
-    int elementPlanes() const { return shape == DG5 ? 5 : shape == STRESS8 ? 8 : shape == PLANE ? 1 : 0; } //!< planes of x * y values
+    int elementPlanes() const { return shape == DG5 ? 5 : shape == DG6 ? 6 : shape == STRESS8 ? 8 : shape == PLANE ? 1 : 0; } //!< planes of x * y values
     std::size_t size(std::size_t nx, std::size_t ny) const { return shape == NODAL ? (2 * nx + 1) * (2 * ny + 1) : elementPlanes() * nx * ny; }
 };
 inline constexpr DynamicsVariable DYNAMICS_VARIABLES[] = {
@@ -78,6 +82,7 @@ inline constexpr DynamicsVariable DYNAMICS_VARIABLES[] = {
     { "s22", DynamicsVariable::STRESS8, &DynamicsState::s22, nullptr, nullptr },
     { "newice", DynamicsVariable::PLANE, nullptr, &FieldStore::newice, nullptr }, // the column model's new-ice volume (NextsimPhysics::m_newice)
     { "hsnow_dg", DynamicsVariable::DG5, &DynamicsState::sdg, nullptr, "data.snow_dg" }, // dynamics.advect_column_state: the advected snow (coefficient 0 = hsnow)
+    { "damage", DynamicsVariable::DG6, &DynamicsState::damage, nullptr, "data.damage" }, // dynamics.rheology = bbm: the damage D, all six coefficients
 };
 
 void DynamicsState::resize(std::size_t nx, std::size_t ny)

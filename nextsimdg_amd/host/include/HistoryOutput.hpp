@@ -52,7 +52,7 @@ public:
     };
     //! model.output_*, read and checked against model.time_step and what the step can sample; throws std::invalid_argument naming the
     //! key.  thermodynamics: the column model runs (hsnow, tice exist).  Touches no device.
-    static Config fromConfiguration(bool thermodynamics);
+    static Config fromConfiguration(bool thermodynamics, bool brittle = false); //!< brittle: dynamics.rheology = bbm (the field "damage" exists)
     //! for a step that cannot write history (HipStep): throws std::invalid_argument if any model.output_* key is given
     static void refuseFor(const std::string& stepName);
 

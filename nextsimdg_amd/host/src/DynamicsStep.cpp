@@ -77,21 +77,35 @@ struct AdvectedField {
     const char* name;
     nsdg_field_bounds bounds; // the closure of the transport step (include/nsdg.h "INPUT DOMAIN AND CLOSURE")
     std::vector<double> FieldStore::*mean; // the host's plane of coefficient 0 ...
-    std::vector<double> DynamicsState::*higher; // ... and of coefficients 1..5 (both nullptr: no host storage -- never uploaded, cleared or downloaded)
-    bool columnState; // present only with dynamics.advect_column_state (such rows last: the fields of a run are the first `nfields`)
+    std::vector<double> DynamicsState::*higher; // ... and of coefficients 1..5
+    std::vector<double> DynamicsState::*full; // or all six coefficients in one host array (no FieldStore plane holds the mean)
+    // (all three nullptr: no host storage -- never uploaded, cleared or downloaded)
+    enum When { ALWAYS, BRITTLE, COLUMN_STATE } when; // present in every run | with dynamics.rheology = bbm | with dynamics.advect_column_state
+    bool stored() const { return mean || full; }
 };
-enum Field { FH, FA, FS, FQ, NFIELD };
-const AdvectedField ADVECTED[NFIELD] = {
-    { "H", { 0., HUGE_VAL, 0, 0 }, &FieldStore::hice, &DynamicsState::hdg, false }, // mean thickness: H >= 0
-    { "A", { 0., 1., 1, 0 }, &FieldStore::cice, &DynamicsState::adg, false }, // concentration in [0, 1], the cell mean capped at 1
-    { "S", { 0., HUGE_VAL, 0, 0 }, &FieldStore::hsnow, &DynamicsState::sdg, true }, // snow volume: S >= 0; plane 0 IS the column's hsnow
-    { "Q", { -HUGE_VAL, HUGE_VAL, 0, 0 }, nullptr, nullptr, true }, // = H tice0, unbounded: rebuilt at every step (nsdg_tracer_weight)
+enum Field { FH, FA, FD, FS, FQ, NFIELD };
+constexpr AdvectedField ADVECTED[NFIELD] = {
+    { "H", { 0., HUGE_VAL, 0, 0 }, &FieldStore::hice, &DynamicsState::hdg, nullptr, AdvectedField::ALWAYS }, // mean thickness: H >= 0
+    { "A", { 0., 1., 1, 0 }, &FieldStore::cice, &DynamicsState::adg, nullptr, AdvectedField::ALWAYS }, // concentration in [0, 1], the cell mean capped at 1
+    { "D", { 0., 1., 0, 0 }, nullptr, nullptr, &DynamicsState::damage, AdvectedField::BRITTLE }, // damage in [0, 1], no cap of the mean
+    { "S", { 0., HUGE_VAL, 0, 0 }, &FieldStore::hsnow, &DynamicsState::sdg, nullptr, AdvectedField::COLUMN_STATE }, // snow volume: S >= 0; plane 0 IS the column's hsnow
+    { "Q", { -HUGE_VAL, HUGE_VAL, 0, 0 }, nullptr, nullptr, nullptr, AdvectedField::COLUMN_STATE }, // = H tice0, unbounded: rebuilt at every step (nsdg_tracer_weight)
 };
-static_assert(NFIELD <= NSDG_RB_MAX_FIELDS, "the transport plan holds every advected field");
+// the table has five rows; a run advects H and A and EITHER the damage OR the column state (configure() refuses both together)
+constexpr int fieldsOfARun(AdvectedField::When w)
+{
+    int n = 0;
+    for (const AdvectedField& a : ADVECTED)
+        n += a.when == AdvectedField::ALWAYS || a.when == w;
+    return n;
+}
+static_assert(fieldsOfARun(AdvectedField::BRITTLE) <= NSDG_RB_MAX_FIELDS && fieldsOfARun(AdvectedField::COLUMN_STATE) <= NSDG_RB_MAX_FIELDS,
+    "the transport plan holds every advected field of a run");
 
 // further device arrays of a block; the stress (its components in the order of STRESS) and the velocity exist twice (ping-pong)
 std::vector<double> DynamicsState::*const STRESS[3] = { &DynamicsState::s11, &DynamicsState::s12, &DynamicsState::s22 };
-enum Arr { S11a, S12a, S22a, S11b, S12b, S22b, PG, VXDG, VYDG, UNX, UNY, Ua, Va, Ub, Vb, UA, VA, UO, VO, PACKED, COL, NARR };
+// (HG, EG, PM, ZERO: the Gauss arrays of nsdg_bbm_prepare and the zero nodal array its packing takes as u0, v0 -- empty under mEVP)
+enum Arr { S11a, S12a, S22a, S11b, S12b, S22b, PG, VXDG, VYDG, UNX, UNY, Ua, Va, Ub, Vb, UA, VA, UO, VO, PACKED, COL, HG, EG, PM, ZERO, NARR };
 // column planes inside COL
 enum Col { C_HSNOW, C_TICE, C_SST, C_SSS, C_TAIR, C_TDEW, C_SLP, C_QSW, C_QLW, C_MLD, C_SNOWFALL, C_WIND, C_NEWICE, NCOL };
 } // namespace
@@ -107,8 +121,11 @@ public:
     nsdg_ctx* ctx = nullptr;
     double* block = nullptr;
     std::vector<double*> d;
-    int nfields = 0; // rows of ADVECTED this run advects
+    int nfields = 0; // rows of ADVECTED this run advects ...
+    int slot[NFIELD]; // ... and where each sits among the device buffers and in the transport plan (-1: not in this run)
     nsdg_rb_mevp* mevp = nullptr;
+    nsdg_rb_bbm* bbm = nullptr; // dynamics.rheology = bbm: the plan of the current sub-iteration count (made when that is known)
+    int bbmNsub = -1;
     nsdg_rb_transport* transport = nullptr;
     int par = 0, tpar = 0; // which buffers hold the velocity/stress iterate and the advected state
     double amax = 0.; // largest concentration of the owned rows at the start of the model step (dynamics.substeps = auto)
@@ -130,8 +147,9 @@ public:
         if (ctx)
             (void)hipSetDevice(device);
         nsdg_rb_mevp_destroy(mevp);
+        nsdg_rb_bbm_destroy(bbm);
         nsdg_rb_transport_destroy(transport);
-        mevp = nullptr, transport = nullptr;
+        mevp = nullptr, bbm = nullptr, transport = nullptr;
         if (block)
             (void)hipFree(block);
         block = nullptr;
@@ -160,7 +178,7 @@ public:
         ctx = nullptr;
     }
     // per advected field, after the arrays of Arr: the two halves of the ping-pong (h = 0, 1; tpar says which is current), the stage buffer (2)
-    double* adv(int k, int h) const { return d[NARR + 3 * k + h]; }
+    double* adv(int k, int h) const { return d[NARR + 3 * slot[k] + h]; } // k: a row of ADVECTED that is in this run
     double* cur(int k) const { return adv(k, tpar); }
     double* curU() const { return d[par == 0 ? Ua : Ub]; }
     double* curV() const { return d[par == 0 ? Va : Vb]; }
@@ -174,7 +192,36 @@ const std::map<int, std::string> Configured<DynamicsStep>::keyMap = { { 0, "dyna
     { 10, "dynamics.devices" }, { 11, "dynamics.loopback_world" }, { 12, "dynamics.closure" }, { 13, "dynamics.min_conc" },
     { 14, "dynamics.min_thick" }, { 15, "dynamics.delta_min" }, { 16, "dynamics.subcycle" }, { 17, "dynamics.substeps" },
     { 18, "dynamics.substep_courant" }, { 19, "dynamics.max_substeps" }, { 20, "dynamics.forcing_file" },
-    { 21, "dynamics.advect_column_state" }, { 22, "dynamics.land_mask_file" } };
+    { 21, "dynamics.advect_column_state" }, { 22, "dynamics.land_mask_file" }, { 23, "dynamics.rheology" },
+    { 24, "dynamics.bbm_courant" } };
+
+// dynamics.rheology = bbm
+struct DynamicsStep::Brittle {
+    nsdg_bbm_params params;
+    double courant = NSDG_BBM_COURANT;
+    bool warned = false; // the line about an explicit dynamics.nsub below the rule's value has been printed
+};
+namespace {
+struct BbmKey {
+    const char* key;
+    double nsdg_bbm_params::*member;
+};
+const BbmKey BBM_KEYS[] = { { "bbm.young", &nsdg_bbm_params::young }, { "bbm.nu", &nsdg_bbm_params::nu }, { "bbm.p0", &nsdg_bbm_params::p0 },
+    { "bbm.lambda0", &nsdg_bbm_params::lambda0 }, { "bbm.tan_phi", &nsdg_bbm_params::tan_phi }, { "bbm.cohesion_lab", &nsdg_bbm_params::cohesion_lab },
+    { "bbm.compr_strength", &nsdg_bbm_params::compr_strength }, { "bbm.t_heal", &nsdg_bbm_params::t_heal }, { "bbm.d_max", &nsdg_bbm_params::d_max } };
+const char* const BBM_EXPONENT_KEY = "bbm.relax_exponent";
+} // namespace
+
+const std::vector<std::string>& DynamicsStep::brittleKeys()
+{
+    static const std::vector<std::string> keys = [] {
+        std::vector<std::string> k = { keyMap.at(23), keyMap.at(24), BBM_EXPONENT_KEY };
+        for (const BbmKey& b : BBM_KEYS)
+            k.push_back(b.key);
+        return k;
+    }();
+    return keys;
+}
 
 DynamicsStep::DynamicsStep() = default;
 DynamicsStep::~DynamicsStep() { release(); }
@@ -210,6 +257,10 @@ void DynamicsStep::configure()
 {
     L = getConfiguration(keyMap.at(0), 512e3);
     nsub = getConfiguration(keyMap.at(1), 120);
+    {
+        std::string raw;
+        nsubGiven = Configurator::lookup(keyMap.at(1), raw);
+    }
     alpha = getConfiguration(keyMap.at(2), 0.);
     beta = getConfiguration(keyMap.at(3), 0.);
     thermo = getConfiguration(keyMap.at(4), false);
@@ -286,9 +337,37 @@ void DynamicsStep::configure()
     if (advectColumn && !thermo)
         throw std::invalid_argument("dynamics.advect_column_state needs dynamics.thermodynamics = true: without the column model there is no "
                                     "snow or surface temperature to carry");
+    // the rheology (include/nsdg.h "brittle rheology"): its keys are read and checked here, before any device is touched
+    m_brittle.reset();
+    {
+        const std::string rheology = getConfiguration(keyMap.at(23), std::string("mevp"));
+        if (rheology != "mevp" && rheology != "bbm")
+            throw std::invalid_argument("dynamics.rheology must be mevp or bbm, got \"" + rheology + "\"");
+        if (rheology == "bbm") {
+            if (advectColumn)
+                throw std::invalid_argument("dynamics.rheology = bbm with dynamics.advect_column_state = true would advect five fields (H, A, D, S, Q); "
+                                            "a transport step carries at most " + std::to_string(NSDG_RB_MAX_FIELDS));
+            if (substeps == 0)
+                throw std::invalid_argument("dynamics.rheology = bbm with dynamics.substeps = auto: that rule is the strength wave of the mEVP "
+                                            "rheology; give an integer");
+            if (graph)
+                throw std::invalid_argument("dynamics.rheology = bbm with dynamics.graph = true: the brittle sub-cycle exchanges after every "
+                                            "sub-iteration and replays no graph");
+            m_brittle = std::make_unique<Brittle>();
+            nsdg_bbm_default_params(&m_brittle->params);
+            for (const BbmKey& k : BBM_KEYS)
+                m_brittle->params.*k.member = getConfiguration(std::string(k.key), m_brittle->params.*k.member);
+            m_brittle->params.relax_exponent = getConfiguration(std::string(BBM_EXPONENT_KEY), (int)m_brittle->params.relax_exponent);
+            if (nsdg_bbm_params_check(&m_brittle->params) != NSDG_OK)
+                throw std::invalid_argument(std::string("[bbm]: ") + nsdg_last_error());
+            m_brittle->courant = getConfiguration(keyMap.at(24), (double)NSDG_BBM_COURANT);
+            if (!(std::isfinite(m_brittle->courant) && m_brittle->courant > 0))
+                throw std::invalid_argument("dynamics.bbm_courant must be positive");
+        }
+    }
     // history output (include/HistoryOutput.hpp): the keys are read and checked here, before any device is touched; period 0 = off
     m_history.reset();
-    const HistoryOutput::Config hc = HistoryOutput::fromConfiguration(thermo);
+    const HistoryOutput::Config hc = HistoryOutput::fromConfiguration(thermo, m_brittle != nullptr);
     if (hc.on())
         m_history = std::make_unique<HistoryOutput>(hc);
     // the time series of the domain totals (SeriesOutput): the same; a multi-process run is refused here, nothing gathers its rows
@@ -396,7 +475,8 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
     // ghost depth: (v k, v k - 1) for k passes of the v-iterations-per-pass kernel between two exchanges
     const int v = NSDG_MEVP_DEFAULT_VARIANT; // the library's default kernel: sub-iterations per pass
     int k = world > 1 ? std::max(1, std::min(passesPerExchange, (nyf / world) / 16)) : 1;
-    const int depthBelow = world > 1 ? v * k : 0, depthAbove = world > 1 ? v * k - 1 : 0;
+    // (the brittle sub-cycle runs one sub-iteration per pass and exchanges after each: (1, 1))
+    const int depthBelow = world > 1 ? (m_brittle ? 1 : v * k) : 0, depthAbove = world > 1 ? (m_brittle ? 1 : v * k - 1) : 0;
     if (world > 1 && nyf < world * 2 * std::max(depthBelow, 1))
         throw std::invalid_argument("too few element rows per block for the ghost depth");
     m_blocks.clear();
@@ -457,7 +537,12 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
         b.NN = (long)(2 * b.nx + 1) * (2 * b.ny + 1);
         const long N = b.N, NN = b.NN;
         const long TS = nsdg_tiled_len(b.nx, b.ny, 8), TP = nsdg_tiled_len(b.nx, b.ny, 9);
-        b.nfields = (int)std::count_if(std::begin(ADVECTED), std::end(ADVECTED), [&](const AdvectedField& a) { return advectColumn || !a.columnState; });
+        b.nfields = 0;
+        for (int k = 0; k < NFIELD; ++k) {
+            const AdvectedField::When w = ADVECTED[k].when;
+            const bool in = w == AdvectedField::ALWAYS || (w == AdvectedField::BRITTLE && m_brittle) || (w == AdvectedField::COLUMN_STATE && advectColumn);
+            b.slot[k] = in ? b.nfields++ : -1;
+        }
         // [6][ny][nx] unless set below: VXDG, VYDG and, after the arrays of Arr, the three buffers of every advected field (DynamicsBlock::adv)
         std::vector<long> sizes(NARR + 3 * b.nfields, 6 * N);
         for (int a : { S11a, S12a, S22a, S11b, S12b, S22b })
@@ -468,6 +553,9 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
             sizes[a] = NN;
         sizes[PACKED] = 8 * NN;
         sizes[COL] = (long)NCOL * N;
+        for (int a : { HG, EG, PM })
+            sizes[a] = m_brittle ? TP : 0;
+        sizes[ZERO] = m_brittle ? NN : 0;
         long total = 0;
         for (long s : sizes)
             total += (s + 1) & ~1L; // keep every sub-array 16-byte aligned
@@ -491,10 +579,18 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
         // a restart: the state a dynamics run left (FieldStore::dyn) -- higher DG2 coefficients, velocity, stress -- for the local
         // rows, ghost rows included (they hold what an exchange would deliver: the neighbours' own values)
         const DynamicsState& dy = f.dyn;
-        for (int k = 0; k < b.nfields; ++k) {
+        for (int k = 0; k < NFIELD; ++k) {
             const AdvectedField& a = ADVECTED[k];
-            if (!a.mean)
+            if (b.slot[k] < 0 || !a.stored())
                 continue;
+            if (a.full) { // six planes of one host array; a file without it: the field starts at zero
+                if (dy.present && (dy.*a.full).size() == 6 * NG)
+                    for (int c = 0; c < 6; ++c)
+                        checkHip(hipMemcpy(b.adv(k, 0) + (long)c * N, (dy.*a.full).data() + (std::size_t)c * NG + first, N * sizeof(double), hipMemcpyHostToDevice), "upload DG coefficients");
+                else if (dy.present && &b == m_blocks[0].get() && m_rank == 0)
+                    std::printf("dynamics rheology bbm: the initial state holds no damage, the run starts undamaged (D = 0)\n");
+                continue;
+            }
             checkHip(hipMemcpy(b.adv(k, 0), (f.*a.mean).data() + first, N * sizeof(double), hipMemcpyHostToDevice), "upload cell means");
             if (!dy.present || (dy.*a.higher).size() != 5 * NG) // (a file without hsnow_dg: the higher coefficients of the snow start at zero)
                 continue;
@@ -526,8 +622,8 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
                 checkHip(hipMemcpy(b.col(c), planes[c]->data() + first, N * sizeof(double), hipMemcpyHostToDevice), "upload column fields");
         }
         if (m_landMask) { // no ice on land, no motion at land nodes, whatever the initial state or the restart file held there
-            for (int k = 0; k < b.nfields; ++k)
-                if (ADVECTED[k].mean)
+            for (int k = 0; k < NFIELD; ++k)
+                if (b.slot[k] >= 0 && ADVECTED[k].stored())
                     check(nsdg_land_clear(b.ctx, 0, b.ny, 6, b.adv(k, 0)), "nsdg_land_clear");
             if (thermo) {
                 check(nsdg_land_clear(b.ctx, 0, b.ny, 1, b.col(C_HSNOW)), "nsdg_land_clear");
@@ -562,7 +658,10 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
         m.s11[0] = b.d[S11a], m.s12[0] = b.d[S12a], m.s22[0] = b.d[S22a], m.u[0] = b.d[Ua], m.v[0] = b.d[Va];
         m.s11[1] = b.d[S11b], m.s12[1] = b.d[S12b], m.s22[1] = b.d[S22b], m.u[1] = b.d[Ub], m.v[1] = b.d[Vb];
         m.packed = b.d[PACKED], m.pg = b.d[PG];
-        check(nsdg_rb_mevp_create(b.ctx, &m, &b.mevp), "nsdg_rb_mevp_create");
+        if (m_brittle) // the brittle plan is made when the sub-iteration count of the step is known (subStep)
+            check(nsdg_bbm_params_set(b.ctx, &m_brittle->params), "nsdg_bbm_params_set");
+        else
+            check(nsdg_rb_mevp_create(b.ctx, &m, &b.mevp), "nsdg_rb_mevp_create");
         nsdg_rb_transport_desc t;
         std::memset(&t, 0, sizeof t);
         t.nx = b.nx, t.ny = b.ny, t.j0 = b.j0, t.j1 = b.j1, t.depth_below = b.depthBelow, t.depth_above = b.depthAbove;
@@ -570,8 +669,9 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
         t.order = 2, t.nfields = b.nfields;
         t.vx_dg = b.d[VXDG], t.vy_dg = b.d[VYDG], t.un_x = b.d[UNX], t.un_y = b.d[UNY];
         t.own_bounds = 1, t.nbounds = closure ? t.nfields : 0; // the closure travels with the plan (its own bounds, not the context's)
-        for (int k = 0; k < b.nfields; ++k)
-            t.phi[k] = b.adv(k, 0), t.t1[k] = b.adv(k, 1), t.t2[k] = b.adv(k, 2), t.bounds[k] = ADVECTED[k].bounds;
+        for (int k = 0; k < NFIELD; ++k)
+            if (const int at = b.slot[k]; at >= 0)
+                t.phi[at] = b.adv(k, 0), t.t1[at] = b.adv(k, 1), t.t2[at] = b.adv(k, 2), t.bounds[at] = ADVECTED[k].bounds;
         check(nsdg_rb_transport_create(b.ctx, &t, &b.transport), "nsdg_rb_transport_create");
         b.par = b.tpar = 0;
     });
@@ -637,7 +737,7 @@ void DynamicsStep::writeDrifters()
 
 // what a history sample and the row totals read: the current side of every ping-pong
 static nsdg_history_sources historySources(const DynamicsBlock& b, bool thermo, bool advectColumn)
-{
+{ // (D: the current damage of a brittle run)
     nsdg_history_sources src;
     std::memset(&src, 0, sizeof src);
     src.H = b.cur(FH), src.A = b.cur(FA), src.u = b.curU(), src.v = b.curV();
@@ -645,6 +745,8 @@ static nsdg_history_sources historySources(const DynamicsBlock& b, bool thermo, 
     src.s11 = b.d[s], src.s12 = b.d[s + 1], src.s22 = b.d[s + 2];
     if (thermo) // the snow plane the column step actually uses: plane 0 of S under dynamics.advect_column_state
         src.hsnow = advectColumn ? b.cur(FS) : b.col(C_HSNOW), src.tice = b.col(C_TICE);
+    if (b.slot[FD] >= 0)
+        src.D = b.cur(FD);
     return src;
 }
 
@@ -766,10 +868,25 @@ void DynamicsStep::subStep(double dt, bool last)
 {
     nsdg_mevp_params p;
     nsdg_mevp_default_params(&p);
-    const SubcycleChoice sc = subcycleChoice(std::min(L / nxf, L / nyf), dt);
-    p.alpha = sc.alpha, p.beta = sc.beta, p.delta_min = sc.deltaMin, p.aevp_c = sc.aevpC, p.aevp_alpha_min = sc.aevpAlphaMin;
+    if (!m_brittle) { // (the brittle pass ignores alpha, beta and the adaptive constants)
+        const SubcycleChoice sc = subcycleChoice(std::min(L / nxf, L / nyf), dt);
+        p.alpha = sc.alpha, p.beta = sc.beta, p.delta_min = sc.deltaMin, p.aevp_c = sc.aevpC, p.aevp_alpha_min = sc.aevpAlphaMin;
+    }
     p.min_conc = closure ? minConc : 0.;
     p.min_thick = closure ? minThick : 0.;
+    // the sub-iterations of a brittle (sub-)step: dynamics.nsub as given, or the elastic-wave rule for this dt
+    int bsub = nsub;
+    if (m_brittle) {
+        int32_t need = 0;
+        check(nsdg_bbm_substep_count(&m_brittle->params, p.rho_ice, std::min(L / nxf, L / nyf), dt, m_brittle->courant, 100000000, &need), "dynamics.bbm_courant");
+        if (!nsubGiven)
+            bsub = need;
+        else if (nsub < need && !m_brittle->warned && m_rank == 0) {
+            std::printf("dynamics rheology bbm: WARNING dynamics.nsub = %d is below the %d sub-iterations the elastic-wave rule asks for at dt = %g s "
+                        "(dynamics.bbm_courant = %g)\n", nsub, (int)need, dt, m_brittle->courant);
+            m_brittle->warned = true;
+        }
+    }
     const double t = m_time;
     const int kind = forcing == "winter" ? NSDG_FORCING_WINTER : NSDG_FORCING_DUMMY;
     const ForcingFile* ff = m_forcingFile.get();
@@ -805,14 +922,43 @@ void DynamicsStep::subStep(double dt, bool last)
                 // snow and the new ice (still the column phase)
                 for (double* plane : { b.cur(FH), b.cur(FA), advectColumn ? b.cur(FS) : b.col(C_HSNOW), b.col(C_NEWICE) })
                     check(nsdg_land_clear(ctx, 0, b.ny, 1, plane), "nsdg_land_clear");
+                if (m_brittle) // and the damage with them
+                    check(nsdg_land_clear(ctx, 0, b.ny, 6, b.cur(FD)), "nsdg_land_clear");
             }
         }
         check(nsdg_phase_mark(ctx, NSDG_PHASE_PREPARE), "nsdg_phase_mark");
-        check(nsdg_ice_strength(ctx, 0, b.ny, b.cur(FH), b.cur(FA), b.d[PG]), "nsdg_ice_strength");
-        check(nsdg_mevp_prepare(ctx, dt, b.cur(FH), b.cur(FA), b.d[UA], b.d[VA], b.d[UO], b.d[VO], b.curU(), b.curV(), b.d[PACKED]), "nsdg_mevp_prepare");
         int32_t out = 0;
-        check(nsdg_phase_mark(ctx, NSDG_PHASE_SUBCYCLE), "nsdg_phase_mark");
-        check(nsdg_rb_mevp_run(ctx, b.mevp, b.par, &out), "nsdg_rb_mevp_run");
+        if (m_brittle) {
+            // the Gauss arrays of the brittle sub-cycle and the mEVP packing for the sub-iteration's dt with u0 = v0 = 0: no ice strength
+            check(nsdg_bbm_prepare(ctx, 0, b.ny, b.cur(FH), b.cur(FA), b.d[HG], b.d[EG], b.d[PM]), "nsdg_bbm_prepare");
+            check(nsdg_mevp_prepare(ctx, bsub > 0 ? dt / bsub : dt, b.cur(FH), b.cur(FA), b.d[UA], b.d[VA], b.d[UO], b.d[VO], b.d[ZERO], b.d[ZERO], b.d[PACKED]),
+                "nsdg_mevp_prepare");
+            if (!b.bbm || b.bbmNsub != bsub) { // the plan holds the count: a new one when the rule gives another (another dt)
+                check(nsdg_ctx_synchronize(ctx), "DynamicsStep: brittle plan");
+                nsdg_rb_bbm_destroy(b.bbm);
+                b.bbm = nullptr;
+                nsdg_rb_bbm_desc m;
+                std::memset(&m, 0, sizeof m);
+                m.nx = b.nx, m.ny = b.ny, m.j0 = b.j0, m.j1 = b.j1, m.depth_below = b.depthBelow, m.depth_above = b.depthAbove;
+                m.rank_below = b.peerBelow, m.rank_above = b.peerAbove;
+                m.nsub = bsub, m.overlap = overlap;
+                m.complete_nodes = b.drift[0] != nullptr; // the drifters' predictor may sit in the ghost row above
+                m.s11[0] = b.d[S11a], m.s12[0] = b.d[S12a], m.s22[0] = b.d[S22a], m.u[0] = b.d[Ua], m.v[0] = b.d[Va];
+                m.s11[1] = b.d[S11b], m.s12[1] = b.d[S12b], m.s22[1] = b.d[S22b], m.u[1] = b.d[Ub], m.v[1] = b.d[Vb];
+                m.packed = b.d[PACKED], m.hg = b.d[HG], m.eg = b.d[EG], m.pm = b.d[PM];
+                // the transport's two buffers of D, and its stage buffer of D -- free between two transport steps -- as the partner
+                m.D[0] = b.adv(FD, 0), m.D[1] = b.adv(FD, 1), m.D_work = b.adv(FD, 2);
+                check(nsdg_rb_bbm_create(ctx, &m, &b.bbm), "nsdg_rb_bbm_create");
+                b.bbmNsub = bsub;
+            }
+            check(nsdg_phase_mark(ctx, NSDG_PHASE_SUBCYCLE), "nsdg_phase_mark");
+            check(nsdg_rb_bbm_run(ctx, b.bbm, b.par, b.tpar, &out), "nsdg_rb_bbm_run");
+        } else {
+            check(nsdg_ice_strength(ctx, 0, b.ny, b.cur(FH), b.cur(FA), b.d[PG]), "nsdg_ice_strength");
+            check(nsdg_mevp_prepare(ctx, dt, b.cur(FH), b.cur(FA), b.d[UA], b.d[VA], b.d[UO], b.d[VO], b.curU(), b.curV(), b.d[PACKED]), "nsdg_mevp_prepare");
+            check(nsdg_phase_mark(ctx, NSDG_PHASE_SUBCYCLE), "nsdg_phase_mark");
+            check(nsdg_rb_mevp_run(ctx, b.mevp, b.par, &out), "nsdg_rb_mevp_run");
+        }
         b.par = out;
         check(nsdg_phase_mark(ctx, NSDG_PHASE_TRANSPORT), "nsdg_phase_mark");
         check(nsdg_prepare_advection(ctx, 2, b.curU(), b.curV(), b.d[VXDG], b.d[VYDG], b.d[UNX], b.d[UNY]), "nsdg_prepare_advection");
@@ -824,8 +970,8 @@ void DynamicsStep::subStep(double dt, bool last)
         if (advectColumn)
             check(nsdg_tracer_recover(ctx, 2, 0, b.ny, b.cur(FH), b.cur(FA), b.cur(FQ), p.min_conc, p.min_thick, b.col(C_TICE)), "nsdg_tracer_recover");
         if (b.drift[0]) {
-            // the drifters of the owned rows move with the velocity the sub-cycle left (its ghost node rows are complete: the plan's ghost
-            // zones are (v k, v k - 1) deep) and the concentration the transport left; then the blocks' lists are merged.  No phase of
+            // the drifters of the owned rows move with the velocity the sub-cycle left (its ghost node rows are complete: the mEVP plan's
+            // ghost zones are (v k, v k - 1) deep, the brittle plan ends with the exchange of every node row: complete_nodes) and the concentration the transport left; then the blocks' lists are merged.  No phase of
             // its own: inside the span, before its end mark
             const int64_t n = (int64_t)(m_drifterStart.size() / 3);
             check(nsdg_drifters_advance(ctx, b.j0, b.j1, dt, m_drifters->config().minConc, n, b.curU(), b.curV(), b.cur(FA), b.drift[b.dpar], b.drift[1 - b.dpar]),
@@ -851,7 +997,10 @@ void DynamicsStep::resolvePhaseTimes()
         check(nsdg_phase_times(b.ctx, &t.table, 0), "nsdg_phase_times");
         t.hasExchange = b.peerBelow >= 0 || b.peerAbove >= 0;
         if (t.hasExchange) {
-            check(nsdg_rb_mevp_stats(b.ctx, b.mevp, &t.subcycleExchange, 0), "nsdg_rb_mevp_stats");
+            if (b.bbm) // (the plan of the last sub-iteration count)
+                check(nsdg_rb_bbm_stats(b.ctx, b.bbm, &t.subcycleExchange, 0), "nsdg_rb_bbm_stats");
+            else if (b.mevp)
+                check(nsdg_rb_mevp_stats(b.ctx, b.mevp, &t.subcycleExchange, 0), "nsdg_rb_mevp_stats");
             check(nsdg_rb_transport_stats(b.ctx, b.transport, &t.transportExchange, 0), "nsdg_rb_transport_stats");
         }
         tables.push_back(t);
@@ -960,11 +1109,17 @@ void DynamicsStep::stop(const Iterator::TimePoint&)
             dy.resize((std::size_t)nyf, (std::size_t)nxf);
         for (int k = 0; k < NFIELD; ++k) {
             const AdvectedField& a = ADVECTED[k];
-            if (!a.mean)
+            if (!a.stored())
                 continue;
+            if (a.full) { // all six planes in one host array, which exists only while the field is advected
+                (dy.*a.full).resize(b.slot[k] >= 0 ? 6 * NG : 0, 0.);
+                for (int c = 0; c < 6 && b.slot[k] >= 0; ++c)
+                    checkHip(hipMemcpy((dy.*a.full).data() + (std::size_t)c * NG + first, b.cur(k) + (long)c * b.N + skip, count * sizeof(double), hipMemcpyDeviceToHost), "download DG coefficients");
+                continue;
+            }
             // the higher coefficients of a field exist only while it is advected: otherwise nothing of them is written
-            (dy.*a.higher).resize(k < b.nfields ? 5 * NG : 0, 0.);
-            if (k >= b.nfields)
+            (dy.*a.higher).resize(b.slot[k] >= 0 ? 5 * NG : 0, 0.);
+            if (b.slot[k] < 0)
                 continue;
             checkHip(hipMemcpy((f.*a.mean).data() + first, b.cur(k) + skip, count * sizeof(double), hipMemcpyDeviceToHost), "download cell means");
             for (int c = 1; c < 6; ++c)
@@ -1053,17 +1208,21 @@ void DynamicsStep::writeRestartFile(const std::string& filePath)
 
 namespace {
 // What a rank sends for its rows [r0, r1), in order: fn(array, offset, length) for the rows of every prognostic plane a run changes; then,
-// unless state < 0, of what DynamicsState owns of DYNAMICS_VARIABLES with its first `state` optional ones -- the rows of every element
-// plane, and of a nodal array the node rows the block owns: [2 r0, 2 r1) and the top boundary row on the last block
+// unless state < 0, of what DynamicsState owns of DYNAMICS_VARIABLES with the optional ones whose bit is set in `state` (bit i: the i-th
+// optional variable of the table) -- the rows of every element plane, and of a nodal array the node rows the block owns: [2 r0, 2 r1) and
+// the top boundary row on the last block
 template <class F> void forPayload(FieldStore& f, bool thermodynamics, int nx, int r0, int r1, int state, F&& fn)
 {
     const std::size_t first = (std::size_t)r0 * nx, rows = (std::size_t)(r1 - r0) * nx, nn = 2 * (std::size_t)nx + 1;
     for (auto* p : { &f.hice, &f.cice, &f.hsnow, &f.tice, &f.newice })
         if (thermodynamics || p == &f.hice || p == &f.cice) // (the column model's planes change only with it)
             fn(*p, first, rows);
+    if (state < 0)
+        return;
+    int bit = 0;
     for (const DynamicsVariable& v : DYNAMICS_VARIABLES) {
-        if (state < 0 || (v.optional() && state-- == 0))
-            break;
+        if (v.optional() && !((state >> bit++) & 1))
+            continue;
         if (!v.state)
             continue; // a plane of the FieldStore: it has travelled above, or does not travel
         if (v.shape == DynamicsVariable::NODAL)
@@ -1076,9 +1235,10 @@ template <class F> void forPayload(FieldStore& f, bool thermodynamics, int nx, i
 
 std::vector<double> DynamicsStep::packRows(FieldStore& f, bool thermodynamics, int nx, int r0, int r1)
 {
-    int state = f.dyn.present ? 0 : -1; // the state of the dynamics travels with the rows, with the optional variables it holds
+    int state = f.dyn.present ? 0 : -1, bit = 0; // the state of the dynamics travels with the rows, with the optional variables it holds
     for (const DynamicsVariable& v : DYNAMICS_VARIABLES)
-        state += f.dyn.present && v.optional() && !v.in(f).empty();
+        if (v.optional())
+            state |= (f.dyn.present && !v.in(f).empty() ? 1 : 0) << bit++;
     std::vector<double> out;
     forPayload(f, thermodynamics, nx, r0, r1, state, [&](std::vector<double>& a, std::size_t at, std::size_t length) { out.insert(out.end(), a.begin() + at, a.begin() + at + length); });
     return out;
@@ -1086,11 +1246,12 @@ std::vector<double> DynamicsStep::packRows(FieldStore& f, bool thermodynamics, i
 
 void DynamicsStep::placeRows(FieldStore& f, bool thermodynamics, int nx, int r0, int r1, const double* data, std::size_t count)
 {
-    // what a rank sent shows in the size alone: its planes, or also the state of the dynamics with none, one, ... of its optional variables
+    // what a rank sent shows in the size alone: its planes, or also the state of the dynamics with one of the sets of its optional
+    // variables (their sizes differ, and a run holds the snow or the damage, never both: the first set that fits is the one)
     const int optional = (int)std::count_if(std::begin(DYNAMICS_VARIABLES), std::end(DYNAMICS_VARIABLES), [](const DynamicsVariable& v) { return v.optional(); });
     std::string sizes;
     int state = -2; // as forPayload reads it, once found
-    for (int k = -1; k <= optional && state < -1; ++k) {
+    for (int k = -1; k < (1 << optional) && state < -1; ++k) {
         std::size_t size = 0;
         forPayload(f, thermodynamics, nx, r0, r1, k, [&](std::vector<double>&, std::size_t, std::size_t length) { size += length; });
         if (size == count)
@@ -1099,11 +1260,14 @@ void DynamicsStep::placeRows(FieldStore& f, bool thermodynamics, int nx, int r0,
     }
     if (state < -1)
         throw std::runtime_error("DynamicsStep: a rank delivered " + std::to_string(count) + " values for its rows, expected one of" + sizes
-            + " (its planes alone, with the state of the dynamics, with each optional variable of that as well)");
-    int optionals = state;
-    for (const DynamicsVariable& v : DYNAMICS_VARIABLES) // whatever of the delivered state nothing has filled yet starts at zero
-        if (state >= 0 && v.state && (!v.optional() || optionals-- > 0) && v.in(f).size() != v.size(f.n / nx, (std::size_t)nx))
+            + " (its planes alone, with the state of the dynamics, with each set of the optional variables of that as well)");
+    int bit = 0;
+    for (const DynamicsVariable& v : DYNAMICS_VARIABLES) { // whatever of the delivered state nothing has filled yet starts at zero
+        const bool sent = !v.optional() || (state >= 0 && ((state >> bit) & 1));
+        bit += v.optional();
+        if (state >= 0 && v.state && sent && v.in(f).size() != v.size(f.n / nx, (std::size_t)nx))
             v.in(f).assign(v.size(f.n / nx, (std::size_t)nx), 0.);
+    }
     f.dyn.present = f.dyn.present || state >= 0;
     forPayload(f, thermodynamics, nx, r0, r1, state, [&](std::vector<double>& a, std::size_t at, std::size_t length) {
         std::copy(data, data + length, a.begin() + at);

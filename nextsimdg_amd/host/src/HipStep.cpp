@@ -1,5 +1,8 @@
 #include "HipStep.hpp"
 
+#include "Configurator.hpp"
+#include "DynamicsStep.hpp"
+
 #include <hip/hip_runtime.h>
 
 #include <stdexcept>
@@ -50,6 +53,12 @@ void HipStep::init()
     HistoryOutput::refuseFor("Nextsim::HipStep"); // before a device is touched: the column step alone writes no history output ...
     SeriesOutput::refuseFor("Nextsim::HipStep"); // ... and no time series
     DriftersOutput::refuseFor("Nextsim::HipStep"); // ... and has no velocity to move drifters with
+    {
+        std::string raw; // ... and no rheology: the keys of the brittle one are the dynamics step's
+        for (const std::string& key : DynamicsStep::brittleKeys())
+            if (Configurator::lookup(key, raw))
+                throw std::invalid_argument(key + " is set, but Nextsim::HipStep runs the column step alone: select Nextsim::DynamicsStep");
+    }
     if (!ctx)
         check(nsdg_ctx_create(0, nullptr, &ctx), "HipStep::init");
     phaseTiming = PhaseTiming::enabled();

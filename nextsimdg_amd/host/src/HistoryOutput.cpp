@@ -85,7 +85,7 @@ void fromHeader(const std::map<std::string, std::string>& h, const std::string& 
 }
 } // namespace
 
-HistoryOutput::Config HistoryOutput::fromConfiguration(bool thermodynamics)
+HistoryOutput::Config HistoryOutput::fromConfiguration(bool thermodynamics, bool brittle)
 {
     typedef Configured<Keys> C;
     Config c;
@@ -138,8 +138,8 @@ HistoryOutput::Config HistoryOutput::fromConfiguration(bool thermodynamics)
                 throw std::invalid_argument(std::string(KEY_FIELDS) + ": field \"" + entry + "\" is listed twice");
         if ((id == NSDG_HIST_HSNOW || id == NSDG_HIST_TICE) && !thermodynamics)
             throw std::invalid_argument(std::string(KEY_FIELDS) + ": field \"" + name + "\" is column state: it needs dynamics.thermodynamics = true");
-        if (id == NSDG_HIST_DAMAGE)
-            throw std::invalid_argument(std::string(KEY_FIELDS) + ": field \"damage\" belongs to the brittle rheology, which this host does not run");
+        if (id == NSDG_HIST_DAMAGE && !brittle)
+            throw std::invalid_argument(std::string(KEY_FIELDS) + ": field \"damage\" belongs to the brittle rheology: it needs dynamics.rheology = bbm");
         c.ids.push_back(id);
         c.stats.push_back(stat);
     }

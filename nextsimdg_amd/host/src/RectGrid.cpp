@@ -143,7 +143,7 @@ namespace {
 const char* const PLANE_NAMES[5] = { "hice", "cice", "hsnow", "sst", "sss" }; // core/src/DevGridIO.cpp:35-40
 const char* const DYNAMICS_FLAG = "data.dynamics"; // sidecar header: the variables of DYNAMICS_VARIABLES follow tice
 // the named dimensions of each DynamicsVariable::Shape in an HDF5 file, slowest first (x, y: the grid's own)
-const std::vector<const char*> SHAPE_DIMENSIONS[] = { { "dg2", "x", "y" }, { "stress8", "x", "y" }, { "x", "y" }, { "xnode", "ynode" } };
+const std::vector<const char*> SHAPE_DIMENSIONS[] = { { "dg2", "x", "y" }, { "stress8", "x", "y" }, { "x", "y" }, { "xnode", "ynode" }, { "dg2full", "x", "y" } };
 // the variables of the dynamics state a file of `f` holds: all of them, the optional ones when they are not empty
 bool written(const DynamicsVariable& v, const FieldStore& f) { return !v.optional() || !v.in(f).empty(); }
 } // namespace
@@ -174,10 +174,13 @@ void RectGrid::dump(const std::string& filePath) const
         w.attachDimensions(data + "/tice", { data + "/x", data + "/y", data + "/nLayers" }); // DevGridIO.cpp:192-201
         if (m_store.dyn.present) { // the state of the dynamics: further variables of the same group (DYNAMICS_VARIABLES)
             const std::uint64_t X = (std::uint64_t)m_nx, Y = (std::uint64_t)m_ny;
-            const std::map<std::string, std::uint64_t> length = { { "x", X }, { "y", Y }, { "dg2", 5 }, { "stress8", 8 }, { "xnode", 2 * X + 1 }, { "ynode", 2 * Y + 1 } };
+            const std::map<std::string, std::uint64_t> length = { { "x", X }, { "y", Y }, { "dg2", 5 }, { "stress8", 8 }, { "xnode", 2 * X + 1 }, { "ynode", 2 * Y + 1 }, { "dg2full", 6 } };
             int dimid = 3; // the further dimensions follow x, y, nLayers
             for (const char* d : { "dg2", "stress8", "xnode", "ynode" })
                 w.dimension(data, d, length.at(d), dimid++);
+            for (const DynamicsVariable& v : DYNAMICS_VARIABLES) // the dimension of the damage exists only in a file that holds it
+                if (v.shape == DynamicsVariable::DG6 && written(v, m_store))
+                    w.dimension(data, "dg2full", length.at("dg2full"), dimid++);
             for (const DynamicsVariable& v : DYNAMICS_VARIABLES) {
                 if (!written(v, m_store))
                     continue;

@@ -295,6 +295,7 @@ class DynamicsCore:
 
     LAND_OPS = ("set_land_mask", "land_clear", "land_clear_nodes")
     BBM_OPS = ("bbm_prepare", "bbm_iterate")
+    BBM_NATIVE_OPS = ("rb_bbm", "rb_transport")
     DAMAGE_BOUNDS = (0.0, 1.0, False)  # the damage D of the brittle rheology: in [0, 1], no cap of the cell mean
     HISTORY_COLUMN_FIELDS = outputs.History.COLUMN_FIELDS
     HAS_COLUMN_STATE = False
@@ -346,8 +347,9 @@ class DynamicsCore:
         # the outputs (nextsimdg_amd/outputs.py), each an object or None; history and series: the names, as given
         self._history = None if history is None else outputs.History(history, ops, blk, device, rheology, self.TRANSPORTED, self.HAS_COLUMN_STATE)
         self._series = None if series is None else outputs.Series(series, series_capacity, extent_conc, ops, blk, device, self.HAS_COLUMN_STATE)
+        # a single-iteration sub-cycle leaves ghost node rows stale: the drifters complete them, unless the native plan does
         self._drifters = None if drifters is None else outputs.Drifters(drifters, drifter_min_conc, ops, blk, hx, hy, self.halo, device,
-                                                                         complete_ghosts=self.per_pass == 1)
+                                                                         complete_ghosts=self.per_pass == 1 and not self._plan_completes_nodes())
         self.history = self._history.entries if self._history is not None else None
         self.series = self._series.names if self._series is not None else None
         self.series_capacity, self.extent_conc, self.drifter_min_conc = int(series_capacity), float(extent_conc), float(drifter_min_conc)
@@ -394,8 +396,10 @@ class DynamicsCore:
             raise ValueError("rheology must be 'mevp' or 'bbm', got %r" % (rheology,))
         self.rheology = rheology
         if rheology == "bbm":
+            if self.use_graph:
+                raise ValueError("use_graph=True needs rheology='mevp': the brittle sub-cycle exchanges after every sub-iteration and replays no graph")
             if self.native:
-                raise ValueError("rheology='bbm' is not built in the native row-block plan (nsdg_rb_mevp_*): use native=False")
+                outputs.require_ops(self.ops, self.BBM_NATIVE_OPS, "rheology='bbm' with native=True", "native row-block calls")
             if blk.world > 1 and (blk.depth_below, blk.depth_above) != (1, 1):
                 raise ValueError("rheology='bbm' runs one sub-iteration per pass: a row block needs the ghost depth (1, 1), got (%d, %d)"
                                  % (blk.depth_below, blk.depth_above))
@@ -444,16 +448,32 @@ class DynamicsCore:
             raise ValueError("drifters_read() needs a core constructed with drifters=")
         return self._drifters.read()
 
+    def _plan_completes_nodes(self):
+        """the native brittle plan ends its call with the exchange of every ghost node row (nsdg_rb_bbm_desc.complete_nodes): the one place
+        that says who completes them, asked by the drifters' constructor and by _init_native"""
+        return self.native and self.rheology == "bbm"
+
     def _init_native(self):
         b = self.blk
         if b.world > 1 and not isinstance(self.halo, NativeHaloExchanger):
             raise ValueError("the native driver exchanges ghost rows through the C ABI: pass a NativeHaloExchanger")
         peers = (self.halo.peer_below, self.halo.peer_above) if b.world > 1 else (None, None)
         self._sbuf, self._uvbuf, self._par = (self.s, self.sb), ((self.u, self.v), (self.ub, self.vb)), 0
-        self._run_mevp, per_pass, group = self.ops.rb_mevp(b, peers, self.nsub, self.overlap, self.use_graph, self._sbuf, self._uvbuf,
-                                                           self.packed, self.pg)
-        assert (per_pass, group) == (self.per_pass, self.group_passes), "native plan and driver disagree on the pass structure"
         self._fbuf, self._tpar = (self._fields(), tuple(self.t1)), 0
+        if self.rheology == "bbm":
+            # the brittle plan (nsdg_rb_bbm_*): the damage ends in the transport's current buffer of D, whatever nsub; Db is its partner
+            # inside the call.  With drifters the plan completes the ghost node rows of the final velocity itself.  (_run_mevp: the
+            # sub-cycle plan of either rheology, under the name the exchange statistics are read by)
+            k = self.TRANSPORTED.index("D")
+            plan = self._run_mevp = self.ops.rb_bbm(b, peers, self.nsub, self.overlap, self._sbuf, self._uvbuf, self.packed,
+                                                    (self.hg, self.eg, self.pm), (self._fbuf[0][k], self._fbuf[1][k]), self.Db,
+                                                    complete_nodes=self._plan_completes_nodes() and self._drifters is not None)
+            self._run_subcycle = lambda par: plan(par, self._tpar)  # the transport's parity of the moment: where D is
+        else:
+            self._run_mevp, per_pass, group = self.ops.rb_mevp(b, peers, self.nsub, self.overlap, self.use_graph, self._sbuf, self._uvbuf,
+                                                               self.packed, self.pg)
+            assert (per_pass, group) == (self.per_pass, self.group_passes), "native plan and driver disagree on the pass structure"
+            self._run_subcycle = self._run_mevp
         self._run_transport = self.ops.rb_transport(b, peers, self._fbuf[0], self._fbuf[1], self.t2, self.adv, bounds=self.BOUNDS if self.closure else ())
 
     def _fields(self):
@@ -472,6 +492,7 @@ class DynamicsCore:
             if run is not None and hasattr(run, "close"):
                 run.close()
             setattr(self, name, None)
+        self._run_subcycle = None
         if self._bounds_before is not None:  # the context is as this core found it
             self.ops.set_transport_bounds(self._bounds_before)
             self._bounds_before = None
@@ -565,10 +586,11 @@ class DynamicsCore:
         return full, rest // 2, rest % 2
 
     def subcycle(self):
-        """the nsub mEVP sub-iterations of one model step (ghost rows exchanged as the ghost depth requires)"""
+        """the nsub sub-iterations of one model step, mEVP or brittle (ghost rows exchanged as the ghost depth requires)"""
         ops, b = self.ops, self.blk
         if self.native:
-            par = self._par = self._run_mevp(self._par)
+            # (the brittle plan leaves D where the transport plan reads it: self.D stays the current buffer)
+            par = self._par = self._run_subcycle(self._par)
             self.s, self.sb = self._sbuf[par], self._sbuf[1 - par]
             (self.u, self.v), (self.ub, self.vb) = self._uvbuf[par], self._uvbuf[1 - par]
             return

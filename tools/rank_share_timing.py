@@ -1,7 +1,7 @@
 """Diagnostic: GPU time of ONE rank's share of the 2048x2048 dynamics step for a world of W row blocks, measured
 on a single GPU with the ghost exchanges replaced by no-ops (the values in the ghost rows go stale, only the
 timing is meaningful).  Gives the compute-side bound on the strong-scaling speed-up that the 8-GPU run of the
-driver can reach: T(1 block) / T(share).  usage: python tools/rank_share_timing.py [--native [--graph]] [--halo native|torch] [--rccl-loopback] [--no-overlap] [--k K,...] [W ...]"""
+driver can reach: T(1 block) / T(share).  usage: python tools/rank_share_timing.py [--bbm] [--native [--graph]] [--halo native|torch] [--rccl-loopback] [--no-overlap] [--k K,...] [W ...]"""
 import gc
 import os
 import sys
@@ -46,7 +46,7 @@ def check_loopback_values(core):
     return n
 
 
-def run(world, kpass, nx=GRID, ny=GRID, nsub=NSUB, steps=3, overlap=True, loopback=False, halo="native", native=False, graph=False):
+def run(world, kpass, nx=GRID, ny=GRID, nsub=NSUB, steps=3, overlap=True, loopback=False, halo="native", native=False, graph=False, rheology="mevp"):
     dev = torch.device("cuda:0")
     ctx = abi.Context(dev)
     L, dt = 512e3, 120.0
@@ -56,7 +56,7 @@ def run(world, kpass, nx=GRID, ny=GRID, nsub=NSUB, steps=3, overlap=True, loopba
         ctx.set_mevp_variant(int(os.environ["NSDG_SHARE_VARIANT"]))
     rank = world // 2
     v = min(ctx.mevp_variant, 4)  # sub-iterations per kernel pass
-    depth = (v * kpass, v * kpass - 1)
+    depth = (v * kpass, v * kpass - 1) if rheology == "mevp" else (1, 1)  # the brittle sub-cycle: one sub-iteration per pass
     blk = rowblock.RowBlock(nx, ny, rank, world, *depth)
     exchanger = None
     if world > 1 and loopback:  # real RCCL send/recv, both neighbours = this rank (periodic wrap: values meaningless)
@@ -71,7 +71,7 @@ def run(world, kpass, nx=GRID, ny=GRID, nsub=NSUB, steps=3, overlap=True, loopba
         exchanger = NullExchanger(blk)
     if native and world > 1 and not isinstance(exchanger, rowblock.NativeHaloExchanger):
         raise SystemExit("--native needs --rccl-loopback with the native halo (or world 1)")
-    core = rowblock.DynamicsCore(ctx, blk, L / nx, L / ny, dt, nsub, dev, exchanger=exchanger, overlap=overlap, native=native, use_graph=graph)
+    core = rowblock.DynamicsCore(ctx, blk, L / nx, L / ny, dt, nsub, dev, exchanger=exchanger, overlap=overlap, native=native, use_graph=graph, rheology=rheology)
     H, A = bt.dg_fields()
     uo, vo = bt.ocean()
     ua, va = bt.wind(0.0)
@@ -93,7 +93,10 @@ def run(world, kpass, nx=GRID, ny=GRID, nsub=NSUB, steps=3, overlap=True, loopba
 if __name__ == "__main__":
     ks = (1, 4)
     args = sys.argv[1:]
-    overlap, loopback, halo, native, graph = True, False, "native", False, False
+    overlap, loopback, halo, native, graph, rheology = True, False, "native", False, False, "mevp"
+    if args and args[0] == "--bbm":  # the brittle sub-cycle: ghost depth (1, 1), an exchange after every sub-iteration
+        rheology, ks = "bbm", (1,)
+        args = args[1:]
     if args and args[0] == "--native":  # sub-cycle and transport as one C call each (csrc/rowblock.hip)
         native = True
         args = args[1:]
@@ -123,9 +126,9 @@ if __name__ == "__main__":
     base = None
     for w in worlds:
         for k in ((1,) if w == 1 else ks):
-            ms, host_ms, rows = run(w, k, overlap=overlap, loopback=loopback, halo=halo, native=native, graph=graph)
+            ms, host_ms, rows = run(w, k, overlap=overlap, loopback=loopback, halo=halo, native=native, graph=graph, rheology=rheology)
             base = ms if w == 1 else base
-            print(("native driver%s  " % (" + graphs" if graph else "") if native else "") + ("RCCL loopback (%s halo)  " % halo if loopback else "") + ("" if overlap else "no-overlap  ") + "world %d  passes/exchange %d  local rows %4d  step %7.3f ms  (host issue %6.3f ms)  speed-up bound %s"
+            print(("bbm  " if rheology == "bbm" else "") + ("native driver%s  " % (" + graphs" if graph else "") if native else "") + ("RCCL loopback (%s halo)  " % halo if loopback else "") + ("" if overlap else "no-overlap  ") + "world %d  passes/exchange %d  local rows %4d  step %7.3f ms  (host issue %6.3f ms)  speed-up bound %s"
                   % (w, k, rows, ms, host_ms, "%.2f" % (base / ms) if base else "-"), flush=True)
     if loopback and halo == "torch":
         import torch.distributed as dist

@@ -59,7 +59,8 @@ extern "C" {
  * nsdg_bbm_prepare / nsdg_bbm_iterate / nsdg_bbm_substep_count (brittle rheology) and nsdg_history_accumulate / nsdg_history_field_name /
  * nsdg_history_field_id, nsdg_history_accumulate_stats / nsdg_history_row_totals / nsdg_history_stat_* / nsdg_history_series_* (history
  * output) and nsdg_drifters_advance / nsdg_comm_max_f64_array (drifters) and nsdg_rb_bbm_create / nsdg_rb_bbm_destroy / nsdg_rb_bbm_run /
- * nsdg_rb_bbm_stats (the brittle sub-cycle of a row block) and nsdg_bbm_params_check are additions; nothing that existed changed. */
+ * nsdg_rb_bbm_stats (the brittle sub-cycle of a row block) and nsdg_bbm_params_check and nsdg_points_sample (point samples) are additions;
+ * nothing that existed changed. */
 #define NSDG_ABI_VERSION 6
 
 typedef enum {
@@ -675,7 +676,7 @@ enum {
     NSDG_HIST_SIGMA_S, NSDG_HIST_HSNOW, NSDG_HIST_TICE, NSDG_HIST_DAMAGE, NSDG_HIST_COUNT
 };
 typedef struct {
-    const double *H, *A; /* DG fields: plane 0 is read */
+    const double *H, *A; /* DG fields: plane 0 is read (nsdg_points_sample: every plane of its order) */
     const double *u, *v; /* CG2 velocity */
     const double *s11, *s12, *s22; /* tiled stress */
     const double *hsnow, *tice; /* one plane each (plane 0 of the snow field S under column state transport) */
@@ -763,6 +764,54 @@ int nsdg_history_series_id(const char* name);
  *   row.  The velocity must be valid on those rows (node rows 2 (j0 - 1) .. 2 (j1 + 1)).  The call belongs to no phase of the phase table. */
 int nsdg_drifters_advance(nsdg_ctx* ctx, int32_t j0, int32_t j1, double dt, double min_conc, int64_t n, const double* u, const double* v,
     const double* A, const double* d_in, double* d_out);
+
+/* ---- point samples: the model at drifter positions and at fixed stations (csrc/points.hip) ---------------------------
+ * No counterpart in the reference snapshot.  What did the buoy see along its track, what passed over this mooring?  Everything a sample needs
+ * is on the device at the end of every step and local to the point's own element.
+ *
+ * nsdg_points_sample: ONE launch on the context's stream, one lane per point, no atomics, no LDS.  x, y: device arrays of n GLOBAL coordinates
+ * in metres (the domain of "drifters"; planes 0 and 1 of a drifter array d[3][n] can be passed as they are).  fields: nfields ids of
+ * NSDG_HIST_* (the names of nsdg_history_field_name); src: the struct the history calls take, with H, A, D the DG fields of `order` p
+ * (1 / 3 / 6 coefficient planes f[c N + e], N = nx ny of the local array) and every plane read.  The result is
+ *     out[k * out_stride + p]   for field k and point p;  no other slot of out is written.
+ * For every point (x, y), in THIS order:
+ *   1. element     ix = min(nx - 1, (int)floor(x / hx)),  iyg = min(ny_global - 1, (int)floor(y / hy))  -- IEEE divisions, never a reciprocal:
+ *                  who owns a point must be the same decision on every rank; the local row is iy = iyg - row0.  (An index is also never
+ *                  below 0: a coordinate below 0 or a NaN, which the hosts refuse, never becomes an address.)
+ *   2. ownership   iy outside [j0, j1): the point is not this launch's -- every one of its nfields slots gets -inf.  Every other case writes
+ *                  all of them, so the elementwise maximum over the launches of a decomposition is the whole table, as for the drifters.
+ *   3. local       xi = x / hx - ix - 1/2,  eta = y / hy - iyg - 1/2, the quotient rounded once and both subtractions exact.  A point on the
+ *                  domain's upper edge has xi = +1/2 (eta = +1/2) in the last element.
+ *   4. samples     taken AT THE POINT, not at the cell centre:
+ *      hice, cice, damage   the DG field with the basis of DESIGN.md section 3,
+ *                               c0 + c1 xi + c2 eta + c3 (xi^2 - 1/12) + c4 (eta^2 - 1/12) + c5 xi eta     (order 0: c0; order 1: the first three),
+ *                           summed in this order, unclamped.
+ *      hsnow, tice          the element's value of their one plane.
+ *      u, v                 V(x, y) exactly as rule 5 of nsdg_drifters_advance states it: the weights L-, L0, L+ of the nodes at -1/2, 0, +1/2,
+ *                           the rows bottom to top, a row west to east.  speed = sqrt(u u + v v).
+ *      divergence, shear    from the derivatives of the same biquadratic at the point, with L-'(t) = 4 t - 1, L0'(t) = -8 t, L+'(t) = 4 t + 1:
+ *                               e11 = (1/hx) sum_r L_r(eta) sum_c L_c'(xi) u_rc,     e22 = (1/hy) sum_r L_r'(eta) sum_c L_c(xi) v_rc,
+ *                               g   = (1/hy) sum_r L_r'(eta) sum_c L_c(xi) u_rc  +  (1/hx) sum_r L_r(eta) sum_c L_c'(xi) v_rc
+ *                           (the sums formed first, then ONE IEEE division by hx or hy each);
+ *                               divergence = e11 + e22,   shear = sqrt((e11 - e22)^2 + g g)      [1/s].
+ *                           At an element centre these are the samples of the history output.
+ *      sigma_n, sigma_s     the three stress components evaluated at the point with all EIGHT basis functions -- the six above, then
+ *                           eta (xi^2 - 1/12) and xi (eta^2 - 1/12) -- read from the tiled arrays, a[T + (c/2) 128 + 2 l + c%2] in "Data layout";
+ *                           then (s11 + s22) / 2 and sqrt((s11 - s22)^2 / 4 + s12^2).  The unit is whatever the rheology stores, as for the history.
+ *      Every operation is one fp64 operation (IEEE add, multiply, divide; the device's square root); the device may contract a product and
+ *      a sum into an FMA.  A NaN source gives a NaN sample of the fields that read it, at the points of its element and nowhere else.
+ *   5. Every source value is loaded at most once per point, whatever the list.
+ * What is read: the point's own element only -- for the velocity the node rows 2 iy .. 2 iy + 2 of OWNED rows.  The top node row of the last
+ *   owned row is the one ghost node row a single-iteration sub-cycle does receive, so no ghost row has to be valid and
+ *   no exchange of complete node rows (nsdg_rb_bbm_desc.complete_nodes, the drifters' own) is needed for a sample.
+ * Checks, as for the history calls: grid set (else NSDG_ERR_STATE); 0 <= j0 <= j1 <= ny; order in 0..2; n >= 0; 1 <= nfields <=
+ *   NSDG_HISTORY_MAX_FIELDS; fields and src non-null; known ids, no id twice; a field whose source pointer is NULL is refused with a message
+ *   that names the field and the source (sources no listed field reads may be NULL); out_stride >= n; x, y, out non-null unless n == 0:
+ *   NSDG_ERR_ARG.  n == 0 launches nothing (and x, y, out may then be NULL).  j0 == j1 is NOT nothing: an empty row range owns no point,
+ *   so it writes -inf into all nfields slots of all n points.  The call belongs to no phase of the phase table: the hosts make it after
+ *   their NSDG_PHASE_END mark or, for the drifters, where they advance them. */
+int nsdg_points_sample(nsdg_ctx* ctx, int32_t j0, int32_t j1, int32_t order, int64_t n, const double* x, const double* y, int32_t nfields,
+    const int32_t* fields, const nsdg_history_sources* src, int64_t out_stride, double* out);
 
 /* ---- row-block decomposition: ghost-row exchange (SURVEY.md section 8(b) "nsdg_halo_exchange", 8(e)) ----------
  * The reference is a single-process, single-thread program; these entry points have no

@@ -93,6 +93,10 @@ class HistorySources(C.Structure):
 # drifters (include/nsdg.h "drifters"): the status values of plane 2, and the lanes per workgroup of the launch (csrc/drifters.hip)
 DRIFTER_ACTIVE, DRIFTER_LEFT, DRIFTER_NO_ICE, DRIFTER_LAND = 0, 1, 2, 3
 DRIFTERS_BLOCK = 256
+# point samples (include/nsdg.h "point samples"): the lanes per workgroup of the launch (csrc/points.hip), and what a field reads
+POINTS_BLOCK = 256
+POINTS_SOURCES = {"hice": ("H",), "cice": ("A",), "u": ("u",), "v": ("v",), "speed": ("u", "v"), "divergence": ("u", "v"), "shear": ("u", "v"),
+                  "sigma_n": ("s11", "s22"), "sigma_s": ("s11", "s12", "s22"), "hsnow": ("hsnow",), "tice": ("tice",), "damage": ("D",)}
 
 COMM_ID_BYTES = 128
 RB_MAX_FIELDS = 4
@@ -182,6 +186,7 @@ SYMBOLS = {
     "nsdg_history_series_name": (C.c_char_p, [I32]),
     "nsdg_history_series_id": (C.c_int, [C.c_char_p]),
     "nsdg_drifters_advance": (C.c_int, [VP, I32, I32, D, D, I64] + [VP] * 5),
+    "nsdg_points_sample": (C.c_int, [VP, I32, I32, I32, I64, VP, VP, I32, C.POINTER(I32), C.POINTER(HistorySources), I64, VP]),
     "nsdg_boxtest_forcing": (C.c_int, [VP, D, D, VP, VP, VP, VP]),
     "nsdg_block_set": (C.c_int, [VP, I32, I32]),
     "nsdg_column_forcing": (C.c_int, [VP, I32, D] + [VP] * 7),
@@ -953,6 +958,31 @@ class Context:
             raise NsdgError("drifters_advance: A has %d values, the grid needs %d" % (A.numel(), self.nx * self.ny))
         self._call(self.lib.nsdg_drifters_advance(self.h, j0, j1, float(dt), float(min_conc), d_in.shape[1], _ptr(u), _ptr(v), _ptr(A),
                                                   _ptr(d_in), _ptr(d_out)))
+
+    # ---- point samples (include/nsdg.h "point samples"; csrc/points.hip)
+    def points_sample(self, j0, j1, order, x, y, fields, sources, out):
+        """nsdg_points_sample: out[k, p] = field k (names of HISTORY_FIELDS) at the point (x[p], y[p]) -- global coordinates in metres -- for
+        the points whose element lies in the local rows [j0, j1), -inf for every other point.  x, y: [n] with unit stride (planes of a
+        drifter array are fine); out: [len(fields), n] with unit stride along the points (a slot of a larger buffer is fine).  sources: as
+        history_accumulate, but H, A, D hold all the coefficient planes of `order` (1 / 3 / 6) and every one is read"""
+        import torch
+
+        ids = self._history_ids(fields, HISTORY_FIELDS, "history field")
+        src = self._history_sources("points_sample", sources, x, y)
+        n, nc = x.numel(), (1, 3, 6)[order] if order in (0, 1, 2) else 1
+        for name in ("H", "A", "D"):  # the ABI takes bare pointers
+            t = sources.get(name)
+            if t is not None and t.numel() < nc * self.nx * self.ny:
+                raise NsdgError("points_sample: source %s has %d values, order %d needs %d" % (name, t.numel(), order, nc * self.nx * self.ny))
+        if x.dim() != 1 or y.dim() != 1 or y.numel() != n or (n > 1 and (x.stride(0) != 1 or y.stride(0) != 1)):
+            raise NsdgError("points_sample: x and y must be [n] arrays of one length with unit stride, got %s and %s" % (tuple(x.shape), tuple(y.shape)))
+        if out.dtype != torch.float64 or not out.is_cuda:
+            raise NsdgError("expected a float64 CUDA tensor")
+        if out.dim() != 2 or tuple(out.shape) != (len(fields), n) or (n > 1 and out.stride(1) != 1) or (len(fields) > 1 and out.stride(0) < n):
+            raise NsdgError("points_sample: out has shape %s and strides %s, expected [%d, %d] with unit stride along the points"
+                            % (tuple(out.shape), tuple(out.stride()), len(fields), n))
+        self._call(self.lib.nsdg_points_sample(self.h, j0, j1, order, n, x.data_ptr(), y.data_ptr(), len(fields), ids, C.byref(src),
+                                               max(out.stride(0), n) if len(fields) > 1 else n, out.data_ptr()))
 
     def boxtest_forcing(self, domain_size, t, wind=None, ocean=None):
         ts = list(wind or (None, None)) + list(ocean or (None, None))

@@ -14,6 +14,11 @@
 //     model.drifters_period    seconds between two blocks, a multiple of model.time_step; 0 (the default): one block, at stop().  stop()
 //                              always writes the block of its time unless a period has just written it
 //     model.drifters_min_conc  the cell-mean concentration below which a drifter has lost its ice (0.15)
+//     model.drifters_fields    a comma-separated list of the history's field names (include/Stations.hpp: the list the stations share),
+//                              sampled AT the new position of every drifter after every (sub-)step (include/nsdg.h "point samples"): the
+//                              header becomes "# time id x y status hice cice shear" and every line ends with the samples as %.17g.  A line
+//                              of 5 + k columns is read as an output line whose samples are ignored, where the file's own header names k
+//                              fields.  Not given (the default): the file is what it always was
 // The restart file holds no drifters: a resumed run names the last block as its model.drifters_file.
 #pragma once
 #include <string>
@@ -27,12 +32,14 @@ public:
         std::string file, output;
         long period = 0;
         double minConc = 0.15;
+        std::vector<std::string> fields; //!< model.drifters_fields: the names ...
+        std::vector<int> fieldIds; //!< ... and their NSDG_HIST_* ids; empty: positions only
         bool on() const { return !file.empty(); }
     };
     //! model.drifters_*, read and checked; throws std::invalid_argument naming the key.  world: the processes of the run (> 1 is refused:
     //! nothing gathers a multi-process list into one file); loopback: dynamics.loopback_world is set (refused: its values wrap around).
-    //! Touches no device.
-    static Config fromConfiguration(int world, bool loopback);
+    //! thermodynamics, brittle: what model.drifters_fields may name (hsnow / tice, damage).  Touches no device.
+    static Config fromConfiguration(int world, bool loopback, bool thermodynamics = false, bool brittle = false);
     //! for a step that moves no drifters (HipStep): throws std::invalid_argument if any model.drifters_* key is given
     static void refuseFor(const std::string& stepName);
 
@@ -40,7 +47,11 @@ public:
     //! 0, 1, 2 or 3, else std::invalid_argument with the file and the line
     static std::vector<double> read(const std::string& path, double Lx, double Ly);
     static std::string headerLine() { return "# time id x y status"; }
+    //! "# time id x y status hice cice shear"
+    static std::string headerLine(const std::vector<std::string>& fields);
     static std::string formatLine(long time, std::size_t id, double x, double y, double status);
+    //! the line with samples[k * stride], k < nfields, at its end
+    static std::string formatLine(long time, std::size_t id, double x, double y, double status, const double* samples, std::size_t nfields, std::size_t stride);
 
     explicit DriftersOutput(const Config& c);
     const Config& config() const { return m_c; }
@@ -50,8 +61,9 @@ public:
     bool step(long dt);
     //! stop(): true if the block of the current clock has not been written yet
     bool dueAtStop() const { return !m_written || m_lastWritten != m_clock; }
-    //! appends the block of the current clock: planes [3][n] as the device holds them
-    void write(const std::vector<double>& planes);
+    //! appends the block of the current clock: planes [3][n] as the device holds them, and the samples [nfields][n] of model.drifters_fields
+    //! (empty without the key)
+    void write(const std::vector<double>& planes, const std::vector<double>& samples = std::vector<double>());
 
 private:
     Config m_c;

@@ -59,6 +59,11 @@
 //                            velocity after every transport step and written as text blocks (include/Drifters.hpp; include/nsdg.h
 //                            "drifters"); works with dynamics.row_blocks (block 0 writes), refused in a multi-process run; no file
 //                            (default): off, nothing changes
+//     model.drifters_fields  history field names sampled AT every drifter's new position after every (sub-)step and written as further
+//                            columns (include/Drifters.hpp; include/nsdg.h "point samples"); not given (default): the file is as it was
+//     model.stations_file, model.stations_output, model.stations_fields, model.stations_buffer   the same fields at fixed points after every
+//                            model step, after the NSDG_PHASE_END mark like the history, one block of lines per step
+//                            (include/Stations.hpp); block 0 writes the maximum over the row blocks; refused in a multi-process run
 //     dynamics.rheology      mevp (default: every run without the key is byte for byte what it was) | bbm -- the brittle Bingham-Maxwell
 //                            sub-cycle (include/nsdg.h "brittle rheology") through the row-block plan nsdg_rb_bbm_*:
 //                            ghost depth (1, 1), one sub-iteration per pass, nsub explicit sub-iterations of dt / nsub; the damage D is a
@@ -95,6 +100,7 @@ class ForcingFile;
 class HistoryOutput;
 class SeriesOutput;
 class DriftersOutput;
+class StationsOutput;
 class LandMaskFile;
 
 class DynamicsBlock; // one row block: context, device arrays, driver plans (DynamicsStep.cpp)
@@ -151,6 +157,9 @@ private:
     void sampleSeries(long dt);
     void flushSeries(); //!< synchronises every block, downloads its slots, adds the rows in global row order and appends the lines
     void writeDrifters(); //!< model.drifters_output: block 0's list (every block holds the same) as the block of the current clock
+    //! model.stations_file: after a model step -- one point-sample launch on every block into the next slot of its buffer, the flush if full
+    void sampleStations(long dt);
+    void flushStations(); //!< synchronises every block, downloads its slots, merges them by the maximum and appends the blocks of lines
     void resolvePhaseTimes(); //!< model.phase_timing: every block's table -> the timer tree and model.phase_timing_file (PhaseTiming.hpp)
     //! dynamics.forcing = file: records k0, k1 resident on the block's device, sampled with time weight w into the block's wind / ocean
     //! (the pairs the file holds) and, with thermodynamics, its column forcing planes
@@ -174,6 +183,8 @@ private:
     std::unique_ptr<SeriesOutput> m_series; // model.series_file: the time series of the domain totals (null: off)
     std::unique_ptr<DriftersOutput> m_drifters; // model.drifters_file: keys, clock and text files of the drifters (null: off)
     std::vector<double> m_drifterStart; // ... and the list the input file holds, [3][n], read and checked in configure()
+    std::unique_ptr<StationsOutput> m_stations; // model.stations_file: keys, clock and text files of the stations (null: off)
+    std::vector<double> m_stationXY; // ... and the positions the input file holds, [2][n], read and checked in configure()
     struct Brittle; // dynamics.rheology = bbm: the parameters and the sub-iteration rule (DynamicsStep.cpp); null: mEVP
     std::unique_ptr<Brittle> m_brittle;
     bool nsubGiven = false; // dynamics.nsub is in the configuration

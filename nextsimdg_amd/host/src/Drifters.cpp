@@ -8,6 +8,7 @@
 #include <stdexcept>
 
 #include "Configured.hpp"
+#include "Stations.hpp"
 
 namespace Nextsim {
 
@@ -17,6 +18,7 @@ const char* const KEY_FILE = "model.drifters_file";
 const char* const KEY_OUTPUT = "model.drifters_output";
 const char* const KEY_PERIOD = "model.drifters_period";
 const char* const KEY_MIN_CONC = "model.drifters_min_conc";
+const char* const KEY_FIELDS = "model.drifters_fields";
 
 long wholeSeconds(const std::string& key, const std::string& v)
 {
@@ -33,14 +35,14 @@ long wholeSeconds(const std::string& key, const std::string& v)
 }
 } // namespace
 
-DriftersOutput::Config DriftersOutput::fromConfiguration(int world, bool loopback)
+DriftersOutput::Config DriftersOutput::fromConfiguration(int world, bool loopback, bool thermodynamics, bool brittle)
 {
     typedef Configured<Keys> C;
     Config c;
     c.file = C::getConfiguration(std::string(KEY_FILE), std::string(""));
     if (!c.on()) {
         std::string raw;
-        for (const char* key : { KEY_OUTPUT, KEY_PERIOD, KEY_MIN_CONC })
+        for (const char* key : { KEY_OUTPUT, KEY_PERIOD, KEY_MIN_CONC, KEY_FIELDS })
             if (Configurator::lookup(key, raw))
                 throw std::invalid_argument(std::string(key) + " is set without " + KEY_FILE + ": there are no drifters to move");
         return c;
@@ -64,13 +66,16 @@ DriftersOutput::Config DriftersOutput::fromConfiguration(int world, bool loopbac
     c.minConc = C::getConfiguration(std::string(KEY_MIN_CONC), 0.15);
     if (!std::isfinite(c.minConc))
         throw std::invalid_argument(std::string(KEY_MIN_CONC) + " must be finite");
+    std::string raw;
+    if (Configurator::lookup(KEY_FIELDS, raw))
+        c.fieldIds = parsePointFields(KEY_FIELDS, C::getConfiguration(std::string(KEY_FIELDS), std::string("")), thermodynamics, brittle, c.fields);
     return c;
 }
 
 void DriftersOutput::refuseFor(const std::string& stepName)
 {
     std::string raw;
-    for (const char* key : { KEY_FILE, KEY_OUTPUT, KEY_PERIOD, KEY_MIN_CONC })
+    for (const char* key : { KEY_FILE, KEY_OUTPUT, KEY_PERIOD, KEY_MIN_CONC, KEY_FIELDS })
         if (Configurator::lookup(key, raw))
             throw std::invalid_argument(std::string(key) + " is set, but " + stepName + " has no ice velocity to move drifters with: select Nextsim::DynamicsStep");
 }
@@ -85,10 +90,21 @@ std::vector<double> DriftersOutput::read(const std::string& path, double Lx, dou
     };
     std::vector<Row> rows;
     std::string line;
+    std::size_t extra = 0; // the fields the file's own header names after "# time id x y status": an output line has 5 + extra columns
     for (long no = 1; std::getline(in, line); ++no) {
         const auto first = line.find_first_not_of(" \t\r");
-        if (first == std::string::npos || line[first] == '#')
+        if (first == std::string::npos)
             continue;
+        if (line[first] == '#') {
+            std::stringstream hs(line.substr(first));
+            std::vector<std::string> words;
+            for (std::string w; hs >> w;)
+                words.push_back(w);
+            const std::vector<std::string> head = { "#", "time", "id", "x", "y", "status" };
+            if (words.size() >= head.size() && std::vector<std::string>(words.begin(), words.begin() + head.size()) == head)
+                extra = words.size() - head.size();
+            continue;
+        }
         const std::string where = std::string(KEY_FILE) + " " + path + ", line " + std::to_string(no) + ": ";
         std::vector<double> v;
         std::stringstream ss(line);
@@ -99,6 +115,8 @@ std::vector<double> DriftersOutput::read(const std::string& path, double Lx, dou
                 throw std::invalid_argument(where + "\"" + tok + "\" is not a number");
             v.push_back(d);
         }
+        if (extra > 0 && v.size() == 5 + extra) // an output line with samples: they are ignored
+            v.resize(5);
         if (v.size() != 2 && v.size() != 3 && v.size() != 5)
             throw std::invalid_argument(where + std::to_string(v.size()) + " columns; a line is \"x y\", \"x y status\" or \"time id x y status\"");
         Row r;
@@ -124,6 +142,26 @@ std::string DriftersOutput::formatLine(long time, std::size_t id, double x, doub
     return buf;
 }
 
+std::string DriftersOutput::headerLine(const std::vector<std::string>& fields)
+{
+    std::string h = headerLine();
+    for (const std::string& f : fields)
+        h += " " + f;
+    return h;
+}
+
+std::string DriftersOutput::formatLine(long time, std::size_t id, double x, double y, double status, const double* samples, std::size_t nfields,
+    std::size_t stride)
+{
+    std::string line = formatLine(time, id, x, y, status);
+    char buf[48];
+    for (std::size_t k = 0; k < nfields; ++k) {
+        std::snprintf(buf, sizeof buf, " %.17g", samples[k * stride]);
+        line += buf;
+    }
+    return line;
+}
+
 DriftersOutput::DriftersOutput(const Config& c)
     : m_c(c)
 {
@@ -136,7 +174,7 @@ void DriftersOutput::start(long time)
     m_clock = time;
     m_written = false;
     std::ofstream out(m_c.output, std::ios::trunc);
-    out << headerLine() << "\n";
+    out << headerLine(m_c.fields) << "\n";
     if (!out)
         throw std::runtime_error(std::string(KEY_OUTPUT) + ": cannot write " + m_c.output);
 }
@@ -147,12 +185,14 @@ bool DriftersOutput::step(long dt)
     return m_c.period > 0 && m_clock % m_c.period == 0;
 }
 
-void DriftersOutput::write(const std::vector<double>& planes)
+void DriftersOutput::write(const std::vector<double>& planes, const std::vector<double>& samples)
 {
-    const std::size_t n = planes.size() / 3;
+    const std::size_t n = planes.size() / 3, nf = m_c.fieldIds.size();
+    if (samples.size() != nf * n)
+        throw std::logic_error("DriftersOutput::write: the samples do not hold fields x drifters values");
     std::ofstream out(m_c.output, std::ios::app);
     for (std::size_t i = 0; i < n; ++i)
-        out << formatLine(m_clock, i, planes[i], planes[n + i], planes[2 * n + i]) << "\n";
+        out << formatLine(m_clock, i, planes[i], planes[n + i], planes[2 * n + i], nf ? samples.data() + i : nullptr, nf, n) << "\n";
     out.flush();
     if (!out)
         throw std::runtime_error(std::string(KEY_OUTPUT) + ": cannot write " + m_c.output);

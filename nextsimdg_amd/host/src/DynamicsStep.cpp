@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <limits>
 #include <atomic>
 #include <cmath>
 #include <cstdio>
@@ -15,6 +16,7 @@
 
 #include "../../../include/nsdg.h"
 #include "Drifters.hpp"
+#include "Stations.hpp"
 #include "ForcingFile.hpp"
 #include "HistoryOutput.hpp"
 #include "LandMaskFile.hpp"
@@ -140,6 +142,10 @@ public:
     // model.drifters_file: the whole list [3][n] on every block, twice -- a step is out of place; dpar says which half is current (null: off)
     double* drift[2] = { nullptr, nullptr };
     int dpar = 0;
+    double* driftSamples = nullptr; // model.drifters_fields: [fields][n], the samples at the current positions (null: off)
+    // model.stations_file: the positions [2][n] and [model.stations_buffer][fields][n] samples (null: off)
+    double* stationXY = nullptr;
+    double* stations = nullptr;
 
     ~DynamicsBlock() { release(); }
     void release()
@@ -169,6 +175,11 @@ public:
             if (p)
                 (void)hipFree(p);
             p = nullptr;
+        }
+        for (double** p : { &driftSamples, &stationXY, &stations }) {
+            if (*p)
+                (void)hipFree(*p);
+            *p = nullptr;
         }
         if (ctx)
             nsdg_ctx_destroy(ctx); // finalises the communicator too
@@ -379,10 +390,18 @@ void DynamicsStep::configure()
     // multi-process run is refused here
     m_drifters.reset();
     m_drifterStart.clear();
-    const DriftersOutput::Config dc = DriftersOutput::fromConfiguration(RankEnvironment::fromEnv().world, loopbackWorld != 0);
+    const DriftersOutput::Config dc = DriftersOutput::fromConfiguration(RankEnvironment::fromEnv().world, loopbackWorld != 0, thermo, m_brittle != nullptr);
     if (dc.on()) {
         m_drifterStart = DriftersOutput::read(dc.file, L, L);
         m_drifters = std::make_unique<DriftersOutput>(dc);
+    }
+    // stations (include/Stations.hpp): the same
+    m_stations.reset();
+    m_stationXY.clear();
+    const StationsOutput::Config stc = StationsOutput::fromConfiguration(RankEnvironment::fromEnv().world, loopbackWorld != 0, thermo, m_brittle != nullptr);
+    if (stc.on()) {
+        m_stationXY = StationsOutput::read(stc.file, L, L);
+        m_stations = std::make_unique<StationsOutput>(stc);
     }
 }
 
@@ -447,6 +466,8 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
         m_series->start((long)startTime);
     if (m_drifters)
         m_drifters->start((long)startTime);
+    if (m_stations)
+        m_stations->start((long)startTime);
     if (m_landMask) {
         m_landMask->checkShape((std::size_t)nyf, (std::size_t)nxf);
         if (m_rank == 0)
@@ -648,6 +669,18 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
                 checkHip(hipMalloc(reinterpret_cast<void**>(&p), bytes), "DynamicsStep: hipMalloc (drifters)");
             checkHip(hipMemcpy(b.drift[0], m_drifterStart.data(), bytes, hipMemcpyHostToDevice), "upload drifters");
             b.dpar = 0;
+            if (const std::size_t nf = m_drifters->config().fieldIds.size()) { // written by the first step before anything reads it
+                checkHip(hipMalloc(reinterpret_cast<void**>(&b.driftSamples), nf * (m_drifterStart.size() / 3) * sizeof(double)),
+                    "DynamicsStep: hipMalloc (drifter samples)");
+            }
+        }
+        if (m_stations && !m_stationXY.empty()) { // every slot is written before it is read: no memset
+            const std::size_t n = m_stationXY.size() / 2;
+            checkHip(hipMalloc(reinterpret_cast<void**>(&b.stationXY), 2 * n * sizeof(double)), "DynamicsStep: hipMalloc (stations)");
+            checkHip(hipMemcpy(b.stationXY, m_stationXY.data(), 2 * n * sizeof(double), hipMemcpyHostToDevice), "upload stations");
+            checkHip(hipMalloc(reinterpret_cast<void**>(&b.stations),
+                         (std::size_t)m_stations->config().buffer * m_stations->config().ids.size() * n * sizeof(double)),
+                "DynamicsStep: hipMalloc (station buffer)");
         }
         // driver plans
         nsdg_rb_mevp_desc m;
@@ -718,6 +751,8 @@ void DynamicsStep::iterate(const Iterator::Duration& dtSeconds)
         sampleSeries((long)dtSeconds);
     if (m_history)
         sampleHistory((long)dtSeconds);
+    if (m_stations)
+        sampleStations((long)dtSeconds);
     if (m_drifters && m_drifters->step((long)dtSeconds))
         writeDrifters();
 }
@@ -725,14 +760,20 @@ void DynamicsStep::iterate(const Iterator::Duration& dtSeconds)
 void DynamicsStep::writeDrifters()
 {
     // every block holds the same list after the merge: row block 0 writes
-    std::vector<double> planes(m_drifterStart.size());
+    std::vector<double> planes(m_drifterStart.size()), samples(m_drifters->config().fieldIds.size() * (m_drifterStart.size() / 3));
     if (!planes.empty()) {
         DynamicsBlock& b = *m_blocks[0];
         checkHip(hipSetDevice(b.device), "hipSetDevice");
         check(nsdg_ctx_synchronize(b.ctx), "DynamicsStep: drifters output");
         checkHip(hipMemcpy(planes.data(), b.drift[b.dpar], planes.size() * sizeof(double), hipMemcpyDeviceToHost), "download drifters");
+        if (!samples.empty()) {
+            if (m_steps == 0) // nothing has sampled yet (a run of no step): the fields of the start positions are not known
+                std::fill(samples.begin(), samples.end(), std::numeric_limits<double>::quiet_NaN());
+            else
+                checkHip(hipMemcpy(samples.data(), b.driftSamples, samples.size() * sizeof(double), hipMemcpyDeviceToHost), "download drifter samples");
+        }
     }
-    m_drifters->write(planes);
+    m_drifters->write(planes, samples);
 }
 
 // what a history sample and the row totals read: the current side of every ping-pong
@@ -790,6 +831,44 @@ void DynamicsStep::sampleSeries(long dt)
     });
     if (m_series->full())
         flushSeries();
+}
+
+void DynamicsStep::sampleStations(long dt)
+{
+    // like the history sample: after the step's last phase mark, outside every captured graph; the host counts the slots
+    const std::vector<int>& ids = m_stations->config().ids;
+    const std::size_t slot = m_stations->step(dt);
+    const int64_t n = (int64_t)(m_stationXY.size() / 2);
+    if (n > 0)
+        forEachBlock([&](DynamicsBlock& b) {
+            checkHip(hipSetDevice(b.device), "hipSetDevice");
+            const nsdg_history_sources src = historySources(b, thermo, advectColumn);
+            check(nsdg_points_sample(b.ctx, b.j0, b.j1, 2, n, b.stationXY, b.stationXY + n, (int32_t)ids.size(), ids.data(), &src, n,
+                      b.stations + slot * ids.size() * n),
+                "nsdg_points_sample");
+        });
+    if (m_stations->full())
+        flushStations();
+}
+
+void DynamicsStep::flushStations()
+{
+    const std::size_t count = m_stations->pending().size(), nf = m_stations->config().ids.size(), n = m_stationXY.size() / 2;
+    if (count == 0) // (a second stop())
+        return;
+    ScopedTimer timer("stations flush");
+    // a station belongs to the block whose rows hold its element; the others hold -inf: the maximum over the blocks is the table
+    std::vector<double> table(count * nf * n, -std::numeric_limits<double>::infinity()), part(table.size());
+    if (!table.empty())
+        for (auto& bp : m_blocks) {
+            DynamicsBlock& b = *bp;
+            checkHip(hipSetDevice(b.device), "hipSetDevice");
+            check(nsdg_ctx_synchronize(b.ctx), "DynamicsStep: stations flush");
+            checkHip(hipMemcpy(part.data(), b.stations, part.size() * sizeof(double), hipMemcpyDeviceToHost), "download stations");
+            for (std::size_t i = 0; i < table.size(); ++i)
+                table[i] = (part[i] > table[i] || part[i] != part[i]) ? part[i] : table[i]; // (a NaN sample is kept)
+        }
+    m_stations->write(m_stationXY, table);
 }
 
 void DynamicsStep::flushSeries()
@@ -979,6 +1058,16 @@ void DynamicsStep::subStep(double dt, bool last)
             b.dpar = 1 - b.dpar;
             if (b.world > 1)
                 check(nsdg_comm_max_f64_array(ctx, b.drift[b.dpar], 3 * n), "nsdg_comm_max_f64_array");
+            if (b.driftSamples) {
+                // model.drifters_fields: the merged list is sampled at its NEW positions from the state the step left -- every block the
+                // points of its own rows, -inf for the others -- and one more maximum makes the whole table
+                const std::vector<int>& ids = m_drifters->config().fieldIds;
+                const nsdg_history_sources src = historySources(b, thermo, advectColumn);
+                check(nsdg_points_sample(ctx, b.j0, b.j1, 2, n, b.drift[b.dpar], b.drift[b.dpar] + n, (int32_t)ids.size(), ids.data(), &src, n, b.driftSamples),
+                    "nsdg_points_sample");
+                if (b.world > 1)
+                    check(nsdg_comm_max_f64_array(ctx, b.driftSamples, (int64_t)ids.size() * n), "nsdg_comm_max_f64_array");
+            }
         }
         if (last) // the model step ends here: what follows until its next mark belongs to no phase
             check(nsdg_phase_mark(ctx, NSDG_PHASE_END), "nsdg_phase_mark");
@@ -1078,6 +1167,8 @@ void DynamicsStep::stop(const Iterator::TimePoint&)
         flushHistory();
     if (m_series)
         flushSeries();
+    if (m_stations)
+        flushStations();
     if (m_drifters && m_drifters->dueAtStop()) // the block of the last time, once (stop() comes twice: the iterator's, the restart file's)
         writeDrifters();
     FieldStore& f = pStructure->fields();

@@ -11,6 +11,7 @@
 #include "../../../include/nsdg.h"
 #include "Drifters.hpp"
 #include "HistoryOutput.hpp"
+#include "Stations.hpp"
 #include "ModuleLoader.hpp"
 #include "PhaseTiming.hpp"
 #include "Timer.hpp"
@@ -53,6 +54,7 @@ void HipStep::init()
     HistoryOutput::refuseFor("Nextsim::HipStep"); // before a device is touched: the column step alone writes no history output ...
     SeriesOutput::refuseFor("Nextsim::HipStep"); // ... and no time series
     DriftersOutput::refuseFor("Nextsim::HipStep"); // ... and has no velocity to move drifters with
+    StationsOutput::refuseFor("Nextsim::HipStep"); // ... and no dynamics state to sample at a station
     {
         std::string raw; // ... and no rheology: the keys of the brittle one are the dynamics step's
         for (const std::string& key : DynamicsStep::brittleKeys())

@@ -300,10 +300,11 @@ class DynamicsCore:
     HISTORY_COLUMN_FIELDS = outputs.History.COLUMN_FIELDS
     HAS_COLUMN_STATE = False
     merge_history, merge_series = staticmethod(outputs.merge_history), staticmethod(outputs.merge_series)
+    merge_stations = staticmethod(outputs.merge_stations)
 
     def __init__(self, ops, blk, hx, hy, dt, nsub, device, exchanger=None, overlap=True, native=False, use_graph=False, closure=True,
                  phase_timing=False, land=None, rheology="mevp", bbm=None, history=None, series=None, series_capacity=1024, extent_conc=0.15,
-                 drifters=None, drifter_min_conc=0.15):
+                 drifters=None, drifter_min_conc=0.15, drifter_fields=None, stations=None, station_fields=None, station_capacity=256):
         self.ops, self.blk, self.hx, self.hy, self.dt, self.nsub, self.overlap = ops, blk, hx, hy, dt, nsub, overlap
         # closure: cap + scaling limiter at the end of every transport step (the ice-free-node rule is a parameter of the
         # sub-cycle, on by default).  False: the bare scheme of rounds 1-4 (frozen fixtures of that scheme)
@@ -348,8 +349,21 @@ class DynamicsCore:
         self._history = None if history is None else outputs.History(history, ops, blk, device, rheology, self.TRANSPORTED, self.HAS_COLUMN_STATE)
         self._series = None if series is None else outputs.Series(series, series_capacity, extent_conc, ops, blk, device, self.HAS_COLUMN_STATE)
         # a single-iteration sub-cycle leaves ghost node rows stale: the drifters complete them, unless the native plan does
+        # drifter_fields= / station_fields=: the fields at a point (include/nsdg.h "point samples"), the history's names and refusals
+        if drifter_fields is not None:
+            if drifters is None:
+                raise ValueError("drifter_fields= samples along the drifters' tracks: it needs drifters=")
+            drifter_fields = outputs.point_fields(drifter_fields, "drifter_field", rheology, self.HAS_COLUMN_STATE)
+        if (stations is None) != (station_fields is None):
+            raise ValueError("stations= and station_fields= go together: the points and the fields sampled at them")
+        if stations is not None:
+            station_fields = outputs.point_fields(station_fields, "station_field", rheology, self.HAS_COLUMN_STATE)
         self._drifters = None if drifters is None else outputs.Drifters(drifters, drifter_min_conc, ops, blk, hx, hy, self.halo, device,
-                                                                         complete_ghosts=self.per_pass == 1 and not self._plan_completes_nodes())
+                                                                         complete_ghosts=self.per_pass == 1 and not self._plan_completes_nodes(),
+                                                                         fields=drifter_fields, order=self.ORDER)
+        self._stations = None if stations is None else outputs.Stations(stations, station_fields, station_capacity, ops, blk, hx, hy, device,
+                                                                         order=self.ORDER)
+        self.drifter_fields, self.station_fields = drifter_fields, station_fields
         self.history = self._history.entries if self._history is not None else None
         self.series = self._series.names if self._series is not None else None
         self.series_capacity, self.extent_conc, self.drifter_min_conc = int(series_capacity), float(extent_conc), float(drifter_min_conc)
@@ -447,6 +461,13 @@ class DynamicsCore:
         if self._drifters is None:
             raise ValueError("drifters_read() needs a core constructed with drifters=")
         return self._drifters.read()
+
+    def stations_read(self, reset=True):
+        """outputs.Stations.read: the fields at the stations for the steps since the last reset, this rank's part (-inf where it does not
+        own the point); merge_stations() joins the ranks"""
+        if self._stations is None:
+            raise ValueError("stations_read() needs a core constructed with stations=")
+        return self._stations.read(reset)
 
     def _plan_completes_nodes(self):
         """the native brittle plan ends its call with the exchange of every ghost node row (nsdg_rb_bbm_desc.complete_nodes): the one place
@@ -764,15 +785,19 @@ class DynamicsCore:
         self._end_step()
 
     def _begin_step(self):
-        if self._series is not None:
-            self._series.room()
+        for output in (self._series, self._stations):
+            if output is not None:
+                output.room()
 
     def _substep(self):
         """the grid, the phases and the drifters at self.dt: step() runs it once, advance() n times"""
         self._set_grid()
         self._phases()
         if self._drifters is not None:
-            self._drifters.step(self.dt, self.u, self.v, self.A)
+            if self._drifters.fields is None:
+                self._drifters.step(self.dt, self.u, self.v, self.A)
+            else:  # the fields along the track are sampled at the new positions, from the state the phases left
+                self._drifters.step(self.dt, self.u, self.v, self.A, self._history_sources())
 
     def _phases(self):
         """what a step computes, in order; a subclass puts its own phases around these"""
@@ -780,9 +805,9 @@ class DynamicsCore:
         self.transport()
 
     def _end_step(self):
-        """the end mark of the span and one sample per model step, after its last sub-step: the row totals, then the history"""
+        """the end mark of the span and one sample per model step, after its last sub-step: the row totals, the history, the stations"""
         self._mark(PHASE_END)
-        for output in (self._series, self._history):
+        for output in (self._series, self._history, self._stations):
             if output is not None:
                 output.sample(self._history_sources())
 

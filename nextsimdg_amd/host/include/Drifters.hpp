@@ -1,5 +1,5 @@
 // Drifters.hpp -- Lagrangian drifters of the C++ host: the keys, the text files and the clock of the output blocks.  Needs no device; the
-// step that owns the device arrays (DynamicsStep) moves the drifters with nsdg_drifters_advance after every transport step and merges the
+// class that holds the device lists (DriftersChannel, src/DynamicsOutputs.hpp) moves the drifters with nsdg_drifters_advance after every transport step and merges the
 // row blocks' lists with nsdg_comm_max_f64_array (include/nsdg.h "drifters").
 //
 // Keys (all under model.*; with none of them given nothing changes):

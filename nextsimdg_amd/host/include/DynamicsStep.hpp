@@ -1,7 +1,10 @@
 // DynamicsStep.hpp -- IModelStep implementation of the dynamics core: per time step the mEVP stress/velocity
 // sub-cycle followed by the DG2 transport of the mean thickness H and concentration A, optionally preceded by
 // the column thermodynamics (BASELINE config 5 coupling).  Everything numerical happens behind the C ABI
-// (include/nsdg.h); this class owns the device arrays and the call sequence.
+// (include/nsdg.h); this class owns the row blocks and the call sequence across them.  Who owns what: a row block (src/DynamicsBlock.hpp)
+// owns its context, its device arrays and its driver plans and builds them from its geometry; each of the four outputs
+// (src/DynamicsOutputs.hpp) owns its host object, its input list and its buffers on every block; configure(), start(), iterate(), subStep()
+// and stop() here are the sequence of named steps over them.
 //
 // The reference has no dynamics component (CMakeLists.txt:43-46); the class plugs into the reference's
 // batched seam (IModelStep, core/src/include/IModelStep.hpp:16-34) exactly like HipStep does and is selected with
@@ -84,6 +87,7 @@
 // start at zero) and receive them back at stop().  Ocean current and wind come from the device-side forcing
 // provider nsdg_boxtest_forcing (the wind is re-evaluated at every step's model time), or from a forcing file's pairs.
 #pragma once
+#include <algorithm>
 #include <memory>
 #include <string>
 #include <vector>
@@ -97,13 +101,9 @@ struct nsdg_ctx;
 namespace Nextsim {
 
 class ForcingFile;
-class HistoryOutput;
-class SeriesOutput;
-class DriftersOutput;
-class StationsOutput;
 class LandMaskFile;
 
-class DynamicsBlock; // one row block: context, device arrays, driver plans (DynamicsStep.cpp)
+class DynamicsBlock; // one row block: context, device arrays, driver plans (src/DynamicsBlock.hpp)
 
 class DynamicsStep : public IModelStep, public Configured<DynamicsStep> {
 public:
@@ -150,21 +150,15 @@ private:
     //! forcing at m_time, column step, ice strength, prepare, sub-cycle and transport with dt, each opened by its phase mark; `last`: the
     //! model step ends with this sub-step (NSDG_PHASE_END)
     void subStep(double dt, bool last);
-    //! model.output_period: after a model step of dt seconds -- one sample on every block if the window asks for one, the flush if it ends
-    void sampleHistory(long dt);
-    void flushHistory(); //!< the window's record: every block's owned rows into one host array, finished per statistic, one file
-    //! model.series_file: after a model step -- one row-totals launch on every block into the next slot of its buffer, the flush if full
-    void sampleSeries(long dt);
-    void flushSeries(); //!< synchronises every block, downloads its slots, adds the rows in global row order and appends the lines
-    void writeDrifters(); //!< model.drifters_output: block 0's list (every block holds the same) as the block of the current clock
-    //! model.stations_file: after a model step -- one point-sample launch on every block into the next slot of its buffer, the flush if full
-    void sampleStations(long dt);
-    void flushStations(); //!< synchronises every block, downloads its slots, merges them by the maximum and appends the blocks of lines
     void resolvePhaseTimes(); //!< model.phase_timing: every block's table -> the timer tree and model.phase_timing_file (PhaseTiming.hpp)
     //! dynamics.forcing = file: records k0, k1 resident on the block's device, sampled with time weight w into the block's wind / ocean
     //! (the pairs the file holds) and, with thermodynamics, its column forcing planes
     void sampleForcingFile(DynamicsBlock& b, std::size_t k0, std::size_t k1, double w);
-    template <class F> void forEachBlock(F&& f); //!< one thread per block when there are several
+    void configureOutputs(); //!< configure(): the four outputs from their keys and input files, last, in the order history, series, drifters, stations
+    void makeBlocks(); //!< start(): the geometry of the blocks of this process, on their devices
+    void communicatorId(unsigned char* id); //!< start(): the RCCL communicator id travels before anything else (multi-process run)
+    int brittleSubIterations(double dt, double rhoIce); //!< the sub-iterations of a brittle (sub-)step of dt: dynamics.nsub as given, or the elastic-wave rule
+    double cellSize() const { return std::min(L / nxf, L / nyf); }
     IStructure* pStructure = nullptr;
     std::vector<std::unique_ptr<DynamicsBlock>> m_blocks;
     int nxf = 0, nyf = 0; // fast / slow grid dimensions as the dynamics ABI names them
@@ -179,12 +173,8 @@ private:
     std::string forcing = "host", devices;
     std::shared_ptr<const ForcingFile> m_forcingFile; // dynamics.forcing = file: the records, read and checked in configure()
     std::shared_ptr<const LandMaskFile> m_landMask; // dynamics.land_mask_file: the element mask, read and checked in configure()
-    std::unique_ptr<HistoryOutput> m_history; // model.output_period > 0: keys, windows and record files (null: off)
-    std::unique_ptr<SeriesOutput> m_series; // model.series_file: the time series of the domain totals (null: off)
-    std::unique_ptr<DriftersOutput> m_drifters; // model.drifters_file: keys, clock and text files of the drifters (null: off)
-    std::vector<double> m_drifterStart; // ... and the list the input file holds, [3][n], read and checked in configure()
-    std::unique_ptr<StationsOutput> m_stations; // model.stations_file: keys, clock and text files of the stations (null: off)
-    std::vector<double> m_stationXY; // ... and the positions the input file holds, [2][n], read and checked in configure()
+    struct Outputs; // model.output_*, series_*, drifters_*, stations_*: the four outputs, each null when off (DynamicsStep.cpp)
+    std::unique_ptr<Outputs> m_out;
     struct Brittle; // dynamics.rheology = bbm: the parameters and the sub-iteration rule (DynamicsStep.cpp); null: mEVP
     std::unique_ptr<Brittle> m_brittle;
     bool nsubGiven = false; // dynamics.nsub is in the configuration

@@ -1,6 +1,6 @@
 // HistoryOutput.hpp -- gridded output at a chosen period: time means and snapshots of element fields that the device accumulates
 // (include/nsdg.h "history output").  This class is the part that needs no device: the keys, the window
-// arithmetic and the record files.  DynamicsStep owns the accumulators, samples after every model step and downloads at a window end.
+// arithmetic and the record files.  HistoryChannel (src/DynamicsOutputs.hpp) holds the accumulators, samples after every model step and downloads at a window end.
 //
 // Configuration keys (all optional; the period 0 -- the default -- turns the output off and nothing of a run changes):
 //     model.output_period   whole seconds, a multiple of model.time_step

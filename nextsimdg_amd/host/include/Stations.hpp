@@ -1,6 +1,6 @@
 // Stations.hpp -- the model sampled at fixed points of the C++ host: the keys, the text files and the clock of the output blocks; and the
-// list of point fields that the drifters' samples (model.drifters_fields, include/Drifters.hpp) share with them.  Needs no device; the step
-// that owns the device arrays (DynamicsStep) samples with nsdg_points_sample after every model step, after its NSDG_PHASE_END mark, like
+// list of point fields that the drifters' samples (model.drifters_fields, include/Drifters.hpp) share with them.  Needs no device; the class
+// that holds the device buffers (StationsChannel, src/DynamicsOutputs.hpp) samples with nsdg_points_sample after every model step, after its NSDG_PHASE_END mark, like
 // the history (include/nsdg.h "point samples").
 //
 // Keys (all under model.*; with none of them given nothing changes):

@@ -15,6 +15,21 @@
  *  - One context per GPU/stream.  Calls on one context must not be issued concurrently from two
  *    host threads; different contexts are independent.  (The reference is single-threaded and
  *    non-re-entrant: static m_dt / m_freezer, core/src/PrognosticData.cpp:12-13.)
+ *  - Streams (held to it on a stream other than the null stream by tests/test_gpu_stream_order.py; its `blocks_host` column is the
+ *    tested form of the list below).  Every launch and copy of a call goes to the context's stream, or to one of the library's own
+ *    non-blocking streams (the communication stream, the stream a row-block plan replays its graphs on) ordered behind it and joined
+ *    back to it with events before the call returns: a call reads what the stream has produced when its work runs, and work enqueued
+ *    on the stream behind it sees its results.  Given a stream other than NULL, the library never uses the null stream.
+ *    These calls BLOCK the host until the context's stream (and, with a communicator, its communication stream) has drained:
+ *    nsdg_ctx_synchronize, nsdg_ctx_destroy, nsdg_mevp_pipeline_health, nsdg_concentration_max, nsdg_phase_times,
+ *    nsdg_halo_stats_get and nsdg_rb_mevp_stats / nsdg_rb_bbm_stats / nsdg_rb_transport_stats (they wait for the last exchange),
+ *    nsdg_comm_finalize (the communication stream only), and nsdg_comm_max_f64_array on the local transport.  nsdg_phase_mark waits only when its ring is full;
+ *    nsdg_halo_start / _finish on the local transport wait for the neighbour THREAD to post, never for the device.  Every other call
+ *    returns without waiting for the device.  Setters (nsdg_grid_set, nsdg_*_params_set, nsdg_*_variant_set, nsdg_land_mask_set, ...)
+ *    store host state that is read when a later call is MADE, not when its work runs: a setter between two enqueued calls acts on the
+ *    second only.
+ *    "One context per stream" permits two contexts on two streams of ONE device, driven concurrently (from one host thread or two):
+ *    they share no launch constants, scratch or device symbols.
  *  - No clamping or input checking is added to the physics (SURVEY.md section 8b "Errors").  The results follow the
  *    reference's arithmetic, including its Inf / NaN / 0 for mld == 0, dt == 0, vanishing fluxes, zero pressure and
  *    non-finite forcing values: every division either is an IEEE division or ends in the IEEE sequence's special-case

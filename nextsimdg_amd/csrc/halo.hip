@@ -823,7 +823,9 @@ int nsdg_comm_max_f64_array(nsdg_ctx* ctx, double* dev, int64_t n)
         return rc;
     std::vector<double>& mine = c->red_stage;
     mine.resize((size_t)n);
-    NSDG_CHECK_HIP(hipMemcpy(mine.data(), dev, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    // (the streams are drained: the copy starts at once; it goes to the context's stream, not to the null stream)
+    NSDG_CHECK_HIP(hipMemcpyAsync(mine.data(), dev, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    NSDG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     LocalGroup* g = c->local;
     {
         std::unique_lock<std::mutex> lock(g->m);

@@ -167,8 +167,9 @@ int nsdg_ctx_create(int device_id, void* stream, nsdg_ctx** out)
     // the report channel of the pipelines' bounded waits: a wait that gives up must reach the host without anybody asking
     c->p2p_count_dev = nullptr, c->p2p_flag_host = nullptr, c->p2p_flag_dev = nullptr, c->p2p_given_up = 0;
     hipError_t e = hipMalloc((void**)&c->p2p_count_dev, sizeof(unsigned));
+    // on the context's own stream: a null-stream memset is not ordered against launches on a non-blocking stream
     if (e == hipSuccess)
-        e = hipMemset(c->p2p_count_dev, 0, sizeof(unsigned));
+        e = hipMemsetAsync(c->p2p_count_dev, 0, sizeof(unsigned), c->stream);
     if (e == hipSuccess)
         e = hipHostMalloc((void**)&c->p2p_flag_host, sizeof(unsigned), hipHostMallocMapped);
     if (e == hipSuccess) {
@@ -229,9 +230,11 @@ int nsdg_mevp_pipeline_health(nsdg_ctx* ctx, uint32_t* waits_given_up)
     NSDG_CHECK_ARG(ctx && waits_given_up, "null argument");
     NSDG_CHECK_HIP(hipSetDevice(ctx->device));
     NSDG_CHECK_HIP(hipStreamSynchronize(ctx->stream)); // no launch of this context is running: read and reset cannot lose an event
+    // read and reset on the context's stream, never the null stream: the next launch on it is ordered behind the reset
     unsigned n = 0;
-    NSDG_CHECK_HIP(hipMemcpy(&n, ctx->p2p_count_dev, sizeof(unsigned), hipMemcpyDeviceToHost));
-    NSDG_CHECK_HIP(hipMemset(ctx->p2p_count_dev, 0, sizeof(unsigned)));
+    NSDG_CHECK_HIP(hipMemcpyAsync(&n, ctx->p2p_count_dev, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    NSDG_CHECK_HIP(hipMemsetAsync(ctx->p2p_count_dev, 0, sizeof(unsigned), ctx->stream));
+    NSDG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     *(volatile unsigned*)ctx->p2p_flag_host = 0;
     ctx->p2p_given_up = 0;
     *waits_given_up = n;
@@ -259,6 +262,7 @@ int nsdg_copy_f64(nsdg_ctx* ctx, double* dst, const double* src, int64_t n)
         return NSDG_OK;
     const long n2 = n >> 1;
     NSDG_CHECK_ARG(n2 < (1L << 39), "count too large");
+    NSDG_CHECK_HIP(hipSetDevice(ctx->device));
     const unsigned blocks = (unsigned)((n2 + 255) / 256);
     if (n2)
         hipLaunchKernelGGL(copy16_kernel, dim3(blocks), dim3(256), 0, ctx->stream, reinterpret_cast<double2*>(dst), reinterpret_cast<const double2*>(src), n2);

@@ -405,8 +405,9 @@ int nsdg_ice_strength(nsdg_ctx* ctx, int32_t j0, int32_t j1, const double* H, co
  * the test of the ice-free-node rule (nsdg_mevp_params.min_conc / min_thick), false for a NaN -- T[e] = mean(Q) / mean(H) (plane 0 of
  * each, one IEEE division); everywhere else T[e] keeps its value (the column step ignores tice0 where there is no ice).
  * Both are element-local: a row block runs them on its ghost rows too, which then stay bit-identical to their owners without an
- * exchange.  Stream-ordered, one launch each; Q must not alias H or T.  A null pointer, an order outside 0..2 or a row range outside
- * the local array: NSDG_ERR_ARG. */
+ * exchange.  Stream-ordered, one launch each; Q must not alias H or T, nor T (nsdg_tracer_recover) H, A or Q.  A null pointer, an order
+ * outside 0..2, a row range outside the local array or an overlap of those arrays (nc(order) nx ny doubles of a DG field, nx ny of T):
+ * NSDG_ERR_ARG, and nothing is launched. */
 int nsdg_tracer_weight(nsdg_ctx* ctx, int32_t order, int32_t j0, int32_t j1, const double* H, const double* T, double* Q);
 int nsdg_tracer_recover(nsdg_ctx* ctx, int32_t order, int32_t j0, int32_t j1, const double* H, const double* A, const double* Q,
     double min_conc, double min_thick, double* T);
@@ -821,8 +822,9 @@ int nsdg_drifters_advance(nsdg_ctx* ctx, int32_t j0, int32_t j1, double dt, doub
  *   no exchange of complete node rows (nsdg_rb_bbm_desc.complete_nodes, the drifters' own) is needed for a sample.
  * Checks, as for the history calls: grid set (else NSDG_ERR_STATE); 0 <= j0 <= j1 <= ny; order in 0..2; n >= 0; 1 <= nfields <=
  *   NSDG_HISTORY_MAX_FIELDS; fields and src non-null; known ids, no id twice; a field whose source pointer is NULL is refused with a message
- *   that names the field and the source (sources no listed field reads may be NULL); out_stride >= n; x, y, out non-null unless n == 0:
- *   NSDG_ERR_ARG.  n == 0 launches nothing (and x, y, out may then be NULL).  j0 == j1 is NOT nothing: an empty row range owns no point,
+ *   that names the field and the source (sources no listed field reads may be NULL); whichever of s11, s12, s22 the list reads 16-byte
+ *   aligned, as every tiled array ("Data layout": the coefficients are loaded in pairs; a component no listed field reads is not looked
+ *   at); out_stride >= n; x, y, out non-null unless n == 0: NSDG_ERR_ARG.  n == 0 launches nothing (and x, y, out may then be NULL).  j0 == j1 is NOT nothing: an empty row range owns no point,
  *   so it writes -inf into all nfields slots of all n points.  The call belongs to no phase of the phase table: the hosts make it after
  *   their NSDG_PHASE_END mark or, for the drifters, where they advance them. */
 int nsdg_points_sample(nsdg_ctx* ctx, int32_t j0, int32_t j1, int32_t order, int64_t n, const double* x, const double* y, int32_t nfields,

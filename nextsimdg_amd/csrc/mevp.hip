@@ -358,9 +358,6 @@ __global__ __launch_bounds__(256) void wind_stress_kernel(long n, double f_atm, 
 
 using namespace nsdg_mevp_detail;
 
-#define NSDG_TILED_MSG "tiled arrays (stress, ice strength) must be 16-byte aligned"
-#define NSDG_CHECK_TILED(...) NSDG_CHECK_ARG(nsdg_aligned16({ __VA_ARGS__ }), NSDG_TILED_MSG)
-
 // the adaptive form of alpha, beta (mevp_common.h) exists in the marching kernels only
 #define NSDG_NOT_ADAPTIVE(ctx)                                                                                                  \
     do {                                                                                                                        \

@@ -105,6 +105,10 @@ static inline bool nsdg_aligned16(std::initializer_list<const void*> ptrs)
     return true;
 }
 
+// the refusal of an unaligned tiled array, the same words from every entry point that reads one 16 bytes at a time
+#define NSDG_TILED_MSG "tiled arrays (stress, ice strength) must be 16-byte aligned"
+#define NSDG_CHECK_TILED(...) NSDG_CHECK_ARG(nsdg_aligned16({ __VA_ARGS__ }), NSDG_TILED_MSG)
+
 // coefficients per element of a DG field of the order 0, 1 or 2
 constexpr int nsdg_nc(int order) { return order == 0 ? 1 : (order == 1 ? 3 : 6); }
 

@@ -234,6 +234,8 @@ int nsdg_points_sample(nsdg_ctx* ctx, int32_t j0, int32_t j1, int32_t order, int
     }
     for (int k = nfields; k < NSDG_HISTORY_MAX_FIELDS; ++k)
         list.id[k] = 0;
+    // stress_value loads the coefficients of the tiled stress in pairs: the components the list reads, and no other
+    NSDG_CHECK_TILED((reads & RD_S11) ? src->s11 : nullptr, (reads & RD_S12) ? src->s12 : nullptr, (reads & RD_S22) ? src->s22 : nullptr);
     NSDG_CHECK_ARG(out_stride >= n, "out_stride is smaller than the n points of one field");
     points_grid g;
     g.nx = ctx->nx, g.ny = ctx->ny, g.row0 = ctx->row0;

@@ -50,6 +50,9 @@ int launch_blocks(const nsdg_ctx* ctx, long n)
     return (int)std::min<long>(nsdg_div_up(n, 256), 8L * ctx->num_cus);
 }
 
+// the na doubles at a and the nb doubles at b share an address
+bool overlap(const double* a, long na, const double* b, long nb) { return a < b + nb && b < a + na; }
+
 } // namespace
 
 extern "C" {
@@ -60,10 +63,12 @@ int nsdg_tracer_weight(nsdg_ctx* ctx, int32_t order, int32_t j0, int32_t j1, con
     NSDG_CHECK_ARG(order >= 0 && order <= 2, "order must be 0, 1 or 2");
     NSDG_CHECK_ARG(0 <= j0 && j0 <= j1 && j1 <= ctx->ny, "row range outside the local array");
     NSDG_CHECK_ARG(H && T && Q, "null pointer");
+    const long N = (long)ctx->nx * ctx->ny, e0 = (long)j0 * ctx->nx, e1 = (long)j1 * ctx->nx;
+    const long nc = nsdg_nc(order);
+    NSDG_CHECK_ARG(!overlap(Q, nc * N, H, nc * N) && !overlap(Q, nc * N, T, N), "Q must not alias or overlap H or T");
     if (j0 == j1)
         return NSDG_OK;
     NSDG_CHECK_HIP(hipSetDevice(ctx->device));
-    const long N = (long)ctx->nx * ctx->ny, e0 = (long)j0 * ctx->nx, e1 = (long)j1 * ctx->nx;
     const dim3 grid((unsigned)launch_blocks(ctx, e1 - e0)), block(256);
     nsdg_with_order(order, [&](auto O) {
         hipLaunchKernelGGL(tracer_weight_kernel<nsdg_nc(decltype(O)::value)>, grid, block, 0, ctx->stream, e0, e1, N, H, T, Q);
@@ -79,10 +84,12 @@ int nsdg_tracer_recover(nsdg_ctx* ctx, int32_t order, int32_t j0, int32_t j1, co
     NSDG_CHECK_ARG(order >= 0 && order <= 2, "order must be 0, 1 or 2");
     NSDG_CHECK_ARG(0 <= j0 && j0 <= j1 && j1 <= ctx->ny, "row range outside the local array");
     NSDG_CHECK_ARG(H && A && Q && T, "null pointer");
+    const long N = (long)ctx->nx * ctx->ny, e0 = (long)j0 * ctx->nx, e1 = (long)j1 * ctx->nx;
+    const long nc = nsdg_nc(order);
+    NSDG_CHECK_ARG(!overlap(T, N, H, nc * N) && !overlap(T, N, A, nc * N) && !overlap(T, N, Q, nc * N), "T must not alias or overlap H, A or Q");
     if (j0 == j1)
         return NSDG_OK;
     NSDG_CHECK_HIP(hipSetDevice(ctx->device));
-    const long e0 = (long)j0 * ctx->nx, e1 = (long)j1 * ctx->nx;
     hipLaunchKernelGGL(tracer_recover_kernel, dim3((unsigned)launch_blocks(ctx, e1 - e0)), dim3(256), 0, ctx->stream, e0, e1, H, A, Q, min_conc,
         min_thick, T);
     NSDG_CHECK_LAUNCH();

@@ -108,6 +108,32 @@ def reduce_row(x, op=op_sum):
     return p[0]
 
 
+def reduce_rows(x, op=op_sum):
+    """reduce_row of every row of x [rows, nx] at once, for arrays of thousands of rows: the same operations in the same sequence, each
+    of them on a vector over the rows (tests/test_stream_geometry_cpu.py holds it to reduce_row bit for bit)"""
+    x = np.asarray(x, dtype=np.float64)
+    if op is op_sum:
+        vop = lambda a, b: a + b
+    else:
+        vop = lambda a, b: np.where((b > a) | (b != b), b, a)
+    p = np.full((x.shape[0], LANES), 0.0 if op is op_sum else -np.inf)
+    with np.errstate(invalid="ignore"):
+        for first in range(0, x.shape[1], LANES):  # lane l folds ix = l, l + 64, ... in ascending order
+            fold = x[:, first:first + LANES]
+            p[:, :fold.shape[1]] = vop(p[:, :fold.shape[1]], fold)
+        s = LANES // 2
+        while s >= 1:
+            p[:, :s] = vop(p[:, :s], p[:, s:2 * s])
+            s //= 2
+    return p[:, 0].copy()
+
+
+def row_totals_of_many_rows(quantities, hx, hy, extent_conc, **src):
+    """row_totals by reduce_rows"""
+    return np.stack([reduce_rows(row_terms(name, hx, hy, extent_conc, **src), op_max if name in MAX_QUANTITIES else op_sum)
+                     for name in quantities])
+
+
 def row_totals(quantities, hx, hy, extent_conc, **src):
     """[nq, ny]: R_k(iy) of every row"""
     out = []

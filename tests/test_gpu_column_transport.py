@@ -119,6 +119,35 @@ def test_argument_errors(ctx):
     assert float(Q.abs().max()) == 0.0 and float(T.max()) == -8.0
     assert lib.nsdg_tracer_weight(ctx.h, 2, 3, 3, p(H), p(T), p(Q)) == 0
     assert lib.nsdg_tracer_recover(ctx.h, 2, 3, 3, p(H), p(A), p(Q), 0.0, 0.0, p(T)) == 0
+    # Q must not alias H or T, nor T (recover) H, A or Q: an overlap of the ranges -- nc(order) nx ny doubles of a DG field, nx ny of T -- is
+    # refused whichever end touches, by one double or by all; arrays that only abut are fine.  Every array is a window of one buffer
+    N = nx * ny
+    big = dev(np.arange(40.0 * N) + 1.0)
+    before = big.clone()
+    at = lambda k: abi.C.c_void_p(big.data_ptr() + 8 * k)
+    message = lambda: lib.nsdg_last_error().decode()
+    for order, nc in ((0, 1), (1, 3), (2, 6)):
+        h, t = 10 * N, 30 * N  # nsdg_tracer_weight: H at h, T at t
+        for q in (h, h + nc * N - 1, h - nc * N + 1, t, t + N - 1, t - nc * N + 1):
+            assert lib.nsdg_tracer_weight(ctx.h, order, 0, ny, at(h), at(t), at(q)) == ERR, (order, q)
+            assert "nsdg_tracer_weight: Q must not alias or overlap H or T" in message()
+            assert lib.nsdg_tracer_weight(ctx.h, order, 3, 3, at(h), at(t), at(q)) == ERR  # an empty row range is no excuse
+        h, a, q = 4 * N, 14 * N, 24 * N  # nsdg_tracer_recover: H, A, Q
+        for x in (h, a, q):
+            for t in (x, x + nc * N - 1, x - N + 1):
+                assert lib.nsdg_tracer_recover(ctx.h, order, 0, ny, at(h), at(a), at(q), 0.0, 0.0, at(t)) == ERR, (order, x, t)
+                assert "nsdg_tracer_recover: T must not alias or overlap H, A or Q" in message()
+    torch.cuda.synchronize()
+    assert torch.equal(big, before)  # a refused call launches nothing
+    for order, nc in ((0, 1), (1, 3), (2, 6)):
+        h, t = 10 * N, 30 * N
+        for q in (h + nc * N, h - nc * N, t + N, t - nc * N):
+            assert lib.nsdg_tracer_weight(ctx.h, order, 0, ny, at(h), at(t), at(q)) == 0, (order, q)
+        h, a, q = 4 * N, 14 * N, 24 * N
+        for x in (h, a, q):
+            for t in (x + nc * N, x - N):
+                assert lib.nsdg_tracer_recover(ctx.h, order, 0, ny, at(h), at(a), at(q), 0.0, 0.0, at(t)) == 0, (order, x, t)
+    torch.cuda.synchronize()
 
 
 def test_limiter_leaves_an_unbounded_field_unchanged(ctx):

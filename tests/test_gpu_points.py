@@ -263,6 +263,27 @@ def test_checks(ctx, gpu):
         less = ctx._history_sources("test", {k: t for k, t in src_t.items() if k != name})
         refused({6: 1, 7: (abi.I32 * 1)(abi.HISTORY_FIELDS.index(field)), 8: abi.C.byref(less)},
                 "field '%s' needs the source %s, which is a null pointer" % (field, name))
+    # the tiled stress is loaded 16 bytes at a time: a view 8 bytes into a buffer is refused for whichever component the list reads, out
+    # stays as it was, and a component no listed field reads is not looked at
+    torch.cuda.synchronize()
+    out.fill_(SENTINEL)
+    shifted = {}
+    for name in ("s11", "s12", "s22"):
+        buf = torch.zeros(src_t[name].numel() + 1, dtype=torch.float64, device="cuda")
+        buf[1:].copy_(src_t[name].reshape(-1))
+        shifted[name] = buf[1:]
+        assert shifted[name].data_ptr() % 16 == 8
+    for name, field in (("s11", "sigma_n"), ("s12", "sigma_s"), ("s22", "sigma_n"), ("s22", "sigma_s")):
+        off = ctx._history_sources("test", dict(src_t, **{name: shifted[name]}))
+        refused({6: 1, 7: (abi.I32 * 1)(abi.HISTORY_FIELDS.index(field)), 8: abi.C.byref(off)},
+                "nsdg_points_sample: tiled arrays (stress, ice strength) must be 16-byte aligned")
+    torch.cuda.synchronize()
+    assert bool((out == SENTINEL).all())
+    off = ctx._history_sources("test", dict(src_t, s12=shifted["s12"]))
+    assert call(*good[:6], 2, (abi.I32 * 2)(abi.HISTORY_FIELDS.index("hice"), abi.HISTORY_FIELDS.index("sigma_n")), abi.C.byref(off), n,
+                out.data_ptr()) == 0  # sigma_n reads s11 and s22 alone
+    torch.cuda.synchronize()
+    assert bool((out[:2] != SENTINEL).all()) and bool((out[2] == SENTINEL).all())
     args = list(good)
     args[3], args[4], args[5], args[10], args[9] = 0, None, None, None, 0
     assert call(*args) == 0  # n == 0 launches nothing

@@ -74,7 +74,8 @@ extern "C" {
  * nsdg_bbm_prepare / nsdg_bbm_iterate / nsdg_bbm_substep_count (brittle rheology) and nsdg_history_accumulate / nsdg_history_field_name /
  * nsdg_history_field_id, nsdg_history_accumulate_stats / nsdg_history_row_totals / nsdg_history_stat_* / nsdg_history_series_* (history
  * output) and nsdg_drifters_advance / nsdg_comm_max_f64_array (drifters) and nsdg_rb_bbm_create / nsdg_rb_bbm_destroy / nsdg_rb_bbm_run /
- * nsdg_rb_bbm_stats (the brittle sub-cycle of a row block) and nsdg_bbm_params_check and nsdg_points_sample (point samples) are additions;
+ * nsdg_rb_bbm_stats (the brittle sub-cycle of a row block) and nsdg_bbm_params_check and nsdg_points_sample (point samples) are additions, and so are the
+ * ice tracers' calls of nsdg_tracers.h;
  * nothing that existed changed. */
 #define NSDG_ABI_VERSION 6
 
@@ -411,6 +412,11 @@ int nsdg_ice_strength(nsdg_ctx* ctx, int32_t j0, int32_t j1, const double* H, co
 int nsdg_tracer_weight(nsdg_ctx* ctx, int32_t order, int32_t j0, int32_t j1, const double* H, const double* T, double* Q);
 int nsdg_tracer_recover(nsdg_ctx* ctx, int32_t order, int32_t j0, int32_t j1, const double* H, const double* A, const double* Q,
     double min_conc, double min_thick, double* T);
+
+/* ---- ice tracers: ice age and passive tracers ride on the moving ice (csrc/tracers.hip) ------------------------
+ * Up to NSDG_TRACERS_MAX intensive planes travel as Q = H T in a transport run of their own: weight before it, recover after it, dilute
+ * after the column step.  The three calls, their arithmetic and their checks are declared in nsdg_tracers.h, which this header includes. */
+#include "nsdg_tracers.h"
 
 /* ---- external forcing providers, evaluated on the device at the model time of each step (csrc/forcing.hip) ----
  * They replace DummyExternalData::setAll (core/src/include/DummyExternalData.hpp:22-34: the same eight constants in

@@ -100,6 +100,8 @@ POINTS_SOURCES = {"hice": ("H",), "cice": ("A",), "u": ("u",), "v": ("v",), "spe
 
 COMM_ID_BYTES = 128
 RB_MAX_FIELDS = 4
+TRACERS_MAX = 4  # NSDG_TRACERS_MAX (include/nsdg.h "ice tracers")
+TRACER_PASSIVE, TRACER_AGE = 0, 1  # NSDG_TRACER_*
 
 
 class RbMevpDesc(C.Structure):
@@ -238,6 +240,13 @@ SYMBOLS = {
     "nsdg_rb_transport_stats": (C.c_int, [VP, VP, C.POINTER(HaloStats), I32]),
 }
 
+# the functions of include/nsdg_tracers.h (the "ice tracers" section, a header of its own that nsdg.h includes), bound like SYMBOLS
+TRACER_SYMBOLS = {
+    "nsdg_tracers_weight": (C.c_int, [VP, I32, I32, I32, VP, I32, C.POINTER(VP), C.POINTER(VP)]),
+    "nsdg_tracers_recover": (C.c_int, [VP, I32, I32, I32, VP, VP, I32, C.POINTER(VP), C.POINTER(I32), D, D, D, C.POINTER(VP)]),
+    "nsdg_tracers_dilute": (C.c_int, [VP, I32, I32, VP, VP, I32, C.POINTER(VP)]),
+}
+
 _lib = None
 
 
@@ -255,7 +264,7 @@ def load_library(path=LIB_PATH):
         raise NsdgError("HIP library %s is missing: build it with `python -m nextsimdg_amd.build` "
                         "(there is no CPU fallback)" % path)
     lib = C.CDLL(path)
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in list(SYMBOLS.items()) + list(TRACER_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -858,6 +867,34 @@ class Context:
         H[0] >= min_thick A[0]); T keeps its value elsewhere"""
         _check_f64(H, A, Q, T)
         self._call(self.lib.nsdg_tracer_recover(self.h, order, j0, j1, _ptr(H), _ptr(A), _ptr(Q), float(min_conc), float(min_thick), _ptr(T)))
+
+    # ---- ice tracers (include/nsdg.h "ice tracers"; csrc/tracers.hip): up to TRACERS_MAX intensive planes per call
+    @staticmethod
+    def _tracer_planes(call, *lists):
+        n = len(lists[0])
+        if not 1 <= n <= TRACERS_MAX or any(len(x) != n for x in lists):
+            raise NsdgError("%s: 1 .. %d tracers, one entry per tracer in every list" % (call, TRACERS_MAX))
+        return n
+
+    def tracers_weight(self, order, j0, j1, H, T, Q):
+        """nsdg_tracers_weight: Q[k][c] = T[k] * H[c] for every tracer k and coefficient plane c of the elements of rows [j0, j1)"""
+        n = self._tracer_planes("tracers_weight", T, Q)
+        _check_f64(H, *T, *Q)
+        self._call(self.lib.nsdg_tracers_weight(self.h, order, j0, j1, _ptr(H), n, _ptr_array(T), _ptr_array(Q)))
+
+    def tracers_recover(self, order, j0, j1, H, A, Q, kinds, dt, min_conc, min_thick, T):
+        """nsdg_tracers_recover: where the element of rows [j0, j1) holds ice T[k] = Q[k][0] / H[0], plus dt for kinds[k] == TRACER_AGE;
+        T[k] = 0 where it does not"""
+        n = self._tracer_planes("tracers_recover", Q, kinds, T)
+        _check_f64(H, A, *Q, *T)
+        self._call(self.lib.nsdg_tracers_recover(self.h, order, j0, j1, _ptr(H), _ptr(A), n, _ptr_array(Q), (I32 * n)(*[int(k) for k in kinds]),
+                                                 float(dt), float(min_conc), float(min_thick), _ptr_array(T)))
+
+    def tracers_dilute(self, j0, j1, h_before, h_after, T):
+        """nsdg_tracers_dilute: growth of the mean thickness from max(h_before, 0) to h_after mixes every T[k] with ice of the value 0"""
+        n = self._tracer_planes("tracers_dilute", T)
+        _check_f64(h_before, h_after, *T)
+        self._call(self.lib.nsdg_tracers_dilute(self.h, j0, j1, _ptr(h_before), _ptr(h_after), n, _ptr_array(T)))
 
     # ---- history output (include/nsdg.h "history output"; csrc/history.hip)
     def history_accumulate(self, j0, j1, fields, sources, store, row0, acc):

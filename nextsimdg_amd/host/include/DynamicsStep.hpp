@@ -80,6 +80,15 @@
 //     dynamics.bbm_courant   cells the elastic wave may cross per sub-iteration (NSDG_BBM_COURANT = 0.25): without an explicit
 //                            dynamics.nsub the count is nsdg_bbm_substep_count for the (sub-)step's dt; an explicit dynamics.nsub is used
 //                            as given, with one warning line if it is below the rule's value
+//     dynamics.tracers       names of up to NSDG_TRACERS_MAX ice tracers, comma-separated (include/nsdg.h "ice tracers"):
+//                            intensive planes that ride on the ice as Q = H T in a transport run of their own after the run of H and A
+//                            (nsdg_tracers_weight, a second transport plan without bounds, nsdg_tracers_recover); `age` grows by the
+//                            (sub-)step's dt where there is ice, every other name is passive; with thermodynamics, ice that grows carries
+//                            the value 0 (nsdg_tracers_dilute after the column step).  Names are identifiers, given once, and none of the
+//                            restart file's own names.  A restart file holds them as `tracer_<name>`; one without a dataset starts that
+//                            tracer at zero.  Not given (default): nothing changes
+//     dynamics.tracer_init   their initial values, one entry per name: a float64 .npy array of the shape (rectgrid.nx, rectgrid.ny) of the
+//                            structure's planes, or - for zeros; a restart file with the state of the dynamics takes precedence
 //     dynamics.row_blocks, dynamics.devices, dynamics.passes_per_exchange (2), dynamics.overlap (true),
 //     dynamics.graph (false), dynamics.loopback_world (0: off; N: rehearse an interior block of N on one GPU with
 //     real RCCL send/recv to the rank itself -- values wrap around, for timing and call-path checks only)
@@ -144,6 +153,9 @@ public:
     static void placeRows(FieldStore& f, bool thermodynamics, int nx, int r0, int r1, const double* data, std::size_t count);
     //! the keys of the brittle rheology (dynamics.rheology, dynamics.bbm_courant, bbm.*): a step that does not run it refuses them
     static const std::vector<std::string>& brittleKeys();
+    //! the names of dynamics.tracers from its value; throws std::invalid_argument, naming the key, for more than NSDG_TRACERS_MAX names, a
+    //! name given twice, one that is no identifier and one that a restart file or the state already uses
+    static std::vector<std::string> tracerNames(const std::string& value);
 
 private:
     void release();
@@ -177,6 +189,8 @@ private:
     std::unique_ptr<Outputs> m_out;
     struct Brittle; // dynamics.rheology = bbm: the parameters and the sub-iteration rule (DynamicsStep.cpp); null: mEVP
     std::unique_ptr<Brittle> m_brittle;
+    std::vector<std::string> m_tracers; // dynamics.tracers: the names, in order
+    std::vector<std::vector<double>> m_tracerInit; // dynamics.tracer_init: one plane per name (empty: zeros), read and checked in configure()
     bool nsubGiven = false; // dynamics.nsub is in the configuration
     int substeps = 1; // dynamics.substeps; 0 = auto
     double substepCourant = 1.5; // dynamics.substep_courant (NSDG_SUBSTEP_COURANT)

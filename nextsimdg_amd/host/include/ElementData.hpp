@@ -29,6 +29,13 @@ struct DynamicsState {
     //! all six coefficients of the damage D of dynamics.rheology = bbm: [6][x][y] (no FieldStore plane holds its mean); EMPTY without that
     //! rheology and after reading a file that does not hold it (a brittle run then starts undamaged)
     std::vector<double> damage;
+    //! the ice tracers of dynamics.tracers, in the order of that key: one plane [x][y] each (include/nsdg.h "ice tracers"), dataset
+    //! `tracer_<name>` of a restart file; EMPTY without the key, and a file's planes that the key does not name are not kept (either format)
+    struct NamedPlane {
+        std::string name;
+        std::vector<double> values;
+    };
+    std::vector<NamedPlane> tracers;
     inline void resize(std::size_t nx, std::size_t ny); //!< every variable that is not optional: zeros of its shape
     inline void clear();
 };
@@ -97,6 +104,7 @@ void DynamicsState::clear()
     for (const DynamicsVariable& v : DYNAMICS_VARIABLES)
         if (v.state)
             (this->*v.state).clear();
+    tracers.clear();
 }
 
 //! Builder with the reference's method names (core/src/include/PrognosticGenerator.hpp:17-90).

@@ -108,8 +108,9 @@ void DynamicsBlock::createContext(bool phaseTiming)
         check(nsdg_phase_timing_set(c, 1), "nsdg_phase_timing_set");
 }
 
-void DynamicsBlock::allocate(bool brittle, bool advectColumn)
+void DynamicsBlock::allocate(bool brittle, bool advectColumn, int ntracers_)
 {
+    ntracers = ntracers_;
     const long TS = nsdg_tiled_len(nx, ny, 8), TP = nsdg_tiled_len(nx, ny, 9);
     nfields = 0;
     for (int k = 0; k < NFIELD; ++k) {
@@ -119,6 +120,11 @@ void DynamicsBlock::allocate(bool brittle, bool advectColumn)
     }
     // [6][ny][nx] unless set below: VXDG, VYDG and, after the arrays of Arr, the three buffers of every advected field (adv)
     std::vector<long> sizes(NARR + 3 * nfields, 6 * N);
+    if (ntracers > 0) { // the planes of the tracers, three buffers [6][ny][nx] per product, the plane of the thickness before the column step
+        sizes.insert(sizes.end(), (std::size_t)ntracers, N);
+        sizes.insert(sizes.end(), 3 * (std::size_t)ntracers, 6 * N);
+        sizes.push_back(N);
+    }
     for (int a : { S11a, S12a, S22a, S11b, S12b, S22b })
         sizes[a] = TS;
     sizes[PG] = TP;
@@ -141,7 +147,7 @@ void DynamicsBlock::allocate(bool brittle, bool advectColumn)
         d.push_back(arrays.get() + off);
         off += (s + 1) & ~1L;
     }
-    par = tpar = 0;
+    par = tpar = qpar = 0;
 }
 
 void DynamicsBlock::setLandMask(const LandMaskFile& mask)
@@ -194,6 +200,24 @@ void DynamicsBlock::upload(const FieldStore& f, bool thermodynamics, bool announ
     }
 }
 
+void DynamicsBlock::uploadTracers(const FieldStore& f, const std::vector<std::string>& names, const std::vector<std::vector<double>>& init, bool announce)
+{
+    const std::size_t first = (std::size_t)lo * nx, NG = (std::size_t)nx * nyGlobal;
+    for (int k = 0; k < ntracers; ++k) {
+        const std::vector<double>* from = init[k].size() == NG ? &init[k] : nullptr; // (none: the plane stays at the zeros of allocate())
+        if (f.dyn.present) { // a restart file takes precedence over dynamics.tracer_init; a file without the dataset: zeros
+            from = nullptr;
+            for (const DynamicsState::NamedPlane& t : f.dyn.tracers)
+                if (t.name == names[k] && t.values.size() == NG)
+                    from = &t.values;
+            if (!from && announce)
+                std::printf("dynamics tracers: the initial state holds no tracer_%s, the tracer starts at zero\n", names[k].c_str());
+        }
+        if (from)
+            toDevice(tracer(k), from->data() + first, (std::size_t)N * sizeof(double), "upload tracer");
+    }
+}
+
 void DynamicsBlock::allocateRecords(std::size_t count)
 {
     records = deviceAlloc<double>(count, "DynamicsStep: hipMalloc (forcing records)");
@@ -210,6 +234,8 @@ void DynamicsBlock::clearLand(bool thermodynamics)
         check(nsdg_land_clear(ctx.get(), 0, ny, 1, col(C_NEWICE)), "nsdg_land_clear");
     }
     check(nsdg_land_clear_nodes(ctx.get(), d[Ua], d[Va]), "nsdg_land_clear_nodes");
+    for (int k = 0; k < ntracers; ++k)
+        check(nsdg_land_clear(ctx.get(), 0, ny, 1, tracer(k)), "nsdg_land_clear");
 }
 
 double* DynamicsBlock::outputBuffer(std::size_t count, const char* what)
@@ -264,6 +290,21 @@ void DynamicsBlock::makeTransportPlan(bool closure)
     nsdg_rb_transport* plan = nullptr;
     check(nsdg_rb_transport_create(ctx.get(), &t, &plan), "nsdg_rb_transport_create");
     transport.reset(plan);
+}
+
+void DynamicsBlock::makeTracerPlan()
+{
+    nsdg_rb_transport_desc t;
+    std::memset(&t, 0, sizeof t);
+    fillGeometry(t, *this);
+    t.order = 2, t.nfields = ntracers;
+    t.vx_dg = d[VXDG], t.vy_dg = d[VYDG], t.un_x = d[UNX], t.un_y = d[UNY];
+    t.own_bounds = 1, t.nbounds = 0; // every product is unbounded: no limiter, no cap, whatever the context says
+    for (int k = 0; k < ntracers; ++k)
+        t.phi[k] = tracerQ(k, 0), t.t1[k] = tracerQ(k, 1), t.t2[k] = tracerQ(k, 2);
+    nsdg_rb_transport* plan = nullptr;
+    check(nsdg_rb_transport_create(ctx.get(), &t, &plan), "nsdg_rb_transport_create (tracers)");
+    tracerTransport.reset(plan);
 }
 
 nsdg_history_sources DynamicsBlock::sources(bool thermodynamics, bool advectColumn) const
@@ -325,6 +366,21 @@ void DynamicsBlock::download(FieldStore& f, bool thermodynamics, bool advectColu
         toHost(t.data(), d[(par == 0 ? S11a : S11b) + k], t.size() * sizeof(double), "download stress");
         untileRows(t, nx, j0, j1 - j0, (dy.*STRESS[k]).data(), NG, (std::size_t)r0);
     }
+}
+
+void DynamicsBlock::downloadTracers(FieldStore& f, const std::vector<std::string>& names) const
+{
+    std::vector<DynamicsState::NamedPlane>& held = f.dyn.tracers;
+    bool same = held.size() == names.size();
+    for (std::size_t k = 0; same && k < names.size(); ++k)
+        same = held[k].name == names[k] && held[k].values.size() == (std::size_t)nx * nyGlobal;
+    if (!same) { // (the blocks of a process write disjoint rows of the same planes: made once)
+        held.clear();
+        for (const std::string& name : names)
+            held.push_back({ name, std::vector<double>((std::size_t)nx * nyGlobal, 0.) });
+    }
+    for (int k = 0; k < ntracers; ++k)
+        ownedRowsToHost(held[k].values.data(), 0, tracer(k), true, "download tracer");
 }
 
 RowRange::RowRange(const DynamicsBlocks& blocks)

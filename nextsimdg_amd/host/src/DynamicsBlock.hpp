@@ -12,6 +12,7 @@
 #include <cstdint>
 #include <exception>
 #include <memory>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -108,11 +109,16 @@ public:
     long recordOf[2] = { -1, -1 };
     DeviceBuffer<double> arrays; // the arrays of Arr and the buffers of the advected fields: one allocation
     NsdgHandle<nsdg_rb_transport, nsdg_rb_transport_destroy> transport;
+    NsdgHandle<nsdg_rb_transport, nsdg_rb_transport_destroy> tracerTransport; // dynamics.tracers: the second transport group, without bounds
     NsdgHandle<nsdg_rb_bbm, nsdg_rb_bbm_destroy> bbm; // dynamics.rheology = bbm: the plan of the current sub-iteration count (made when that is known)
     int bbmNsub = -1;
     NsdgHandle<nsdg_rb_mevp, nsdg_rb_mevp_destroy> mevp;
 
-    std::vector<double*> d; // the arrays of Arr, then three buffers per advected field (adv)
+    // the arrays of Arr, then three buffers per advected field (adv), then -- dynamics.tracers -- one plane per tracer, three buffers per
+    // tracer's product Q = H T and the plane of the mean thickness before the column step
+    std::vector<double*> d;
+    int ntracers = 0; // dynamics.tracers: how many
+    int qpar = 0; // which buffers hold the tracers' products (the parity of the second transport plan)
     int nfields = 0; // rows of ADVECTED this run advects ...
     int slot[NFIELD]; // ... and where each sits among the device buffers and in the transport plan (-1: not in this run)
     int par = 0, tpar = 0; // which buffers hold the velocity/stress iterate and the advected state
@@ -122,12 +128,16 @@ public:
     //! the context on the block's device (made current), with phase timing if asked for
     void createContext(bool phaseTiming);
     //! which rows of ADVECTED this run advects; the arrays of Arr and the advected fields: one allocation, zeroed, every array 16-byte aligned
-    void allocate(bool brittle, bool advectColumn);
+    //! ntracers: the planes and buffers of dynamics.tracers as well
+    void allocate(bool brittle, bool advectColumn, int ntracers = 0);
     //! the block's rows of the mask, ghost rows included, on the device and on the context: the mask is static, nothing is ever exchanged
     void setLandMask(const LandMaskFile& mask);
     //! the local rows, ghost rows included, of the structure's cell means and, if a dynamics run left it (FieldStore::dyn), of its state;
     //! with thermodynamics the column planes.  announce: this block prints the line about a restart file without damage
     void upload(const FieldStore& f, bool thermodynamics, bool announce);
+    //! dynamics.tracers: the local rows of every named tracer -- from the state a restart file left (FieldStore::dyn.tracers, by name), else
+    //! from the plane of dynamics.tracer_init (empty: zeros).  announce: this block prints the line about a restart file without a tracer
+    void uploadTracers(const FieldStore& f, const std::vector<std::string>& names, const std::vector<std::vector<double>>& init, bool announce);
     //! dynamics.forcing = file: room for `count` doubles of records, none resident yet
     void allocateRecords(std::size_t count);
     //! no ice on land, no motion at land nodes, whatever the initial state or the restart file held there
@@ -138,6 +148,7 @@ public:
     //! replaces the brittle plan, after the work queued on the context, which may still run the old one
     void makeBbmPlan(int nsub, bool overlap, bool completeNodes);
     void makeTransportPlan(bool closure);
+    void makeTracerPlan(); //!< dynamics.tracers: a second transport plan over the tracers' products, created without bounds
 
     // ---- reading the state
     // per advected field, after the arrays of Arr: the two halves of the ping-pong (h = 0, 1; tpar says which is current), the stage buffer (2)
@@ -146,6 +157,11 @@ public:
     double* curU() const { return d[par == 0 ? Ua : Ub]; }
     double* curV() const { return d[par == 0 ? Va : Vb]; }
     double* col(int k) const { return d[COL] + (long)k * N; }
+    // dynamics.tracers, after the advected fields: the plane of tracer k, the buffers of its product (h as for adv; qpar says which is
+    // current), the plane of the mean thickness before the column step
+    double* tracer(int k) const { return d[NARR + 3 * nfields + k]; }
+    double* tracerQ(int k, int h) const { return d[NARR + 3 * nfields + ntracers + 3 * k + h]; }
+    double* thicknessBefore() const { return d[NARR + 3 * nfields + 4 * ntracers]; }
     //! what a history sample, the row totals and the point samples read: the current side of every ping-pong
     nsdg_history_sources sources(bool thermodynamics, bool advectColumn) const;
     //! the owned rows of a device plane of nx columns -- of the owned rows alone, or (ghosted) of every local row -- into a host plane
@@ -153,6 +169,8 @@ public:
     void ownedRowsToHost(double* hostPlane, int row0, const double* devicePlane, bool ghosted, const char* what) const;
     //! stop(): the owned rows of the state a restart needs into the structure (the caller has drained the context)
     void download(FieldStore& f, bool thermodynamics, bool advectColumn) const;
+    //! stop(): the owned rows of the tracers into FieldStore::dyn.tracers, under their names
+    void downloadTracers(FieldStore& f, const std::vector<std::string>& names) const;
 };
 
 using DynamicsBlocks = std::vector<std::unique_ptr<DynamicsBlock>>;

@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -36,7 +37,7 @@ const std::map<int, std::string> Configured<DynamicsStep>::keyMap = { { 0, "dyna
     { 14, "dynamics.min_thick" }, { 15, "dynamics.delta_min" }, { 16, "dynamics.subcycle" }, { 17, "dynamics.substeps" },
     { 18, "dynamics.substep_courant" }, { 19, "dynamics.max_substeps" }, { 20, "dynamics.forcing_file" },
     { 21, "dynamics.advect_column_state" }, { 22, "dynamics.land_mask_file" }, { 23, "dynamics.rheology" },
-    { 24, "dynamics.bbm_courant" } };
+    { 24, "dynamics.bbm_courant" }, { 25, "dynamics.tracers" }, { 26, "dynamics.tracer_init" } };
 
 // dynamics.rheology = bbm
 struct DynamicsStep::Brittle {
@@ -73,6 +74,34 @@ const BbmKey BBM_KEYS[] = { { "bbm.young", &nsdg_bbm_params::young }, { "bbm.nu"
     { "bbm.compr_strength", &nsdg_bbm_params::compr_strength }, { "bbm.t_heal", &nsdg_bbm_params::t_heal }, { "bbm.d_max", &nsdg_bbm_params::d_max } };
 const char* const BBM_EXPONENT_KEY = "bbm.relax_exponent";
 } // namespace
+
+std::vector<std::string> DynamicsStep::tracerNames(const std::string& value)
+{
+    const std::string key = "dynamics.tracers";
+    // what a restart file, the state of the dynamics and the column model already call something
+    static const char* const TAKEN[] = { "hice", "cice", "hsnow", "sst", "sss", "tice", "newice", "hice_dg", "cice_dg", "hsnow_dg", "damage", "u", "v",
+        "s11", "s12", "s22", "H", "A", "S", "Q", "D", "tice0", "tracers" };
+    std::vector<std::string> names;
+    std::stringstream ss(value);
+    for (std::string name; std::getline(ss, name, ',');) {
+        name.erase(0, name.find_first_not_of(" \t"));
+        name.erase(name.find_last_not_of(" \t") + 1);
+        bool identifier = !name.empty() && !std::isdigit((unsigned char)name[0]);
+        for (const char c : name)
+            identifier = identifier && (std::isalnum((unsigned char)c) || c == '_');
+        if (!identifier)
+            throw std::invalid_argument(key + ": \"" + name + "\" is not an identifier (letters, digits and _, not starting with a digit)");
+        for (const char* taken : TAKEN)
+            if (name == taken)
+                throw std::invalid_argument(key + ": \"" + name + "\" collides with a name of the state");
+        if (std::find(names.begin(), names.end(), name) != names.end())
+            throw std::invalid_argument(key + ": \"" + name + "\" is named more than once");
+        names.push_back(name);
+    }
+    if (names.size() > NSDG_TRACERS_MAX)
+        throw std::invalid_argument(key + ": " + std::to_string(names.size()) + " names; the tracer group carries at most " + std::to_string(NSDG_TRACERS_MAX));
+    return names;
+}
 
 const std::vector<std::string>& DynamicsStep::brittleKeys()
 {
@@ -227,6 +256,32 @@ void DynamicsStep::configure()
                 throw std::invalid_argument("dynamics.bbm_courant must be positive");
         }
     }
+    // ice tracers (include/nsdg.h "ice tracers"): the names and the files of their initial values, read and checked here
+    m_tracers = tracerNames(getConfiguration(keyMap.at(25), std::string("")));
+    m_tracerInit.assign(m_tracers.size(), std::vector<double>());
+    {
+        const std::string key = keyMap.at(26), value = getConfiguration(key, std::string(""));
+        std::vector<std::string> files;
+        std::stringstream ss(value);
+        for (std::string item; std::getline(ss, item, ',');)
+            files.push_back(item);
+        if (!value.empty() && files.size() != m_tracers.size())
+            throw std::invalid_argument(key + ": " + std::to_string(files.size()) + " entries for the " + std::to_string(m_tracers.size())
+                + " names of dynamics.tracers (a .npy file or - for each)");
+        for (std::size_t k = 0; k < files.size(); ++k) {
+            if (files[k] == "-")
+                continue;
+            Npy a;
+            try {
+                a = readNpy(files[k]);
+            } catch (const std::exception& e) {
+                throw std::invalid_argument(key + ": " + e.what());
+            }
+            if (a.shape.size() != 2 || (pStructure && (a.shape[0] != (std::uint64_t)pStructure->nx() || a.shape[1] != (std::uint64_t)pStructure->ny())))
+                throw std::invalid_argument(key + ": " + files[k] + " does not have the shape (rectgrid.nx, rectgrid.ny) of the structure's planes");
+            m_tracerInit[k] = std::move(a.values);
+        }
+    }
     configureOutputs();
 }
 
@@ -342,6 +397,9 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
             std::printf("dynamics land mask: %zu of %zu elements are land (%s)\n", m_landMask->landElements(), (std::size_t)nxf * nyf,
                 m_landMask->path().c_str());
     }
+    for (std::size_t k = 0; k < m_tracers.size(); ++k)
+        if (!m_tracerInit[k].empty() && m_tracerInit[k].size() != (std::size_t)nxf * nyf)
+            throw std::invalid_argument("dynamics.tracer_init: the array of \"" + m_tracers[k] + "\" does not have the shape (rectgrid.nx, rectgrid.ny) of the structure's planes");
     makeBlocks();
     const long group = g_localGroup++;
     unsigned char commId[NSDG_COMM_ID_BYTES];
@@ -366,13 +424,14 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
             check(nsdg_column_params_set(ctx, &p), "nsdg_column_params_set");
         }
         // ---- arrays
-        b.allocate(m_brittle != nullptr, advectColumn);
+        b.allocate(m_brittle != nullptr, advectColumn, (int)m_tracers.size());
         check(nsdg_grid_set(ctx, b.nx, b.ny, L / nxf, L / nyf), "nsdg_grid_set");
         check(nsdg_block_set(ctx, b.lo, b.nyGlobal), "nsdg_block_set");
         // ---- land mask, upload
         if (m_landMask)
             b.setLandMask(*m_landMask);
         b.upload(f, thermo, b.index == 0 && m_rank == 0);
+        b.uploadTracers(f, m_tracers, m_tracerInit, b.index == 0 && m_rank == 0);
         // ---- forcing: the analytic box test, evaluated on the device (ocean once, wind at the current model time every step); a forcing
         // file's wind and ocean pairs replace it at every step
         check(nsdg_boxtest_forcing(ctx, L, m_time, b.d[UA], b.d[VA], b.d[UO], b.d[VO]), "nsdg_boxtest_forcing");
@@ -388,6 +447,8 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
         else
             b.makeMevpPlan(nsub, overlap, graph);
         b.makeTransportPlan(closure);
+        if (b.ntracers > 0)
+            b.makeTracerPlan();
     });
 }
 
@@ -472,6 +533,8 @@ void DynamicsStep::subStep(double dt, bool last)
     DriftersChannel* drifters = m_out->drifters && m_out->drifters->any() ? m_out->drifters.get() : nullptr;
     forEachBlock(m_blocks, [&](DynamicsBlock& b) {
         nsdg_ctx* ctx = b.ctx.get();
+        double* tr[NSDG_TRACERS_MAX] = {}; // dynamics.tracers: the planes of the tracers and the current buffers of their products
+        double* tq[NSDG_TRACERS_MAX] = {};
         check(nsdg_mevp_params_set(ctx, &p), "nsdg_mevp_params_set");
         check(nsdg_phase_mark(ctx, NSDG_PHASE_FORCING), "nsdg_phase_mark");
         if (!ff || !ff->hasWind())
@@ -487,6 +550,8 @@ void DynamicsStep::subStep(double dt, bool last)
                 check(nsdg_column_wind(ctx, b.d[UA], b.d[VA], b.col(C_WIND)), "nsdg_column_wind");
             }
             check(nsdg_phase_mark(ctx, NSDG_PHASE_COLUMN), "nsdg_phase_mark");
+            if (b.ntracers > 0) // the mean thickness the column step starts from (nsdg_tracers_dilute below)
+                check(nsdg_copy_f64(ctx, b.thicknessBefore(), b.cur(FH), b.N), "nsdg_copy_f64");
             // the column physics needs no exchange: it runs on the ghost rows too, redundantly
             check(nsdg_column_step(ctx, b.N, dt, b.cur(FH), b.cur(FA), advectColumn ? b.cur(FS) : b.col(C_HSNOW), b.col(C_TICE), b.col(C_SST), b.col(C_SSS), b.col(C_TAIR),
                       b.col(C_TDEW), b.col(C_SLP), b.col(C_QSW), b.col(C_QLW), b.col(C_MLD), b.col(C_SNOWFALL), b.col(C_WIND), b.col(C_NEWICE),
@@ -499,6 +564,11 @@ void DynamicsStep::subStep(double dt, bool last)
                     check(nsdg_land_clear(ctx, 0, b.ny, 1, plane), "nsdg_land_clear");
                 if (m_brittle) // and the damage with them
                     check(nsdg_land_clear(ctx, 0, b.ny, 6, b.cur(FD)), "nsdg_land_clear");
+            }
+            if (b.ntracers > 0) { // ice that grew carries the value 0 (every local row: element-local, as the column step)
+                for (int k = 0; k < b.ntracers; ++k)
+                    tr[k] = b.tracer(k);
+                check(nsdg_tracers_dilute(ctx, 0, b.ny, b.thicknessBefore(), b.cur(FH), b.ntracers, tr), "nsdg_tracers_dilute");
             }
         }
         check(nsdg_phase_mark(ctx, NSDG_PHASE_PREPARE), "nsdg_phase_mark");
@@ -524,10 +594,25 @@ void DynamicsStep::subStep(double dt, bool last)
         // the surface temperature travels as Q = H tice0 (every local row: element-local, the ghost rows stay equal to their owners)
         if (advectColumn)
             check(nsdg_tracer_weight(ctx, 2, 0, b.ny, b.cur(FH), b.col(C_TICE), b.cur(FQ)), "nsdg_tracer_weight");
+        if (b.ntracers > 0) { // the tracers' products, with the thickness the step starts from (every local row, as above)
+            for (int k = 0; k < b.ntracers; ++k)
+                tr[k] = b.tracer(k), tq[k] = b.tracerQ(k, b.qpar);
+            check(nsdg_tracers_weight(ctx, 2, 0, b.ny, b.cur(FH), b.ntracers, tr, tq), "nsdg_tracers_weight");
+        }
         check(nsdg_rb_transport_run(ctx, b.transport.get(), dt, b.tpar, &out), "nsdg_rb_transport_run");
         b.tpar = out;
         if (advectColumn)
             check(nsdg_tracer_recover(ctx, 2, 0, b.ny, b.cur(FH), b.cur(FA), b.cur(FQ), p.min_conc, p.min_thick, b.col(C_TICE)), "nsdg_tracer_recover");
+        if (b.ntracers > 0) {
+            // the second transport group: the same prepared velocity and dt, no bounds; then the division back, which ages `age` by dt
+            check(nsdg_rb_transport_run(ctx, b.tracerTransport.get(), dt, b.qpar, &out), "nsdg_rb_transport_run (tracers)");
+            b.qpar = out;
+            int32_t kinds[NSDG_TRACERS_MAX] = {};
+            for (int k = 0; k < b.ntracers; ++k)
+                tq[k] = b.tracerQ(k, b.qpar), kinds[k] = m_tracers[k] == "age" ? NSDG_TRACER_AGE : NSDG_TRACER_PASSIVE;
+            check(nsdg_tracers_recover(ctx, 2, 0, b.ny, b.cur(FH), b.cur(FA), b.ntracers, tq, kinds, dt, p.min_conc, p.min_thick, tr),
+                "nsdg_tracers_recover");
+        }
         if (drifters)
             drifters->advance(b, dt);
         if (last) // the model step ends here: what follows until its next mark belongs to no phase
@@ -640,6 +725,7 @@ void DynamicsStep::stop(const Iterator::TimePoint&)
         if (gaveUp)
             throw std::runtime_error("DynamicsStep: " + std::to_string(gaveUp) + " wait(s) of the mEVP pipeline gave up: the fields are not to be trusted");
         b.download(f, thermo, advectColumn);
+        b.downloadTracers(f, m_tracers);
         // owned node rows: [2 r0, 2 r1) plus the top boundary row on the last block
         const long nn = 2L * b.nx + 1, rows = 2L * b.ownedRows() + (b.peerAbove < 0 ? 1 : 0);
         for (long k = 2L * b.r0 * nn; k < (2L * b.r0 + rows) * nn; ++k) {
@@ -739,6 +825,8 @@ template <class F> void forPayload(FieldStore& f, bool thermodynamics, int nx, i
         for (int c = 0; c < v.elementPlanes(); ++c)
             fn(v.in(f), (std::size_t)c * f.n + first, rows);
     }
+    for (DynamicsState::NamedPlane& t : f.dyn.tracers) // dynamics.tracers: every rank runs the same names, so both ends hold the same planes
+        fn(t.values, first, rows);
 }
 } // namespace
 

@@ -9,6 +9,7 @@
 #include <sstream>
 #include <stdexcept>
 
+#include "DynamicsStep.hpp"
 #include "Hdf5Subset.hpp"
 #include "ModuleLoader.hpp"
 
@@ -94,8 +95,12 @@ void RectGrid::incrCursor()
 
 namespace {
 const char* MAGIC = "NSDG-RESTART 1";
-//! `on`: receives every other key of the header whose value is 1 (data.dynamics and the flags of the optional variables)
-bool readHeader(std::istream& f, std::string& type, int& nx, int& ny, int& nl, std::set<std::string>* on = nullptr)
+const std::string TRACER_FLAG = "data.tracer."; // sidecar header: data.tracer.<name>=1, one line per tracer plane, in file order
+const std::string TRACER_DATASET = "tracer_"; // the dataset (HDF5) / the entry of variables= (sidecar) of a tracer: tracer_<name>
+//! `on`: receives every other key of the header whose value is 1 (data.dynamics and the flags of the optional variables); `tracers`: the
+//! names of the data.tracer.<name>=1 lines, in their order
+bool readHeader(std::istream& f, std::string& type, int& nx, int& ny, int& nl, std::set<std::string>* on = nullptr,
+    std::vector<std::string>* tracers = nullptr)
 {
     std::string line;
     if (!std::getline(f, line) || line != MAGIC)
@@ -115,6 +120,8 @@ bool readHeader(std::istream& f, std::string& type, int& nx, int& ny, int& nl, s
             ny = std::stoi(v);
         else if (k == "data.nLayers")
             nl = std::stoi(v);
+        else if (tracers && v == "1" && k.compare(0, TRACER_FLAG.size(), TRACER_FLAG) == 0)
+            tracers->push_back(k.substr(TRACER_FLAG.size()));
         else if (on && v == "1")
             on->insert(k);
     }
@@ -191,6 +198,10 @@ void RectGrid::dump(const std::string& filePath) const
                 w.dataset(data + "/" + v.name, dims, v.in(m_store));
                 w.attachDimensions(data + "/" + v.name, scales);
             }
+            for (const DynamicsState::NamedPlane& t : m_store.dyn.tracers) { // dynamics.tracers: one plane each
+                w.dataset(data + "/" + TRACER_DATASET + t.name, { X, Y }, t.values);
+                w.attachDimensions(data + "/" + TRACER_DATASET + t.name, { data + "/x", data + "/y" });
+            }
         }
         w.write(filePath);
         return;
@@ -212,15 +223,22 @@ void RectGrid::dump(const std::string& filePath) const
                     f << v.sidecarFlag << "=1\n";
                 variables += std::string(",") + v.name;
             }
+        for (const DynamicsState::NamedPlane& t : m_store.dyn.tracers) {
+            f << TRACER_FLAG << t.name << "=1\n";
+            variables += "," + TRACER_DATASET + t.name;
+        }
     }
     f << variables << "\nEND-HEADER\n";
     for (const auto* v : { &m_store.hice, &m_store.cice, &m_store.hsnow, &m_store.sst, &m_store.sss })
         f.write(reinterpret_cast<const char*>(v->data()), (std::streamsize)(v->size() * sizeof(double)));
     f.write(reinterpret_cast<const char*>(t.data()), (std::streamsize)(t.size() * sizeof(double)));
-    if (m_store.dyn.present)
+    if (m_store.dyn.present) {
         for (const DynamicsVariable& v : DYNAMICS_VARIABLES)
             if (written(v, m_store))
                 f.write(reinterpret_cast<const char*>(v.in(m_store).data()), (std::streamsize)(v.in(m_store).size() * sizeof(double)));
+        for (const DynamicsState::NamedPlane& t : m_store.dyn.tracers)
+            f.write(reinterpret_cast<const char*>(t.values.data()), (std::streamsize)(t.values.size() * sizeof(double)));
+    }
 }
 
 void RectGrid::init(const std::string& filePath)
@@ -270,6 +288,16 @@ void RectGrid::init(const std::string& filePath)
                     throw std::runtime_error("restart file " + filePath + ": " + v.name + " does not have the size the grid asks for");
                 v.in(m_store).swap(a);
             }
+            // the tracers the configuration names (DynamicsStep::tracerNames: the one reading of dynamics.tracers), in its order; one the
+            // file does not hold is left out, one it holds beside them is not read
+            for (const std::string& name : DynamicsStep::tracerNames(Configured<RectGrid>::getConfiguration("dynamics.tracers", std::string("")))) {
+                if (!h.exists(g + TRACER_DATASET + name))
+                    continue;
+                std::vector<double> a = h.readDoubles(g + TRACER_DATASET + name);
+                if (a.size() != m_store.n)
+                    throw std::runtime_error("restart file " + filePath + ": " + TRACER_DATASET + name + " does not have x*y elements");
+                m_store.dyn.tracers.push_back({ name, std::move(a) });
+            }
             m_store.dyn.present = true;
         }
         resetCursor();
@@ -279,7 +307,8 @@ void RectGrid::init(const std::string& filePath)
     std::string type;
     int nx, ny, nl;
     std::set<std::string> on;
-    if (!f || !readHeader(f, type, nx, ny, nl, &on))
+    std::vector<std::string> tracers;
+    if (!f || !readHeader(f, type, nx, ny, nl, &on, &tracers))
         throw std::runtime_error("cannot read restart file " + filePath);
     if (structureType() == "devgrid" && (nx != 10 || ny != 10))
         throw std::runtime_error("devgrid restart files must be 10x10");
@@ -296,6 +325,16 @@ void RectGrid::init(const std::string& filePath)
             v.in(m_store).resize(v.size((std::size_t)nx, (std::size_t)ny));
             f.read(reinterpret_cast<char*>(v.in(m_store).data()), (std::streamsize)(v.in(m_store).size() * sizeof(double)));
         }
+        // as from an HDF5 file: the tracers the configuration names, in its order; the file's other tracer planes are passed over
+        std::map<std::string, std::vector<double>> held;
+        for (const std::string& name : tracers) {
+            std::vector<double>& a = held[name];
+            a.resize(m_store.n);
+            f.read(reinterpret_cast<char*>(a.data()), (std::streamsize)(m_store.n * sizeof(double)));
+        }
+        for (const std::string& name : DynamicsStep::tracerNames(Configured<RectGrid>::getConfiguration("dynamics.tracers", std::string(""))))
+            if (held.count(name))
+                m_store.dyn.tracers.push_back({ name, std::move(held[name]) });
         m_store.dyn.present = true;
     }
     if (!f)

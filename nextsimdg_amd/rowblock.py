@@ -282,7 +282,12 @@ class DynamicsCore:
 
     step() = one model time step: nodal means of H and A, ice strength at the Gauss points, wind
     stress, `nsub` mEVP sub-iterations (velocity halo after each), advection-velocity preparation and
-    one SSP-RK3 DG2 transport step of H and A (element halo after each stage)."""
+    one SSP-RK3 DG2 transport step of H and A (element halo after each stage).
+
+    tracers=("age", "origin"): named intensive planes that ride on the ice (include/nsdg.h "ice tracers") as
+    Q = H T in a transport group of their own after the run of H and A; "age" grows by dt where there is ice, every other name is
+    passive; tracers_read() / load_tracers() and the key "tracers" of state_dict() hold them.  None or (): no tracers, the same calls as
+    ever."""
 
     ORDER = 2
     # closure of the transported fields (include/nsdg.h "INPUT DOMAIN AND CLOSURE"): mean thickness H >= 0; concentration
@@ -297,6 +302,11 @@ class DynamicsCore:
     BBM_OPS = ("bbm_prepare", "bbm_iterate")
     BBM_NATIVE_OPS = ("rb_bbm", "rb_transport")
     DAMAGE_BOUNDS = (0.0, 1.0, False)  # the damage D of the brittle rheology: in [0, 1], no cap of the cell mean
+    # tracers= (include/nsdg.h "ice tracers"): the calls it needs, the name that ages, and the names a tracer may not take -- the keys of
+    # state_dict() and of the column state
+    TRACER_OPS = ("tracers_weight", "tracers_recover", "tracers_dilute")
+    AGE_TRACER = "age"
+    STATE_KEYS = ("rows", "ny_global", "nx", "H", "A", "S", "Q", "D", "u", "v", "s11", "s12", "s22", "drifters", "tracers", "hsnow", "tice0")
     HISTORY_COLUMN_FIELDS = outputs.History.COLUMN_FIELDS
     HAS_COLUMN_STATE = False
     merge_history, merge_series = staticmethod(outputs.merge_history), staticmethod(outputs.merge_series)
@@ -304,7 +314,8 @@ class DynamicsCore:
 
     def __init__(self, ops, blk, hx, hy, dt, nsub, device, exchanger=None, overlap=True, native=False, use_graph=False, closure=True,
                  phase_timing=False, land=None, rheology="mevp", bbm=None, history=None, series=None, series_capacity=1024, extent_conc=0.15,
-                 drifters=None, drifter_min_conc=0.15, drifter_fields=None, stations=None, station_fields=None, station_capacity=256):
+                 drifters=None, drifter_min_conc=0.15, drifter_fields=None, stations=None, station_fields=None, station_capacity=256,
+                 tracers=None, min_conc=1e-12, min_thick=0.01):
         self.ops, self.blk, self.hx, self.hy, self.dt, self.nsub, self.overlap = ops, blk, hx, hy, dt, nsub, overlap
         # closure: cap + scaling limiter at the end of every transport step (the ice-free-node rule is a parameter of the
         # sub-cycle, on by default).  False: the bare scheme of rounds 1-4 (frozen fixtures of that scheme)
@@ -318,6 +329,10 @@ class DynamicsCore:
         # Everything that can refuse comes first: a constructor that raises has changed nothing on `ops`
         self._check_rheology(rheology, bbm)
         self.TRANSPORTED, self.BOUNDS = self._transported()
+        # tracers: names of intensive quantities that ride on the ice (include/nsdg.h "ice tracers"), "age" the one
+        # that ages; min_conc / min_thick: the ice test of their recovery (the ice-free-node rule's defaults; 0 and 0 with closure = False)
+        self.tracers = self._check_tracers(tracers)
+        self.min_conc, self.min_thick = (float(min_conc), float(min_thick)) if closure else (0.0, 0.0)
         # land: bool array [ny_global, nx] of the WHOLE domain (True = land; include/nsdg.h "land mask"): the nodes of
         # land elements hold u = v = 0 like the array edge.  This rank keeps its rows, ghost rows included -- the mask is static, nothing
         # is exchanged -- and sets them on the ops object whenever it sets the grid
@@ -398,6 +413,12 @@ class DynamicsCore:
             self.Db = z(6, ny, nx)
             self.hg, self.eg, self.pm = (ops.private_zeros(9, ny, nx, device) for _ in range(3))
             self._zero_nodal = z(*nodal)
+        if self.tracers:
+            # the second transport group: one plane T per tracer, its product Q = H T and the stage buffers of the Qs' own transport run
+            nt = len(self.tracers)
+            self._tracer_kinds = tuple(abi.TRACER_AGE if name == self.AGE_TRACER else abi.TRACER_PASSIVE for name in self.tracers)
+            self._tr = [z(ny, nx) for _ in range(nt)]
+            self._tq, self._tq1, self._tq2 = ([z(6, ny, nx) for _ in range(nt)] for _ in range(3))
         if native:
             self._init_native()
 
@@ -420,6 +441,25 @@ class DynamicsCore:
             outputs.require_ops(self.ops, self.BBM_OPS, "rheology='bbm'", "BBM calls")
         elif bbm is not None:
             raise ValueError("bbm= parameters need rheology='bbm'")
+
+    def _check_tracers(self, tracers):
+        """tracers= as a tuple of names (None and () alike: none), refused before anything is asked of `ops` but the presence of the calls"""
+        names = () if tracers is None else ((tracers,) if isinstance(tracers, str) else tuple(tracers))
+        if not names:
+            return ()
+        if len(names) > abi.TRACERS_MAX:
+            raise ValueError("tracers= names %d tracers (%s); the tracer group carries at most %d"
+                             % (len(names), ", ".join(map(str, names)), abi.TRACERS_MAX))
+        for name in names:
+            if not isinstance(name, str) or not name.isidentifier():
+                raise ValueError("tracer name %r is not an identifier" % (name,))
+            if name in self.STATE_KEYS:
+                raise ValueError("tracer name %r collides with a key of the state (%s)" % (name, " ".join(self.STATE_KEYS)))
+        dup = sorted({n for n in names if names.count(n) > 1})
+        if dup:
+            raise ValueError("tracers= names %s more than once" % ", ".join(dup))
+        outputs.require_ops(self.ops, self.TRACER_OPS, "tracers=", "ice tracer calls")
+        return names
 
     def _more_transported(self):
         """(names, bounds) of the fields a subclass advects besides the class's TRANSPORTED"""
@@ -496,6 +536,10 @@ class DynamicsCore:
             assert (per_pass, group) == (self.per_pass, self.group_passes), "native plan and driver disagree on the pass structure"
             self._run_subcycle = self._run_mevp
         self._run_transport = self.ops.rb_transport(b, peers, self._fbuf[0], self._fbuf[1], self.t2, self.adv, bounds=self.BOUNDS if self.closure else ())
+        if self.tracers:
+            # the tracer group: a second plan without bounds (every Q is unbounded), with its own ping-pong parity
+            self._qbuf, self._qpar = (tuple(self._tq), tuple(self._tq1)), 0
+            self._run_tracers = self.ops.rb_transport(b, peers, self._qbuf[0], self._qbuf[1], self._tq2, self.adv, bounds=())
 
     def _fields(self):
         """the current buffers of the advected fields, in the order of TRANSPORTED"""
@@ -508,7 +552,7 @@ class DynamicsCore:
     def close(self):
         """releases the native driver plans (device buffers and events of their ghost exchanges); call it before the
         context is closed"""
-        for name in ("_run_mevp", "_run_transport"):
+        for name in ("_run_mevp", "_run_transport", "_run_tracers"):
             run = getattr(self, name, None)
             if run is not None and hasattr(run, "close"):
                 run.close()
@@ -545,6 +589,9 @@ class DynamicsCore:
         for f in self._fields():
             self.ops.land_clear(f)
         self.ops.land_clear_nodes(self.u, self.v)
+        if self.tracers:
+            for t in self._tr:
+                self.ops.land_clear(t)
 
     def _set_grid(self):
         self.ops.set_grid(self.blk.nx, self.blk.ny, self.hx, self.hy)
@@ -750,33 +797,76 @@ class DynamicsCore:
     def transport(self):
         ops, b = self.ops, self.blk
         self._mark(PHASE_TRANSPORT)
+        if self.tracers:
+            # every local row, ghost rows included (as the recovery below): both calls are element-local, the ghost rows stay equal to their
+            # owners.  The products are formed with the thickness the step starts from
+            ops.tracers_weight(self.ORDER, 0, b.ny, self.H, self._tr, self._tq)
         ops.prepare_advection(self.ORDER, self.u, self.v, *self.adv)
         if self.native:
             par = self._tpar = self._run_transport(self.dt, self._tpar)
             self._set_fields(self._fbuf[par])
             self.t1[:] = self._fbuf[1 - par]
-            return
-        f = list(self._fields())
+        else:
+            f = list(self._fields())
+            self._transport_stages(f, self.t1, self.t2, self.closure)
+            # the new state is t1 (ghost rows refreshed); swap buffers instead of copying
+            new = list(self.t1)
+            self.t1[:] = f
+            self._set_fields(new)
+        if self.tracers:
+            self._transport_tracers()
+
+    def _transport_stages(self, f, t1, t2, limit):
+        """one SSP-RK3 step of the fields f composed from the stage calls; the new state is left in t1, its ghost rows refreshed"""
+        ops, b = self.ops, self.blk
         # Shu-Osher SSP-RK3: out = a*phi0 + b*(phis + dt L(phis)).  A stage reads one element row on each side
         # of the rows it updates: with at least 3 ghost rows per interior side the first two stages also
         # advance 2 / 1 ghost rows redundantly (bit-identically to their owners) and the ghost rows are
         # exchanged once per step instead of after every stage.
         deep = b.world > 1 and min(b.depth_below, b.depth_above) >= 3
         ext = (lambda e: (max(b.j0 - e, 0), min(b.j1 + e, b.ny))) if deep else (lambda e: (b.j0, b.j1))
-        ops.transport_stage(self.ORDER, *ext(2), self.dt, 0.0, 1.0, f, f, self.t1, self.adv)
+        ops.transport_stage(self.ORDER, *ext(2), self.dt, 0.0, 1.0, f, f, t1, self.adv)
         if not deep:
-            self.halo.element(self.t1)
-        ops.transport_stage(self.ORDER, *ext(1), self.dt, 0.75, 0.25, f, self.t1, self.t2, self.adv)
+            self.halo.element(t1)
+        ops.transport_stage(self.ORDER, *ext(1), self.dt, 0.75, 0.25, f, t1, t2, self.adv)
         if not deep:
-            self.halo.element(self.t2)
-        ops.transport_stage(self.ORDER, b.j0, b.j1, self.dt, 1.0 / 3.0, 2.0 / 3.0, f, self.t2, self.t1, self.adv)
-        if self.closure:  # the step entry points of the library do this themselves; a step composed of stages calls it
-            ops.transport_limit(self.ORDER, b.j0, b.j1, self.t1)
-        self.halo.element(self.t1)
-        # the new state is t1 (ghost rows refreshed); swap buffers instead of copying
-        new = list(self.t1)
-        self.t1[:] = f
-        self._set_fields(new)
+            self.halo.element(t2)
+        ops.transport_stage(self.ORDER, b.j0, b.j1, self.dt, 1.0 / 3.0, 2.0 / 3.0, f, t2, t1, self.adv)
+        if limit:  # the step entry points of the library do this themselves; a step composed of stages calls it
+            ops.transport_limit(self.ORDER, b.j0, b.j1, t1)
+        self.halo.element(t1)
+
+    def _transport_tracers(self):
+        """the second transport group: the products Q_k = H T_k in a run of their own -- the prepared velocity and
+        the dt of the first, stage buffers of their own, no limiter (every Q is unbounded) -- and the division back, which ages "age" by dt"""
+        ops, b = self.ops, self.blk
+        if self.native:
+            par = self._qpar = self._run_tracers(self.dt, self._qpar)
+            self._tq, self._tq1 = list(self._qbuf[par]), list(self._qbuf[1 - par])
+        else:
+            self._transport_stages(self._tq, self._tq1, self._tq2, False)
+            self._tq, self._tq1 = self._tq1, self._tq
+        ops.tracers_recover(self.ORDER, 0, b.ny, self.H, self.A, self._tq, self._tracer_kinds, self.dt, self.min_conc, self.min_thick, self._tr)
+
+    # ---- the tracers' values (include/nsdg.h "ice tracers"): one [ny, nx] plane each, zero where there is no ice
+    def tracers_read(self):
+        """{name: numpy [owned rows, nx]} of the tracers"""
+        b = self.blk
+        return {name: t[b.j0:b.j1].detach().cpu().numpy().copy() for name, t in zip(self.tracers, self._tr if self.tracers else ())}
+
+    def load_tracers(self, fields):
+        """fields: {name: global [ny_global, nx] array} for some or all of the tracers; fills the local rows, ghost rows included"""
+        unknown = [k for k in fields if k not in self.tracers]
+        if unknown:
+            raise ValueError("load_tracers: %s: not among this core's tracers (%s)" % (", ".join(map(str, unknown)), ", ".join(self.tracers) or "none"))
+        es = self.blk.elem_slice()
+        for name, t in zip(self.tracers, self._tr if self.tracers else ()):
+            if name in fields:
+                a = np.asarray(fields[name], dtype=np.float64)
+                if a.shape != (self.blk.ny_glob, self.blk.nx):
+                    raise ValueError("tracer %r must be a [ny_global, nx] = [%d, %d] array, got shape %s" % (name, self.blk.ny_glob, self.blk.nx, a.shape))
+                _put(t, a[es])
+        self._clear_land()
 
     # ---- the frame of a model step: begin, one or several sub-steps of the phases, end
     def step(self):
@@ -872,6 +962,8 @@ class DynamicsCore:
             out[name] = self.ops.private_to_planes(f, nx)[:, b.j0:b.j1].detach().cpu().numpy().copy()
         if self._drifters is not None:
             out["drifters"] = self._drifters.state()
+        if self.tracers:
+            out["tracers"] = self.tracers_read()
         return out
 
     def load_state_dict(self, state):
@@ -893,6 +985,13 @@ class DynamicsCore:
             _put(self.D, state["D"][:, es])
         if self._drifters is not None:
             self._drifters.load_state(state)
+        if self.tracers:  # a state without the key, or without one of the names, loads zeros
+            held = state.get("tracers", {})
+            for name, t in zip(self.tracers, self._tr):
+                if name in held:
+                    _put(t, held[name][es])
+                else:
+                    t.zero_()
         self._clear_land()
 
     @staticmethod
@@ -908,6 +1007,8 @@ class DynamicsCore:
         if "drifters" in states[0]:  # every rank holds the whole list
             assert all(np.array_equal(s["drifters"], states[0]["drifters"]) for s in states), "the ranks' drifter lists differ"
             out["drifters"] = states[0]["drifters"].copy()
+        if "tracers" in states[0]:
+            out["tracers"] = {name: np.concatenate([s["tracers"][name] for s in states], axis=0) for name in states[0]["tracers"]}
         return out
 
 
@@ -976,7 +1077,10 @@ class CoupledCore(DynamicsCore):
     advect_column_state = True ("column state transport", include/nsdg.h): the snow and the surface temperature move with the ice.  The
     snow is a DG2 field S whose plane 0 IS the column's hsnow (col["hsnow"] is a view of it); tice0 travels as Q = H tice0, formed before
     the transport (nsdg_tracer_weight) and divided back after it (nsdg_tracer_recover, with min_conc / min_thick of the ice-free-node
-    rule).  The transport then carries H, A, S and Q."""
+    rule).  The transport then carries H, A, S and Q.
+
+    tracers= (DynamicsCore): the column step's growth dilutes them -- plane 0 of H is copied before the column step and
+    nsdg_tracers_dilute runs after it (and its land clear): ice that grew carries the value 0."""
 
     COLUMN_STATE = ("hsnow", "tice0")
     # closure of the column state transport's extra fields: snow volume S >= 0, the product Q = H T unbounded (include/nsdg.h)
@@ -994,10 +1098,12 @@ class CoupledCore(DynamicsCore):
         advect_column_state: the snow and the surface temperature ride on the ice (class docstring); min_conc / min_thick: the ice test of
         nsdg_tracer_recover (the defaults of the ice-free-node rule, nsdg_mevp_default_params; 0 and 0 with closure = False, as the C++ host)"""
         self.advect_column_state = bool(advect_column_state)  # (read by _more_transported() while the base class constructs)
-        super().__init__(ops, blk, hx, hy, dt, nsub, device, **kw)
-        closure = kw.get("closure", True)
-        self.min_conc, self.min_thick = (min_conc, min_thick) if closure else (0.0, 0.0)
+        if kw.get("tracers"):  # (refused before the base class changes anything on `ops`)
+            outputs.require_ops(ops, ("copy_f64",), "tracers= in a coupled core", "copy call")
+        super().__init__(ops, blk, hx, hy, dt, nsub, device, min_conc=min_conc, min_thick=min_thick, **kw)
         z = lambda: torch.zeros(blk.ny, blk.nx, dtype=torch.float64, device=device)
+        if self.tracers:
+            self._h_before = z()  # the mean thickness the column step starts from (nsdg_tracers_dilute)
         self.col = {k: z() for k in self.COLUMN_STATE + self.COLUMN_FORCING}
         if self.advect_column_state:
             self.col["hsnow"] = self.S[0]
@@ -1063,12 +1169,17 @@ class CoupledCore(DynamicsCore):
         self._mark(PHASE_COLUMN)
         state = {"hice": self.H[0], "cice": self.A[0], "hsnow": self.col["hsnow"], "tice0": self.col["tice0"]}
         forcing = {k: self.col[k] for k in self.COLUMN_FORCING}
+        if self.tracers:
+            self.ops.copy_f64(self._h_before, self.H[0])
         self.ops.column_step(self.dt, state, forcing, self.newice)
         if self.land is not None:
             # the column step computes on land elements too (it is pinned to the reference case by case); its result there is discarded:
             # the cell means of H, A (and S), the snow and the new ice (still the COLUMN phase of the phase table)
             for f in (self.H[0], self.A[0], self.col["hsnow"], self.newice):
                 self.ops.land_clear(f)
+        if self.tracers:
+            # ice that grew carries the value 0 (every local row: element-local, as the column step)
+            self.ops.tracers_dilute(0, self.blk.ny, self._h_before, self.H[0], self._tr)
 
     def _record(self, k):
         """record k of the forcing series on the device: {name: [nyr, nxr] tensor}"""

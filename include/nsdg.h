@@ -477,7 +477,7 @@ int nsdg_mevp_stress(nsdg_ctx* ctx, int32_t k0, int32_t k1, const double* u, con
  * (6 doubles per node, csrc/mevp_common.h), valid for the whole sub-cycle of one time step because
  * u0, v0, the wind stress, the ocean current and the nodal H, A do not change inside it.  The context
  * remembers dt and the mEVP parameters of the packing for the following iterate/velocity calls.
- * `packed` must hold 8*(2nx+1)*(2ny+1) doubles (6 used) and be 16-byte aligned. */
+ * `packed` must hold 8*(2nx+1)*(2ny+1) doubles (6 used; 8 with a depth array set, nsdg_basal.h) and be 16-byte aligned. */
 int nsdg_mevp_pack_nodal(nsdg_ctx* ctx, double dt, const double* u0, const double* v0, const double* tax,
     const double* tay, const double* uo, const double* vo, const double* cgh, const double* cga, double* packed);
 
@@ -582,6 +582,12 @@ int nsdg_mevp_occupancy_set(nsdg_ctx* ctx, int32_t waves_per_simd);
 int nsdg_land_mask_set(nsdg_ctx* ctx, const uint8_t* land);
 int nsdg_land_clear(nsdg_ctx* ctx, int32_t j0, int32_t j1, int32_t nplanes, double* f);
 int nsdg_land_clear_nodes(nsdg_ctx* ctx, double* u, double* v);
+
+/* ---- landfast ice: grounding on shoals as a basal stress in the momentum update (csrc/basal.hip) ---------------
+ * A static water depth per element makes the packing store the critical stress T_b of Lemieux et al. (2015) as the seventh packed
+ * coefficient of a node, and the passes that read such a packing add C_b = T_b / (|u| + u0) to the denominator of the velocity update.
+ * The parameters, the depth array, the diagnostic T_b and their checks are declared in nsdg_basal.h, which this header includes. */
+#include "nsdg_basal.h"
 
 /* ---- brittle rheology: the brittle Bingham-Maxwell (BBM) sub-cycle (csrc/bbm.hip, csrc/bbm_common.h) ------------
  * A second rheology beside mEVP: damage, a Mohr-Coulomb envelope, Maxwell relaxation.  No counterpart in the reference snapshot; built from

@@ -41,6 +41,11 @@ class BbmParams(C.Structure):
         ("relax_exponent", C.c_int32), ("reserved", C.c_int32)]
 
 
+class BasalParams(C.Structure):
+    """nsdg_basal_params: the grounding scheme of landfast ice (include/nsdg_basal.h)"""
+    _fields_ = [(n, C.c_double) for n in ("k1", "k2", "alpha_b", "u0")]
+
+
 SUBCYCLE_ADAPTIVE, SUBCYCLE_KEEP_ALPHA, SUBCYCLE_KEEP_DELTA_MIN, SUBCYCLE_ADAPTIVE_CONVERGED = 0, 1, 2, 3  # modes of nsdg_mevp_stable_params
 
 
@@ -247,6 +252,14 @@ TRACER_SYMBOLS = {
     "nsdg_tracers_dilute": (C.c_int, [VP, I32, I32, VP, VP, I32, C.POINTER(VP)]),
 }
 
+# the functions of include/nsdg_basal.h (the "landfast ice" section, a header of its own that nsdg.h includes), bound like SYMBOLS
+BASAL_SYMBOLS = {
+    "nsdg_basal_default_params": (None, [C.POINTER(BasalParams)]),
+    "nsdg_basal_params_set": (C.c_int, [VP, C.POINTER(BasalParams)]),
+    "nsdg_basal_depth_set": (C.c_int, [VP, VP]),
+    "nsdg_basal_critical": (C.c_int, [VP, VP, VP, VP]),
+}
+
 _lib = None
 
 
@@ -264,7 +277,7 @@ def load_library(path=LIB_PATH):
         raise NsdgError("HIP library %s is missing: build it with `python -m nextsimdg_amd.build` "
                         "(there is no CPU fallback)" % path)
     lib = C.CDLL(path)
-    for name, (res, args) in list(SYMBOLS.items()) + list(TRACER_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(TRACER_SYMBOLS.items()) + list(BASAL_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -311,6 +324,17 @@ def bbm_default_params(**kw):
     for k, v in kw.items():
         if not hasattr(p, k):
             raise NsdgError("unknown BBM parameter " + k)
+        setattr(p, k, v)
+    return p
+
+
+def basal_default_params(**kw):
+    """nsdg_basal_default_params with members replaced by keyword (host only)"""
+    p = BasalParams()
+    load_library().nsdg_basal_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise NsdgError("unknown basal parameter " + k)
         setattr(p, k, v)
     return p
 
@@ -464,6 +488,7 @@ class Context:
         self.nx = self.ny = 0
         self.mevp_variant = DEFAULT_MEVP_VARIANT  # the library default (four sub-iterations per pass)
         self.land_mask = None  # the tensor behind nsdg_land_mask_set (set_land_mask keeps it alive)
+        self.basal_depth = None  # the tensor behind nsdg_basal_depth_set (set_basal_depth keeps it alive)
 
     def _call(self, rc):
         if rc != 0:
@@ -747,7 +772,7 @@ class Context:
     def set_grid(self, nx, ny, hx, hy):
         self._call(self.lib.nsdg_grid_set(self.h, nx, ny, float(hx), float(hy)))
         if (nx, ny) != (self.nx, self.ny):
-            self.land_mask = None  # the library dropped a mask of the old shape
+            self.land_mask = self.basal_depth = None  # the library dropped a mask and a depth array of the old shape
         self.nx, self.ny = nx, ny
 
     # ---- land mask (include/nsdg.h "land mask"): coastlines as fixed nodes of the sub-cycle
@@ -779,6 +804,32 @@ class Context:
         if u.numel() != n or v.numel() != n:
             raise NsdgError("land_clear_nodes: the nodal arrays of the grid hold %d values" % n)
         self._call(self.lib.nsdg_land_clear_nodes(self.h, _ptr(u), _ptr(v)))
+
+    # ---- landfast ice (include/nsdg_basal.h): grounding on shoals as a basal stress in the momentum update
+    def basal_default_params(self, **kw):
+        return basal_default_params(**kw)
+
+    def set_basal_params(self, p):
+        """nsdg_basal_params_set: acts from the next coefficient packing on"""
+        self._call(self.lib.nsdg_basal_params_set(self.h, C.byref(p)))
+
+    def set_basal_depth(self, depth):
+        """nsdg_basal_depth_set: `depth` = a contiguous float64 CUDA tensor [ny, nx] of the local array (metres, >= 0), kept alive by this
+        object while it is set; None clears it.  Acts from the next coefficient packing on"""
+        if depth is not None:
+            _check_f64(depth)
+            if tuple(depth.shape) != (self.ny, self.nx):
+                raise NsdgError("the depth array has shape %s, the local array is [%d, %d]" % (tuple(depth.shape), self.ny, self.nx))
+        self._call(self.lib.nsdg_basal_depth_set(self.h, _ptr(depth)))
+        self.basal_depth = depth
+
+    def basal_critical(self, cgh, cga, tb):
+        """nsdg_basal_critical: tb = the critical stress T_b at every node of the CG2 lattice, what the next packing would store"""
+        _check_f64(cgh, cga, tb)
+        n = (2 * self.nx + 1) * (2 * self.ny + 1)
+        if cgh.numel() != n or cga.numel() != n or tb.numel() != n:
+            raise NsdgError("basal_critical: the nodal arrays of the grid hold %d values" % n)
+        self._call(self.lib.nsdg_basal_critical(self.h, _ptr(cgh), _ptr(cga), _ptr(tb)))
 
     def set_mevp_variant(self, variant):
         self._call(self.lib.nsdg_mevp_variant_set(self.h, variant))

@@ -5,7 +5,7 @@
 //
 // The march is the one of mevp_pipeline.h, all of it: the frame of a wave that owns 63 element columns x R element rows (march_frame), the
 // row loop with its prologue row, velocity gather, carried contributions, update of the four owned nodes by
-// owned_node_updates<false, LAND> with the BBM launch constants K1 = K2 = rho_i / dt_s (explicit in stress and Coriolis, implicit in ocean
+// owned_node_updates<false, LAND, BASAL> with the BBM launch constants K1 = K2 = rho_i / dt_s (explicit in stress and Coriolis, implicit in ocean
 // drag) and their store (march_strip); the strip height is the rule of mevp_fused.hip at this kernel's one wave per SIMD
 // (nsdg_march_strip_rows), the checks of a pass those of nsdg_pass_check (mevp.hip).  What is this file's own is the element step inside
 // the march (bbm_common.h: bbm_element_step): elastic predictor, Maxwell relaxation, Mohr-Coulomb test and damage update at the 3x3 Gauss
@@ -28,8 +28,9 @@ namespace nsdg_mevp_detail {
 // 1 wave per SIMD: the element step holds 9 Gauss points x (3 strain rates + 3 stresses + damage + 3 per-step values) beside the march's
 // carried contributions (resource figures: profiles/r09_bbm.md)
 // LAND: the instantiation that holds land nodes at 0 (mevp_common.h: node_update), launched after a packing that saw a land mask
-template <bool LAND>
-__global__ __launch_bounds__(256, 1) void bbm_fused_kernel(NodalConsts K, BbmConsts B, int nx, int ny, int k0, int j0, int j1, int R, int ncw,
+// BASAL: the instantiation with the seabed stress (mevp_common.h: node_update), launched after a packing that saw a depth array
+template <bool LAND, bool BASAL>
+__global__ __launch_bounds__(256, 1) void bbm_fused_kernel(NodalConstsOf<BASAL> K, BbmConsts B, int nx, int ny, int k0, int j0, int j1, int R, int ncw,
     double hx, double hy, StressPtrs S, const double* __restrict__ D_in, double* __restrict__ D_out, const double* __restrict__ u_old,
     const double* __restrict__ v_old, const double* __restrict__ packed, const double* __restrict__ hgp, const double* __restrict__ egp,
     const double* __restrict__ pmp, double* __restrict__ u_new, double* __restrict__ v_new)
@@ -42,10 +43,10 @@ __global__ __launch_bounds__(256, 1) void bbm_fused_kernel(NodalConsts K, BbmCon
     if (M.y0 >= j1)
         return; // wave-uniform
     M.y1 = min(M.y0 + R, j1);
-    march_frame<63, 1>(M, K, AdaptConsts { 0., 0., 0. }, nx, ny, lane, cw, hx, hy, 0., 0.); // 63 owned columns, lane 0 recomputes the column left of them
+    march_frame<63, 1>(M, K, AdaptConsts { 0., 0., 0. }, nx, ny, lane, cw, hx, hy, 0., 0., nodal_u0<BASAL>(K)); // 63 owned columns, lane 0 recomputes the column left of them
     const long N = (long)nx * ny;
 
-    march_strip<false, LAND, false>(M, k0, j0, u_old, v_old, packed, u_new, v_new,
+    march_strip<false, LAND, false, BASAL>(M, k0, j0, u_old, v_old, packed, u_new, v_new,
         [&](int iy, bool store, long, const double (&ul)[9], const double (&vl)[9], double (&m11)[8], double (&m12)[8], double (&m22)[8], double&) {
             const long ts = tile_off(M.ix, iy, M.ntx, 8), tp = tile_off(M.ix, iy, M.ntx, 9), e = (long)iy * nx + M.ix;
             double hg[9], eg[9], pm[9], s11[8], s12[8], s22[8], d[6];
@@ -190,15 +191,18 @@ int nsdg_bbm_iterate(nsdg_ctx* ctx, int32_t k0, int32_t j0, int32_t j1, const do
     const StressPtrs S = { s11_in, s12_in, s22_in, s11_out, s12_out, s22_out };
     // the BBM momentum step: the mEVP node update with K1 = K2 = rho_i / dt_s (and u0 = v0 = 0 in the packing)
     const double rdt = ctx->mevp.rho_ice / ctx->pack_dt;
-    const NodalConsts K = { rdt, rdt, ctx->mevp.rho_ice * ctx->mevp.fc, rdt };
+    const NodalConstsBasal K = { { rdt, rdt, ctx->mevp.rho_ice * ctx->mevp.fc, rdt }, ctx->basal.u0 };
     const BbmConsts B = nsdg_bbm_consts(ctx);
     const dim3 grid(nsdg_div_up(nwaves, 4)), block(256);
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, K, B, ctx->nx, ctx->ny, k0, j0, j1, R, ncw, ctx->hx, ctx->hy, S, D_in, D_out, u_old, v_old, packed,
             hg, eg, pm, u_new, v_new);
     };
-    // masked or not: the instantiation goes with the packing the pass reads, as in nsdg_mevp_pass
-    ctx->pack_land ? launch(bbm_fused_kernel<true>) : launch(bbm_fused_kernel<false>);
+    // masked or not, with the seabed stress or not: the instantiation goes with the packing the pass reads, as in nsdg_mevp_pass
+    if (ctx->pack_basal)
+        ctx->pack_land ? launch(bbm_fused_kernel<true, true>) : launch(bbm_fused_kernel<false, true>);
+    else
+        ctx->pack_land ? launch(bbm_fused_kernel<true, false>) : launch(bbm_fused_kernel<false, false>);
     NSDG_CHECK_LAUNCH();
     return NSDG_OK;
 }

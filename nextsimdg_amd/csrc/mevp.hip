@@ -59,9 +59,10 @@ __device__ __forceinline__ void load_stress(const double* __restrict__ S11, cons
     tile_load8(S22, ts, s22);
 }
 
-// the velocity kernel's body; LAND: the instantiation that holds land nodes at 0 (mevp_common.h: node_update)
-template <bool LAND>
-__device__ __forceinline__ void mevp_velocity_body(NodalConsts K, int nx, int ny, int j0, int j1, double hx, double hy,
+// the velocity kernel's body; LAND: the instantiation that holds land nodes at 0 (mevp_common.h: node_update); BASAL: the one that reads
+// the fourth coefficient pair and adds the seabed stress
+template <bool LAND, bool BASAL>
+__device__ __forceinline__ void mevp_velocity_body(NodalConstsOf<BASAL> K, int nx, int ny, int j0, int j1, double hx, double hy,
     const double* __restrict__ S11, const double* __restrict__ S12, const double* __restrict__ S22,
     const double* __restrict__ u_old, const double* __restrict__ v_old, const double* __restrict__ packed,
     double* __restrict__ u_new, double* __restrict__ v_new)
@@ -112,21 +113,21 @@ __device__ __forceinline__ void mevp_velocity_body(NodalConsts K, int nx, int ny
     // inverse lumped masses: 4, 2, 2, 1 adjacent elements times LUMP = 1/36, 1/9, 1/9, 4/9 of the cell area
     if (hasL && hasB) { // vertex
         load_nodal(packed, nplane, nV, c);
-        node_update<false, LAND>(K, c, u_old[nV], v_old[nV], vx_, vy_, 9. * iarea, un[0], vn[0]);
+        node_update<false, LAND, BASAL>(K, c, u_old[nV], v_old[nV], vx_, vy_, 9. * iarea, un[0], vn[0], 0., 0., BASAL ? load_nodal_tb(packed, nplane, nV) : 0., nodal_u0<BASAL>(K));
     } else
         un[0] = vn[0] = 0.;
     if (hasB) { // bottom edge-mid
         load_nodal(packed, nplane, nV + 1, c);
-        node_update<false, LAND>(K, c, u_old[nV + 1], v_old[nV + 1], exx, exy, 4.5 * iarea, un[1], vn[1]);
+        node_update<false, LAND, BASAL>(K, c, u_old[nV + 1], v_old[nV + 1], exx, exy, 4.5 * iarea, un[1], vn[1], 0., 0., BASAL ? load_nodal_tb(packed, nplane, nV + 1) : 0., nodal_u0<BASAL>(K));
     } else
         un[1] = vn[1] = 0.;
     if (hasL) { // left edge-mid
         load_nodal(packed, nplane, nV + nn, c);
-        node_update<false, LAND>(K, c, u_old[nV + nn], v_old[nV + nn], eyx, eyy, 4.5 * iarea, un[2], vn[2]);
+        node_update<false, LAND, BASAL>(K, c, u_old[nV + nn], v_old[nV + nn], eyx, eyy, 4.5 * iarea, un[2], vn[2], 0., 0., BASAL ? load_nodal_tb(packed, nplane, nV + nn) : 0., nodal_u0<BASAL>(K));
     } else
         un[2] = vn[2] = 0.;
     load_nodal(packed, nplane, nV + nn + 1, c); // centre
-    node_update<false, LAND>(K, c, u_old[nV + nn + 1], v_old[nV + nn + 1], ccx, ccy, 2.25 * iarea, un[3], vn[3]);
+    node_update<false, LAND, BASAL>(K, c, u_old[nV + nn + 1], v_old[nV + nn + 1], ccx, ccy, 2.25 * iarea, un[3], vn[3], 0., 0., BASAL ? load_nodal_tb(packed, nplane, nV + nn + 1) : 0., nodal_u0<BASAL>(K));
     // with the zeros of the right column / top row of the local lattice: boundary nodes (v = 0)
     store_owned_nodes(nV, nn, ix == nx - 1, iy == ny - 1, un, vn, u_new, v_new);
 }
@@ -136,7 +137,7 @@ __global__ __launch_bounds__(256) void mevp_velocity_kernel(NodalConsts K, int n
     const double* __restrict__ u_old, const double* __restrict__ v_old, const double* __restrict__ packed,
     double* __restrict__ u_new, double* __restrict__ v_new)
 {
-    mevp_velocity_body<false>(K, nx, ny, j0, j1, hx, hy, S11, S12, S22, u_old, v_old, packed, u_new, v_new);
+    mevp_velocity_body<false, false>(K, nx, ny, j0, j1, hx, hy, S11, S12, S22, u_old, v_old, packed, u_new, v_new);
 }
 
 // the same after a packing that saw a land mask
@@ -145,7 +146,17 @@ __global__ __launch_bounds__(256) void mevp_velocity_land_kernel(NodalConsts K, 
     const double* __restrict__ u_old, const double* __restrict__ v_old, const double* __restrict__ packed,
     double* __restrict__ u_new, double* __restrict__ v_new)
 {
-    mevp_velocity_body<true>(K, nx, ny, j0, j1, hx, hy, S11, S12, S22, u_old, v_old, packed, u_new, v_new);
+    mevp_velocity_body<true, false>(K, nx, ny, j0, j1, hx, hy, S11, S12, S22, u_old, v_old, packed, u_new, v_new);
+}
+
+// the same after a packing that saw a depth array (landfast ice, basal.hip), masked or not
+template <bool LAND>
+__global__ __launch_bounds__(256) void mevp_velocity_basal_kernel(NodalConstsBasal K, int nx, int ny, int j0, int j1, double hx, double hy,
+    const double* __restrict__ S11, const double* __restrict__ S12, const double* __restrict__ S22,
+    const double* __restrict__ u_old, const double* __restrict__ v_old, const double* __restrict__ packed,
+    double* __restrict__ u_new, double* __restrict__ v_new)
+{
+    mevp_velocity_body<LAND, true>(K, nx, ny, j0, j1, hx, hy, S11, S12, S22, u_old, v_old, packed, u_new, v_new);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -184,10 +195,14 @@ __device__ __forceinline__ double node_average(int nx, int ny, int nc, const dou
     return s / cnt;
 }
 
-// per-step momentum coefficients of one node, 6 doubles (layout: mevp_common.h)
+// per-step momentum coefficients of one node, 6 doubles (layout: mevp_common.h); BASAL: pair 3 = (T_b, 0) from the node's mean water
+// depth hwn as well (landfast ice, mevp_common.h: basal_critical_stress)
+template <bool BASAL>
 __device__ __forceinline__ void pack_node(const nsdg_mevp_params& P, double dt, double u0, double v0, double tax, double tay,
-    double uoc, double voc, double cgh, double cga, double* __restrict__ packed, long plane, long n, bool land = false)
+    double uoc, double voc, double cgh, double cga, double* __restrict__ packed, long plane, long n, bool land, const nsdg_basal_params& B, double hwn)
 {
+    if constexpr (BASAL)
+        store_nodal_tb(packed, plane, n, basal_critical_stress(P, B, cgh, cga, hwn, land));
     // Land node (csrc/landmask.hip; before the ice-free rule): the flag cd = c[1] < 0 -- every real node has cd >= 0, and a signed zero
     // cannot serve under -fno-signed-zeros -- beside fixed finite constants that depend neither on the forcing nor on H and A there
     // (h' = h_min: the adaptive form divides by the centre node's h').  The LAND kernels hold such a node at u = v = 0.
@@ -204,6 +219,7 @@ __device__ __forceinline__ void pack_node(const nsdg_mevp_params& P, double dt, 
     //   u' = (K1 h' u + c2 + drag u_o + K3 h' v + div_x / M) / (K2 h' + drag),  drag = cd |v_o - v|,
     // homogeneous of degree 0 in (h', cd, c2, c3, div): scaling the four packed coefficients by 2^100 (exact: a power of two)
     // leaves every other term as it is and weights the divergence by 2^-100 -- below the last bit of the sum.  Both 0: rule off.
+    // (the expression of mevp_common.h: ice_free_node, which T_b tests; written out here, where it has always stood)
     const bool ice_free = (P.min_conc > 0. || P.min_thick > 0.) && (cga < P.min_conc || cgh < P.min_thick * cga || cgh <= P.h_min);
     const double a = ice_free ? 1. : fmin(fmax(cga, 0.), 1.);
     const double mdt = P.rho_ice * h / dt;
@@ -221,21 +237,25 @@ __device__ __forceinline__ void wind_tau(double f_atm, double ua, double va, dou
 }
 
 // LAND: with the element land mask of the local array (nx x ny elements), land nodes are packed with the flag
-template <bool LAND>
+// BASAL: with the water depth of the same elements, pair 3 of a node is (T_b, 0)
+template <bool LAND, bool BASAL>
 __global__ __launch_bounds__(256) void mevp_pack_nodal_kernel(nsdg_mevp_params P, long nnodes, double dt,
     const double* __restrict__ u0, const double* __restrict__ v0, const double* __restrict__ tax,
     const double* __restrict__ tay, const double* __restrict__ uo, const double* __restrict__ vo,
-    const double* __restrict__ cgh, const double* __restrict__ cga, double* __restrict__ packed, int nx, int ny, const uint8_t* __restrict__ land)
+    const double* __restrict__ cgh, const double* __restrict__ cga, double* __restrict__ packed, int nx, int ny, const uint8_t* __restrict__ land,
+    nsdg_basal_params B, const double* __restrict__ depth)
 {
     const long n = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= nnodes)
         return;
+    const int nn = 2 * nx + 1;
     bool is_land = false;
-    if constexpr (LAND) {
-        const int nn = 2 * nx + 1;
+    if constexpr (LAND)
         is_land = land_node(land, nx, ny, (int)(n % nn), (int)(n / nn));
-    }
-    pack_node(P, dt, u0[n], v0[n], tax[n], tay[n], uo[n], vo[n], cgh[n], cga[n], packed, nodal_plane(nnodes), n, is_land);
+    double hwn = 0.;
+    if constexpr (BASAL)
+        hwn = node_mean_of(nx, ny, (int)(n % nn), (int)(n / nn), [&](int ix, int iy) { return depth[(long)iy * nx + ix]; });
+    pack_node<BASAL>(P, dt, u0[n], v0[n], tax[n], tay[n], uo[n], vo[n], cgh[n], cga[n], packed, nodal_plane(nnodes), n, is_land, B, hwn);
 }
 
 // node_average() on a tile of DG coefficients staged in LDS: tile[c][iy - ey0][ix - ex0]; same loops, same order of
@@ -267,14 +287,16 @@ __device__ __forceinline__ double node_average_tile(int nx, int ny, const double
 // instead of being gathered by every node lane from memory (a vertex node reads 4 elements x 6 coefficients x 2
 // fields: the gather form issued ~57 loads per lane and was bound by vector-memory issue, 0.67 ms at 2048^2).
 // LAND: the mask bytes of the same 33 x 3 elements are staged beside the tile and land nodes are packed with the flag.
-template <bool LAND>
+// BASAL: so are their water depths, and pair 3 of a node is (T_b, 0).
+template <bool LAND, bool BASAL>
 __global__ __launch_bounds__(256) void mevp_prepare_kernel(nsdg_mevp_params P, int nx, int ny, double dt,
     const double* __restrict__ H, const double* __restrict__ A, const double* __restrict__ ua, const double* __restrict__ va,
     const double* __restrict__ uo, const double* __restrict__ vo, const double* __restrict__ u0, const double* __restrict__ v0,
-    double* __restrict__ packed, const uint8_t* __restrict__ land)
+    double* __restrict__ packed, const uint8_t* __restrict__ land, nsdg_basal_params B, const double* __restrict__ depth)
 {
     __shared__ double tile[2][6][PREP_TH][PREP_TW];
     __shared__ uint8_t ltile[LAND ? PREP_TH : 1][PREP_TW];
+    __shared__ double dtile[BASAL ? PREP_TH : 1][PREP_TW];
     const int gx0 = blockIdx.x * 64, gy0 = blockIdx.y * 4;
     const int ex0 = gx0 / 2 - 1, ey0 = gy0 / 2 - 1;
     const long N = (long)nx * ny;
@@ -294,6 +316,13 @@ __global__ __launch_bounds__(256) void mevp_prepare_kernel(nsdg_mevp_params P, i
             ltile[r][col] = (ix >= 0 && ix < nx && iy >= 0 && iy < ny) ? land[(long)iy * nx + ix] : 0;
         }
     }
+    if constexpr (BASAL) {
+        if (tid < PREP_TH * PREP_TW) {
+            const int col = tid % PREP_TW, r = tid / PREP_TW;
+            const int ix = ex0 + col, iy = ey0 + r;
+            dtile[r][col] = (ix >= 0 && ix < nx && iy >= 0 && iy < ny) ? depth[(long)iy * nx + ix] : 0.;
+        }
+    }
     __syncthreads();
     const int gx = gx0 + threadIdx.x;
     const int gy = gy0 + threadIdx.y;
@@ -307,7 +336,10 @@ __global__ __launch_bounds__(256) void mevp_prepare_kernel(nsdg_mevp_params P, i
     bool is_land = false;
     if constexpr (LAND)
         is_land = land_node_of(nx, ny, gx, gy, [&](int ix, int iy) { return ltile[iy - ey0][ix - ex0]; });
-    pack_node(P, dt, u0[n], v0[n], tax, tay, uo[n], vo[n], cgh, cga, packed, nodal_plane((long)nn * nm), n, is_land);
+    double hwn = 0.;
+    if constexpr (BASAL)
+        hwn = node_mean_of(nx, ny, gx, gy, [&](int ix, int iy) { return dtile[iy - ey0][ix - ex0]; });
+    pack_node<BASAL>(P, dt, u0[n], v0[n], tax, tay, uo[n], vo[n], cgh, cga, packed, nodal_plane((long)nn * nm), n, is_land, B, hwn);
 }
 
 // one lane per CG2 node
@@ -446,15 +478,18 @@ int nsdg_mevp_pack_nodal(nsdg_ctx* ctx, double dt, const double* u0, const doubl
     NSDG_CHECK_ARG(((uintptr_t)packed & 15) == 0, "packed must be 16-byte aligned");
     NSDG_CHECK_HIP(hipSetDevice(ctx->device));
     const long nnodes = (long)(2 * ctx->nx + 1) * (2 * ctx->ny + 1);
-    if (ctx->land)
-        hipLaunchKernelGGL(mevp_pack_nodal_kernel<true>, dim3(nsdg_div_up(nnodes, 256)), dim3(256), 0, ctx->stream, ctx->mevp, nnodes, dt, u0,
-            v0, tax, tay, uo, vo, cgh, cga, packed, ctx->nx, ctx->ny, ctx->land);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(nsdg_div_up(nnodes, 256)), dim3(256), 0, ctx->stream, ctx->mevp, nnodes, dt, u0, v0, tax, tay, uo, vo, cgh, cga,
+            packed, ctx->nx, ctx->ny, ctx->land, ctx->basal, ctx->depth);
+    };
+    if (ctx->depth)
+        ctx->land ? launch(mevp_pack_nodal_kernel<true, true>) : launch(mevp_pack_nodal_kernel<false, true>);
     else
-        hipLaunchKernelGGL(mevp_pack_nodal_kernel<false>, dim3(nsdg_div_up(nnodes, 256)), dim3(256), 0, ctx->stream, ctx->mevp, nnodes, dt, u0,
-            v0, tax, tay, uo, vo, cgh, cga, packed, ctx->nx, ctx->ny, ctx->land);
+        ctx->land ? launch(mevp_pack_nodal_kernel<true, false>) : launch(mevp_pack_nodal_kernel<false, false>);
     NSDG_CHECK_LAUNCH();
     ctx->pack_dt = dt; // the launch constants K1, K2 of the velocity update belong to this packing
-    ctx->pack_land = ctx->land != nullptr; // and so does the choice of the passes' instantiation: this packing flagged land nodes, or not
+    ctx->pack_land = ctx->land != nullptr; // and so does the choice of the passes' instantiation: this packing flagged land nodes, or not,
+    ctx->pack_basal = ctx->depth != nullptr; // and stored T_b as the seventh coefficient, or not
     return NSDG_OK;
 }
 
@@ -467,15 +502,18 @@ int nsdg_mevp_prepare(nsdg_ctx* ctx, double dt, const double* H, const double* A
     NSDG_CHECK_ARG(((uintptr_t)packed & 15) == 0, "packed must be 16-byte aligned");
     NSDG_CHECK_HIP(hipSetDevice(ctx->device));
     const dim3 block(64, 4), grid(nsdg_div_up(2 * ctx->nx + 1, 64), nsdg_div_up(2 * ctx->ny + 1, 4));
-    if (ctx->land)
-        hipLaunchKernelGGL(mevp_prepare_kernel<true>, grid, block, 0, ctx->stream, ctx->mevp, ctx->nx, ctx->ny, dt, H, A, ua, va, uo, vo, u0, v0,
-            packed, ctx->land);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, ctx->mevp, ctx->nx, ctx->ny, dt, H, A, ua, va, uo, vo, u0, v0, packed, ctx->land,
+            ctx->basal, ctx->depth);
+    };
+    if (ctx->depth)
+        ctx->land ? launch(mevp_prepare_kernel<true, true>) : launch(mevp_prepare_kernel<false, true>);
     else
-        hipLaunchKernelGGL(mevp_prepare_kernel<false>, grid, block, 0, ctx->stream, ctx->mevp, ctx->nx, ctx->ny, dt, H, A, ua, va, uo, vo, u0, v0,
-            packed, ctx->land);
+        ctx->land ? launch(mevp_prepare_kernel<true, false>) : launch(mevp_prepare_kernel<false, false>);
     NSDG_CHECK_LAUNCH();
     ctx->pack_dt = dt;
     ctx->pack_land = ctx->land != nullptr;
+    ctx->pack_basal = ctx->depth != nullptr;
     return NSDG_OK;
 }
 
@@ -496,8 +534,14 @@ int nsdg_mevp_velocity(nsdg_ctx* ctx, int32_t j0, int32_t j1, const double* s11,
         nsdg_set_error("nsdg_mevp_velocity: nsdg_mevp_pack_nodal was not called on this context");
         return NSDG_ERR_STATE;
     }
-    hipLaunchKernelGGL(ctx->pack_land ? mevp_velocity_land_kernel : mevp_velocity_kernel, grid, block, 0, ctx->stream, nsdg_nodal_consts(ctx), ctx->nx, ctx->ny, j0, j1,
-        ctx->hx, ctx->hy, s11, s12, s22, u_old, v_old, packed, u_new, v_new);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, nsdg_nodal_consts_basal(ctx), ctx->nx, ctx->ny, j0, j1, ctx->hx, ctx->hy, s11, s12, s22, u_old, v_old,
+            packed, u_new, v_new);
+    };
+    if (ctx->pack_basal)
+        ctx->pack_land ? launch(mevp_velocity_basal_kernel<true>) : launch(mevp_velocity_basal_kernel<false>);
+    else
+        ctx->pack_land ? launch(mevp_velocity_land_kernel) : launch(mevp_velocity_kernel);
     NSDG_CHECK_LAUNCH();
     return NSDG_OK;
 }
@@ -569,12 +613,13 @@ int nsdg_mevp_pass(nsdg_ctx* ctx, int v, int k0, int j0, int j1, bool pair, int 
     if (!run)
         return checked;
     // masked or not: the instantiation goes with the packing the pass reads (nsdg_mevp_pack_nodal / nsdg_mevp_prepare remembered whether
-    // they flagged land nodes); the two-kernel form's velocity kernel (nsdg_mevp_velocity) reads the same flag
-    const bool land = ctx->pack_land;
+    // they flagged land nodes, and whether they stored T_b from a depth array); the two-kernel form's velocity kernel (nsdg_mevp_velocity)
+    // reads the same flags
+    const bool land = ctx->pack_land, basal = ctx->pack_basal;
     if (v >= 2) // a pass of the stage-per-wave pipeline with v stages
-        return nsdg_launch_mevp_fused4_ranges(ctx, land, v, j0, j1, j0b, j1b, b);
+        return nsdg_launch_mevp_fused4_ranges(ctx, land, basal, v, j0, j1, j0b, j1b, b);
     if (ctx->mevp_variant >= 1 || nsdg_adaptive(ctx)) // variants 2-4 use the single-iteration fused kernel for one sub-iteration; so does variant 0 in the adaptive form
-        return nsdg_launch_mevp_fused(ctx, land, k0, j0, j1, b);
+        return nsdg_launch_mevp_fused(ctx, land, basal, k0, j0, j1, b);
     const int rc = launch_stress(ctx, k0, j1, b.u_old, b.v_old, b.pg, b.s11i, b.s12i, b.s22i, b.s11, b.s12, b.s22);
     return rc ? rc : nsdg_mevp_velocity(ctx, j0, j1, b.s11, b.s12, b.s22, b.u_old, b.v_old, b.u_new, b.v_new, b.packed);
 }
@@ -635,7 +680,7 @@ int nsdg_mevp_subcycle(nsdg_ctx* ctx, double dt, int32_t nsub, double* s11, doub
     NSDG_CHECK_ARG(((uintptr_t)scratch & 15) == 0, "scratch must be 16-byte aligned");
     const long nnodes = (long)(2 * ctx->nx + 1) * (2 * ctx->ny + 1);
     const long M = nsdg_tiled_len(ctx->nx, ctx->ny, 8);
-    // scratch: [packed nodal 6*nnodes (8*nnodes reserved)][u, v ping-pong 2*nnodes][stress ping-pong 3*M]
+    // scratch: [packed nodal 8*nnodes (6*nnodes used without a depth array)][u, v ping-pong 2*nnodes][stress ping-pong 3*M]
     double* packed = scratch;
     double *ua = u, *va = v, *ub = scratch + 8 * nnodes, *vb = ub + nnodes;
     double *sa[3] = { s11, s12, s22 };

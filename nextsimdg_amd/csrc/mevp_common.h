@@ -517,25 +517,57 @@ struct NodalConsts {
     double k1, k2, k3;
     double rdt; // rho_ice / dt (the adaptive form: K1 = rdt beta_n, K2 = rdt (1 + beta_n) per node)
 };
+// the launch constants of a BASAL instantiation: those and the speed u0 of the seabed stress C_b = T_b / (|u| + u0) (include/nsdg_basal.h).
+// A type of its own, so that the kernels without the term keep the argument list they had; it converts to NodalConsts where one is taken.
+struct NodalConstsBasal : NodalConsts {
+    double u0;
+};
+template <bool BASAL>
+using NodalConstsOf = std::conditional_t<BASAL, NodalConstsBasal, NodalConsts>;
+template <bool BASAL>
+__device__ __forceinline__ double nodal_u0(const NodalConstsOf<BASAL>& K)
+{
+    if constexpr (BASAL)
+        return K.u0;
+    else
+        return 0.;
+}
 
 // The node update.  AD selects only the denominator and c1: the uniform form with the launch constants K1, K2; the adaptive form with the
 // node's own beta -- qmax = the largest offer alpha_e h'_c of the adjacent elements, beta_n h'_n = max(alpha_min h'_n, qmax); at an ice-free
 // node c[0] is h'_n scaled by 2^100 and the first argument wins: beta_n = alpha_min.
 // LAND (the kernels launched when the packing saw a land mask, csrc/landmask.hip): a land node is packed with cd = c[1] < 0 -- every
 // real node has cd >= 0 -- and holds u = v = 0 like a node on the array edge.  LAND = false is the code without the test.
-template <bool AD, bool LAND>
+// BASAL (the kernels launched when the packing saw a depth array, csrc/basal.hip): tb is the node's seventh packed
+// coefficient, the critical stress T_b, u0 the launch constant of NodalConstsBasal, and the seabed stress C_b = T_b / (|u| + u0) -- the
+// speed of the ice itself -- joins the implicit terms of the denominator.  The sum without C_b is formed first, by the expression the
+// other instantiations have, and C_b, formed in a statement of its own, is added to it in the next: -ffp-contract=on fuses inside one
+// expression only, so nothing is contracted across the three.  T_b = 0 gives C_b = +0 and x + 0 = x: where nothing is grounded the
+// result is, bit for bit, that of BASAL = false, whose statements are left as they were.
+template <bool AD, bool LAND, bool BASAL = false>
 __device__ __forceinline__ void node_update(const NodalConsts& K, const double (&c)[6], double uu, double vv, double divx, double divy,
-    double ilumped, double& un, double& vn, double qmax = 0., double amin = 0.)
+    double ilumped, double& un, double& vn, double qmax = 0., double amin = 0., double tb = 0., double u0 = 0.)
 {
     const double du = c[4] - uu, dv = c[5] - vv;
     const double drag = c[1] * fast_sqrt(du * du + dv * dv);
+    double cb = 0.; // BASAL only
+    if constexpr (BASAL)
+        cb = tb * fast_rcp(fast_sqrt(uu * uu + vv * vv) + u0);
     double denom, c1;
     if constexpr (AD) {
         const double bh = __builtin_fmax(amin * c[0], qmax); // beta_n h'_n
-        denom = fast_rcp(__builtin_fma(K.rdt, bh + c[0], drag));
+        if constexpr (BASAL) {
+            const double implicit = __builtin_fma(K.rdt, bh + c[0], drag);
+            denom = fast_rcp(implicit + cb);
+        } else
+            denom = fast_rcp(__builtin_fma(K.rdt, bh + c[0], drag));
         c1 = K.rdt * bh;
     } else {
-        denom = fast_rcp(K.k2 * c[0] + drag);
+        if constexpr (BASAL) {
+            const double implicit = K.k2 * c[0] + drag;
+            denom = fast_rcp(implicit + cb);
+        } else
+            denom = fast_rcp(K.k2 * c[0] + drag);
         c1 = K.k1 * c[0];
     }
     const double cor = K.k3 * c[0];
@@ -545,6 +577,43 @@ __device__ __forceinline__ void node_update(const NodalConsts& K, const double (
         if (c[1] < 0.)
             un = vn = 0.;
     }
+}
+
+// The ice-free-node rule (the packing, mevp.hip: pack_node, states what it does to the coefficients and tests it
+// with this expression, written out there): a node whose mean concentration is below min_conc, whose true thickness cgH / cgA is below
+// min_thick or whose mean thickness is at the mass floor h_min.  Both thresholds 0: rule off.
+__device__ __forceinline__ bool ice_free_node(const nsdg_mevp_params& P, double cgh, double cga)
+{
+    return (P.min_conc > 0. || P.min_thick > 0.) && (cga < P.min_conc || cgh < P.min_thick * cga || cgh <= P.h_min);
+}
+
+// Landfast ice (include/nsdg_basal.h; Lemieux et al. 2015): the critical stress T_b of a node from its nodal means of thickness,
+// concentration and water depth -- the ONE statement of it, shared by the packing (pair 3 of a node) and nsdg_basal_critical.  The
+// thickness is cgH itself, not raised to the mass floor; land and the ice-free rule come first.
+__device__ __forceinline__ double basal_critical_stress(const nsdg_mevp_params& P, const nsdg_basal_params& B, double cgh, double cga, double hwn, bool land)
+{
+    if (land || ice_free_node(P, cgh, cga))
+        return 0.;
+    const double a = fmin(fmax(cga, 0.), 1.);
+    const double hc = a * hwn / B.k1;
+    return B.k2 * fmax(0., cgh - hc) * exp(-B.alpha_b * (1. - a));
+}
+
+// the nodal mean of an element-wise array (the water depth): the mean over the 1 / 2 / 4 elements adjacent to node (gx, gy) inside the
+// array, summed in the order of node_average (mevp.hip) -- rows outward, columns inward.  `at(ix, iy)` reads an element inside the array.
+template <class At>
+__device__ __forceinline__ double node_mean_of(int nx, int ny, int gx, int gy, At at)
+{
+    const int ix_hi = min(gx >> 1, nx - 1), ix_lo = max((gx & 1) ? gx >> 1 : (gx >> 1) - 1, 0);
+    const int iy_hi = min(gy >> 1, ny - 1), iy_lo = max((gy & 1) ? gy >> 1 : (gy >> 1) - 1, 0);
+    double s = 0.;
+    int cnt = 0;
+    for (int iy = iy_lo; iy <= iy_hi; ++iy)
+        for (int ix = ix_lo; ix <= ix_hi; ++ix) {
+            s += at(ix, iy);
+            ++cnt;
+        }
+    return s / cnt;
 }
 
 // Land mask (include/nsdg.h "land mask"): a CG2 node (gx, gy) is a land node if any of the 1 / 2 / 4 elements adjacent to it inside
@@ -571,6 +640,8 @@ static inline NodalConsts nsdg_nodal_consts(const nsdg_ctx* ctx)
     const nsdg_mevp_params& P = ctx->mevp;
     return NodalConsts { P.rho_ice * P.beta / ctx->pack_dt, P.rho_ice * (1. + P.beta) / ctx->pack_dt, P.rho_ice * P.fc, P.rho_ice / ctx->pack_dt };
 }
+// the same with the speed u0 of the seabed stress: what every launcher passes -- a kernel without the term takes its NodalConsts part
+static inline NodalConstsBasal nsdg_nodal_consts_basal(const nsdg_ctx* ctx) { return NodalConstsBasal { nsdg_nodal_consts(ctx), ctx->basal.u0 }; }
 static inline bool nsdg_adaptive(const nsdg_ctx* ctx) { return ctx->mevp.aevp_c > 0.; }
 static inline AdaptConsts nsdg_adapt_consts(const nsdg_ctx* ctx)
 {
@@ -596,6 +667,17 @@ __device__ __forceinline__ void store_nodal(double* __restrict__ packed, long pl
 #pragma unroll
     for (int k = 0; k < 3; ++k)
         *reinterpret_cast<double2*>(p + k * plane) = make_double2(c[2 * k], c[2 * k + 1]);
+}
+
+// BASAL: the fourth pair of a node, (T_b, 0) -- one more 16-byte access beside the three of load_nodal / store_nodal
+__device__ __forceinline__ double load_nodal_tb(const double* __restrict__ packed, long plane, long n)
+{
+    return reinterpret_cast<const double2*>(packed + nodal_off(n) + 3 * plane)->x;
+}
+
+__device__ __forceinline__ void store_nodal_tb(double* __restrict__ packed, long plane, long n, double tb)
+{
+    *reinterpret_cast<double2*>(packed + nodal_off(n) + 3 * plane) = make_double2(tb, 0.);
 }
 
 } // namespace nsdg_mevp_detail

@@ -35,8 +35,9 @@ namespace nsdg_mevp_detail {
 
 // MINW: the register budget, 1 or 2 waves per SIMD; AD: local, solution-adaptive alpha and beta (mevp_common.h)
 // LAND: the instantiation that holds land nodes at 0 (mevp_common.h: node_update), launched after a packing that saw a land mask
-template <int MINW, bool AD, bool LAND>
-__global__ __launch_bounds__(256, MINW) void mevp_fused_kernel(NodalConsts K, AdaptConsts AC, int nx, int ny, int k0, int j0, int j1, int R, int ncw, double hx,
+// BASAL: the instantiation with the seabed stress (mevp_common.h: node_update), launched after a packing that saw a depth array
+template <int MINW, bool AD, bool LAND, bool BASAL>
+__global__ __launch_bounds__(256, MINW) void mevp_fused_kernel(NodalConstsOf<BASAL> K, AdaptConsts AC, int nx, int ny, int k0, int j0, int j1, int R, int ncw, double hx,
     double hy, double ialpha, double dmin2, StressPtrs S, const double* __restrict__ u_old, const double* __restrict__ v_old,
     const double* __restrict__ packed, const double* __restrict__ pg, double* __restrict__ u_new, double* __restrict__ v_new)
 {
@@ -48,10 +49,10 @@ __global__ __launch_bounds__(256, MINW) void mevp_fused_kernel(NodalConsts K, Ad
     if (M.y0 >= j1)
         return; // wave-uniform
     M.y1 = min(M.y0 + R, j1);
-    march_frame<63, 1>(M, K, AC, nx, ny, lane, cw, hx, hy, ialpha, dmin2); // 63 owned columns, lane 0 recomputes the column left of them
+    march_frame<63, 1>(M, K, AC, nx, ny, lane, cw, hx, hy, ialpha, dmin2, nodal_u0<BASAL>(K)); // 63 owned columns, lane 0 recomputes the column left of them
 
     // the element step of the mEVP rheology: the stress is relaxed in registers, stored, and is itself what the momentum equation takes
-    march_strip<AD, LAND, MINW >= 2>(M, k0, j0, u_old, v_old, packed, u_new, v_new,
+    march_strip<AD, LAND, MINW >= 2, BASAL>(M, k0, j0, u_old, v_old, packed, u_new, v_new,
         [&](int iy, bool store, long nV, const double (&ul)[9], const double (&vl)[9], double (&s11)[8], double (&s12)[8], double (&s22)[8], double& qe) {
             const long ts = tile_off(M.ix, iy, M.ntx, 8), tp = tile_off(M.ix, iy, M.ntx, 9);
             double Pq[9];
@@ -118,14 +119,14 @@ int nsdg_march_strip_rows(const nsdg_ctx* ctx, int rows, int ncw, int waves_per_
     return R;
 }
 
-int nsdg_launch_mevp_fused(nsdg_ctx* ctx, bool land, int k0, int j0, int j1, const nsdg_mevp_bufs& b)
+int nsdg_launch_mevp_fused(nsdg_ctx* ctx, bool land, bool basal, int k0, int j0, int j1, const nsdg_mevp_bufs& b)
 {
     const int ncw = nsdg_div_up(ctx->nx, 63); // 63 owned columns per wave
     const int R = nsdg_march_strip_rows(ctx, j1 - k0, ncw, 2); // 2 waves per SIMD at ~204 VGPRs
     const int nstrips = nsdg_div_up(j1 - k0, R);
     const long nwaves = (long)ncw * nstrips;
     const StressPtrs S = { b.s11i, b.s12i, b.s22i, b.s11, b.s12, b.s22 };
-    const NodalConsts K = nsdg_nodal_consts(ctx);
+    const NodalConstsBasal K = nsdg_nodal_consts_basal(ctx);
     const AdaptConsts AC = nsdg_adapt_consts(ctx);
     const double ialpha = 1. / ctx->mevp.alpha, dmin2 = ctx->mevp.delta_min * ctx->mevp.delta_min;
     const dim3 grid(nsdg_div_up(nwaves, 4)), block(256);
@@ -135,12 +136,20 @@ int nsdg_launch_mevp_fused(nsdg_ctx* ctx, bool land, int k0, int j0, int j1, con
         hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, K, AC, ctx->nx, ctx->ny, k0, j0, j1, R, ncw, ctx->hx, ctx->hy, ialpha, dmin2, S, b.u_old, b.v_old,
             b.packed, b.pg, b.u_new, b.v_new);
     };
+    auto pick = [&](auto minw, auto ad) {
+        constexpr int W = decltype(minw)::value;
+        constexpr bool A = decltype(ad)::value;
+        if (basal)
+            land ? launch(mevp_fused_kernel<W, A, true, true>) : launch(mevp_fused_kernel<W, A, false, true>);
+        else
+            land ? launch(mevp_fused_kernel<W, A, true, false>) : launch(mevp_fused_kernel<W, A, false, false>);
+    };
     if (nsdg_adaptive(ctx))
-        land ? launch(mevp_fused_kernel<1, true, true>) : launch(mevp_fused_kernel<1, true, false>);
+        pick(std::integral_constant<int, 1>(), std::true_type());
     else if (ctx->fused_min_waves >= 2)
-        land ? launch(mevp_fused_kernel<2, false, true>) : launch(mevp_fused_kernel<2, false, false>);
+        pick(std::integral_constant<int, 2>(), std::false_type());
     else
-        land ? launch(mevp_fused_kernel<1, false, true>) : launch(mevp_fused_kernel<1, false, false>);
+        pick(std::integral_constant<int, 1>(), std::false_type());
     NSDG_CHECK_LAUNCH();
     return NSDG_OK;
 }

@@ -35,6 +35,13 @@
 // of stage k waits for row r - 2 of stage k + 1, which waited for row r - 1 of stage k), so no wave can wait for ever.
 //
 // The arithmetic is the same sequence of inlined functions as in every other variant: bit-identical to four passes of variant 1.
+//
+// THIS FILE IS COMPILED TWICE.  As itself it holds the instantiations without the seabed stress; mevp_fused4_basal.hip includes it with
+// NSDG_FUSED4_BASAL_TU defined and holds the BASAL ones (landfast ice), so that this file's own listing keeps the
+// four kernels its resource tests and tools/isa_flops.py read.  Two consequences for whoever edits it: (1) every definition here that is
+// not a template or inline is defined in BOTH translation units and collides at link time unless it is guarded by
+// #ifndef NSDG_FUSED4_BASAL_TU, as the launcher's head and the stamped build's readers are; (2) the stamped diagnostic build
+// (NSDG_P2P_SPINSTAT) is undefined in the second translation unit: its counters and phase stamps do NOT cover the BASAL kernels.
 #include "mevp_p2p.h"
 
 namespace nsdg_mevp_detail {
@@ -94,6 +101,7 @@ constexpr int P4_LDS = 3 * P4_HSLOTS * P4_SLOT + P4_PRING * (P4_PSLOT + P4_CSLOT
 struct Fetch {
     double P[9]; // ice strength at the Gauss points of the row the stage works on next
     double c[4][6]; // packed momentum coefficients of its 4 owned nodes
+    double tb[4]; // BASAL only: their seventh coefficient, the critical stress T_b of the seabed stress (mevp_common.h: node_update)
     double s11[8], s12[8], s22[8]; // stage 0 only: the stress the pass starts from
     double ub[3], vb[3], um[3], vm[3], ut[3], vt[3]; // stage 0 only: u, v of the pass's start on the three node rows
 };
@@ -172,6 +180,7 @@ __device__ __forceinline__ void store_stress(const StressPtrs& S, long ts, const
 //   B   8  u, v, two node rows (4 x (16 + 8 B))    ring block, after A                                  projected stress
 //   C  12  stress (3 x 4 x 16 B)                   after the relaxation | bit 2: behind the hand-over   relaxation
 //   D  12  nodal coefficients (4 x 3 x 16 B)       request_c, after the node updates                    ring write of the pair, node updates
+//      +4  BASAL: the fourth pair (4 x 16 B), issued behind the twelve: the group is 16 loads           node updates
 //
 // Bit 2 requests C at the very end of the row, behind the hand-over of the row's own stress: the working registers are dead there, the
 // request can take them and the compiler has no copy to make (requested anywhere earlier the new stress needs a second register set,
@@ -191,6 +200,14 @@ __device__ __forceinline__ void store_stress(const StressPtrs& S, long ts, const
 // out of the accumulation registers there); the stamped build times those three (NSDG_LAND_PROBE).  With a bit set the prologue of the
 // march lets all its loads land before the first row, so the loop's waits are those of its own requests; in the last row of a stage
 // nrow == row and the same loads are issued once more.
+//
+// BASAL (the fourth pair, landfast ice): every stage reads it from memory in request_c, beside the pairs it reads there anyway; there is no
+// ring for it (the LDS is full).  In the loader the four loads join group D, so every count of the table stands: L1 counts the loads
+// YOUNGER than D (C A' B' = 25, or A' B' = 13), and D growing from 12 to 16 loads does not change what is younger than it; the prologue's
+// p2p_land<0> waits for everything whatever was requested.  T_b is consumed at the node updates, behind L1 and behind the relaxation's
+// wait for C, and vmcnt retires loads in order: the fourth pair, older than C, has landed there and the compiler's own wait costs nothing.
+// The counts of the stamped build's probes (12 at the top, P4_NA in the ring block, 4 before request_c) restate the compiler's waits of
+// the switch-at-0 build without a depth array and are not launched with one.  The stages 1-3 have no hand-placed count.
 constexpr int P4_NA = 5, P4_NB = 8, P4_NC = 12;
 constexpr bool P4_LAND_COEFF = (NSDG_P2P_LAND & 1) != 0, P4_LAND_ORDER = (NSDG_P2P_LAND & 2) != 0;
 constexpr int P4_L1 = P4_LAND_ORDER ? P4_NC + P4_NA + P4_NB : P4_NA + P4_NB;
@@ -202,7 +219,7 @@ __device__ __forceinline__ void request_stress(const StressPtrs& S, long ts, Fet
     tile_load8_nt<(NSDG_P2P_NT & 1) != 0>(S.i22, ts, f.s22);
 }
 // One row of one stage.  FIRST: the loader (stage 0): inputs from memory, ice strength into the ring.
-template <bool FIRST, bool AD, bool LAND>
+template <bool FIRST, bool AD, bool LAND, bool BASAL>
 __device__ __forceinline__ void p2p_row(const MarchConst& M, const Stage& G, int row, Fetch& f, TopCarry& carry, double* __restrict__ lds,
     volatile lds_int* flags, const P2PReport& rep, const StressPtrs& S, const double* __restrict__ u_old, const double* __restrict__ v_old,
     const double* __restrict__ packed, const double* __restrict__ pg, double* __restrict__ u_new, double* __restrict__ v_new NSDG_SPIN_ARG)
@@ -212,14 +229,17 @@ __device__ __forceinline__ void p2p_row(const MarchConst& M, const Stage& G, int
     const int ix = M.ix, nn = M.nn;
     double* const ring = lds + 3 * P4_HSLOTS * P4_SLOT;
     double* const cring = ring + P4_PRING * P4_PSLOT;
-    // the coefficients of row r: a stage >= 1 takes two pairs from memory and the third from the ring
+    // the coefficients of row r: a stage >= 1 takes two pairs from memory and the third from the ring; BASAL: every stage takes the
+    // fourth from memory
     auto request_c = [&](int r) {
         if (FIRST)
             load_owned_nodal(M, r, f.c, packed);
-        else {
+        else
             load_owned_nodal2(M, r, f.c, packed);
+        if constexpr (BASAL)
+            load_owned_nodal_tb(M, r, f.tb, packed);
+        if (!FIRST)
             ring_read_c(cring, r, M.lane, f.c);
-        }
     };
     const long nVn = (long)(2 * nrow) * nn + 2 * ix; // vertex node of the next row
     double s11[8], s12[8], s22[8], uu[4], vv[4], ul[9], vl[9], un[4], vn[4];
@@ -341,7 +361,7 @@ __device__ __forceinline__ void p2p_row(const MarchConst& M, const Stage& G, int
     {
         double cx[9], cy[9];
         node_contrib_all(s11, s12, s22, M.hx, M.hy, cx, cy);
-        owned_node_updates<AD, LAND>(M, row > 0, f.c, uu, vv, carry, cx, cy, un, vn, qe);
+        owned_node_updates<AD, LAND, BASAL>(M, row > 0, f.c, uu, vv, carry, cx, cy, un, vn, qe, f.tb);
         if (row < G.upd0) { // wave-uniform: the first row of a stage only feeds the carried contributions
 #pragma unroll
             for (int k = 0; k < 4; ++k)
@@ -382,8 +402,9 @@ __device__ __forceinline__ void p2p_row(const MarchConst& M, const Stage& G, int
 }
 
 // LAND: the instantiation that holds land nodes at 0 (mevp_common.h: node_update), launched after a packing that saw a land mask
-template <bool AD, bool LAND>
-__global__ __launch_bounds__(256) void mevp_fused4_kernel(NodalConsts K, AdaptConsts AC, int nst, int nx, int ny, int j0, int j1, int j0b, int j1b, int nsA, int R, int ncw,
+// BASAL: the instantiation with the seabed stress (mevp_common.h: node_update), launched after a packing that saw a depth array
+template <bool AD, bool LAND, bool BASAL>
+__global__ __launch_bounds__(256) void mevp_fused4_kernel(NodalConstsOf<BASAL> K, AdaptConsts AC, int nst, int nx, int ny, int j0, int j1, int j0b, int j1b, int nsA, int R, int ncw,
     double hx, double hy, double ialpha, double dmin2, P2PReport rep, StressPtrs S, const double* __restrict__ u_old, const double* __restrict__ v_old,
     const double* __restrict__ packed, const double* __restrict__ pg, double* __restrict__ u_new, double* __restrict__ v_new)
 {
@@ -403,7 +424,7 @@ __global__ __launch_bounds__(256) void mevp_fused4_kernel(NodalConsts K, AdaptCo
     if (M.y0 >= j1)
         return; // workgroup-uniform: no wave of this workgroup reaches the barrier or a counter
     M.y1 = min(M.y0 + R, j1);
-    march_frame<P4_OWNED, P4_LEFT>(M, K, AC, nx, ny, lane, cw, hx, hy, ialpha, dmin2);
+    march_frame<P4_OWNED, P4_LEFT>(M, K, AC, nx, ny, lane, cw, hx, hy, ialpha, dmin2, nodal_u0<BASAL>(K));
 
     // a pass of nst sub-iterations (2 <= nst <= 4): stage s works on the rows y0 - nst + s .. y1 + nst - 2 - s, the last one (nst - 1)
     // on y0 - 1 .. y1 - 1; the waves s >= nst have nothing to do
@@ -451,6 +472,8 @@ __global__ __launch_bounds__(256) void mevp_fused4_kernel(NodalConsts K, AdaptCo
         tile_load8_nt<(NSDG_P2P_NT & 1) != 0>(S.i22, ts, f.s22);
         tile_load9_nt<(NSDG_P2P_NT & 4) != 0>(pg, tile_off(M.ix, row, M.ntx, 9), M.ix & 63, f.P);
         load_owned_nodal(M, row, f.c, packed);
+        if constexpr (BASAL)
+            load_owned_nodal_tb(M, row, f.tb, packed);
         if constexpr (NSDG_P2P_LAND != 0) {
             // everything the prologue requested lands here, once per strip: a load still in flight at the head of the loop is one
             // the compiler has to assume in flight in every row, and it waits for it wherever a later row reuses the register
@@ -460,10 +483,10 @@ __global__ __launch_bounds__(256) void mevp_fused4_kernel(NodalConsts K, AdaptCo
                 p2p_name(f.c[n][0], f.c[n][1], f.c[n][2], f.c[n][3]);
         }
         for (int row = G.first; row <= G.last; ++row)
-            p2p_row<true, AD, LAND>(M, G, row, f, carry, lds, flags, rep, S, u_old, v_old, packed, pg, u_new, v_new NSDG_SPIN_PASS);
+            p2p_row<true, AD, LAND, BASAL>(M, G, row, f, carry, lds, flags, rep, S, u_old, v_old, packed, pg, u_new, v_new NSDG_SPIN_PASS);
     } else {
         for (int row = G.first; row <= G.last; ++row)
-            p2p_row<false, AD, LAND>(M, G, row, f, carry, lds, flags, rep, S, u_old, v_old, packed, pg, u_new, v_new NSDG_SPIN_PASS);
+            p2p_row<false, AD, LAND, BASAL>(M, G, row, f, carry, lds, flags, rep, S, u_old, v_old, packed, pg, u_new, v_new NSDG_SPIN_PASS);
     }
 #ifdef NSDG_P2P_SPINSTAT
     if (lane == 0) {
@@ -506,8 +529,20 @@ extern "C" int nsdg_debug_p2p_landstat(unsigned long long* out4) // cycles at th
 }
 #endif
 
-int nsdg_launch_mevp_fused4_ranges(nsdg_ctx* ctx, bool land, int nst, int j0, int j1, int j0b, int j1b, const nsdg_mevp_bufs& b)
+// The launcher.  This file is compiled twice: as itself, with the instantiations without the seabed stress -- the kernels of a context
+// without a depth array, the ones its resource tests and tools/isa_flops.py list --, and through mevp_fused4_basal.hip, which defines
+// NSDG_FUSED4_BASAL_TU and holds the BASAL instantiations behind nsdg_launch_mevp_fused4_basal_ranges.
+#ifdef NSDG_FUSED4_BASAL_TU
+int nsdg_launch_mevp_fused4_basal_ranges(nsdg_ctx* ctx, bool land, int nst, int j0, int j1, int j0b, int j1b, const nsdg_mevp_bufs& b)
 {
+    constexpr bool BASAL = true;
+#else
+int nsdg_launch_mevp_fused4_ranges(nsdg_ctx* ctx, bool land, bool basal, int nst, int j0, int j1, int j0b, int j1b, const nsdg_mevp_bufs& b)
+{
+    constexpr bool BASAL = false;
+    if (basal)
+        return nsdg_launch_mevp_fused4_basal_ranges(ctx, land, nst, j0, j1, j0b, j1b, b);
+#endif
     const int ncw = nsdg_div_up(ctx->nx, P4_OWNED);
     const int rowsB = j0b < j1b ? j1b - j0b : 0;
     int R = ctx->strip_rows;
@@ -533,18 +568,19 @@ int nsdg_launch_mevp_fused4_ranges(nsdg_ctx* ctx, bool land, int nst, int j0, in
     const int nsA = nsdg_div_up(j1 - j0, R), nsB = nsdg_div_up(rowsB, R);
     const long ngroups = (long)ncw * (nsA + nsB);
     const StressPtrs S = { b.s11i, b.s12i, b.s22i, b.s11, b.s12, b.s22 };
-    const NodalConsts K = nsdg_nodal_consts(ctx);
+    const NodalConstsBasal K = nsdg_nodal_consts_basal(ctx);
     const AdaptConsts AC = nsdg_adapt_consts(ctx);
     const P2PReport rep = { ctx->p2p_count_dev, ctx->p2p_flag_dev };
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(ngroups), dim3(256), 0, ctx->stream, K, AC, nst, ctx->nx, ctx->ny, j0, j1, j0b, j1b, nsA, R, ncw, ctx->hx, ctx->hy,
             1. / ctx->mevp.alpha, ctx->mevp.delta_min * ctx->mevp.delta_min, rep, S, b.u_old, b.v_old, b.packed, b.pg, b.u_new, b.v_new);
     };
-    // adaptive: local, solution-adaptive alpha and beta (mevp_common.h); land: the packing flagged land nodes (nsdg_mevp_pass)
+    // adaptive: local, solution-adaptive alpha and beta (mevp_common.h); land: the packing flagged land nodes; BASAL: it stored T_b from a
+    // depth array (nsdg_mevp_pass)
     if (!land)
-        nsdg_adaptive(ctx) ? launch(mevp_fused4_kernel<true, false>) : launch(mevp_fused4_kernel<false, false>);
+        nsdg_adaptive(ctx) ? launch(mevp_fused4_kernel<true, false, BASAL>) : launch(mevp_fused4_kernel<false, false, BASAL>);
     else
-        nsdg_adaptive(ctx) ? launch(mevp_fused4_kernel<true, true>) : launch(mevp_fused4_kernel<false, true>);
+        nsdg_adaptive(ctx) ? launch(mevp_fused4_kernel<true, true, BASAL>) : launch(mevp_fused4_kernel<false, true, BASAL>);
     NSDG_CHECK_LAUNCH();
     return NSDG_OK;
 }

@@ -19,6 +19,7 @@ namespace nsdg_mevp_detail {
 
 struct MarchConst {
     NodalConsts K;
+    double u0; // BASAL instantiations only: the speed u0 of the seabed stress (NodalConstsBasal)
     int nx, ny, y0, y1, ix, ntx, nn, lane;
     long nplane; // doubles between two pair planes of the packed nodal coefficients
     bool own, hasL, lastcol;
@@ -48,14 +49,25 @@ __device__ __forceinline__ void load_owned_nodal(const MarchConst& M, int row, d
     load_nodal(packed, M.nplane, nV + M.nn + 1, c[3]);
 }
 
+// BASAL: the fourth pair's first member, T_b, of the same four nodes
+__device__ __forceinline__ void load_owned_nodal_tb(const MarchConst& M, int row, double (&tb)[4], const double* __restrict__ packed)
+{
+    const long nV = (long)(2 * row) * M.nn + 2 * M.ix;
+    tb[0] = load_nodal_tb(packed, M.nplane, nV);
+    tb[1] = load_nodal_tb(packed, M.nplane, nV + 1);
+    tb[2] = load_nodal_tb(packed, M.nplane, nV + M.nn);
+    tb[3] = load_nodal_tb(packed, M.nplane, nV + M.nn + 1);
+}
+
 // the four owned nodes of one element row from the carried contributions of the row below (`carry`), the
 // contributions of this row (cx, cy) and the left neighbour's right-column contributions, summed in the oracle's order: below-left,
 // below, left, own.  Inverse lumped masses: 4, 2, 2, 1 adjacent elements times 1/36, 1/9, 1/9, 4/9 of the cell area.
 // (AD: adaptive form -- `q` is this element's offer q_e = alpha_e h'_c of this sub-iteration, a node takes the largest offer of its adjacent elements)
-// (LAND: land nodes stay at 0, node_update)
-template <bool AD, bool LAND>
+// (LAND: land nodes stay at 0, node_update; BASAL: tb = T_b of the four nodes, the seabed stress of node_update -- read only then)
+template <bool AD, bool LAND, bool BASAL = false>
 __device__ __forceinline__ void owned_node_updates(const MarchConst& M, bool hasB, const double (&c)[4][6], const double (&uu)[4],
-    const double (&vv)[4], const TopCarry& carry, const double (&cx)[9], const double (&cy)[9], double (&un)[4], double (&vn)[4], double q = 0.)
+    const double (&vv)[4], const TopCarry& carry, const double (&cx)[9], const double (&cy)[9], double (&un)[4], double (&vn)[4], double q,
+    const double (&tb)[4])
 {
     const double l2x = lane_from_left(cx[2]), l2y = lane_from_left(cy[2]);
     const double l5x = lane_from_left(cx[5]), l5y = lane_from_left(cy[5]);
@@ -66,19 +78,19 @@ __device__ __forceinline__ void owned_node_updates(const MarchConst& M, bool has
     }
     const double amin = M.AC.amin;
     if (M.hasL && hasB)
-        node_update<AD, LAND>(M.K, c[0], uu[0], vv[0], ((carry.xl8 + carry.x6) + l2x) + cx[0], ((carry.yl8 + carry.y6) + l2y) + cy[0], 9. * M.iarea,
-            un[0], vn[0], AD ? __builtin_fmax(__builtin_fmax(carry.ql, carry.q), qmid) : 0., amin);
+        node_update<AD, LAND, BASAL>(M.K, c[0], uu[0], vv[0], ((carry.xl8 + carry.x6) + l2x) + cx[0], ((carry.yl8 + carry.y6) + l2y) + cy[0], 9. * M.iarea,
+            un[0], vn[0], AD ? __builtin_fmax(__builtin_fmax(carry.ql, carry.q), qmid) : 0., amin, BASAL ? tb[0] : 0., BASAL ? M.u0 : 0.);
     else
         un[0] = vn[0] = 0.;
     if (hasB)
-        node_update<AD, LAND>(M.K, c[1], uu[1], vv[1], carry.x7 + cx[1], carry.y7 + cy[1], 4.5 * M.iarea, un[1], vn[1], qbot, amin);
+        node_update<AD, LAND, BASAL>(M.K, c[1], uu[1], vv[1], carry.x7 + cx[1], carry.y7 + cy[1], 4.5 * M.iarea, un[1], vn[1], qbot, amin, BASAL ? tb[1] : 0., BASAL ? M.u0 : 0.);
     else
         un[1] = vn[1] = 0.;
     if (M.hasL)
-        node_update<AD, LAND>(M.K, c[2], uu[2], vv[2], l5x + cx[3], l5y + cy[3], 4.5 * M.iarea, un[2], vn[2], qmid, amin);
+        node_update<AD, LAND, BASAL>(M.K, c[2], uu[2], vv[2], l5x + cx[3], l5y + cy[3], 4.5 * M.iarea, un[2], vn[2], qmid, amin, BASAL ? tb[2] : 0., BASAL ? M.u0 : 0.);
     else
         un[2] = vn[2] = 0.;
-    node_update<AD, LAND>(M.K, c[3], uu[3], vv[3], cx[4], cy[4], 2.25 * M.iarea, un[3], vn[3], q, amin);
+    node_update<AD, LAND, BASAL>(M.K, c[3], uu[3], vv[3], cx[4], cy[4], 2.25 * M.iarea, un[3], vn[3], q, amin, BASAL ? tb[3] : 0., BASAL ? M.u0 : 0.);
 }
 
 template <bool AD>
@@ -127,8 +139,9 @@ __device__ __forceinline__ void store_owned_nodes(long nV, int nn, bool lastcol,
 // columns; lanes outside the array load a clamped column and store nothing.
 template <int OWNED, int LEFT>
 __device__ __forceinline__ void march_frame(MarchConst& M, const NodalConsts& K, const AdaptConsts& AC, int nx, int ny, int lane, int cw,
-    double hx, double hy, double ialpha, double dmin2)
+    double hx, double hy, double ialpha, double dmin2, double u0 = 0.)
 {
+    M.u0 = u0;
     const int ixr = cw * OWNED - LEFT + lane;
     const bool valid = ixr >= 0 && ixr < nx;
     M.K = K, M.AC = AC;
@@ -151,7 +164,8 @@ __device__ __forceinline__ void march_frame(MarchConst& M, const NodalConsts& K,
 // needs, updates its state and stores it where `store` is true, and returns the coefficients of the stress of the momentum equation in
 // m?? and, in the adaptive form, the element's offer in qe.
 // FENCE: a compiler fence between the contributions and the nodal-coefficient loads (the 2-waves-per-SIMD build of mevp_fused.hip)
-template <bool AD, bool LAND, bool FENCE, class Element>
+// BASAL: the fourth coefficient pair is loaded beside the three and the node updates add the seabed stress (node_update)
+template <bool AD, bool LAND, bool FENCE, bool BASAL, class Element>
 __device__ __forceinline__ void march_strip(const MarchConst& M, int k0, int j0, const double* __restrict__ u_old, const double* __restrict__ v_old,
     const double* __restrict__ packed, double* __restrict__ u_new, double* __restrict__ v_new, Element&& element)
 {
@@ -176,10 +190,12 @@ __device__ __forceinline__ void march_strip(const MarchConst& M, int k0, int j0,
             asm volatile("" ::: "memory"); // keep the nodal-coefficient loads below this point
 
         if (!prologue && iy >= j0) { // wave-uniform
-            double c[4][6], un[4], vn[4];
+            double c[4][6], un[4], vn[4], tb[4] = { 0., 0., 0., 0. };
             load_owned_nodal(M, iy, c, packed);
+            if constexpr (BASAL)
+                load_owned_nodal_tb(M, iy, tb, packed);
             const double uu[4] = { ul[0], ul[1], ul[3], ul[4] }, vv[4] = { vl[0], vl[1], vl[3], vl[4] };
-            owned_node_updates<AD, LAND>(M, iy > 0, c, uu, vv, carry, cx, cy, un, vn, qe);
+            owned_node_updates<AD, LAND, BASAL>(M, iy > 0, c, uu, vv, carry, cx, cy, un, vn, qe, tb);
             if (M.own)
                 store_owned_nodes(nV, nn, M.lastcol, iy == M.ny - 1, un, vn, u_new, v_new);
         }

@@ -28,6 +28,9 @@ struct nsdg_ctx {
     double pack_dt; // time step the packed nodal coefficients were built for (0 = never packed)
     const uint8_t* land; // element land mask of the local array (landmask.hip), null = none; owned by the caller
     bool pack_land; // the packing saw a mask: land nodes carry the flag cd < 0 and the passes run the LAND instantiations
+    nsdg_basal_params basal; // landfast ice (basal.hip): the grounding scheme's parameters
+    const double* depth; // water depth per element of the local array, null = none; owned by the caller
+    bool pack_basal; // the packing saw a depth array: pair 3 of a node holds (T_b, 0) and the passes run the BASAL instantiations
     int transport_variant, transport_rows; // transport stage kernel: 0 one element per lane / 2 two elements per lane; rows per workgroup
     int fused_min_waves; // register budget of the fused kernel: 1 or 2 waves per SIMD
     int nbounds; // closure of a transport step: bounds of the advected fields (0 = none), nsdg_transport_bounds_set
@@ -151,9 +154,12 @@ int nsdg_mevp_pass(nsdg_ctx* ctx, int v, int k0, int j0, int j1, bool pair, int 
 
 // the launchers behind it, unchecked: the fused single-iteration kernel (mevp_fused.hip); the stage-per-wave pipeline of nst = 2, 3
 // or 4 sub-iterations on the rows [j0, j1) and, if j0b < j1b, on a second disjoint range (mevp_fused4.hip)
-// land: run the instantiation that holds land nodes at 0 -- chosen in ONE place, nsdg_mevp_pass, from what the packing saw
-int nsdg_launch_mevp_fused(nsdg_ctx* ctx, bool land, int k0, int j0, int j1, const nsdg_mevp_bufs& b);
-int nsdg_launch_mevp_fused4_ranges(nsdg_ctx* ctx, bool land, int nst, int j0, int j1, int j0b, int j1b, const nsdg_mevp_bufs& b);
+// land: run the instantiation that holds land nodes at 0; basal: the one with the seabed stress -- both chosen in ONE place,
+// nsdg_mevp_pass, from what the packing saw
+int nsdg_launch_mevp_fused(nsdg_ctx* ctx, bool land, bool basal, int k0, int j0, int j1, const nsdg_mevp_bufs& b);
+int nsdg_launch_mevp_fused4_ranges(nsdg_ctx* ctx, bool land, bool basal, int nst, int j0, int j1, int j0b, int j1b, const nsdg_mevp_bufs& b);
+// the BASAL instantiations of the pipeline, a translation unit of their own (mevp_fused4_basal.hip); nsdg_launch_mevp_fused4_ranges forwards to it
+int nsdg_launch_mevp_fused4_basal_ranges(nsdg_ctx* ctx, bool land, int nst, int j0, int j1, int j0b, int j1b, const nsdg_mevp_bufs& b);
 
 // rows per strip of a single-iteration march over `rows` element rows with ncw column-waves, in a kernel built for `waves_per_simd`
 // resident waves: the context's strip_rows, or the automatic height (mevp_fused.hip)

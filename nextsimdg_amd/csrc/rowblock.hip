@@ -124,7 +124,7 @@ int make_plan(nsdg_ctx* ctx, const Geometry& g, const SegList& L, nsdg_halo** ou
 // Delta_min^2, the cell size, the strip height, the kernel variant, the masked or unmasked instantiation): the cache remembers the values its graphs were
 // recorded with and is dropped when any of them has changed, so a replay never mixes two parameter sets.
 struct GraphStamp {
-    double v[10];
+    double v[11];
     int k[8];
     bool operator==(const GraphStamp& o) const { return std::memcmp(this, &o, sizeof *this) == 0; }
 };
@@ -136,9 +136,11 @@ GraphStamp graph_stamp(const nsdg_ctx* c)
     const nsdg_mevp_params& P = c->mevp;
     // aevp_c and aevp_alpha_min: the adaptive form's constants (alpha_min follows dt under NSDG_SUBCYCLE_ADAPTIVE_CONVERGED, so a host that
     // sub-steps changes it between model steps)
-    const double v[10] = { c->pack_dt, P.alpha, P.beta, P.rho_ice, P.fc, P.delta_min, c->hx, c->hy, P.aevp_c, P.aevp_alpha_min };
-    // pack_land: a captured launch is the kernel that was recorded -- a packing with a land mask must not replay the unmasked passes
-    const int k[8] = { c->strip_rows, c->mevp_variant, c->fused_min_waves, c->nx, c->ny, c->num_cus, (int)c->pack_land, 0 };
+    // basal.u0: the launch constant of the seabed stress (the other parameters of the grounding scheme act through the packing, which is data)
+    const double v[11] = { c->pack_dt, P.alpha, P.beta, P.rho_ice, P.fc, P.delta_min, c->hx, c->hy, P.aevp_c, P.aevp_alpha_min, c->basal.u0 };
+    // pack_land, pack_basal: a captured launch is the kernel that was recorded -- a packing with a land mask or a depth array must not
+    // replay the passes recorded without one
+    const int k[8] = { c->strip_rows, c->mevp_variant, c->fused_min_waves, c->nx, c->ny, c->num_cus, (int)c->pack_land, (int)c->pack_basal };
     std::memcpy(s.v, v, sizeof v);
     std::memcpy(s.k, k, sizeof k);
     return s;

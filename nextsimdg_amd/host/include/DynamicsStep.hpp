@@ -48,6 +48,12 @@
 //                            (include/LandMaskFile.hpp; include/nsdg.h "land mask"): the nodes of land elements hold u = v = 0, H, A, the
 //                            snow and the new ice are cleared on land at the start and after every column step; read and checked when the
 //                            step is configured.  The restart file holds no mask: a resumed run names the same file
+//     dynamics.bathymetry_file  a .npy array of float64, the water depth in metres per element, shape and orientation of the mask
+//                            (include/BathymetryFile.hpp; include/nsdg_basal.h): finite and >= 0 at ocean
+//                            elements, stored as 0 on land; ice whose keels reach the seabed feels a basal stress in the momentum update
+//                            and stays fast over a shoal.  Read and checked when the step is configured; the restart file holds no copy
+//     [basal] k1, k2, alpha_b, u0  the grounding scheme's parameters, one key per member of nsdg_basal_params (defaults: the published 8,
+//                            15 N m^-3, 20, 5e-5 m/s; k1 > 0, k2 >= 0, alpha_b >= 0, u0 > 0, all finite); they need dynamics.bathymetry_file
 //     dynamics.substeps      sub-steps per model step: an integer >= 1 (default 1: the unsplit step, bit for bit) or auto -- n decided at
 //                            the start of every model step from the state's strength wave speed, the same on every block
 //                            (nsdg_concentration_max, nsdg_comm_max_f64, nsdg_substep_count: include/nsdg.h "sub-stepping"); the whole
@@ -96,6 +102,7 @@
 // start at zero) and receive them back at stop().  Ocean current and wind come from the device-side forcing
 // provider nsdg_boxtest_forcing (the wind is re-evaluated at every step's model time), or from a forcing file's pairs.
 #pragma once
+#include "../../../include/nsdg_basal.h"
 #include <algorithm>
 #include <memory>
 #include <string>
@@ -111,6 +118,7 @@ namespace Nextsim {
 
 class ForcingFile;
 class LandMaskFile;
+class BathymetryFile;
 
 class DynamicsBlock; // one row block: context, device arrays, driver plans (src/DynamicsBlock.hpp)
 
@@ -185,6 +193,8 @@ private:
     std::string forcing = "host", devices;
     std::shared_ptr<const ForcingFile> m_forcingFile; // dynamics.forcing = file: the records, read and checked in configure()
     std::shared_ptr<const LandMaskFile> m_landMask; // dynamics.land_mask_file: the element mask, read and checked in configure()
+    std::shared_ptr<const BathymetryFile> m_bathymetry; // dynamics.bathymetry_file: the water depth, read and checked in configure()
+    nsdg_basal_params m_basal; // [basal]: the grounding scheme's parameters (used with m_bathymetry)
     struct Outputs; // model.output_*, series_*, drifters_*, stations_*: the four outputs, each null when off (DynamicsStep.cpp)
     std::unique_ptr<Outputs> m_out;
     struct Brittle; // dynamics.rheology = bbm: the parameters and the sub-iteration rule (DynamicsStep.cpp); null: mEVP

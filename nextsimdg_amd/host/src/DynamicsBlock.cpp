@@ -7,6 +7,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "BathymetryFile.hpp"
 #include "LandMaskFile.hpp"
 
 namespace Nextsim {
@@ -155,6 +156,14 @@ void DynamicsBlock::setLandMask(const LandMaskFile& mask)
     land = deviceAlloc<std::uint8_t>((std::size_t)N, "DynamicsStep: hipMalloc (land mask)");
     toDevice(land.get(), mask.data() + (std::size_t)lo * nx, (std::size_t)N, "upload land mask");
     check(nsdg_land_mask_set(ctx.get(), land.get()), "nsdg_land_mask_set");
+}
+
+void DynamicsBlock::setBathymetry(const BathymetryFile& bathymetry, const nsdg_basal_params& params)
+{
+    depth = deviceAlloc<double>((std::size_t)N, "DynamicsStep: hipMalloc (bathymetry)");
+    toDevice(depth.get(), bathymetry.data() + (std::size_t)lo * nx, (std::size_t)N * sizeof(double), "upload bathymetry");
+    check(nsdg_basal_params_set(ctx.get(), &params), "nsdg_basal_params_set");
+    check(nsdg_basal_depth_set(ctx.get(), depth.get()), "nsdg_basal_depth_set");
 }
 
 void DynamicsBlock::upload(const FieldStore& f, bool thermodynamics, bool announce)

@@ -22,6 +22,7 @@
 namespace Nextsim {
 
 class LandMaskFile;
+class BathymetryFile;
 
 //! one row block per process, ghost rows over RCCL: a dead neighbour then ends the process in check()
 void setMultiProcess(bool on);
@@ -101,6 +102,7 @@ public:
     // ---- the handles, in the reverse of the order in which they go: the plans, the arrays, the forcing records, the outputs' buffers
     // (first asked for, first freed), the context (which finalises the communicator too) and last the land mask the context held
     DeviceBuffer<std::uint8_t> land; // dynamics.land_mask_file: the mask of the local rows, ghost rows included (set on the context)
+    DeviceBuffer<double> depth; // dynamics.bathymetry_file: the water depth of the same rows (set on the context, freed after it like the mask)
     NsdgHandle<nsdg_ctx, nsdg_ctx_destroy> ctx;
     std::vector<DeviceBuffer<double>> outputBuffers; // what outputBuffer() handed out
     // dynamics.forcing = file: two records of every variable of the file on the device (slot s: variables one after the other, in the
@@ -132,6 +134,9 @@ public:
     void allocate(bool brittle, bool advectColumn, int ntracers = 0);
     //! the block's rows of the mask, ghost rows included, on the device and on the context: the mask is static, nothing is ever exchanged
     void setLandMask(const LandMaskFile& mask);
+    //! the block's rows of the water depth, ghost rows included, and the grounding scheme's parameters, on the device and on the context
+    //! (landfast ice, include/nsdg_basal.h): static like the mask, nothing is ever exchanged
+    void setBathymetry(const BathymetryFile& bathymetry, const nsdg_basal_params& params);
     //! the local rows, ghost rows included, of the structure's cell means and, if a dynamics run left it (FieldStore::dyn), of its state;
     //! with thermodynamics the column planes.  announce: this block prints the line about a restart file without damage
     void upload(const FieldStore& f, bool thermodynamics, bool announce);

@@ -16,6 +16,7 @@
 #include "DynamicsBlock.hpp"
 #include "DynamicsOutputs.hpp"
 #include "ForcingFile.hpp"
+#include "BathymetryFile.hpp"
 #include "LandMaskFile.hpp"
 #include "ModuleLoader.hpp"
 #include "PhaseTiming.hpp"
@@ -37,7 +38,8 @@ const std::map<int, std::string> Configured<DynamicsStep>::keyMap = { { 0, "dyna
     { 14, "dynamics.min_thick" }, { 15, "dynamics.delta_min" }, { 16, "dynamics.subcycle" }, { 17, "dynamics.substeps" },
     { 18, "dynamics.substep_courant" }, { 19, "dynamics.max_substeps" }, { 20, "dynamics.forcing_file" },
     { 21, "dynamics.advect_column_state" }, { 22, "dynamics.land_mask_file" }, { 23, "dynamics.rheology" },
-    { 24, "dynamics.bbm_courant" }, { 25, "dynamics.tracers" }, { 26, "dynamics.tracer_init" } };
+    { 24, "dynamics.bbm_courant" }, { 25, "dynamics.tracers" }, { 26, "dynamics.tracer_init" },
+    { 27, "dynamics.bathymetry_file" } };
 
 // dynamics.rheology = bbm
 struct DynamicsStep::Brittle {
@@ -73,6 +75,13 @@ const BbmKey BBM_KEYS[] = { { "bbm.young", &nsdg_bbm_params::young }, { "bbm.nu"
     { "bbm.lambda0", &nsdg_bbm_params::lambda0 }, { "bbm.tan_phi", &nsdg_bbm_params::tan_phi }, { "bbm.cohesion_lab", &nsdg_bbm_params::cohesion_lab },
     { "bbm.compr_strength", &nsdg_bbm_params::compr_strength }, { "bbm.t_heal", &nsdg_bbm_params::t_heal }, { "bbm.d_max", &nsdg_bbm_params::d_max } };
 const char* const BBM_EXPONENT_KEY = "bbm.relax_exponent";
+// [basal]: one key per member of nsdg_basal_params (include/nsdg_basal.h)
+struct BasalKey {
+    const char* key;
+    double nsdg_basal_params::*member;
+};
+const BasalKey BASAL_KEYS[] = { { "basal.k1", &nsdg_basal_params::k1 }, { "basal.k2", &nsdg_basal_params::k2 },
+    { "basal.alpha_b", &nsdg_basal_params::alpha_b }, { "basal.u0", &nsdg_basal_params::u0 } };
 } // namespace
 
 std::vector<std::string> DynamicsStep::tracerNames(const std::string& value)
@@ -219,6 +228,29 @@ void DynamicsStep::configure()
             m_landMask = std::make_shared<const LandMaskFile>(path);
             if (pStructure)
                 m_landMask->checkShape((std::size_t)pStructure->nx(), (std::size_t)pStructure->ny());
+        }
+    }
+    // landfast ice (include/nsdg_basal.h): the water depth, checked against the mask just read, and the [basal] parameters -- the rule of
+    // nsdg_basal_params_set, applied here, before any device is touched
+    m_bathymetry.reset();
+    nsdg_basal_default_params(&m_basal);
+    {
+        const std::string path = getConfiguration(keyMap.at(27), std::string(""));
+        bool given = false;
+        for (const BasalKey& k : BASAL_KEYS) {
+            const double value = getConfiguration(std::string(k.key), m_basal.*k.member);
+            given = given || value != m_basal.*k.member;
+            m_basal.*k.member = value;
+            if (!std::isfinite(value) || value < 0. || (value == 0. && (k.member == &nsdg_basal_params::k1 || k.member == &nsdg_basal_params::u0)))
+                throw std::invalid_argument(std::string("[basal]: ") + k.key + " = " + std::to_string(value)
+                    + ": need k1 > 0, k2 >= 0, alpha_b >= 0 and u0 > 0, all finite");
+        }
+        if (path.empty() && given)
+            throw std::invalid_argument("[basal]: the grounding scheme's parameters need dynamics.bathymetry_file");
+        if (!path.empty()) {
+            m_bathymetry = std::make_shared<const BathymetryFile>(path, m_landMask.get());
+            if (pStructure)
+                m_bathymetry->checkShape((std::size_t)pStructure->nx(), (std::size_t)pStructure->ny());
         }
     }
     if (loopbackWorld != 0 && loopbackWorld < 3)
@@ -397,6 +429,12 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
             std::printf("dynamics land mask: %zu of %zu elements are land (%s)\n", m_landMask->landElements(), (std::size_t)nxf * nyf,
                 m_landMask->path().c_str());
     }
+    if (m_bathymetry) {
+        m_bathymetry->checkShape((std::size_t)nyf, (std::size_t)nxf);
+        if (m_rank == 0)
+            std::printf("dynamics bathymetry: the shallowest ocean element has %g m of water; k1 = %g, k2 = %g N m^-3, alpha_b = %g, u0 = %g m/s (%s)\n",
+                m_bathymetry->shallowest(), m_basal.k1, m_basal.k2, m_basal.alpha_b, m_basal.u0, m_bathymetry->path().c_str());
+    }
     for (std::size_t k = 0; k < m_tracers.size(); ++k)
         if (!m_tracerInit[k].empty() && m_tracerInit[k].size() != (std::size_t)nxf * nyf)
             throw std::invalid_argument("dynamics.tracer_init: the array of \"" + m_tracers[k] + "\" does not have the shape (rectgrid.nx, rectgrid.ny) of the structure's planes");
@@ -430,6 +468,8 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
         // ---- land mask, upload
         if (m_landMask)
             b.setLandMask(*m_landMask);
+        if (m_bathymetry)
+            b.setBathymetry(*m_bathymetry, m_basal);
         b.upload(f, thermo, b.index == 0 && m_rank == 0);
         b.uploadTracers(f, m_tracers, m_tracerInit, b.index == 0 && m_rank == 0);
         // ---- forcing: the analytic box test, evaluated on the device (ocean once, wind at the current model time every step); a forcing

@@ -299,6 +299,7 @@ class DynamicsCore:
     TRANSPORTED = ("H", "A")
 
     LAND_OPS = ("set_land_mask", "land_clear", "land_clear_nodes")
+    BASAL_OPS = ("set_basal_depth", "set_basal_params", "basal_critical")
     BBM_OPS = ("bbm_prepare", "bbm_iterate")
     BBM_NATIVE_OPS = ("rb_bbm", "rb_transport")
     DAMAGE_BOUNDS = (0.0, 1.0, False)  # the damage D of the brittle rheology: in [0, 1], no cap of the cell mean
@@ -315,7 +316,7 @@ class DynamicsCore:
     def __init__(self, ops, blk, hx, hy, dt, nsub, device, exchanger=None, overlap=True, native=False, use_graph=False, closure=True,
                  phase_timing=False, land=None, rheology="mevp", bbm=None, history=None, series=None, series_capacity=1024, extent_conc=0.15,
                  drifters=None, drifter_min_conc=0.15, drifter_fields=None, stations=None, station_fields=None, station_capacity=256,
-                 tracers=None, min_conc=1e-12, min_thick=0.01):
+                 tracers=None, min_conc=1e-12, min_thick=0.01, bathymetry=None, basal=None):
         self.ops, self.blk, self.hx, self.hy, self.dt, self.nsub, self.overlap = ops, blk, hx, hy, dt, nsub, overlap
         # closure: cap + scaling limiter at the end of every transport step (the ice-free-node rule is a parameter of the
         # sub-cycle, on by default).  False: the bare scheme of rounds 1-4 (frozen fixtures of that scheme)
@@ -343,6 +344,25 @@ class DynamicsCore:
             if land.shape != (blk.ny_glob, blk.nx):
                 raise ValueError("land must be a [ny_global, nx] = [%d, %d] array, got shape %s" % (blk.ny_glob, blk.nx, land.shape))
             self.land = torch.from_numpy(np.ascontiguousarray(land[blk.elem_slice()] != 0).astype(np.uint8)).to(device)
+        # bathymetry: float64 [ny_global, nx] water depth in metres of the WHOLE domain (include/nsdg_basal.h): ice
+        # whose keels reach the seabed feels a basal stress and can stay fast over a shoal.  Like the mask: this rank keeps its rows, ghost
+        # rows included, nothing is exchanged, and they go to the ops object with the grid.  basal: an abi.BasalParams (None: whatever
+        # the ops object holds, the published defaults on a new context)
+        self.depth, self._basal_params, self._depth_on_ops = None, basal, False
+        if bathymetry is not None:
+            outputs.require_ops(ops, self.BASAL_OPS, "bathymetry=", "landfast-ice calls")
+            depth = np.asarray(bathymetry, dtype=np.float64)
+            if depth.shape != (blk.ny_glob, blk.nx):
+                raise ValueError("bathymetry must be a [ny_global, nx] = [%d, %d] array, got shape %s" % (blk.ny_glob, blk.nx, depth.shape))
+            ocean = np.ones(depth.shape, dtype=bool) if land is None else np.asarray(land) == 0
+            bad = ocean & ~(np.isfinite(depth) & (depth >= 0.0))
+            if bad.any():
+                iy, ix = (int(k) for k in np.argwhere(bad)[0])
+                raise ValueError("bathymetry must be finite and >= 0 at ocean elements: %r at (row %d, column %d)" % (float(depth[iy, ix]), iy, ix))
+            depth = np.where(ocean, depth, 0.0)  # land elements are stored as 0
+            self.depth = torch.from_numpy(np.ascontiguousarray(depth[blk.elem_slice()])).to(device)
+        elif basal is not None:
+            raise ValueError("basal= parameters need bathymetry=")
         # phase_timing: step() brackets its parts with the library's phase marks (include/nsdg.h "per-phase device timing": one event per
         # mark on the ops' stream, read by phase_times()); off, nothing is asked of `ops` beyond the kernels
         self._phase_timing, self._phase_open = bool(phase_timing), PHASE_END
@@ -564,6 +584,22 @@ class DynamicsCore:
         if self._land_on_ops:  # set with the grid (_set_grid)
             self.ops.set_land_mask(None)
         self.land, self._land_on_ops = None, False
+        if self._depth_on_ops:
+            self.ops.set_basal_depth(None)
+        self.depth, self._depth_on_ops = None, False
+
+    def basal_read(self):
+        """the critical stress T_b [N m^-2] of the grounding scheme at the node rows this rank owns, from the current H and A: what the
+        next coefficient packing stores (nsdg_basal_critical)"""
+        if self.depth is None:
+            raise ValueError("basal_read() needs a core constructed with bathymetry=")
+        self._set_grid()
+        nodal = (2 * self.blk.ny + 1, 2 * self.blk.nx + 1)
+        cgh, cga, tb = (torch.zeros(*nodal, dtype=torch.float64, device=self.H.device) for _ in range(3))
+        self.ops.dg_to_cg(self.H, cgh)
+        self.ops.dg_to_cg(self.A, cga)
+        self.ops.basal_critical(cgh, cga, tb)
+        return self.owned(tb)
 
     def load_global(self, H, A, uo, vo, ua, va, u=None, v=None, D=None):
         """fill the local arrays (ghost rows included) from global numpy arrays; D: the damage of rheology="bbm" (None: left as it is)"""
@@ -598,6 +634,11 @@ class DynamicsCore:
         if self.land is not None:
             self.ops.set_land_mask(self.land)
             self._land_on_ops = True
+        if self.depth is not None:
+            if self._basal_params is not None:
+                self.ops.set_basal_params(self._basal_params)
+            self.ops.set_basal_depth(self.depth)
+            self._depth_on_ops = True
         place = getattr(self.ops, "set_block", None)
         if place is not None:  # where the local array sits in the global domain (device-side forcing providers)
             place(self.blk.lo, self.blk.ny_glob)

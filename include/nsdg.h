@@ -589,6 +589,12 @@ int nsdg_land_clear_nodes(nsdg_ctx* ctx, double* u, double* v);
  * The parameters, the depth array, the diagnostic T_b and their checks are declared in nsdg_basal.h, which this header includes. */
 #include "nsdg_basal.h"
 
+/* ---- slab ocean: the mixed layer's heat and salt follow the ice (csrc/column_step.hip) ------------------------
+ * The column step above leaves sst and sss as it found them.  Its fused twin advances them by the ice-ocean and open-water fluxes and
+ * by the fresh water and salt the pack takes up and releases, with an optional relaxation towards external values.  The call, its
+ * parameters, its arithmetic and its checks are declared in nsdg_ocean.h, which this header includes. */
+#include "nsdg_ocean.h"
+
 /* ---- brittle rheology: the brittle Bingham-Maxwell (BBM) sub-cycle (csrc/bbm.hip, csrc/bbm_common.h) ------------
  * A second rheology beside mEVP: damage, a Mohr-Coulomb envelope, Maxwell relaxation.  No counterpart in the reference snapshot; built from
  * the published formulation (Olason et al. 2022, "A new brittle rheology and numerical framework for large-scale sea-ice models", JAMES;

@@ -46,6 +46,11 @@ class BasalParams(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("k1", "k2", "alpha_b", "u0")]
 
 
+class SlabParams(C.Structure):
+    """nsdg_slab_params: the slab ocean of nsdg_column_step_ocean (include/nsdg_ocean.h)"""
+    _fields_ = [(n, C.c_double) for n in ("relax_t", "relax_s", "ice_salinity")] + [("reserved", C.c_int32 * 2)]
+
+
 SUBCYCLE_ADAPTIVE, SUBCYCLE_KEEP_ALPHA, SUBCYCLE_KEEP_DELTA_MIN, SUBCYCLE_ADAPTIVE_CONVERGED = 0, 1, 2, 3  # modes of nsdg_mevp_stable_params
 
 
@@ -260,6 +265,13 @@ BASAL_SYMBOLS = {
     "nsdg_basal_critical": (C.c_int, [VP, VP, VP, VP]),
 }
 
+# the functions of include/nsdg_ocean.h (the "slab ocean" section, a header of its own that nsdg.h includes), bound like SYMBOLS
+OCEAN_SYMBOLS = {
+    "nsdg_slab_default_params": (None, [C.POINTER(SlabParams)]),
+    "nsdg_slab_params_set": (C.c_int, [VP, C.POINTER(SlabParams)]),
+    "nsdg_column_step_ocean": (C.c_int, [VP, I64, D] + [VP] * 18),
+}
+
 _lib = None
 
 
@@ -277,7 +289,7 @@ def load_library(path=LIB_PATH):
         raise NsdgError("HIP library %s is missing: build it with `python -m nextsimdg_amd.build` "
                         "(there is no CPU fallback)" % path)
     lib = C.CDLL(path)
-    for name, (res, args) in list(SYMBOLS.items()) + list(TRACER_SYMBOLS.items()) + list(BASAL_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(TRACER_SYMBOLS.items()) + list(BASAL_SYMBOLS.items()) + list(OCEAN_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -335,6 +347,17 @@ def basal_default_params(**kw):
     for k, v in kw.items():
         if not hasattr(p, k):
             raise NsdgError("unknown basal parameter " + k)
+        setattr(p, k, v)
+    return p
+
+
+def slab_default_params(**kw):
+    """nsdg_slab_default_params with members replaced by keyword (host only)"""
+    p = SlabParams()
+    load_library().nsdg_slab_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k == "reserved" or not hasattr(p, k):
+            raise NsdgError("unknown slab-ocean parameter " + k)
         setattr(p, k, v)
     return p
 
@@ -755,6 +778,30 @@ class Context:
         if diag is not None and diag.numel() != NDIAG * n:
             raise NsdgError("column_step: diag has %d elements, expected NDIAG * n = %d" % (diag.numel(), NDIAG * n))
         self._call(self.lib.nsdg_column_step(self.h, n, float(dt), *[_ptr(t) for t in ts], _ptr(diag)))
+
+    # ---- slab ocean (include/nsdg_ocean.h): the column step that also advances the mixed layer's sst and sss
+    def slab_default_params(self, **kw):
+        return slab_default_params(**kw)
+
+    def set_slab_params(self, p):
+        """nsdg_slab_params_set: acts on the next column_step_ocean"""
+        self._call(self.lib.nsdg_slab_params_set(self.h, C.byref(p)))
+
+    def column_step_ocean(self, dt, state, forcing, newice, ext=None, skip=None):
+        """nsdg_column_step_ocean: column_step that writes forcing["sst"], forcing["sss"] too.  ext: {"sst": , "sss": } relaxation targets
+        (read only under their relaxation time; either may be absent otherwise); skip: a uint8 tensor of n bytes or None"""
+        import torch
+
+        ts = [state[k] for k in STATE] + [forcing[k] for k in FORCING] + [newice]
+        ex = [(ext or {}).get(k) for k in ("sst", "sss")]
+        _check_f64(*ts, *ex)
+        n = ts[0].numel()
+        for name, t in zip(STATE + FORCING + ["newice", "sst_ext", "sss_ext"], ts + ex):
+            if t is not None and t.numel() != n:
+                raise NsdgError("column_step_ocean: %s has %d elements, hice has %d" % (name, t.numel(), n))
+        if skip is not None and (skip.dtype != torch.uint8 or not skip.is_contiguous() or not skip.is_cuda or skip.numel() != n):
+            raise NsdgError("column_step_ocean: skip must be a contiguous uint8 CUDA tensor of %d bytes" % n)
+        self._call(self.lib.nsdg_column_step_ocean(self.h, n, float(dt), *[_ptr(t) for t in ts], _ptr(ex[0]), _ptr(ex[1]), _ptr(skip)))
 
     # ---- dynamics
     def mevp_default_params(self, **kw):

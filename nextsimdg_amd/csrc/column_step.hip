@@ -132,10 +132,16 @@ struct ColumnIn {
 struct ColumnOut {
     double hice, cice, hsnow, tice0, newice;
 };
+// what the slab ocean (below) takes from the element: the FINAL fluxes, as the diagnostic planes hold them, and the evaporation
+struct ColumnFlux {
+    double Qio, Qow, subl, evap;
+};
 
-// The column physics of ONE element (everything DevStep::iterate does to it), on register values.
-template <bool DIAG>
-__device__ __forceinline__ ColumnOut column_element(const nsdg_column_params& P, double dt, const ColumnIn& in, double* d /* NSDG_NDIAG or unused */)
+// The column physics of ONE element (everything DevStep::iterate does to it), on register values.  FLUX: the final fluxes go to *fx
+// (registers once inlined); without it fx is not looked at and the instantiation is the code it was.
+template <bool DIAG, bool FLUX = false>
+__device__ __forceinline__ ColumnOut column_element(const nsdg_column_params& P, double dt, const ColumnIn& in, double* d /* NSDG_NDIAG or unused */,
+    ColumnFlux* fx = nullptr)
 {
     const double thick = in.thick, conc = in.conc, snow = in.snow, tice = in.tice;
     const double sst = in.sst, sss = in.sss, tair = in.tair, tdew = in.tdew, slp = in.slp;
@@ -293,6 +299,12 @@ __device__ __forceinline__ ColumnOut column_element(const nsdg_column_params& P,
         d[NSDG_D_HIFROMS] = hifroms;
         d[NSDG_D_QOW] = Qow;
     }
+    if (FLUX) {
+        fx->Qio = Qio;
+        fx->Qow = Qow;
+        fx->subl = subl;
+        fx->evap = evap;
+    }
     // ---- PrognosticData::updateAndIntegrate (core/src/PrognosticData.cpp:63-71; PhysicsData.hpp:61,66)
     return ColumnOut { hi * c_new, c_new, hs * c_new, Tnew, newice };
 }
@@ -379,6 +391,134 @@ __global__ __launch_bounds__(256, NSDG_COL_WAVES) void column_step_kernel_x2(nsd
     col_store(newice_ + i, ox.newice, oy.newice);
 }
 
+// ---- slab ocean (include/nsdg_ocean.h): the column step and the mixed layer's heat and salt in one launch ----------
+// The launch's constants: g_T = dt / relax_t and g_S = dt / relax_s are formed on the host (one IEEE division each), 0 = no relaxation.
+struct SlabArgs {
+    double g_t, g_s, s_ice;
+    int relax_t, relax_s;
+};
+struct SlabOut {
+    double sst, sss;
+};
+
+// The slab update of ONE element on register values: the sequence of nsdg_ocean.h, one IEEE operation per statement.  -ffp-contract=on
+// fuses inside one expression only, so nothing below is contracted; the divisions are plain (mld, M + W free: what IEEE gives).
+__device__ __forceinline__ SlabOut slab_element(const SlabArgs& K, double dt, const ColumnIn& in, const ColumnOut& o, const ColumnFlux& fx, double t_ext,
+    double s_ext)
+{
+    const double c = in.conc, T = in.sst, S = in.sss;
+    // heat
+    const double m1 = in.mld * WATER_RHOOCEAN;
+    const double mlbhc = m1 * WATER_CP;
+    const double oc = 1.0 - c;
+    const double a = c * fx.Qio;
+    const double b = oc * fx.Qow;
+    const double qnet = a + b;
+    const double e = qnet * dt;
+    const double q = e / mlbhc;
+    double T1 = T - q;
+    if (K.relax_t) {
+        const double d = t_ext - T;
+        const double r = K.g_t * d;
+        T1 = T1 + r;
+    }
+    // salt
+    const double dh = o.hice - in.thick;
+    const double dMi = ICE_RHO * dh;
+    const double ds = o.hsnow - in.snow;
+    const double dMs = ICE_RHOSNOW * ds;
+    const double f = c * fx.subl;
+    const double g = oc * fx.evap;
+    const double v = f + g;
+    const double p = in.snowfall - v;
+    double w = p * dt;
+    w = w - dMi;
+    const double W = w - dMs;
+    const double M = WATER_RHOOCEAN * in.mld;
+    const double x = M * S;
+    const double y = K.s_ice * dMi;
+    const double z = x - y;
+    const double D = M + W;
+    double S1 = z / D;
+    if (K.relax_s) {
+        const double d = s_ext - S;
+        const double r = K.g_s * d;
+        S1 = S1 + r;
+    }
+    return SlabOut { T1, S1 };
+}
+
+// Scalar twin (one element per lane): the odd tail element, and everything when a plane is not aligned for the pair kernel.
+__global__ __launch_bounds__(256) void column_step_ocean_kernel(nsdg_column_params P, SlabArgs K, long first, long n, double dt,
+    double* __restrict__ hice, double* __restrict__ cice, double* __restrict__ hsnow, double* __restrict__ tice0, double* __restrict__ sst_,
+    double* __restrict__ sss_, const double* __restrict__ tair_, const double* __restrict__ tdew_, const double* __restrict__ slp_,
+    const double* __restrict__ qsw_, const double* __restrict__ qlw_, const double* __restrict__ mld_, const double* __restrict__ snowfall_,
+    const double* __restrict__ wind_, double* __restrict__ newice_, const double* __restrict__ sst_ext, const double* __restrict__ sss_ext,
+    const uint8_t* __restrict__ skip)
+{
+    const long e = first + (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n)
+        return;
+    const ColumnIn in = { hice[e], cice[e], hsnow[e], tice0[e], sst_[e], sss_[e], tair_[e], tdew_[e], slp_[e], qsw_[e], qlw_[e], mld_[e],
+        snowfall_[e], wind_[e], newice_[e] };
+    const double t_ext = K.relax_t ? sst_ext[e] : 0.0, s_ext = K.relax_s ? sss_ext[e] : 0.0;
+    const bool keep = skip != nullptr && skip[e] != 0;
+    ColumnFlux fx;
+    const ColumnOut o = column_element<false, true>(P, dt, in, nullptr, &fx);
+    const SlabOut s = slab_element(K, dt, in, o, fx, t_ext, s_ext);
+    hice[e] = o.hice;
+    cice[e] = o.cice;
+    hsnow[e] = o.hsnow;
+    tice0[e] = o.tice0;
+    newice_[e] = o.newice;
+    sst_[e] = keep ? in.sst : s.sst;
+    sss_[e] = keep ? in.sss : s.sss;
+}
+
+// Production kernel, the shape of column_step_kernel_x2: two adjacent elements per lane, every plane access a 16-byte streaming load or
+// store; sst and sss are loaded once and stored once; the targets are loaded only under their relaxation (wave-uniform), the mask as ONE
+// 2-byte load per lane.  15 (+2) loads and 7 stores per element pair against 15 and 5.
+__global__ __launch_bounds__(256, NSDG_COL_WAVES) void column_step_ocean_kernel_x2(nsdg_column_params P, SlabArgs K, long npairs, double dt,
+    double2* __restrict__ hice, double2* __restrict__ cice, double2* __restrict__ hsnow, double2* __restrict__ tice0, double2* __restrict__ sst_,
+    double2* __restrict__ sss_, const double2* __restrict__ tair_, const double2* __restrict__ tdew_, const double2* __restrict__ slp_,
+    const double2* __restrict__ qsw_, const double2* __restrict__ qlw_, const double2* __restrict__ mld_, const double2* __restrict__ snowfall_,
+    const double2* __restrict__ wind_, double2* __restrict__ newice_, const double2* __restrict__ sst_ext, const double2* __restrict__ sss_ext,
+    const uint16_t* __restrict__ skip)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npairs)
+        return;
+    const double2 a0 = col_load(hice + i), a1 = col_load(cice + i), a2 = col_load(hsnow + i), a3 = col_load(tice0 + i), a4 = col_load(sst_ + i),
+                  a5 = col_load(sss_ + i), a6 = col_load(tair_ + i), a7 = col_load(tdew_ + i), a8 = col_load(slp_ + i), a9 = col_load(qsw_ + i),
+                  a10 = col_load(qlw_ + i), a11 = col_load(mld_ + i), a12 = col_load(snowfall_ + i), a13 = col_load(wind_ + i),
+                  a14 = col_load(newice_ + i);
+    const double2 te = K.relax_t ? col_load(sst_ext + i) : make_double2(0.0, 0.0);
+    const double2 se = K.relax_s ? col_load(sss_ext + i) : make_double2(0.0, 0.0);
+    const unsigned m = skip != nullptr ? (unsigned)__builtin_nontemporal_load(skip + i) : 0u; // little endian: the low byte is element 2 i
+    const ColumnIn inx = { a0.x, a1.x, a2.x, a3.x, a4.x, a5.x, a6.x, a7.x, a8.x, a9.x, a10.x, a11.x, a12.x, a13.x, a14.x };
+    const ColumnIn iny = { a0.y, a1.y, a2.y, a3.y, a4.y, a5.y, a6.y, a7.y, a8.y, a9.y, a10.y, a11.y, a12.y, a13.y, a14.y };
+    ColumnFlux fx, fy;
+    const ColumnOut ox = column_element<false, true>(P, dt, inx, nullptr, &fx);
+    const ColumnOut oy = column_element<false, true>(P, dt, iny, nullptr, &fy);
+    const SlabOut sx = slab_element(K, dt, inx, ox, fx, te.x, se.x);
+    const SlabOut sy = slab_element(K, dt, iny, oy, fy, te.y, se.y);
+    const bool kx = (m & 0xffu) != 0, ky = (m & 0xff00u) != 0;
+    col_store(hice + i, ox.hice, oy.hice);
+    col_store(cice + i, ox.cice, oy.cice);
+    col_store(hsnow + i, ox.hsnow, oy.hsnow);
+    col_store(tice0 + i, ox.tice0, oy.tice0);
+    col_store(newice_ + i, ox.newice, oy.newice);
+    col_store(sst_ + i, kx ? a4.x : sx.sst, ky ? a4.y : sy.sst);
+    col_store(sss_ + i, kx ? a5.x : sx.sss, ky ? a5.y : sy.sss);
+}
+
+// [p, p + bytes) and [q, q + qbytes) share a byte
+inline bool slab_overlap(const void* p, size_t bytes, const void* q, size_t qbytes)
+{
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a < b + qbytes && b < a + bytes;
+}
+
 } // namespace
 
 extern "C" int nsdg_column_step(nsdg_ctx* ctx, int64_t n, double dt, double* hice, double* cice, double* hsnow,
@@ -416,6 +556,82 @@ extern "C" int nsdg_column_step(nsdg_ctx* ctx, int64_t n, double dt, double* hic
             hipLaunchKernelGGL(column_step_kernel<false>, dim3(nsdg_div_up(n - done, 256)), block, 0, ctx->stream, ctx->column, done, (long)n,
                 (long)n, dt, hice, cice, hsnow, tice0, sst, sss, tair, tdew, slp, qsw, qlw, mld, snowfall, wind, newice, diag);
     }
+    NSDG_CHECK_LAUNCH();
+    return NSDG_OK;
+}
+
+// ---- slab ocean (include/nsdg_ocean.h) ----------------------------------------------------------------------------------------------------
+extern "C" void nsdg_slab_default_params(nsdg_slab_params* p)
+{
+    if (!p)
+        return;
+    p->relax_t = p->relax_s = 0.0;
+    p->ice_salinity = ICE_S;
+    p->reserved[0] = p->reserved[1] = 0;
+}
+
+extern "C" int nsdg_slab_params_set(nsdg_ctx* ctx, const nsdg_slab_params* p)
+{
+    NSDG_CHECK_ARG(ctx != nullptr, "null context");
+    NSDG_CHECK_ARG(p != nullptr, "null parameters");
+    NSDG_CHECK_ARG(std::isfinite(p->relax_t) && p->relax_t >= 0, "relax_t must be finite and >= 0 (0 = no relaxation)");
+    NSDG_CHECK_ARG(std::isfinite(p->relax_s) && p->relax_s >= 0, "relax_s must be finite and >= 0 (0 = no relaxation)");
+    NSDG_CHECK_ARG(std::isfinite(p->ice_salinity) && p->ice_salinity >= 0, "ice_salinity must be finite and >= 0");
+    ctx->slab = *p;
+    return NSDG_OK;
+}
+
+extern "C" int nsdg_column_step_ocean(nsdg_ctx* ctx, int64_t n, double dt, double* hice, double* cice, double* hsnow, double* tice0,
+    double* sst, double* sss, const double* tair, const double* tdew, const double* slp, const double* qsw, const double* qlw,
+    const double* mld, const double* snowfall, const double* wind, double* newice, const double* sst_ext, const double* sss_ext,
+    const uint8_t* skip)
+{
+    NSDG_CHECK_ARG(ctx != nullptr, "null context");
+    NSDG_CHECK_ARG(n >= 0, "negative element count");
+    if (n == 0)
+        return NSDG_OK;
+    NSDG_CHECK_ARG(hice && cice && hsnow && tice0 && sst && sss && tair && tdew && slp && qsw && qlw && mld && snowfall && wind && newice,
+        "null field pointer");
+    NSDG_CHECK_ARG(n < (1LL << 31) * 256, "element count too large for one launch");
+    const bool relax_t = ctx->slab.relax_t > 0, relax_s = ctx->slab.relax_s > 0;
+    NSDG_CHECK_ARG(!relax_t || sst_ext, "null sst_ext while relax_t > 0");
+    NSDG_CHECK_ARG(!relax_s || sss_ext, "null sss_ext while relax_s > 0");
+    // sst and sss are written: neither may share a byte with the other or with any other plane the launch reads or writes
+    const double* planes[15] = { hice, cice, hsnow, tice0, sst, sss, tair, tdew, slp, qsw, qlw, mld, snowfall, wind, newice };
+    const size_t bytes = (size_t)n * sizeof(double);
+    for (int k = 4; k <= 5; ++k) { // planes[4] = sst, planes[5] = sss
+        const double* w = planes[k];
+        for (int j = 0; j < 15; ++j)
+            NSDG_CHECK_ARG(j == k || !slab_overlap(w, bytes, planes[j], bytes), "sst / sss overlap another plane");
+        NSDG_CHECK_ARG(!(relax_t && slab_overlap(w, bytes, sst_ext, bytes)) && !(relax_s && slab_overlap(w, bytes, sss_ext, bytes)),
+            "sst / sss overlap a relaxation target");
+        NSDG_CHECK_ARG(!(skip && slab_overlap(w, bytes, skip, (size_t)n)), "sst / sss overlap the skip mask");
+    }
+    NSDG_CHECK_HIP(hipSetDevice(ctx->device));
+    SlabArgs K;
+    K.relax_t = relax_t, K.relax_s = relax_s;
+    K.g_t = relax_t ? dt / ctx->slab.relax_t : 0.0;
+    K.g_s = relax_s ? dt / ctx->slab.relax_s : 0.0;
+    K.s_ice = ctx->slab.ice_salinity;
+    if (!relax_t)
+        sst_ext = nullptr;
+    if (!relax_s)
+        sss_ext = nullptr;
+    // 16-byte path for the even part when every plane is 16-byte aligned (the mask: 2-byte), the scalar twin for the rest
+    bool aligned = (((uintptr_t)sst_ext | (uintptr_t)sss_ext) & 15) == 0 && ((uintptr_t)skip & 1) == 0;
+    for (const double* p : planes)
+        aligned = aligned && (((uintptr_t)p & 15) == 0);
+    const dim3 block(256);
+    const long npairs = aligned ? n / 2 : 0;
+    if (npairs > 0)
+        hipLaunchKernelGGL(column_step_ocean_kernel_x2, dim3(nsdg_div_up(npairs, 256)), block, 0, ctx->stream, ctx->column, K, npairs, dt,
+            (double2*)hice, (double2*)cice, (double2*)hsnow, (double2*)tice0, (double2*)sst, (double2*)sss, (const double2*)tair,
+            (const double2*)tdew, (const double2*)slp, (const double2*)qsw, (const double2*)qlw, (const double2*)mld, (const double2*)snowfall,
+            (const double2*)wind, (double2*)newice, (const double2*)sst_ext, (const double2*)sss_ext, (const uint16_t*)skip);
+    const long done = 2 * npairs;
+    if (done < n)
+        hipLaunchKernelGGL(column_step_ocean_kernel, dim3(nsdg_div_up(n - done, 256)), block, 0, ctx->stream, ctx->column, K, done, (long)n, dt,
+            hice, cice, hsnow, tice0, sst, sss, tair, tdew, slp, qsw, qlw, mld, snowfall, wind, newice, sst_ext, sss_ext, skip);
     NSDG_CHECK_LAUNCH();
     return NSDG_OK;
 }

@@ -136,6 +136,7 @@ int nsdg_ctx_create(int device_id, void* stream, nsdg_ctx** out)
     c->device = device_id;
     c->stream = (hipStream_t)stream;
     nsdg_column_default_params(&c->column);
+    nsdg_slab_default_params(&c->slab);
     nsdg_mevp_default_params(&c->mevp);
     nsdg_bbm_default_params(&c->bbm);
     c->nx = c->ny = 0;

@@ -17,6 +17,7 @@ struct nsdg_ctx {
     int device;
     hipStream_t stream;
     nsdg_column_params column;
+    nsdg_slab_params slab; // slab ocean (column_step.hip, nsdg_column_step_ocean): relaxation times and the salinity of the ice
     nsdg_mevp_params mevp;
     nsdg_bbm_params bbm; // brittle rheology (bbm.hip)
     int nx, ny; // local element array

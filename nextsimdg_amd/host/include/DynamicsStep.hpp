@@ -95,6 +95,12 @@
 //                            tracer at zero.  Not given (default): nothing changes
 //     dynamics.tracer_init   their initial values, one entry per name: a float64 .npy array of the shape (rectgrid.nx, rectgrid.ny) of the
 //                            structure's planes, or - for zeros; a restart file with the state of the dynamics takes precedence
+//     dynamics.slab_ocean    false (default: nothing changes) | true -- the mixed layer's sst and sss are prognostic (include/nsdg_ocean.h,
+//                            DESIGN.md section 3.11): the column step is nsdg_column_step_ocean, with the block's land bytes as its skip
+//                            mask; the restart file's sst, sss datasets then hold the evolved ocean.  Needs dynamics.thermodynamics = true
+//     [slabocean] relax_t, relax_s, ice_salinity   the members of nsdg_slab_params (defaults: nsdg_slab_default_params), by the rule of
+//                            nsdg_slab_params_set; refused without dynamics.slab_ocean.  The relaxation targets are the forcing file's
+//                            optional pair sst, sss sampled on the device, or, without it, the initial sst, sss
 //     dynamics.row_blocks, dynamics.devices, dynamics.passes_per_exchange (2), dynamics.overlap (true),
 //     dynamics.graph (false), dynamics.loopback_world (0: off; N: rehearse an interior block of N on one GPU with
 //     real RCCL send/recv to the rank itself -- values wrap around, for timing and call-path checks only)
@@ -103,6 +109,7 @@
 // provider nsdg_boxtest_forcing (the wind is re-evaluated at every step's model time), or from a forcing file's pairs.
 #pragma once
 #include "../../../include/nsdg_basal.h"
+#include "../../../include/nsdg_ocean.h"
 #include <algorithm>
 #include <memory>
 #include <string>
@@ -154,11 +161,11 @@ public:
     //! rows [r0, r1) of block `rank` of `world` (the same split as nextsimdg_amd/rowblock.py split_rows)
     static void splitRows(int ny, int world, int rank, int& r0, int& r1);
 
-    //! rows [r0, r1) (nx values each) of every prognostic plane a run changes (hice, cice; with thermodynamics hsnow, tice, newice) and of the
-    //! state of the dynamics, one after the other -- what a rank sends for the restart file ...
-    static std::vector<double> packRows(FieldStore& f, bool thermodynamics, int nx, int r0, int r1);
+    //! rows [r0, r1) (nx values each) of every prognostic plane a run changes (hice, cice; with thermodynamics hsnow, tice, newice; with a
+    //! slab ocean sst, sss after them) and of the state of the dynamics, one after the other -- what a rank sends for the restart file ...
+    static std::vector<double> packRows(FieldStore& f, bool thermodynamics, int nx, int r0, int r1, bool slabOcean = false);
     //! ... and how rank 0 puts it into its structure; throws std::runtime_error when the size is not that of the rows
-    static void placeRows(FieldStore& f, bool thermodynamics, int nx, int r0, int r1, const double* data, std::size_t count);
+    static void placeRows(FieldStore& f, bool thermodynamics, int nx, int r0, int r1, const double* data, std::size_t count, bool slabOcean = false);
     //! the keys of the brittle rheology (dynamics.rheology, dynamics.bbm_courant, bbm.*): a step that does not run it refuses them
     static const std::vector<std::string>& brittleKeys();
     //! the names of dynamics.tracers from its value; throws std::invalid_argument, naming the key, for more than NSDG_TRACERS_MAX names, a
@@ -195,6 +202,8 @@ private:
     std::shared_ptr<const LandMaskFile> m_landMask; // dynamics.land_mask_file: the element mask, read and checked in configure()
     std::shared_ptr<const BathymetryFile> m_bathymetry; // dynamics.bathymetry_file: the water depth, read and checked in configure()
     nsdg_basal_params m_basal; // [basal]: the grounding scheme's parameters (used with m_bathymetry)
+    bool slabOcean = false; // dynamics.slab_ocean: sst and sss follow the ice (nsdg_column_step_ocean)
+    nsdg_slab_params m_slab; // [slabocean]: relaxation times and the salinity of the ice (used with slabOcean)
     struct Outputs; // model.output_*, series_*, drifters_*, stations_*: the four outputs, each null when off (DynamicsStep.cpp)
     std::unique_ptr<Outputs> m_out;
     struct Brittle; // dynamics.rheology = bbm: the parameters and the sub-iteration rule (DynamicsStep.cpp); null: mEVP

@@ -5,6 +5,7 @@
 //     time                                  (nt)            model seconds, the clock of model.start; strictly increasing
 //     tair tdew slp qsw qlw mld snowfall    (nt, nyr, nxr)  the column forcing planes, units of the structure's planes
 //     wind_u wind_v, ocean_u ocean_v        (nt, nyr, nxr)  optional, each pair complete or absent [m/s]
+//     sst sss                               (nt, nyr, nxr)  optional, a pair: the relaxation targets of dynamics.slab_ocean [deg C, psu]
 // All variables share one lattice: cell-centred over the model's square domain, point i at x / L = (i + 1/2) / nxr.  There are
 // no coordinate variables: lon/lat or other lattices, chunked or compressed datasets and unknown variables are refused.
 // Every check happens when the file is opened, before a device is touched; each error names the file, the variable and the
@@ -20,7 +21,7 @@ namespace Nextsim {
 class ForcingFile {
 public:
     static const std::vector<std::string>& columnVariables(); //!< tair tdew slp qsw qlw mld snowfall
-    static const std::vector<std::string>& knownVariables(); //!< the column variables, wind_u wind_v, ocean_u ocean_v
+    static const std::vector<std::string>& knownVariables(); //!< the column variables, wind_u wind_v, ocean_u ocean_v, sst sss
 
     //! Reads and checks the file; needColumn: the seven column variables must be present (dynamics.thermodynamics = true).
     //! Throws std::runtime_error naming the file.
@@ -35,6 +36,7 @@ public:
     bool hasColumn() const;
     bool hasWind() const { return has("wind_u"); }
     bool hasOcean() const { return has("ocean_u"); }
+    bool hasSlabTargets() const { return has("sst"); } //!< the pair sst, sss
     std::vector<std::string> variables() const; //!< present variables, in the order of knownVariables()
 
     //! The records around model time t: k0 = the last record with time[k0] <= t, k1 = k0 + 1, w = (t - time[k0]) / (time[k1] - time[k0]);

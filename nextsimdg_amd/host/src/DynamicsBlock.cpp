@@ -227,6 +227,25 @@ void DynamicsBlock::uploadTracers(const FieldStore& f, const std::vector<std::st
     }
 }
 
+void DynamicsBlock::setSlabOcean(const nsdg_slab_params& params)
+{
+    check(nsdg_slab_params_set(ctx.get(), &params), "nsdg_slab_params_set");
+    const int planes = (params.relax_t > 0) + (params.relax_s > 0);
+    sstExt = sssExt = nullptr;
+    if (planes == 0)
+        return;
+    const std::size_t stride = ((std::size_t)N + 1) & ~(std::size_t)1; // both planes 16-byte aligned
+    slabTargets = deviceAlloc<double>(planes * stride, "DynamicsStep: hipMalloc (slab ocean targets)");
+    double* at = slabTargets.get();
+    if (params.relax_t > 0)
+        sstExt = at, at += stride;
+    if (params.relax_s > 0)
+        sssExt = at;
+    for (const auto& pr : { std::make_pair(sstExt, col(C_SST)), std::make_pair(sssExt, col(C_SSS)) })
+        if (pr.first)
+            checkHip(hipMemcpy(pr.first, pr.second, (std::size_t)N * sizeof(double), hipMemcpyDeviceToDevice), "slab ocean targets");
+}
+
 void DynamicsBlock::allocateRecords(std::size_t count)
 {
     records = deviceAlloc<double>(count, "DynamicsStep: hipMalloc (forcing records)");
@@ -335,8 +354,12 @@ void DynamicsBlock::ownedRowsToHost(double* hostPlane, int row0, const double* d
     toHost(hostPlane + (std::size_t)(r0 - row0) * nx, devicePlane + (ghosted ? (std::size_t)j0 * nx : 0), (std::size_t)ownedRows() * nx * sizeof(double), what);
 }
 
-void DynamicsBlock::download(FieldStore& f, bool thermodynamics, bool advectColumn) const
+void DynamicsBlock::download(FieldStore& f, bool thermodynamics, bool advectColumn, bool slabOcean) const
 {
+    if (slabOcean) { // the evolved mixed layer
+        ownedRowsToHost(f.sst.data(), 0, col(C_SST), true, "download sst");
+        ownedRowsToHost(f.sss.data(), 0, col(C_SSS), true, "download sss");
+    }
     if (thermodynamics) {
         if (!advectColumn) // (otherwise f.hsnow receives the mean of S below: S is advected only under thermodynamics)
             ownedRowsToHost(f.hsnow.data(), 0, col(C_HSNOW), true, "download hsnow");

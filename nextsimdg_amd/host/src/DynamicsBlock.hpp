@@ -109,6 +109,9 @@ public:
     // order of ForcingFile::variables()), and which record each slot holds (-1: none)
     DeviceBuffer<double> records;
     long recordOf[2] = { -1, -1 };
+    // dynamics.slab_ocean: the relaxation targets of sst and sss, N doubles each, for the relaxation times that are set (null: not read)
+    DeviceBuffer<double> slabTargets;
+    double *sstExt = nullptr, *sssExt = nullptr;
     DeviceBuffer<double> arrays; // the arrays of Arr and the buffers of the advected fields: one allocation
     NsdgHandle<nsdg_rb_transport, nsdg_rb_transport_destroy> transport;
     NsdgHandle<nsdg_rb_transport, nsdg_rb_transport_destroy> tracerTransport; // dynamics.tracers: the second transport group, without bounds
@@ -143,6 +146,9 @@ public:
     //! dynamics.tracers: the local rows of every named tracer -- from the state a restart file left (FieldStore::dyn.tracers, by name), else
     //! from the plane of dynamics.tracer_init (empty: zeros).  announce: this block prints the line about a restart file without a tracer
     void uploadTracers(const FieldStore& f, const std::vector<std::string>& names, const std::vector<std::vector<double>>& init, bool announce);
+    //! dynamics.slab_ocean, after upload(): the parameters on the context, and a target plane per relaxation time that is set, filled with
+    //! the initial sst / sss of the local rows (what a forcing file's pair sst, sss replaces at every step)
+    void setSlabOcean(const nsdg_slab_params& params);
     //! dynamics.forcing = file: room for `count` doubles of records, none resident yet
     void allocateRecords(std::size_t count);
     //! no ice on land, no motion at land nodes, whatever the initial state or the restart file held there
@@ -173,7 +179,8 @@ public:
     //! that starts at global row `row0`
     void ownedRowsToHost(double* hostPlane, int row0, const double* devicePlane, bool ghosted, const char* what) const;
     //! stop(): the owned rows of the state a restart needs into the structure (the caller has drained the context)
-    void download(FieldStore& f, bool thermodynamics, bool advectColumn) const;
+    //! slabOcean: sst and sss with them
+    void download(FieldStore& f, bool thermodynamics, bool advectColumn, bool slabOcean = false) const;
     //! stop(): the owned rows of the tracers into FieldStore::dyn.tracers, under their names
     void downloadTracers(FieldStore& f, const std::vector<std::string>& names) const;
 };

@@ -39,7 +39,7 @@ const std::map<int, std::string> Configured<DynamicsStep>::keyMap = { { 0, "dyna
     { 18, "dynamics.substep_courant" }, { 19, "dynamics.max_substeps" }, { 20, "dynamics.forcing_file" },
     { 21, "dynamics.advect_column_state" }, { 22, "dynamics.land_mask_file" }, { 23, "dynamics.rheology" },
     { 24, "dynamics.bbm_courant" }, { 25, "dynamics.tracers" }, { 26, "dynamics.tracer_init" },
-    { 27, "dynamics.bathymetry_file" } };
+    { 27, "dynamics.bathymetry_file" }, { 28, "dynamics.slab_ocean" } };
 
 // dynamics.rheology = bbm
 struct DynamicsStep::Brittle {
@@ -80,6 +80,13 @@ struct BasalKey {
     const char* key;
     double nsdg_basal_params::*member;
 };
+// [slabocean]: one key per member of nsdg_slab_params (include/nsdg_ocean.h)
+struct SlabKey {
+    const char* key;
+    double nsdg_slab_params::*member;
+};
+const SlabKey SLAB_KEYS[] = { { "slabocean.relax_t", &nsdg_slab_params::relax_t }, { "slabocean.relax_s", &nsdg_slab_params::relax_s },
+    { "slabocean.ice_salinity", &nsdg_slab_params::ice_salinity } };
 const BasalKey BASAL_KEYS[] = { { "basal.k1", &nsdg_basal_params::k1 }, { "basal.k2", &nsdg_basal_params::k2 },
     { "basal.alpha_b", &nsdg_basal_params::alpha_b }, { "basal.u0", &nsdg_basal_params::u0 } };
 } // namespace
@@ -252,6 +259,23 @@ void DynamicsStep::configure()
             if (pStructure)
                 m_bathymetry->checkShape((std::size_t)pStructure->nx(), (std::size_t)pStructure->ny());
         }
+    }
+    // slab ocean (include/nsdg_ocean.h): the mode and the [slabocean] parameters -- the rule of nsdg_slab_params_set, applied here, before
+    // any device is touched
+    slabOcean = getConfiguration(keyMap.at(28), false);
+    if (slabOcean && !thermo)
+        throw std::invalid_argument("dynamics.slab_ocean needs dynamics.thermodynamics = true: the mixed layer follows the fluxes of the "
+                                    "column step, and without the column model there are none");
+    nsdg_slab_default_params(&m_slab);
+    for (const SlabKey& k : SLAB_KEYS) {
+        std::string raw;
+        if (Configurator::lookup(k.key, raw) && !slabOcean)
+            throw std::invalid_argument(std::string("[slabocean]: ") + k.key + " needs dynamics.slab_ocean = true");
+        const double value = getConfiguration(std::string(k.key), m_slab.*k.member);
+        m_slab.*k.member = value;
+        if (!std::isfinite(value) || value < 0.)
+            throw std::invalid_argument(std::string("[slabocean]: ") + k.key + " = " + std::to_string(value)
+                + ": need relax_t >= 0, relax_s >= 0 and ice_salinity >= 0, all finite");
     }
     if (loopbackWorld != 0 && loopbackWorld < 3)
         throw std::invalid_argument("dynamics.loopback_world needs an interior block: at least 3");
@@ -435,6 +459,10 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
             std::printf("dynamics bathymetry: the shallowest ocean element has %g m of water; k1 = %g, k2 = %g N m^-3, alpha_b = %g, u0 = %g m/s (%s)\n",
                 m_bathymetry->shallowest(), m_basal.k1, m_basal.k2, m_basal.alpha_b, m_basal.u0, m_bathymetry->path().c_str());
     }
+    if (slabOcean && m_rank == 0)
+        std::printf("dynamics slab ocean: relax_t = %g s, relax_s = %g s, ice_salinity = %g; relaxation targets: %s\n", m_slab.relax_t, m_slab.relax_s,
+            m_slab.ice_salinity,
+            !(m_slab.relax_t > 0 || m_slab.relax_s > 0) ? "none" : (m_forcingFile && m_forcingFile->hasSlabTargets() ? "the forcing file's sst, sss" : "the initial sst, sss"));
     for (std::size_t k = 0; k < m_tracers.size(); ++k)
         if (!m_tracerInit[k].empty() && m_tracerInit[k].size() != (std::size_t)nxf * nyf)
             throw std::invalid_argument("dynamics.tracer_init: the array of \"" + m_tracers[k] + "\" does not have the shape (rectgrid.nx, rectgrid.ny) of the structure's planes");
@@ -472,6 +500,8 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
             b.setBathymetry(*m_bathymetry, m_basal);
         b.upload(f, thermo, b.index == 0 && m_rank == 0);
         b.uploadTracers(f, m_tracers, m_tracerInit, b.index == 0 && m_rank == 0);
+        if (slabOcean) // (after the upload: the relaxation targets start as the initial sst, sss)
+            b.setSlabOcean(m_slab);
         // ---- forcing: the analytic box test, evaluated on the device (ocean once, wind at the current model time every step); a forcing
         // file's wind and ocean pairs replace it at every step
         check(nsdg_boxtest_forcing(ctx, L, m_time, b.d[UA], b.d[VA], b.d[UO], b.d[VO]), "nsdg_boxtest_forcing");
@@ -593,10 +623,16 @@ void DynamicsStep::subStep(double dt, bool last)
             if (b.ntracers > 0) // the mean thickness the column step starts from (nsdg_tracers_dilute below)
                 check(nsdg_copy_f64(ctx, b.thicknessBefore(), b.cur(FH), b.N), "nsdg_copy_f64");
             // the column physics needs no exchange: it runs on the ghost rows too, redundantly
-            check(nsdg_column_step(ctx, b.N, dt, b.cur(FH), b.cur(FA), advectColumn ? b.cur(FS) : b.col(C_HSNOW), b.col(C_TICE), b.col(C_SST), b.col(C_SSS), b.col(C_TAIR),
-                      b.col(C_TDEW), b.col(C_SLP), b.col(C_QSW), b.col(C_QLW), b.col(C_MLD), b.col(C_SNOWFALL), b.col(C_WIND), b.col(C_NEWICE),
-                      nullptr),
-                "nsdg_column_step");
+            if (slabOcean) // the fused step: sst and sss follow the fluxes; land elements (the block's land bytes) keep theirs
+                check(nsdg_column_step_ocean(ctx, b.N, dt, b.cur(FH), b.cur(FA), advectColumn ? b.cur(FS) : b.col(C_HSNOW), b.col(C_TICE), b.col(C_SST),
+                          b.col(C_SSS), b.col(C_TAIR), b.col(C_TDEW), b.col(C_SLP), b.col(C_QSW), b.col(C_QLW), b.col(C_MLD), b.col(C_SNOWFALL),
+                          b.col(C_WIND), b.col(C_NEWICE), b.sstExt, b.sssExt, b.land.get()),
+                    "nsdg_column_step_ocean");
+            else
+                check(nsdg_column_step(ctx, b.N, dt, b.cur(FH), b.cur(FA), advectColumn ? b.cur(FS) : b.col(C_HSNOW), b.col(C_TICE), b.col(C_SST), b.col(C_SSS), b.col(C_TAIR),
+                          b.col(C_TDEW), b.col(C_SLP), b.col(C_QSW), b.col(C_QLW), b.col(C_MLD), b.col(C_SNOWFALL), b.col(C_WIND), b.col(C_NEWICE),
+                          nullptr),
+                    "nsdg_column_step");
             if (b.land) {
                 // the column step computes on land elements too and its result there is discarded: the cell means of H, A (and S), the
                 // snow and the new ice (still the column phase)
@@ -739,6 +775,16 @@ void DynamicsStep::sampleForcingFile(DynamicsBlock& b, std::size_t k0, std::size
         }
         check(nsdg_forcing_sample(b.ctx.get(), NSDG_AT_ELEMENTS, ff.nxr(), ff.nyr(), 7, r0.data(), r1.data(), w, out.data()),
             "nsdg_forcing_sample (elements)");
+        // dynamics.slab_ocean: the file's pair sst, sss into the relaxation targets that exist, a launch of their own
+        r0.clear(), r1.clear(), out.clear();
+        if (slabOcean && ff.hasSlabTargets())
+            for (const auto& pr : { std::make_pair("sst", b.sstExt), std::make_pair("sss", b.sssExt) })
+                if (pr.second) {
+                    r0.push_back(rec(0, pr.first)), r1.push_back(rec(1, pr.first)), out.push_back(pr.second);
+                }
+        if (!out.empty())
+            check(nsdg_forcing_sample(b.ctx.get(), NSDG_AT_ELEMENTS, ff.nxr(), ff.nyr(), (int32_t)out.size(), r0.data(), r1.data(), w, out.data()),
+                "nsdg_forcing_sample (slab ocean targets)");
     }
 }
 
@@ -764,7 +810,7 @@ void DynamicsStep::stop(const Iterator::TimePoint&)
         check(nsdg_mevp_pipeline_health(b.ctx.get(), &gaveUp), "nsdg_mevp_pipeline_health");
         if (gaveUp)
             throw std::runtime_error("DynamicsStep: " + std::to_string(gaveUp) + " wait(s) of the mEVP pipeline gave up: the fields are not to be trusted");
-        b.download(f, thermo, advectColumn);
+        b.download(f, thermo, advectColumn, slabOcean);
         b.downloadTracers(f, m_tracers);
         // owned node rows: [2 r0, 2 r1) plus the top boundary row on the last block
         const long nn = 2L * b.nx + 1, rows = 2L * b.ownedRows() + (b.peerAbove < 0 ? 1 : 0);
@@ -823,7 +869,7 @@ void DynamicsStep::writeRestartFile(const std::string& filePath)
     FieldStore& f = pStructure->fields();
     int r0, r1;
     splitRows(nyf, m_world, m_rank, r0, r1);
-    const std::vector<double> mine = (m_rank == 0 || own) ? std::vector<double>() : packRows(f, thermo, nxf, r0, r1);
+    const std::vector<double> mine = (m_rank == 0 || own) ? std::vector<double>() : packRows(f, thermo, nxf, r0, r1, slabOcean);
     gatherToRankZero(
         env, mine.data(), mine.size() * sizeof(double),
         [&](int rank, const char* data, std::size_t bytes) {
@@ -831,7 +877,7 @@ void DynamicsStep::writeRestartFile(const std::string& filePath)
                 return; // rank 0 itself failed: the rows are received and dropped, the senders are told below
             int a, b;
             splitRows(nyf, m_world, rank, a, b);
-            placeRows(f, thermo, nxf, a, b, reinterpret_cast<const double*>(data), bytes / sizeof(double));
+            placeRows(f, thermo, nxf, a, b, reinterpret_cast<const double*>(data), bytes / sizeof(double), slabOcean);
         },
         timeout,
         [&]() {
@@ -846,11 +892,14 @@ namespace {
 // unless state < 0, of what DynamicsState owns of DYNAMICS_VARIABLES with the optional ones whose bit is set in `state` (bit i: the i-th
 // optional variable of the table) -- the rows of every element plane, and of a nodal array the node rows the block owns: [2 r0, 2 r1) and
 // the top boundary row on the last block
-template <class F> void forPayload(FieldStore& f, bool thermodynamics, int nx, int r0, int r1, int state, F&& fn)
+template <class F> void forPayload(FieldStore& f, bool thermodynamics, bool slabOcean, int nx, int r0, int r1, int state, F&& fn)
 {
     const std::size_t first = (std::size_t)r0 * nx, rows = (std::size_t)(r1 - r0) * nx, nn = 2 * (std::size_t)nx + 1;
     for (auto* p : { &f.hice, &f.cice, &f.hsnow, &f.tice, &f.newice })
         if (thermodynamics || p == &f.hice || p == &f.cice) // (the column model's planes change only with it)
+            fn(*p, first, rows);
+    if (slabOcean) // (the mixed layer changes only with dynamics.slab_ocean: every rank runs the same mode)
+        for (auto* p : { &f.sst, &f.sss })
             fn(*p, first, rows);
     if (state < 0)
         return;
@@ -870,18 +919,18 @@ template <class F> void forPayload(FieldStore& f, bool thermodynamics, int nx, i
 }
 } // namespace
 
-std::vector<double> DynamicsStep::packRows(FieldStore& f, bool thermodynamics, int nx, int r0, int r1)
+std::vector<double> DynamicsStep::packRows(FieldStore& f, bool thermodynamics, int nx, int r0, int r1, bool slabOcean)
 {
     int state = f.dyn.present ? 0 : -1, bit = 0; // the state of the dynamics travels with the rows, with the optional variables it holds
     for (const DynamicsVariable& v : DYNAMICS_VARIABLES)
         if (v.optional())
             state |= (f.dyn.present && !v.in(f).empty() ? 1 : 0) << bit++;
     std::vector<double> out;
-    forPayload(f, thermodynamics, nx, r0, r1, state, [&](std::vector<double>& a, std::size_t at, std::size_t length) { out.insert(out.end(), a.begin() + at, a.begin() + at + length); });
+    forPayload(f, thermodynamics, slabOcean, nx, r0, r1, state, [&](std::vector<double>& a, std::size_t at, std::size_t length) { out.insert(out.end(), a.begin() + at, a.begin() + at + length); });
     return out;
 }
 
-void DynamicsStep::placeRows(FieldStore& f, bool thermodynamics, int nx, int r0, int r1, const double* data, std::size_t count)
+void DynamicsStep::placeRows(FieldStore& f, bool thermodynamics, int nx, int r0, int r1, const double* data, std::size_t count, bool slabOcean)
 {
     // what a rank sent shows in the size alone: its planes, or also the state of the dynamics with one of the sets of its optional
     // variables (their sizes differ, and a run holds the snow or the damage, never both: the first set that fits is the one)
@@ -890,7 +939,7 @@ void DynamicsStep::placeRows(FieldStore& f, bool thermodynamics, int nx, int r0,
     int state = -2; // as forPayload reads it, once found
     for (int k = -1; k < (1 << optional) && state < -1; ++k) {
         std::size_t size = 0;
-        forPayload(f, thermodynamics, nx, r0, r1, k, [&](std::vector<double>&, std::size_t, std::size_t length) { size += length; });
+        forPayload(f, thermodynamics, slabOcean, nx, r0, r1, k, [&](std::vector<double>&, std::size_t, std::size_t length) { size += length; });
         if (size == count)
             state = k;
         sizes += " " + std::to_string(size);
@@ -906,7 +955,7 @@ void DynamicsStep::placeRows(FieldStore& f, bool thermodynamics, int nx, int r0,
             v.in(f).assign(v.size(f.n / nx, (std::size_t)nx), 0.);
     }
     f.dyn.present = f.dyn.present || state >= 0;
-    forPayload(f, thermodynamics, nx, r0, r1, state, [&](std::vector<double>& a, std::size_t at, std::size_t length) {
+    forPayload(f, thermodynamics, slabOcean, nx, r0, r1, state, [&](std::vector<double>& a, std::size_t at, std::size_t length) {
         std::copy(data, data + length, a.begin() + at);
         data += length;
     });

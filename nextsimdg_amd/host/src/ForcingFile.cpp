@@ -26,7 +26,7 @@ const std::vector<std::string>& ForcingFile::columnVariables()
 const std::vector<std::string>& ForcingFile::knownVariables()
 {
     static const std::vector<std::string> v = { "tair", "tdew", "slp", "qsw", "qlw", "mld", "snowfall", "wind_u", "wind_v", "ocean_u",
-        "ocean_v" };
+        "ocean_v", "sst", "sss" };
     return v;
 }
 
@@ -91,8 +91,8 @@ ForcingFile::ForcingFile(const std::string& path, bool needColumn)
         fail(e.what());
     }
     if (m_vars.empty())
-        fail("no forcing variable (known: tair tdew slp qsw qlw mld snowfall wind_u wind_v ocean_u ocean_v)");
-    for (const auto& pair : { std::make_pair("wind_u", "wind_v"), std::make_pair("ocean_u", "ocean_v") })
+        fail("no forcing variable (known: tair tdew slp qsw qlw mld snowfall wind_u wind_v ocean_u ocean_v sst sss)");
+    for (const auto& pair : { std::make_pair("wind_u", "wind_v"), std::make_pair("ocean_u", "ocean_v"), std::make_pair("sst", "sss") })
         if (has(pair.first) != has(pair.second))
             fail(std::string("variable ") + (has(pair.first) ? pair.first : pair.second) + " without " + (has(pair.first) ? pair.second : pair.first)
                 + ": the components come as a pair");

@@ -29,7 +29,7 @@ void usage()
 {
     std::cerr << "usage: make_forcing --out FILE --time TIME.npy NAME=ARRAY.npy ...\n"
                  "       make_forcing --check FILE\n"
-                 "NAME: tair tdew slp qsw qlw mld snowfall wind_u wind_v ocean_u ocean_v; TIME (nt) in model seconds, every ARRAY\n"
+                 "NAME: tair tdew slp qsw qlw mld snowfall wind_u wind_v ocean_u ocean_v sst sss; TIME (nt) in model seconds, every ARRAY\n"
                  "(nt, nyr, nxr) float64 on one cell-centred lattice over the model's square domain\n";
 }
 

@@ -1045,6 +1045,9 @@ class DynamicsCore:
                 out[k] = np.concatenate([s[k] for s in states], axis=1)
         for k in ("u", "v"):
             out[k] = np.concatenate([s[k] for s in states], axis=0)
+        for k in ("sst", "sss"):
+            if k in states[0]:  # the slab ocean of a CoupledCore with slab_ocean: [rows, nx] planes
+                out[k] = np.concatenate([s[k] for s in states], axis=0)
         if "drifters" in states[0]:  # every rank holds the whole list
             assert all(np.array_equal(s["drifters"], states[0]["drifters"]) for s in states), "the ranks' drifter lists differ"
             out["drifters"] = states[0]["drifters"].copy()
@@ -1063,6 +1066,7 @@ class ForcingSeries:
     COLUMN = ("tair", "tdew", "slp", "qsw", "qlw", "mld", "snowfall")
     WIND = ("wind_u", "wind_v")
     OCEAN = ("ocean_u", "ocean_v")
+    SLAB = ("sst", "sss")  # the relaxation targets of a slab ocean (CoupledCore(slab_ocean=True)), a pair
 
     def __init__(self, times, fields):
         t = np.array(times, dtype=np.float64)
@@ -1072,7 +1076,7 @@ class ForcingSeries:
             raise ValueError("times must be finite and strictly increasing")
         if not fields:
             raise ValueError("a forcing series needs at least one field")
-        known = self.COLUMN + self.WIND + self.OCEAN
+        known = self.COLUMN + self.WIND + self.OCEAN + self.SLAB
         out = {}
         for name, a in fields.items():
             if name not in known:
@@ -1087,7 +1091,7 @@ class ForcingSeries:
         shapes = {a.shape for a in out.values()}
         if len(shapes) != 1:
             raise ValueError("all forcing fields must be on one lattice, got shapes %s" % sorted(shapes))
-        for pair in (self.WIND, self.OCEAN):
+        for pair in (self.WIND, self.OCEAN, self.SLAB):
             if (pair[0] in out) != (pair[1] in out):
                 raise ValueError("forcing fields %s and %s come as a pair" % pair)
         self.times, self.fields = t, out
@@ -1121,15 +1125,24 @@ class CoupledCore(DynamicsCore):
     rule).  The transport then carries H, A, S and Q.
 
     tracers= (DynamicsCore): the column step's growth dilutes them -- plane 0 of H is copied before the column step and
-    nsdg_tracers_dilute runs after it (and its land clear): ice that grew carries the value 0."""
+    nsdg_tracers_dilute runs after it (and its land clear): ice that grew carries the value 0.
+
+    slab_ocean = True (include/nsdg_ocean.h): col["sst"] and col["sss"] are prognostic.  The column step is the
+    fused nsdg_column_step_ocean, which advances them by the fluxes it computes, on every local row (element-local: the ghost rows stay
+    equal to their owners without a message); land elements keep their sst, sss bits (`skip` = the land mask's local rows).  slab: an
+    abi.SlabParams (None: the defaults, no relaxation).  With a relaxation time col["sst_ext"] / col["sss_ext"] hold the targets:
+    load_column fills them from the keys sst_ext / sss_ext, or from sst / sss without them, and a ForcingSeries that holds the pair
+    sst, sss samples it into them at every step."""
 
     COLUMN_STATE = ("hsnow", "tice0")
     # closure of the column state transport's extra fields: snow volume S >= 0, the product Q = H T unbounded (include/nsdg.h)
     COLUMN_STATE_BOUNDS = ((0.0, float("inf"), False), (-float("inf"), float("inf"), False))
     COLUMN_FORCING = ("sst", "sss", "tair", "tdew", "slp", "qsw", "qlw", "mld", "snowfall", "wind")
     HAS_COLUMN_STATE = True
+    SLAB_OPS = ("column_step_ocean", "slab_default_params", "set_slab_params")
 
-    def __init__(self, ops, blk, hx, hy, dt, nsub, device, forcing=None, advect_column_state=False, min_conc=1e-12, min_thick=0.01, **kw):
+    def __init__(self, ops, blk, hx, hy, dt, nsub, device, forcing=None, advect_column_state=False, min_conc=1e-12, min_thick=0.01,
+                 slab_ocean=False, slab=None, **kw):
         """forcing: None = the forcing planes are whatever load_column() put there (constant in time);
         "dummy" / "winter" = regenerated on the device at every step's model time (nsdg_column_forcing) and the
         column wind speed is |u_a| of the dynamics' wind (nsdg_column_wind) -- the replacement of the reference's
@@ -1141,6 +1154,17 @@ class CoupledCore(DynamicsCore):
         self.advect_column_state = bool(advect_column_state)  # (read by _more_transported() while the base class constructs)
         if kw.get("tracers"):  # (refused before the base class changes anything on `ops`)
             outputs.require_ops(ops, ("copy_f64",), "tracers= in a coupled core", "copy call")
+        self.slab_ocean = bool(slab_ocean)
+        if slab is not None and not self.slab_ocean:
+            raise ValueError("slab= needs slab_ocean=True")
+        if self.slab_ocean:
+            outputs.require_ops(ops, self.SLAB_OPS, "slab_ocean=True", "slab-ocean calls")
+            if set(kw.get("tracers") or ()) & {"sst", "sss"}:
+                raise ValueError("a tracer name collides with the slab ocean's sst / sss")
+            for k in ("relax_t", "relax_s", "ice_salinity"):
+                v = float(getattr(slab, k)) if slab is not None else 0.0
+                if not (np.isfinite(v) and v >= 0.0):
+                    raise ValueError("slab.%s must be finite and >= 0, got %r" % (k, v))
         super().__init__(ops, blk, hx, hy, dt, nsub, device, min_conc=min_conc, min_thick=min_thick, **kw)
         z = lambda: torch.zeros(blk.ny, blk.nx, dtype=torch.float64, device=device)
         if self.tracers:
@@ -1150,6 +1174,14 @@ class CoupledCore(DynamicsCore):
             self.col["hsnow"] = self.S[0]
         self.newice = z()
         self.forcing, self.time = forcing, 0.0
+        self._slab_ext = None
+        if self.slab_ocean:
+            self._slab = slab if slab is not None else ops.slab_default_params()
+            # the relaxation targets exist only under a relaxation time
+            for k, on in (("sst", self._slab.relax_t > 0), ("sss", self._slab.relax_s > 0)):
+                if on:
+                    self.col[k + "_ext"] = z()
+            self._slab_ext = {k: self.col.get(k + "_ext") for k in ("sst", "sss")}
         if isinstance(forcing, ForcingSeries):
             missing = [k for k in ForcingSeries.COLUMN if k not in forcing.fields]
             if missing:
@@ -1160,6 +1192,11 @@ class CoupledCore(DynamicsCore):
                      if names[0] in forcing.fields]
             if nodal:
                 self._series_groups.append(("nodes", sum((n for n, _ in nodal), ()), [o for _, outs in nodal for o in outs]))
+            if self.slab_ocean and "sst" in forcing.fields:
+                # the slab's relaxation targets, a launch of their own (NSDG_FORCING_MAX_FIELDS planes per launch)
+                ext = [(k, self.col[k + "_ext"]) for k in ForcingSeries.SLAB if k + "_ext" in self.col]
+                if ext:
+                    self._series_groups.append(("elements", tuple(k for k, _ in ext), [o for _, o in ext]))
             self._records, self._device = {}, device
         elif forcing not in (None, "dummy", "winter"):
             raise ValueError("forcing must be None, 'dummy', 'winter' or a ForcingSeries, got %r" % (forcing,))
@@ -1177,6 +1214,8 @@ class CoupledCore(DynamicsCore):
         """fields: dict name -> global [ny, nx] numpy array for hsnow, tice0 and the 10 forcing fields"""
         es = self.blk.elem_slice()
         for k, dst in self.col.items():
+            if k.endswith("_ext") and k not in fields:  # a slab ocean's relaxation target: the initial sst / sss without a key of its own
+                k = k[:-4]
             _put(dst, fields[k][es])
 
     def transport(self):
@@ -1195,13 +1234,30 @@ class CoupledCore(DynamicsCore):
         out = super().state_dict()
         if self.advect_column_state:
             out["S"] = self.owned(self.S).detach().cpu().numpy().copy()
+        if self.slab_ocean:
+            out.update({k: v for k, v in self.ocean_read().items() if k != "rows"})
+        return out
+
+    def ocean_read(self):
+        """the slab ocean's state on the owned rows: {"rows": (r0, r1), "sst": [rows, nx], "sss": [rows, nx]}"""
+        if not self.slab_ocean:
+            raise ValueError("ocean_read needs slab_ocean=True")
+        b = self.blk
+        out = {"rows": (b.r0, b.r1)}
+        for k in ("sst", "sss"):
+            out[k] = self.col[k][b.j0:b.j1].detach().cpu().numpy().copy()
         return out
 
     def load_state_dict(self, state):
         """DynamicsCore.load_state_dict and, with advect_column_state, the snow S (required: plane 0 is the column's hsnow)"""
         if self.advect_column_state and "S" not in state:
             raise ValueError("a CoupledCore with advect_column_state needs the snow S in the state")
+        if self.slab_ocean and not ("sst" in state and "sss" in state):
+            raise ValueError("a CoupledCore with slab_ocean needs sst and sss in the state")
         super().load_state_dict(state)
+        if self.slab_ocean:
+            for k in ("sst", "sss"):
+                _put(self.col[k], state[k][self.blk.elem_slice()])
         if self.advect_column_state:
             _put(self.S, state["S"][:, self.blk.elem_slice()])
             self._clear_land()
@@ -1212,7 +1268,11 @@ class CoupledCore(DynamicsCore):
         forcing = {k: self.col[k] for k in self.COLUMN_FORCING}
         if self.tracers:
             self.ops.copy_f64(self._h_before, self.H[0])
-        self.ops.column_step(self.dt, state, forcing, self.newice)
+        if self.slab_ocean:
+            self.ops.set_slab_params(self._slab)  # (host only: a context that several cores share holds this core's at its call)
+            self.ops.column_step_ocean(self.dt, state, forcing, self.newice, self._slab_ext, self.land)
+        else:
+            self.ops.column_step(self.dt, state, forcing, self.newice)
         if self.land is not None:
             # the column step computes on land elements too (it is pinned to the reference case by case); its result there is discarded:
             # the cell means of H, A (and S), the snow and the new ice (still the COLUMN phase of the phase table)

@@ -595,6 +595,12 @@ int nsdg_land_clear_nodes(nsdg_ctx* ctx, double* u, double* v);
  * parameters, its arithmetic and its checks are declared in nsdg_ocean.h, which this header includes. */
 #include "nsdg_ocean.h"
 
+/* ---- snow load: the momentum equation feels the snow's weight (csrc/snowload.hip) ------------------------------
+ * A snow field on the context makes the packing take the nodal mass from h' = max(cgH + (rho_snow / rho_ice) max(cgS, 0), h_min) where the
+ * node is neither land nor ice-free; the passes read c[0] as ever.  The field, the diagnostic h' and their checks are declared in
+ * nsdg_snow.h, which this header includes. */
+#include "nsdg_snow.h"
+
 /* ---- brittle rheology: the brittle Bingham-Maxwell (BBM) sub-cycle (csrc/bbm.hip, csrc/bbm_common.h) ------------
  * A second rheology beside mEVP: damage, a Mohr-Coulomb envelope, Maxwell relaxation.  No counterpart in the reference snapshot; built from
  * the published formulation (Olason et al. 2022, "A new brittle rheology and numerical framework for large-scale sea-ice models", JAMES;

@@ -272,6 +272,13 @@ OCEAN_SYMBOLS = {
     "nsdg_column_step_ocean": (C.c_int, [VP, I64, D] + [VP] * 18),
 }
 
+# the functions of include/nsdg_snow.h (the "snow load" section, a header of its own that nsdg.h includes), bound like SYMBOLS
+SNOW_SYMBOLS = {
+    "nsdg_snow_load_set": (C.c_int, [VP, VP, I32, C.c_double]),
+    "nsdg_snow_load_nodal": (C.c_int, [VP, VP, VP, VP]),
+}
+SNOW_DENSITY = 330.0  # NSDG_SNOW_DENSITY: the column step's rho_s
+
 _lib = None
 
 
@@ -289,7 +296,7 @@ def load_library(path=LIB_PATH):
         raise NsdgError("HIP library %s is missing: build it with `python -m nextsimdg_amd.build` "
                         "(there is no CPU fallback)" % path)
     lib = C.CDLL(path)
-    for name, (res, args) in list(SYMBOLS.items()) + list(TRACER_SYMBOLS.items()) + list(BASAL_SYMBOLS.items()) + list(OCEAN_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(TRACER_SYMBOLS.items()) + list(BASAL_SYMBOLS.items()) + list(OCEAN_SYMBOLS.items()) + list(SNOW_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -512,6 +519,7 @@ class Context:
         self.mevp_variant = DEFAULT_MEVP_VARIANT  # the library default (four sub-iterations per pass)
         self.land_mask = None  # the tensor behind nsdg_land_mask_set (set_land_mask keeps it alive)
         self.basal_depth = None  # the tensor behind nsdg_basal_depth_set (set_basal_depth keeps it alive)
+        self.snow_load = None  # the tensor behind nsdg_snow_load_set (set_snow_load keeps it alive)
 
     def _call(self, rc):
         if rc != 0:
@@ -819,7 +827,7 @@ class Context:
     def set_grid(self, nx, ny, hx, hy):
         self._call(self.lib.nsdg_grid_set(self.h, nx, ny, float(hx), float(hy)))
         if (nx, ny) != (self.nx, self.ny):
-            self.land_mask = self.basal_depth = None  # the library dropped a mask and a depth array of the old shape
+            self.land_mask = self.basal_depth = self.snow_load = None  # the library dropped a mask, a depth array and a snow field of the old shape
         self.nx, self.ny = nx, ny
 
     # ---- land mask (include/nsdg.h "land mask"): coastlines as fixed nodes of the sub-cycle
@@ -877,6 +885,29 @@ class Context:
         if cgh.numel() != n or cga.numel() != n or tb.numel() != n:
             raise NsdgError("basal_critical: the nodal arrays of the grid hold %d values" % n)
         self._call(self.lib.nsdg_basal_critical(self.h, _ptr(cgh), _ptr(cga), _ptr(tb)))
+
+    # ---- snow load (include/nsdg_snow.h): the momentum equation feels the snow's weight
+    def set_snow_load(self, snow, rho_snow=SNOW_DENSITY):
+        """nsdg_snow_load_set: `snow` = a contiguous float64 CUDA tensor of the local array, [ny, nx] (the column plane hsnow) or
+        [nc, ny, nx] with nc = 1, 3 or 6 (the DG field S), kept alive by this object while it is set; None clears it.  Read by the next
+        coefficient packing"""
+        ncoef = 0
+        if snow is not None:
+            _check_f64(snow)
+            if snow.dim() not in (2, 3) or tuple(snow.shape[-2:]) != (self.ny, self.nx):
+                raise NsdgError("the snow field has shape %s, the local array is [%d, %d]" % (tuple(snow.shape), self.ny, self.nx))
+            ncoef = 1 if snow.dim() == 2 else snow.shape[0]
+        self._call(self.lib.nsdg_snow_load_set(self.h, _ptr(snow), ncoef, float(rho_snow)))
+        self.snow_load = snow
+
+    def snow_load_nodal(self, cgh, cga, out):
+        """nsdg_snow_load_nodal: out = the thickness h' behind the nodal mass at every node of the CG2 lattice, what the next packing
+        would store as its first coefficient before the ice-free scaling"""
+        _check_f64(cgh, cga, out)
+        n = (2 * self.nx + 1) * (2 * self.ny + 1)
+        if cgh.numel() != n or cga.numel() != n or out.numel() != n:
+            raise NsdgError("snow_load_nodal: the nodal arrays of the grid hold %d values" % n)
+        self._call(self.lib.nsdg_snow_load_nodal(self.h, _ptr(cgh), _ptr(cga), _ptr(out)))
 
     def set_mevp_variant(self, variant):
         self._call(self.lib.nsdg_mevp_variant_set(self.h, variant))

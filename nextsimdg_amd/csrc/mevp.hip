@@ -16,6 +16,7 @@
 // Variant 1 ("fused march") lives in mevp_fused.hip.
 #include <algorithm>
 #include <initializer_list>
+#include <type_traits>
 
 #include "mevp_pipeline.h"
 
@@ -160,46 +161,14 @@ __global__ __launch_bounds__(256) void mevp_velocity_basal_kernel(NodalConstsBas
 }
 
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double psi_rt(int c, double x, double y)
-{
-    switch (c) {
-    case 0: return 1.;
-    case 1: return x;
-    case 2: return y;
-    case 3: return x * x - 1. / 12.;
-    case 4: return y * y - 1. / 12.;
-    default: return x * y;
-    }
-}
-
-// nodal average of a DG field at CG2 node (gx, gy): mean over the 1/2/4 adjacent elements of the DG value there
-__device__ __forceinline__ double node_average(int nx, int ny, int nc, const double* __restrict__ f, int gx, int gy)
-{
-    const long N = (long)nx * ny;
-    const int ix_hi = gx / 2, ix_lo = (gx % 2 == 0) ? gx / 2 - 1 : gx / 2;
-    const int iy_hi = gy / 2, iy_lo = (gy % 2 == 0) ? gy / 2 - 1 : gy / 2;
-    double s = 0.;
-    int cnt = 0;
-    for (int iy = iy_lo; iy <= iy_hi; ++iy)
-        for (int ix = ix_lo; ix <= ix_hi; ++ix) {
-            if (ix < 0 || ix >= nx || iy < 0 || iy >= ny)
-                continue;
-            const double x = -0.5 + 0.5 * (gx - 2 * ix), y = -0.5 + 0.5 * (gy - 2 * iy);
-            const long e = (long)iy * nx + ix;
-            double val = 0.;
-            for (int c = 0; c < nc; ++c)
-                val += f[c * N + e] * psi_rt(c, x, y);
-            s += val;
-            ++cnt;
-        }
-    return s / cnt;
-}
-
+// psi_rt, node_average: mevp_common.h
 // per-step momentum coefficients of one node, 6 doubles (layout: mevp_common.h); BASAL: pair 3 = (T_b, 0) from the node's mean water
-// depth hwn as well (landfast ice, mevp_common.h: basal_critical_stress)
-template <bool BASAL>
+// depth hwn as well (landfast ice, mevp_common.h: basal_critical_stress); SNOW: the mass of a node that is neither land nor ice-free
+// carries the snow's nodal mean cgs, weighted by r = rho_snow / rho_ice (snow load, mevp_common.h: snow_loaded_thickness)
+template <bool BASAL, bool SNOW>
 __device__ __forceinline__ void pack_node(const nsdg_mevp_params& P, double dt, double u0, double v0, double tax, double tay,
-    double uoc, double voc, double cgh, double cga, double* __restrict__ packed, long plane, long n, bool land, const nsdg_basal_params& B, double hwn)
+    double uoc, double voc, double cgh, double cga, double* __restrict__ packed, long plane, long n, bool land, const nsdg_basal_params& B, double hwn,
+    double r, double cgs)
 {
     if constexpr (BASAL)
         store_nodal_tb(packed, plane, n, basal_critical_stress(P, B, cgh, cga, hwn, land));
@@ -211,7 +180,7 @@ __device__ __forceinline__ void pack_node(const nsdg_mevp_params& P, double dt, 
         store_nodal(packed, plane, n, c);
         return;
     }
-    const double h = fmax(cgh, P.h_min);
+    double h = fmax(cgh, P.h_min);
     // Ice-free-node rule (round 5; the shape of the column model's cut-off  c_new < minc || hi < minh,
     // physics/src/modules/NextsimPhysics.cpp:210-219): a node whose mean concentration is below min_conc, whose TRUE thickness
     // cgH / cgA is below min_thick or whose mean thickness is at the mass floor h_min (a made-up mass) is in FREE DRIFT -- full exposure (a = 1) to wind stress and ocean drag, Coriolis, its floor mass
@@ -221,6 +190,9 @@ __device__ __forceinline__ void pack_node(const nsdg_mevp_params& P, double dt, 
     // leaves every other term as it is and weights the divergence by 2^-100 -- below the last bit of the sum.  Both 0: rule off.
     // (the expression of mevp_common.h: ice_free_node, which T_b tests; written out here, where it has always stood)
     const bool ice_free = (P.min_conc > 0. || P.min_thick > 0.) && (cga < P.min_conc || cgh < P.min_thick * cga || cgh <= P.h_min);
+    if constexpr (SNOW)
+        if (!ice_free)
+            h = fmax(snow_loaded_thickness(cgh, r, cgs), P.h_min);
     const double a = ice_free ? 1. : fmin(fmax(cga, 0.), 1.);
     const double mdt = P.rho_ice * h / dt;
     const double cor = P.rho_ice * h * P.fc;
@@ -238,12 +210,13 @@ __device__ __forceinline__ void wind_tau(double f_atm, double ua, double va, dou
 
 // LAND: with the element land mask of the local array (nx x ny elements), land nodes are packed with the flag
 // BASAL: with the water depth of the same elements, pair 3 of a node is (T_b, 0)
-template <bool LAND, bool BASAL>
+// SNOW: with the ncs coefficient planes of the snow on the same elements, the mass of a node carries its nodal mean
+template <bool LAND, bool BASAL, bool SNOW>
 __global__ __launch_bounds__(256) void mevp_pack_nodal_kernel(nsdg_mevp_params P, long nnodes, double dt,
     const double* __restrict__ u0, const double* __restrict__ v0, const double* __restrict__ tax,
     const double* __restrict__ tay, const double* __restrict__ uo, const double* __restrict__ vo,
     const double* __restrict__ cgh, const double* __restrict__ cga, double* __restrict__ packed, int nx, int ny, const uint8_t* __restrict__ land,
-    nsdg_basal_params B, const double* __restrict__ depth)
+    nsdg_basal_params B, const double* __restrict__ depth, const double* __restrict__ snow, int ncs, double r)
 {
     const long n = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= nnodes)
@@ -255,13 +228,16 @@ __global__ __launch_bounds__(256) void mevp_pack_nodal_kernel(nsdg_mevp_params P
     double hwn = 0.;
     if constexpr (BASAL)
         hwn = node_mean_of(nx, ny, (int)(n % nn), (int)(n / nn), [&](int ix, int iy) { return depth[(long)iy * nx + ix]; });
-    pack_node<BASAL>(P, dt, u0[n], v0[n], tax[n], tay[n], uo[n], vo[n], cgh[n], cga[n], packed, nodal_plane(nnodes), n, is_land, B, hwn);
+    double cgs = 0.;
+    if constexpr (SNOW)
+        cgs = node_average(nx, ny, ncs, snow, (int)(n % nn), (int)(n / nn));
+    pack_node<BASAL, SNOW>(P, dt, u0[n], v0[n], tax[n], tay[n], uo[n], vo[n], cgh[n], cga[n], packed, nodal_plane(nnodes), n, is_land, B, hwn, r, cgs);
 }
 
 // node_average() on a tile of DG coefficients staged in LDS: tile[c][iy - ey0][ix - ex0]; same loops, same order of
 // summation, so the result is bit-identical to the global-memory form
 constexpr int PREP_TW = 33, PREP_TH = 3; // element columns / rows under a 64 x 4 block of nodes
-__device__ __forceinline__ double node_average_tile(int nx, int ny, const double (*tile)[PREP_TH][PREP_TW], int ex0, int ey0, int gx, int gy)
+__device__ __forceinline__ double node_average_tile(int nx, int ny, const double (*tile)[PREP_TH][PREP_TW], int ex0, int ey0, int gx, int gy, int nc = 6)
 {
     const int ix_hi = gx / 2, ix_lo = (gx % 2 == 0) ? gx / 2 - 1 : gx / 2;
     const int iy_hi = gy / 2, iy_lo = (gy % 2 == 0) ? gy / 2 - 1 : gy / 2;
@@ -273,7 +249,7 @@ __device__ __forceinline__ double node_average_tile(int nx, int ny, const double
                 continue;
             const double x = -0.5 + 0.5 * (gx - 2 * ix), y = -0.5 + 0.5 * (gy - 2 * iy);
             double val = 0.;
-            for (int c = 0; c < 6; ++c)
+            for (int c = 0; c < nc; ++c)
                 val += tile[c][iy - ey0][ix - ex0] * psi_rt(c, x, y);
             s += val;
             ++cnt;
@@ -288,13 +264,17 @@ __device__ __forceinline__ double node_average_tile(int nx, int ny, const double
 // fields: the gather form issued ~57 loads per lane and was bound by vector-memory issue, 0.67 ms at 2048^2).
 // LAND: the mask bytes of the same 33 x 3 elements are staged beside the tile and land nodes are packed with the flag.
 // BASAL: so are their water depths, and pair 3 of a node is (T_b, 0).
-template <bool LAND, bool BASAL>
+// SNOW: so are the ncs (1, 3 or 6) coefficient planes of the snow, 4.6 KB more for six planes (14.3 KB in all); the nodal mean is read with
+// the loops of node_average_tile over ncs coefficients, the order of nsdg_dg_to_cg(ncs).
+template <bool LAND, bool BASAL, bool SNOW>
 __global__ __launch_bounds__(256) void mevp_prepare_kernel(nsdg_mevp_params P, int nx, int ny, double dt,
     const double* __restrict__ H, const double* __restrict__ A, const double* __restrict__ ua, const double* __restrict__ va,
     const double* __restrict__ uo, const double* __restrict__ vo, const double* __restrict__ u0, const double* __restrict__ v0,
-    double* __restrict__ packed, const uint8_t* __restrict__ land, nsdg_basal_params B, const double* __restrict__ depth)
+    double* __restrict__ packed, const uint8_t* __restrict__ land, nsdg_basal_params B, const double* __restrict__ depth,
+    const double* __restrict__ snow, int ncs, double r)
 {
     __shared__ double tile[2][6][PREP_TH][PREP_TW];
+    __shared__ double stile[SNOW ? 6 : 1][PREP_TH][PREP_TW];
     __shared__ uint8_t ltile[LAND ? PREP_TH : 1][PREP_TW];
     __shared__ double dtile[BASAL ? PREP_TH : 1][PREP_TW];
     const int gx0 = blockIdx.x * 64, gy0 = blockIdx.y * 4;
@@ -323,6 +303,16 @@ __global__ __launch_bounds__(256) void mevp_prepare_kernel(nsdg_mevp_params P, i
             dtile[r][col] = (ix >= 0 && ix < nx && iy >= 0 && iy < ny) ? depth[(long)iy * nx + ix] : 0.;
         }
     }
+    if constexpr (SNOW) {
+        for (int k = tid; k < ncs * PREP_TH * PREP_TW; k += 256) {
+            const int col = k % PREP_TW, rr = (k / PREP_TW) % PREP_TH, c = k / (PREP_TW * PREP_TH);
+            const int ix = ex0 + col, iy = ey0 + rr;
+            double val = 0.;
+            if (ix >= 0 && ix < nx && iy >= 0 && iy < ny)
+                val = snow[c * N + (long)iy * nx + ix];
+            stile[c][rr][col] = val;
+        }
+    }
     __syncthreads();
     const int gx = gx0 + threadIdx.x;
     const int gy = gy0 + threadIdx.y;
@@ -339,7 +329,10 @@ __global__ __launch_bounds__(256) void mevp_prepare_kernel(nsdg_mevp_params P, i
     double hwn = 0.;
     if constexpr (BASAL)
         hwn = node_mean_of(nx, ny, gx, gy, [&](int ix, int iy) { return dtile[iy - ey0][ix - ex0]; });
-    pack_node<BASAL>(P, dt, u0[n], v0[n], tax, tay, uo[n], vo[n], cgh, cga, packed, nodal_plane((long)nn * nm), n, is_land, B, hwn);
+    double cgs = 0.;
+    if constexpr (SNOW)
+        cgs = node_average_tile(nx, ny, stile, ex0, ey0, gx, gy, ncs);
+    pack_node<BASAL, SNOW>(P, dt, u0[n], v0[n], tax, tay, uo[n], vo[n], cgh, cga, packed, nodal_plane((long)nn * nm), n, is_land, B, hwn, r, cgs);
 }
 
 // one lane per CG2 node
@@ -478,14 +471,21 @@ int nsdg_mevp_pack_nodal(nsdg_ctx* ctx, double dt, const double* u0, const doubl
     NSDG_CHECK_ARG(((uintptr_t)packed & 15) == 0, "packed must be 16-byte aligned");
     NSDG_CHECK_HIP(hipSetDevice(ctx->device));
     const long nnodes = (long)(2 * ctx->nx + 1) * (2 * ctx->ny + 1);
+    const int snow_rc = nsdg_snow_check_packed(ctx, __func__, packed);
+    if (snow_rc)
+        return snow_rc;
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(nsdg_div_up(nnodes, 256)), dim3(256), 0, ctx->stream, ctx->mevp, nnodes, dt, u0, v0, tax, tay, uo, vo, cgh, cga,
-            packed, ctx->nx, ctx->ny, ctx->land, ctx->basal, ctx->depth);
+            packed, ctx->nx, ctx->ny, ctx->land, ctx->basal, ctx->depth, ctx->snow, ctx->snow_ncoef, nsdg_snow_ratio(ctx));
     };
-    if (ctx->depth)
-        ctx->land ? launch(mevp_pack_nodal_kernel<true, true>) : launch(mevp_pack_nodal_kernel<false, true>);
-    else
-        ctx->land ? launch(mevp_pack_nodal_kernel<true, false>) : launch(mevp_pack_nodal_kernel<false, false>);
+    auto choose = [&](auto snow) { // snow load (snowload.hip): a context without a snow field launches the instantiations it always did
+        constexpr bool SNOW = decltype(snow)::value;
+        if (ctx->depth)
+            ctx->land ? launch(mevp_pack_nodal_kernel<true, true, SNOW>) : launch(mevp_pack_nodal_kernel<false, true, SNOW>);
+        else
+            ctx->land ? launch(mevp_pack_nodal_kernel<true, false, SNOW>) : launch(mevp_pack_nodal_kernel<false, false, SNOW>);
+    };
+    ctx->snow ? choose(std::true_type()) : choose(std::false_type());
     NSDG_CHECK_LAUNCH();
     ctx->pack_dt = dt; // the launch constants K1, K2 of the velocity update belong to this packing
     ctx->pack_land = ctx->land != nullptr; // and so does the choice of the passes' instantiation: this packing flagged land nodes, or not,
@@ -502,14 +502,21 @@ int nsdg_mevp_prepare(nsdg_ctx* ctx, double dt, const double* H, const double* A
     NSDG_CHECK_ARG(((uintptr_t)packed & 15) == 0, "packed must be 16-byte aligned");
     NSDG_CHECK_HIP(hipSetDevice(ctx->device));
     const dim3 block(64, 4), grid(nsdg_div_up(2 * ctx->nx + 1, 64), nsdg_div_up(2 * ctx->ny + 1, 4));
+    const int snow_rc = nsdg_snow_check_packed(ctx, __func__, packed);
+    if (snow_rc)
+        return snow_rc;
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, ctx->mevp, ctx->nx, ctx->ny, dt, H, A, ua, va, uo, vo, u0, v0, packed, ctx->land,
-            ctx->basal, ctx->depth);
+            ctx->basal, ctx->depth, ctx->snow, ctx->snow_ncoef, nsdg_snow_ratio(ctx));
     };
-    if (ctx->depth)
-        ctx->land ? launch(mevp_prepare_kernel<true, true>) : launch(mevp_prepare_kernel<false, true>);
-    else
-        ctx->land ? launch(mevp_prepare_kernel<true, false>) : launch(mevp_prepare_kernel<false, false>);
+    auto choose = [&](auto snow) {
+        constexpr bool SNOW = decltype(snow)::value;
+        if (ctx->depth)
+            ctx->land ? launch(mevp_prepare_kernel<true, true, SNOW>) : launch(mevp_prepare_kernel<false, true, SNOW>);
+        else
+            ctx->land ? launch(mevp_prepare_kernel<true, false, SNOW>) : launch(mevp_prepare_kernel<false, false, SNOW>);
+    };
+    ctx->snow ? choose(std::true_type()) : choose(std::false_type());
     NSDG_CHECK_LAUNCH();
     ctx->pack_dt = dt;
     ctx->pack_land = ctx->land != nullptr;

@@ -587,6 +587,53 @@ __device__ __forceinline__ bool ice_free_node(const nsdg_mevp_params& P, double 
     return (P.min_conc > 0. || P.min_thick > 0.) && (cga < P.min_conc || cgh < P.min_thick * cga || cgh <= P.h_min);
 }
 
+// the DG basis and the nodal mean of a DG field, shared by nsdg_dg_to_cg and the packing (mevp.hip) and by the snow load (snowload.hip)
+__device__ __forceinline__ double psi_rt(int c, double x, double y)
+{
+    switch (c) {
+    case 0: return 1.;
+    case 1: return x;
+    case 2: return y;
+    case 3: return x * x - 1. / 12.;
+    case 4: return y * y - 1. / 12.;
+    default: return x * y;
+    }
+}
+
+// nodal average of a DG field at CG2 node (gx, gy): mean over the 1/2/4 adjacent elements of the DG value there
+__device__ __forceinline__ double node_average(int nx, int ny, int nc, const double* __restrict__ f, int gx, int gy)
+{
+    const long N = (long)nx * ny;
+    const int ix_hi = gx / 2, ix_lo = (gx % 2 == 0) ? gx / 2 - 1 : gx / 2;
+    const int iy_hi = gy / 2, iy_lo = (gy % 2 == 0) ? gy / 2 - 1 : gy / 2;
+    double s = 0.;
+    int cnt = 0;
+    for (int iy = iy_lo; iy <= iy_hi; ++iy)
+        for (int ix = ix_lo; ix <= ix_hi; ++ix) {
+            if (ix < 0 || ix >= nx || iy < 0 || iy >= ny)
+                continue;
+            const double x = -0.5 + 0.5 * (gx - 2 * ix), y = -0.5 + 0.5 * (gy - 2 * iy);
+            const long e = (long)iy * nx + ix;
+            double val = 0.;
+            for (int c = 0; c < nc; ++c)
+                val += f[c * N + e] * psi_rt(c, x, y);
+            s += val;
+            ++cnt;
+        }
+    return s / cnt;
+}
+
+// Snow load (include/nsdg_snow.h): the thickness that carries the snow's weight, hl = cgH + r max(cgS, 0), r = rho_snow / rho_ice -- the
+// ONE statement of it, shared by the packing (pack_node applies it to a node that is neither land nor ice-free) and nsdg_snow_load_nodal.
+// The product is a statement of its own: -ffp-contract=on fuses inside one expression only, and p must be rounded before the sum.
+__device__ __forceinline__ double snow_loaded_thickness(double cgh, double r, double cgs)
+{
+    const double s = fmax(cgs, 0.);
+    const double p = r * s;
+    const double hl = cgh + p;
+    return hl;
+}
+
 // Landfast ice (include/nsdg_basal.h; Lemieux et al. 2015): the critical stress T_b of a node from its nodal means of thickness,
 // concentration and water depth -- the ONE statement of it, shared by the packing (pair 3 of a node) and nsdg_basal_critical.  The
 // thickness is cgH itself, not raised to the mass floor; land and the ice-free rule come first.

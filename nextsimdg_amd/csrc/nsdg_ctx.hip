@@ -158,6 +158,7 @@ int nsdg_ctx_create(int device_id, void* stream, nsdg_ctx** out)
     c->land = nullptr, c->pack_land = false;
     nsdg_basal_default_params(&c->basal);
     c->depth = nullptr, c->pack_basal = false;
+    c->snow = nullptr, c->snow_ncoef = 0, c->rho_snow = 0.;
     c->d_ptrs = nullptr;
     c->comm = nullptr;
     c->comm_group = 0;
@@ -303,7 +304,7 @@ int nsdg_grid_set(nsdg_ctx* ctx, int32_t nx, int32_t ny, double hx, double hy)
     if (ctx->nx != nx || ctx->ny != ny || ctx->hx != hx || ctx->hy != hy)
         ctx->pack_dt = 0.; // packed nodal coefficients belong to the old grid
     if (ctx->nx != nx || ctx->ny != ny)
-        ctx->land = nullptr, ctx->depth = nullptr; // and so do the land mask (nsdg_land_mask_set) and the water depth (nsdg_basal_depth_set): nx * ny entries of the old shape
+        ctx->land = nullptr, ctx->depth = nullptr, ctx->snow = nullptr; // and so do the land mask (nsdg_land_mask_set), the water depth (nsdg_basal_depth_set) and the snow field (nsdg_snow_load_set): nx * ny entries of the old shape
     ctx->nx = nx;
     ctx->ny = ny;
     ctx->hx = hx;

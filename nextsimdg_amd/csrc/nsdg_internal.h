@@ -32,6 +32,11 @@ struct nsdg_ctx {
     nsdg_basal_params basal; // landfast ice (basal.hip): the grounding scheme's parameters
     const double* depth; // water depth per element of the local array, null = none; owned by the caller
     bool pack_basal; // the packing saw a depth array: pair 3 of a node holds (T_b, 0) and the passes run the BASAL instantiations
+    // snow load (snowload.hip, include/nsdg_snow.h): the snow's coefficient planes on the local array, null = none, owned by the caller; the
+    // packing reads them and the passes read c[0] as ever -- no flag of the packing goes with them
+    const double* snow;
+    int snow_ncoef; // 1, 3 or 6 planes
+    double rho_snow;
     int transport_variant, transport_rows; // transport stage kernel: 0 one element per lane / 2 two elements per lane; rows per workgroup
     int fused_min_waves; // register budget of the fused kernel: 1 or 2 waves per SIMD
     int nbounds; // closure of a transport step: bounds of the advected fields (0 = none), nsdg_transport_bounds_set
@@ -127,6 +132,12 @@ inline auto nsdg_with_order(int order, F&& f)
     default: return f(std::integral_constant<int, 2>());
     }
 }
+
+// ---- snow load (snowload.hip) ---------------------------------------------------------------------------------------------------
+// r = rho_snow / rho_ice of the packing being launched: one IEEE division on the host, with the rho_ice the context holds now
+static inline double nsdg_snow_ratio(const nsdg_ctx* ctx) { return ctx->snow ? ctx->rho_snow / ctx->mevp.rho_ice : 0.; }
+// NSDG_ERR_ARG, reported under `fn`, if the context's snow field overlaps the 8 (2nx+1)(2ny+1) doubles of `packed`; NSDG_OK without a field
+int nsdg_snow_check_packed(const nsdg_ctx* ctx, const char* fn, const double* packed);
 
 // ---- mEVP passes (mevp.hip) -----------------------------------------------------------------------------------------------------
 // the buffers of a pass: the stress S_in -> S_out (tiled), the velocity u_old -> u_new, the packed nodal coefficients, the ice strength

@@ -101,6 +101,13 @@
 //     [slabocean] relax_t, relax_s, ice_salinity   the members of nsdg_slab_params (defaults: nsdg_slab_default_params), by the rule of
 //                            nsdg_slab_params_set; refused without dynamics.slab_ocean.  The relaxation targets are the forcing file's
 //                            optional pair sst, sss sampled on the device, or, without it, the initial sst, sss
+//     dynamics.snow_load     false (default: nothing changes) | true -- the momentum equation feels the snow's weight (include/nsdg_snow.h,
+//                            DESIGN.md section 3.12): before every coefficient packing the block's snow -- the DG field S under
+//                            dynamics.advect_column_state, else the plane hsnow -- is set on the context (nsdg_snow_load_set), and the
+//                            nodal mass is rho_i cgH + rho_snow max(cgS, 0) where the node is neither land nor ice-free; both rheologies.
+//                            Needs dynamics.thermodynamics = true.  The restart file needs nothing new: the snow is in it
+//     dynamics.rho_snow      the density of that snow [kg m^-3], finite and >= 0 (default 330, the column step's); refused without
+//                            dynamics.snow_load
 //     dynamics.row_blocks, dynamics.devices, dynamics.passes_per_exchange (2), dynamics.overlap (true),
 //     dynamics.graph (false), dynamics.loopback_world (0: off; N: rehearse an interior block of N on one GPU with
 //     real RCCL send/recv to the rank itself -- values wrap around, for timing and call-path checks only)
@@ -110,6 +117,7 @@
 #pragma once
 #include "../../../include/nsdg_basal.h"
 #include "../../../include/nsdg_ocean.h"
+#include "../../../include/nsdg_snow.h"
 #include <algorithm>
 #include <memory>
 #include <string>
@@ -203,6 +211,8 @@ private:
     std::shared_ptr<const BathymetryFile> m_bathymetry; // dynamics.bathymetry_file: the water depth, read and checked in configure()
     nsdg_basal_params m_basal; // [basal]: the grounding scheme's parameters (used with m_bathymetry)
     bool slabOcean = false; // dynamics.slab_ocean: sst and sss follow the ice (nsdg_column_step_ocean)
+    bool snowLoad = false; // dynamics.snow_load: the packing takes the nodal mass from ice and snow (nsdg_snow_load_set before every packing)
+    double rhoSnow = NSDG_SNOW_DENSITY; // dynamics.rho_snow
     nsdg_slab_params m_slab; // [slabocean]: relaxation times and the salinity of the ice (used with slabOcean)
     struct Outputs; // model.output_*, series_*, drifters_*, stations_*: the four outputs, each null when off (DynamicsStep.cpp)
     std::unique_ptr<Outputs> m_out;

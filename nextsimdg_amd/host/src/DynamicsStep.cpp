@@ -39,7 +39,7 @@ const std::map<int, std::string> Configured<DynamicsStep>::keyMap = { { 0, "dyna
     { 18, "dynamics.substep_courant" }, { 19, "dynamics.max_substeps" }, { 20, "dynamics.forcing_file" },
     { 21, "dynamics.advect_column_state" }, { 22, "dynamics.land_mask_file" }, { 23, "dynamics.rheology" },
     { 24, "dynamics.bbm_courant" }, { 25, "dynamics.tracers" }, { 26, "dynamics.tracer_init" },
-    { 27, "dynamics.bathymetry_file" }, { 28, "dynamics.slab_ocean" } };
+    { 27, "dynamics.bathymetry_file" }, { 28, "dynamics.slab_ocean" }, { 29, "dynamics.snow_load" }, { 30, "dynamics.rho_snow" } };
 
 // dynamics.rheology = bbm
 struct DynamicsStep::Brittle {
@@ -276,6 +276,19 @@ void DynamicsStep::configure()
         if (!std::isfinite(value) || value < 0.)
             throw std::invalid_argument(std::string("[slabocean]: ") + k.key + " = " + std::to_string(value)
                 + ": need relax_t >= 0, relax_s >= 0 and ice_salinity >= 0, all finite");
+    }
+    // snow load (include/nsdg_snow.h): the momentum equation feels the snow's weight -- the rule of nsdg_snow_load_set, applied here, before
+    // any device is touched
+    snowLoad = getConfiguration(keyMap.at(29), false);
+    if (snowLoad && !thermo)
+        throw std::invalid_argument("dynamics.snow_load needs dynamics.thermodynamics = true: without the column model there is no snow to weigh");
+    {
+        std::string raw;
+        if (Configurator::lookup(keyMap.at(30), raw) && !snowLoad)
+            throw std::invalid_argument("dynamics.rho_snow needs dynamics.snow_load = true");
+        rhoSnow = getConfiguration(keyMap.at(30), (double)NSDG_SNOW_DENSITY);
+        if (!std::isfinite(rhoSnow) || rhoSnow < 0.)
+            throw std::invalid_argument("dynamics.rho_snow = " + std::to_string(rhoSnow) + ": need a finite density >= 0");
     }
     if (loopbackWorld != 0 && loopbackWorld < 3)
         throw std::invalid_argument("dynamics.loopback_world needs an interior block: at least 3");
@@ -648,6 +661,8 @@ void DynamicsStep::subStep(double dt, bool last)
             }
         }
         check(nsdg_phase_mark(ctx, NSDG_PHASE_PREPARE), "nsdg_phase_mark");
+        if (snowLoad) // the snow as it stands after this step's column step; the transport's ping-pong moves S: set before every packing
+            check(nsdg_snow_load_set(ctx, advectColumn ? b.cur(FS) : b.col(C_HSNOW), advectColumn ? 6 : 1, rhoSnow), "nsdg_snow_load_set");
         int32_t out = 0;
         if (m_brittle) {
             // the Gauss arrays of the brittle sub-cycle and the mEVP packing for the sub-iteration's dt with u0 = v0 = 0: no ice strength

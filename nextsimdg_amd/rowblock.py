@@ -316,7 +316,9 @@ class DynamicsCore:
     def __init__(self, ops, blk, hx, hy, dt, nsub, device, exchanger=None, overlap=True, native=False, use_graph=False, closure=True,
                  phase_timing=False, land=None, rheology="mevp", bbm=None, history=None, series=None, series_capacity=1024, extent_conc=0.15,
                  drifters=None, drifter_min_conc=0.15, drifter_fields=None, stations=None, station_fields=None, station_capacity=256,
-                 tracers=None, min_conc=1e-12, min_thick=0.01, bathymetry=None, basal=None):
+                 tracers=None, min_conc=1e-12, min_thick=0.01, bathymetry=None, basal=None, snow_load=False, rho_snow=None):
+        if snow_load or rho_snow is not None:  # (CoupledCore takes the two itself and does not pass them on)
+            raise ValueError("snow_load= needs the column state of a CoupledCore: a DynamicsCore carries no snow")
         self.ops, self.blk, self.hx, self.hy, self.dt, self.nsub, self.overlap = ops, blk, hx, hy, dt, nsub, overlap
         # closure: cap + scaling limiter at the end of every transport step (the ice-free-node rule is a parameter of the
         # sub-cycle, on by default).  False: the bare scheme of rounds 1-4 (frozen fixtures of that scheme)
@@ -1132,7 +1134,12 @@ class CoupledCore(DynamicsCore):
     equal to their owners without a message); land elements keep their sst, sss bits (`skip` = the land mask's local rows).  slab: an
     abi.SlabParams (None: the defaults, no relaxation).  With a relaxation time col["sst_ext"] / col["sss_ext"] hold the targets:
     load_column fills them from the keys sst_ext / sss_ext, or from sst / sss without them, and a ForcingSeries that holds the pair
-    sst, sss samples it into them at every step."""
+    sst, sss samples it into them at every step.
+
+    snow_load = True (include/nsdg_snow.h): the momentum equation feels the snow's weight.  prepare() hands the
+    snow as it stands after this step's column step -- the DG field S under advect_column_state, else the plane col["hsnow"] -- to the
+    ops object immediately before the coefficient packing, which takes the nodal mass from rho_i cgH + rho_snow max(cgS, 0) where the
+    node is neither land nor ice-free.  Both rheologies pack through the same call.  The state dict is what it was: the snow is in it."""
 
     COLUMN_STATE = ("hsnow", "tice0")
     # closure of the column state transport's extra fields: snow volume S >= 0, the product Q = H T unbounded (include/nsdg.h)
@@ -1140,9 +1147,10 @@ class CoupledCore(DynamicsCore):
     COLUMN_FORCING = ("sst", "sss", "tair", "tdew", "slp", "qsw", "qlw", "mld", "snowfall", "wind")
     HAS_COLUMN_STATE = True
     SLAB_OPS = ("column_step_ocean", "slab_default_params", "set_slab_params")
+    SNOW_OPS = ("set_snow_load", "snow_load_nodal")
 
     def __init__(self, ops, blk, hx, hy, dt, nsub, device, forcing=None, advect_column_state=False, min_conc=1e-12, min_thick=0.01,
-                 slab_ocean=False, slab=None, **kw):
+                 slab_ocean=False, slab=None, snow_load=False, rho_snow=None, **kw):
         """forcing: None = the forcing planes are whatever load_column() put there (constant in time);
         "dummy" / "winter" = regenerated on the device at every step's model time (nsdg_column_forcing) and the
         column wind speed is |u_a| of the dynamics' wind (nsdg_column_wind) -- the replacement of the reference's
@@ -1154,6 +1162,15 @@ class CoupledCore(DynamicsCore):
         self.advect_column_state = bool(advect_column_state)  # (read by _more_transported() while the base class constructs)
         if kw.get("tracers"):  # (refused before the base class changes anything on `ops`)
             outputs.require_ops(ops, ("copy_f64",), "tracers= in a coupled core", "copy call")
+        self.snow_load = bool(snow_load)
+        if rho_snow is not None and not self.snow_load:
+            raise ValueError("rho_snow= needs snow_load=True")
+        self.rho_snow = abi.SNOW_DENSITY if rho_snow is None else float(rho_snow)
+        if self.snow_load:
+            outputs.require_ops(ops, self.SNOW_OPS, "snow_load=True", "snow-load calls")
+            if not (np.isfinite(self.rho_snow) and self.rho_snow >= 0.0):
+                raise ValueError("rho_snow must be finite and >= 0, got %r" % (self.rho_snow,))
+        self._snow_on_ops = False
         self.slab_ocean = bool(slab_ocean)
         if slab is not None and not self.slab_ocean:
             raise ValueError("slab= needs slab_ocean=True")
@@ -1203,6 +1220,20 @@ class CoupledCore(DynamicsCore):
 
     def _more_transported(self):
         return (("S", "Q"), self.COLUMN_STATE_BOUNDS) if self.advect_column_state else ((), ())
+
+    def prepare(self):
+        if self.snow_load:
+            # the transport's ping-pong moves S (and the plane col["hsnow"] with it): the pointer is set before every packing
+            snow = self.S[:(1, 3, 6)[self.ORDER]] if self.advect_column_state else self.col["hsnow"]
+            self.ops.set_snow_load(snow, self.rho_snow)
+            self._snow_on_ops = True
+        super().prepare()
+
+    def close(self):
+        if self._snow_on_ops:
+            self.ops.set_snow_load(None)
+            self._snow_on_ops = False
+        super().close()
 
     def _history_sources(self):
         """and the column state: the snow plane the column step actually uses (plane 0 of S under advect_column_state) and tice0"""

@@ -601,6 +601,12 @@ int nsdg_land_clear_nodes(nsdg_ctx* ctx, double* u, double* v);
  * nsdg_snow.h, which this header includes. */
 #include "nsdg_snow.h"
 
+/* ---- sea-surface tilt from a sea-surface height (csrc/tilt.hip) ------------------------------------------------
+ * A sea-surface height on the context makes the packing write the tilt force as -m g grad(eta), from a centred difference on the CG2
+ * lattice, in place of the Coriolis terms of the ocean current; the passes read c2, c3 as ever.  The field, the diagnostic gradient, the box
+ * test's height and their checks are declared in nsdg_tilt.h, which this header includes. */
+#include "nsdg_tilt.h"
+
 /* ---- brittle rheology: the brittle Bingham-Maxwell (BBM) sub-cycle (csrc/bbm.hip, csrc/bbm_common.h) ------------
  * A second rheology beside mEVP: damage, a Mohr-Coulomb envelope, Maxwell relaxation.  No counterpart in the reference snapshot; built from
  * the published formulation (Olason et al. 2022, "A new brittle rheology and numerical framework for large-scale sea-ice models", JAMES;

@@ -279,6 +279,14 @@ SNOW_SYMBOLS = {
 }
 SNOW_DENSITY = 330.0  # NSDG_SNOW_DENSITY: the column step's rho_s
 
+# the functions of include/nsdg_tilt.h (the "sea-surface tilt" section, a header of its own that nsdg.h includes), bound like SYMBOLS
+TILT_SYMBOLS = {
+    "nsdg_tilt_set": (C.c_int, [VP, VP, C.c_double]),
+    "nsdg_tilt_nodal": (C.c_int, [VP, VP, VP]),
+    "nsdg_boxtest_ssh": (C.c_int, [VP, C.c_double, C.c_double, C.c_double, VP]),
+}
+GRAVITY = 9.81  # NSDG_GRAVITY
+
 _lib = None
 
 
@@ -296,7 +304,7 @@ def load_library(path=LIB_PATH):
         raise NsdgError("HIP library %s is missing: build it with `python -m nextsimdg_amd.build` "
                         "(there is no CPU fallback)" % path)
     lib = C.CDLL(path)
-    for name, (res, args) in list(SYMBOLS.items()) + list(TRACER_SYMBOLS.items()) + list(BASAL_SYMBOLS.items()) + list(OCEAN_SYMBOLS.items()) + list(SNOW_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(TRACER_SYMBOLS.items()) + list(BASAL_SYMBOLS.items()) + list(OCEAN_SYMBOLS.items()) + list(SNOW_SYMBOLS.items()) + list(TILT_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -520,6 +528,7 @@ class Context:
         self.land_mask = None  # the tensor behind nsdg_land_mask_set (set_land_mask keeps it alive)
         self.basal_depth = None  # the tensor behind nsdg_basal_depth_set (set_basal_depth keeps it alive)
         self.snow_load = None  # the tensor behind nsdg_snow_load_set (set_snow_load keeps it alive)
+        self.ssh = None  # the tensor behind nsdg_tilt_set (set_tilt keeps it alive)
 
     def _call(self, rc):
         if rc != 0:
@@ -828,6 +837,7 @@ class Context:
         self._call(self.lib.nsdg_grid_set(self.h, nx, ny, float(hx), float(hy)))
         if (nx, ny) != (self.nx, self.ny):
             self.land_mask = self.basal_depth = self.snow_load = None  # the library dropped a mask, a depth array and a snow field of the old shape
+            self.ssh = None  # and a sea-surface height
         self.nx, self.ny = nx, ny
 
     # ---- land mask (include/nsdg.h "land mask"): coastlines as fixed nodes of the sub-cycle
@@ -908,6 +918,32 @@ class Context:
         if cgh.numel() != n or cga.numel() != n or out.numel() != n:
             raise NsdgError("snow_load_nodal: the nodal arrays of the grid hold %d values" % n)
         self._call(self.lib.nsdg_snow_load_nodal(self.h, _ptr(cgh), _ptr(cga), _ptr(out)))
+
+    # ---- sea-surface tilt (include/nsdg_tilt.h): the tilt force from the gradient of a sea-surface height
+    def set_tilt(self, ssh, gravity=GRAVITY):
+        """nsdg_tilt_set: `ssh` = a contiguous float64 CUDA tensor of the local CG2 lattice, [2 ny + 1, 2 nx + 1] metres, kept alive by this
+        object while it is set; None clears it.  Read by the next coefficient packing"""
+        if ssh is not None:
+            _check_f64(ssh)
+            if ssh.numel() != (2 * self.nx + 1) * (2 * self.ny + 1):
+                raise NsdgError("the sea-surface height has shape %s, the local lattice is [%d, %d]" % (tuple(ssh.shape), 2 * self.ny + 1, 2 * self.nx + 1))
+        self._call(self.lib.nsdg_tilt_set(self.h, _ptr(ssh), float(gravity)))
+        self.ssh = ssh
+
+    def tilt_nodal(self, sx, sy):
+        """nsdg_tilt_nodal: sx, sy = the gradient of the sea-surface height the next packing would use, at every node of the CG2 lattice"""
+        _check_f64(sx, sy)
+        n = (2 * self.nx + 1) * (2 * self.ny + 1)
+        if sx.numel() != n or sy.numel() != n:
+            raise NsdgError("tilt_nodal: the nodal arrays of the grid hold %d values" % n)
+        self._call(self.lib.nsdg_tilt_nodal(self.h, _ptr(sx), _ptr(sy)))
+
+    def boxtest_ssh(self, domain_size, fc, gravity, ssh):
+        """nsdg_boxtest_ssh: ssh = the sea-surface height whose geostrophic current is the box test's gyre (boxtest_forcing: ocean)"""
+        _check_f64(ssh)
+        if ssh.numel() != (2 * self.nx + 1) * (2 * self.ny + 1):
+            raise NsdgError("boxtest_ssh: the nodal arrays of the grid hold %d values" % ((2 * self.nx + 1) * (2 * self.ny + 1)))
+        self._call(self.lib.nsdg_boxtest_ssh(self.h, float(domain_size), float(fc), float(gravity), _ptr(ssh)))
 
     def set_mevp_variant(self, variant):
         self._call(self.lib.nsdg_mevp_variant_set(self.h, variant))

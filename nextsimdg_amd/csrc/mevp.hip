@@ -164,11 +164,13 @@ __global__ __launch_bounds__(256) void mevp_velocity_basal_kernel(NodalConstsBas
 // psi_rt, node_average: mevp_common.h
 // per-step momentum coefficients of one node, 6 doubles (layout: mevp_common.h); BASAL: pair 3 = (T_b, 0) from the node's mean water
 // depth hwn as well (landfast ice, mevp_common.h: basal_critical_stress); SNOW: the mass of a node that is neither land nor ice-free
-// carries the snow's nodal mean cgs, weighted by r = rho_snow / rho_ice (snow load, mevp_common.h: snow_loaded_thickness)
-template <bool BASAL, bool SNOW>
+// carries the snow's nodal mean cgs, weighted by r = rho_snow / rho_ice (snow load, mevp_common.h: snow_loaded_thickness); TILT: the
+// sea-surface tilt is -m g (sx, sy) from the gradient of a sea-surface height (include/nsdg_tilt.h, mevp_common.h: tilt_gradient) in
+// place of the Coriolis terms of the ocean current
+template <bool BASAL, bool SNOW, bool TILT>
 __device__ __forceinline__ void pack_node(const nsdg_mevp_params& P, double dt, double u0, double v0, double tax, double tay,
     double uoc, double voc, double cgh, double cga, double* __restrict__ packed, long plane, long n, bool land, const nsdg_basal_params& B, double hwn,
-    double r, double cgs)
+    double r, double cgs, double g, double sx, double sy)
 {
     if constexpr (BASAL)
         store_nodal_tb(packed, plane, n, basal_critical_stress(P, B, cgh, cga, hwn, land));
@@ -197,6 +199,15 @@ __device__ __forceinline__ void pack_node(const nsdg_mevp_params& P, double dt, 
     const double mdt = P.rho_ice * h / dt;
     const double cor = P.rho_ice * h * P.fc;
     const double w = ice_free ? 0x1p100 : 1.;
+    if constexpr (TILT) {
+        // the products are statements of their own: rounded before they meet the sum (-ffp-contract=on fuses inside one expression only)
+        const double m_g = (P.rho_ice * h) * g;
+        const double tx = m_g * sx;
+        const double ty = m_g * sy;
+        const double c[6] = { w * h, w * (a * (P.c_ocean * P.rho_ocean)), w * (mdt * u0 + a * tax - tx), w * (mdt * v0 + a * tay - ty), uoc, voc };
+        store_nodal(packed, plane, n, c);
+        return;
+    }
     const double c[6] = { w * h, w * (a * (P.c_ocean * P.rho_ocean)), w * (mdt * u0 + a * tax - cor * voc), w * (mdt * v0 + a * tay + cor * uoc), uoc, voc };
     store_nodal(packed, plane, n, c);
 }
@@ -211,12 +222,14 @@ __device__ __forceinline__ void wind_tau(double f_atm, double ua, double va, dou
 // LAND: with the element land mask of the local array (nx x ny elements), land nodes are packed with the flag
 // BASAL: with the water depth of the same elements, pair 3 of a node is (T_b, 0)
 // SNOW: with the ncs coefficient planes of the snow on the same elements, the mass of a node carries its nodal mean
-template <bool LAND, bool BASAL, bool SNOW>
+// TILT: with the sea-surface height on the nodes, an ocean node reads it at its four lattice neighbours; a land node reads nothing of it
+template <bool LAND, bool BASAL, bool SNOW, bool TILT>
 __global__ __launch_bounds__(256) void mevp_pack_nodal_kernel(nsdg_mevp_params P, long nnodes, double dt,
     const double* __restrict__ u0, const double* __restrict__ v0, const double* __restrict__ tax,
     const double* __restrict__ tay, const double* __restrict__ uo, const double* __restrict__ vo,
     const double* __restrict__ cgh, const double* __restrict__ cga, double* __restrict__ packed, int nx, int ny, const uint8_t* __restrict__ land,
-    nsdg_basal_params B, const double* __restrict__ depth, const double* __restrict__ snow, int ncs, double r)
+    nsdg_basal_params B, const double* __restrict__ depth, const double* __restrict__ snow, int ncs, double r,
+    const double* __restrict__ ssh, double g, double hx, double hy)
 {
     const long n = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= nnodes)
@@ -231,7 +244,12 @@ __global__ __launch_bounds__(256) void mevp_pack_nodal_kernel(nsdg_mevp_params P
     double cgs = 0.;
     if constexpr (SNOW)
         cgs = node_average(nx, ny, ncs, snow, (int)(n % nn), (int)(n / nn));
-    pack_node<BASAL, SNOW>(P, dt, u0[n], v0[n], tax[n], tay[n], uo[n], vo[n], cgh[n], cga[n], packed, nodal_plane(nnodes), n, is_land, B, hwn, r, cgs);
+    double sx = 0., sy = 0.;
+    if constexpr (TILT)
+        if (!is_land)
+            tilt_gradient(nn, 2 * ny + 1, (int)(n % nn), (int)(n / nn), hx, hy, [&](int gx, int gy) { return ssh[(long)gy * nn + gx]; }, sx, sy);
+    pack_node<BASAL, SNOW, TILT>(P, dt, u0[n], v0[n], tax[n], tay[n], uo[n], vo[n], cgh[n], cga[n], packed, nodal_plane(nnodes), n, is_land, B, hwn, r, cgs,
+        g, sx, sy);
 }
 
 // node_average() on a tile of DG coefficients staged in LDS: tile[c][iy - ey0][ix - ex0]; same loops, same order of
@@ -266,12 +284,15 @@ __device__ __forceinline__ double node_average_tile(int nx, int ny, const double
 // BASAL: so are their water depths, and pair 3 of a node is (T_b, 0).
 // SNOW: so are the ncs (1, 3 or 6) coefficient planes of the snow, 4.6 KB more for six planes (14.3 KB in all); the nodal mean is read with
 // the loops of node_average_tile over ncs coefficients, the order of nsdg_dg_to_cg(ncs).
-template <bool LAND, bool BASAL, bool SNOW>
+// TILT: an ocean node reads the sea-surface height at its four lattice neighbours from global memory: the rows above and below are the
+// coalesced loads of ua, va, uo, vo over again; staging the 66 x 6 halo in LDS compiled to ~45 instructions and 3.1 KB of LDS more for
+// loads the cache already serves (profiles/tilt.md).
+template <bool LAND, bool BASAL, bool SNOW, bool TILT>
 __global__ __launch_bounds__(256) void mevp_prepare_kernel(nsdg_mevp_params P, int nx, int ny, double dt,
     const double* __restrict__ H, const double* __restrict__ A, const double* __restrict__ ua, const double* __restrict__ va,
     const double* __restrict__ uo, const double* __restrict__ vo, const double* __restrict__ u0, const double* __restrict__ v0,
     double* __restrict__ packed, const uint8_t* __restrict__ land, nsdg_basal_params B, const double* __restrict__ depth,
-    const double* __restrict__ snow, int ncs, double r)
+    const double* __restrict__ snow, int ncs, double r, const double* __restrict__ ssh, double g, double hx, double hy)
 {
     __shared__ double tile[2][6][PREP_TH][PREP_TW];
     __shared__ double stile[SNOW ? 6 : 1][PREP_TH][PREP_TW];
@@ -332,7 +353,12 @@ __global__ __launch_bounds__(256) void mevp_prepare_kernel(nsdg_mevp_params P, i
     double cgs = 0.;
     if constexpr (SNOW)
         cgs = node_average_tile(nx, ny, stile, ex0, ey0, gx, gy, ncs);
-    pack_node<BASAL, SNOW>(P, dt, u0[n], v0[n], tax, tay, uo[n], vo[n], cgh, cga, packed, nodal_plane((long)nn * nm), n, is_land, B, hwn, r, cgs);
+    double sx = 0., sy = 0.;
+    if constexpr (TILT)
+        if (!is_land)
+            tilt_gradient(nn, nm, gx, gy, hx, hy, [&](int x, int y) { return ssh[(long)y * nn + x]; }, sx, sy);
+    pack_node<BASAL, SNOW, TILT>(P, dt, u0[n], v0[n], tax, tay, uo[n], vo[n], cgh, cga, packed, nodal_plane((long)nn * nm), n, is_land, B, hwn, r, cgs, g,
+        sx, sy);
 }
 
 // one lane per CG2 node
@@ -474,18 +500,24 @@ int nsdg_mevp_pack_nodal(nsdg_ctx* ctx, double dt, const double* u0, const doubl
     const int snow_rc = nsdg_snow_check_packed(ctx, __func__, packed);
     if (snow_rc)
         return snow_rc;
+    const int tilt_rc = nsdg_tilt_check_packed(ctx, __func__, packed);
+    if (tilt_rc)
+        return tilt_rc;
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(nsdg_div_up(nnodes, 256)), dim3(256), 0, ctx->stream, ctx->mevp, nnodes, dt, u0, v0, tax, tay, uo, vo, cgh, cga,
-            packed, ctx->nx, ctx->ny, ctx->land, ctx->basal, ctx->depth, ctx->snow, ctx->snow_ncoef, nsdg_snow_ratio(ctx));
+            packed, ctx->nx, ctx->ny, ctx->land, ctx->basal, ctx->depth, ctx->snow, ctx->snow_ncoef, nsdg_snow_ratio(ctx), ctx->ssh,
+            ctx->gravity, ctx->hx, ctx->hy);
     };
-    auto choose = [&](auto snow) { // snow load (snowload.hip): a context without a snow field launches the instantiations it always did
-        constexpr bool SNOW = decltype(snow)::value;
+    // snow load (snowload.hip), sea-surface tilt (tilt.hip): a context without the field launches the instantiations it always did
+    auto choose = [&](auto snow, auto tilt) {
+        constexpr bool SNOW = decltype(snow)::value, TILT = decltype(tilt)::value;
         if (ctx->depth)
-            ctx->land ? launch(mevp_pack_nodal_kernel<true, true, SNOW>) : launch(mevp_pack_nodal_kernel<false, true, SNOW>);
+            ctx->land ? launch(mevp_pack_nodal_kernel<true, true, SNOW, TILT>) : launch(mevp_pack_nodal_kernel<false, true, SNOW, TILT>);
         else
-            ctx->land ? launch(mevp_pack_nodal_kernel<true, false, SNOW>) : launch(mevp_pack_nodal_kernel<false, false, SNOW>);
+            ctx->land ? launch(mevp_pack_nodal_kernel<true, false, SNOW, TILT>) : launch(mevp_pack_nodal_kernel<false, false, SNOW, TILT>);
     };
-    ctx->snow ? choose(std::true_type()) : choose(std::false_type());
+    auto choose_tilt = [&](auto snow) { ctx->ssh ? choose(snow, std::true_type()) : choose(snow, std::false_type()); };
+    ctx->snow ? choose_tilt(std::true_type()) : choose_tilt(std::false_type());
     NSDG_CHECK_LAUNCH();
     ctx->pack_dt = dt; // the launch constants K1, K2 of the velocity update belong to this packing
     ctx->pack_land = ctx->land != nullptr; // and so does the choice of the passes' instantiation: this packing flagged land nodes, or not,
@@ -505,18 +537,23 @@ int nsdg_mevp_prepare(nsdg_ctx* ctx, double dt, const double* H, const double* A
     const int snow_rc = nsdg_snow_check_packed(ctx, __func__, packed);
     if (snow_rc)
         return snow_rc;
+    const int tilt_rc = nsdg_tilt_check_packed(ctx, __func__, packed);
+    if (tilt_rc)
+        return tilt_rc;
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, ctx->mevp, ctx->nx, ctx->ny, dt, H, A, ua, va, uo, vo, u0, v0, packed, ctx->land,
-            ctx->basal, ctx->depth, ctx->snow, ctx->snow_ncoef, nsdg_snow_ratio(ctx));
+            ctx->basal, ctx->depth, ctx->snow, ctx->snow_ncoef, nsdg_snow_ratio(ctx), ctx->ssh,
+            ctx->gravity, ctx->hx, ctx->hy);
     };
-    auto choose = [&](auto snow) {
-        constexpr bool SNOW = decltype(snow)::value;
+    auto choose = [&](auto snow, auto tilt) {
+        constexpr bool SNOW = decltype(snow)::value, TILT = decltype(tilt)::value;
         if (ctx->depth)
-            ctx->land ? launch(mevp_prepare_kernel<true, true, SNOW>) : launch(mevp_prepare_kernel<false, true, SNOW>);
+            ctx->land ? launch(mevp_prepare_kernel<true, true, SNOW, TILT>) : launch(mevp_prepare_kernel<false, true, SNOW, TILT>);
         else
-            ctx->land ? launch(mevp_prepare_kernel<true, false, SNOW>) : launch(mevp_prepare_kernel<false, false, SNOW>);
+            ctx->land ? launch(mevp_prepare_kernel<true, false, SNOW, TILT>) : launch(mevp_prepare_kernel<false, false, SNOW, TILT>);
     };
-    ctx->snow ? choose(std::true_type()) : choose(std::false_type());
+    auto choose_tilt = [&](auto snow) { ctx->ssh ? choose(snow, std::true_type()) : choose(snow, std::false_type()); };
+    ctx->snow ? choose_tilt(std::true_type()) : choose_tilt(std::false_type());
     NSDG_CHECK_LAUNCH();
     ctx->pack_dt = dt;
     ctx->pack_land = ctx->land != nullptr;

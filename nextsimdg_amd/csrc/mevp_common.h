@@ -634,6 +634,25 @@ __device__ __forceinline__ double snow_loaded_thickness(double cgh, double r, do
     return hl;
 }
 
+// Sea-surface tilt (include/nsdg_tilt.h): the gradient of the sea-surface height at CG2 node (gx, gy) of the nn x nm lattice, whose nodes
+// are hx/2, hy/2 apart -- the ONE statement of it, shared by both packings (mevp.hip) and nsdg_tilt_nodal (tilt.hip).  `eta(gx, gy)` reads
+// the height at a node inside the lattice.  Centred difference; on the outermost row or column the one-sided difference over half the
+// distance, written as twice the difference (exact) over the same divisor.  A difference and one IEEE division: nothing to contract.
+template <class Eta>
+__device__ __forceinline__ void tilt_gradient(int nn, int nm, int gx, int gy, double hx, double hy, Eta eta, double& sx, double& sy)
+{
+    const int xl = max(gx - 1, 0), xh = min(gx + 1, nn - 1);
+    const int yl = max(gy - 1, 0), yh = min(gy + 1, nm - 1);
+    double dx = eta(xh, gy) - eta(xl, gy);
+    double dy = eta(gx, yh) - eta(gx, yl);
+    if (xh - xl == 1)
+        dx = 2. * dx;
+    if (yh - yl == 1)
+        dy = 2. * dy;
+    sx = dx / hx;
+    sy = dy / hy;
+}
+
 // Landfast ice (include/nsdg_basal.h; Lemieux et al. 2015): the critical stress T_b of a node from its nodal means of thickness,
 // concentration and water depth -- the ONE statement of it, shared by the packing (pair 3 of a node) and nsdg_basal_critical.  The
 // thickness is cgH itself, not raised to the mass floor; land and the ice-free rule come first.

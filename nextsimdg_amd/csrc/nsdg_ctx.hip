@@ -159,6 +159,7 @@ int nsdg_ctx_create(int device_id, void* stream, nsdg_ctx** out)
     nsdg_basal_default_params(&c->basal);
     c->depth = nullptr, c->pack_basal = false;
     c->snow = nullptr, c->snow_ncoef = 0, c->rho_snow = 0.;
+    c->ssh = nullptr, c->gravity = 0.;
     c->d_ptrs = nullptr;
     c->comm = nullptr;
     c->comm_group = 0;
@@ -303,6 +304,8 @@ int nsdg_grid_set(nsdg_ctx* ctx, int32_t nx, int32_t ny, double hx, double hy)
     NSDG_CHECK_ARG((long)(2 * (long)nx + 1) * (2 * (long)ny + 1) < (1L << 31), "grid too large for 32-bit node indices");
     if (ctx->nx != nx || ctx->ny != ny || ctx->hx != hx || ctx->hy != hy)
         ctx->pack_dt = 0.; // packed nodal coefficients belong to the old grid
+    if (ctx->nx != nx || ctx->ny != ny)
+        ctx->ssh = nullptr; // the sea-surface height (nsdg_tilt_set): (2nx+1)(2ny+1) nodes of the old shape
     if (ctx->nx != nx || ctx->ny != ny)
         ctx->land = nullptr, ctx->depth = nullptr, ctx->snow = nullptr; // and so do the land mask (nsdg_land_mask_set), the water depth (nsdg_basal_depth_set) and the snow field (nsdg_snow_load_set): nx * ny entries of the old shape
     ctx->nx = nx;

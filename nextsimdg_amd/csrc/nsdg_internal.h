@@ -37,6 +37,10 @@ struct nsdg_ctx {
     const double* snow;
     int snow_ncoef; // 1, 3 or 6 planes
     double rho_snow;
+    // sea-surface tilt (tilt.hip, include/nsdg_tilt.h): the sea-surface height on the nodes of the local lattice, null = none (the tilt is
+    // then that of the geostrophic current, as ever), owned by the caller; the packing reads it -- no flag of the packing goes with it
+    const double* ssh;
+    double gravity;
     int transport_variant, transport_rows; // transport stage kernel: 0 one element per lane / 2 two elements per lane; rows per workgroup
     int fused_min_waves; // register budget of the fused kernel: 1 or 2 waves per SIMD
     int nbounds; // closure of a transport step: bounds of the advected fields (0 = none), nsdg_transport_bounds_set
@@ -138,6 +142,10 @@ inline auto nsdg_with_order(int order, F&& f)
 static inline double nsdg_snow_ratio(const nsdg_ctx* ctx) { return ctx->snow ? ctx->rho_snow / ctx->mevp.rho_ice : 0.; }
 // NSDG_ERR_ARG, reported under `fn`, if the context's snow field overlaps the 8 (2nx+1)(2ny+1) doubles of `packed`; NSDG_OK without a field
 int nsdg_snow_check_packed(const nsdg_ctx* ctx, const char* fn, const double* packed);
+
+// ---- sea-surface tilt (tilt.hip) ------------------------------------------------------------------------------------------------
+// NSDG_ERR_ARG, reported under `fn`, if the context's sea-surface height overlaps the 8 (2nx+1)(2ny+1) doubles of `packed`; NSDG_OK without one
+int nsdg_tilt_check_packed(const nsdg_ctx* ctx, const char* fn, const double* packed);
 
 // ---- mEVP passes (mevp.hip) -----------------------------------------------------------------------------------------------------
 // the buffers of a pass: the stress S_in -> S_out (tiled), the velocity u_old -> u_new, the packed nodal coefficients, the ice strength

@@ -108,6 +108,13 @@
 //                            Needs dynamics.thermodynamics = true.  The restart file needs nothing new: the snow is in it
 //     dynamics.rho_snow      the density of that snow [kg m^-3], finite and >= 0 (default 330, the column step's); refused without
 //                            dynamics.snow_load
+//     dynamics.tilt          geostrophic (default: nothing changes) | ssh -- the sea-surface tilt is -m g grad(eta) of a sea-surface
+//                            height (include/nsdg_tilt.h) and (uo, vo) is the drag velocity alone: before every
+//                            coefficient packing the block's height is set on the context (nsdg_tilt_set); both rheologies.  The height
+//                            is the forcing file's optional variable ssh [m], sampled at the nodes with the wind and ocean pairs; with
+//                            any other forcing it is the box test's (nsdg_boxtest_ssh).  Refused: a forcing file with ocean_u / ocean_v
+//                            but no ssh, and ssh in the file without dynamics.tilt = ssh.  The restart file needs nothing new
+//     dynamics.gravity       g [m s^-2] of that tilt, finite and > 0 (default 9.81); refused without dynamics.tilt = ssh
 //     dynamics.row_blocks, dynamics.devices, dynamics.passes_per_exchange (2), dynamics.overlap (true),
 //     dynamics.graph (false), dynamics.loopback_world (0: off; N: rehearse an interior block of N on one GPU with
 //     real RCCL send/recv to the rank itself -- values wrap around, for timing and call-path checks only)
@@ -118,6 +125,7 @@
 #include "../../../include/nsdg_basal.h"
 #include "../../../include/nsdg_ocean.h"
 #include "../../../include/nsdg_snow.h"
+#include "../../../include/nsdg_tilt.h"
 #include <algorithm>
 #include <memory>
 #include <string>
@@ -176,6 +184,8 @@ public:
     static void placeRows(FieldStore& f, bool thermodynamics, int nx, int r0, int r1, const double* data, std::size_t count, bool slabOcean = false);
     //! the keys of the brittle rheology (dynamics.rheology, dynamics.bbm_courant, bbm.*): a step that does not run it refuses them
     static const std::vector<std::string>& brittleKeys();
+    //! dynamics.tilt and dynamics.gravity: the keys that Nextsim::HipStep, which has no momentum equation, refuses
+    static const std::vector<std::string>& tiltKeys();
     //! the names of dynamics.tracers from its value; throws std::invalid_argument, naming the key, for more than NSDG_TRACERS_MAX names, a
     //! name given twice, one that is no identifier and one that a restart file or the state already uses
     static std::vector<std::string> tracerNames(const std::string& value);
@@ -213,6 +223,8 @@ private:
     bool slabOcean = false; // dynamics.slab_ocean: sst and sss follow the ice (nsdg_column_step_ocean)
     bool snowLoad = false; // dynamics.snow_load: the packing takes the nodal mass from ice and snow (nsdg_snow_load_set before every packing)
     double rhoSnow = NSDG_SNOW_DENSITY; // dynamics.rho_snow
+    bool tiltSsh = false; // dynamics.tilt = ssh: the packing takes the tilt from the block's sea-surface height (nsdg_tilt_set before every packing)
+    double gravity = NSDG_GRAVITY; // dynamics.gravity
     nsdg_slab_params m_slab; // [slabocean]: relaxation times and the salinity of the ice (used with slabOcean)
     struct Outputs; // model.output_*, series_*, drifters_*, stations_*: the four outputs, each null when off (DynamicsStep.cpp)
     std::unique_ptr<Outputs> m_out;

@@ -6,6 +6,7 @@
 //     tair tdew slp qsw qlw mld snowfall    (nt, nyr, nxr)  the column forcing planes, units of the structure's planes
 //     wind_u wind_v, ocean_u ocean_v        (nt, nyr, nxr)  optional, each pair complete or absent [m/s]
 //     sst sss                               (nt, nyr, nxr)  optional, a pair: the relaxation targets of dynamics.slab_ocean [deg C, psu]
+//     ssh                                   (nt, nyr, nxr)  optional: the sea-surface height of dynamics.tilt = ssh [m]
 // All variables share one lattice: cell-centred over the model's square domain, point i at x / L = (i + 1/2) / nxr.  There are
 // no coordinate variables: lon/lat or other lattices, chunked or compressed datasets and unknown variables are refused.
 // Every check happens when the file is opened, before a device is touched; each error names the file, the variable and the
@@ -21,7 +22,7 @@ namespace Nextsim {
 class ForcingFile {
 public:
     static const std::vector<std::string>& columnVariables(); //!< tair tdew slp qsw qlw mld snowfall
-    static const std::vector<std::string>& knownVariables(); //!< the column variables, wind_u wind_v, ocean_u ocean_v, sst sss
+    static const std::vector<std::string>& knownVariables(); //!< the column variables, wind_u wind_v, ocean_u ocean_v, sst sss, ssh
 
     //! Reads and checks the file; needColumn: the seven column variables must be present (dynamics.thermodynamics = true).
     //! Throws std::runtime_error naming the file.
@@ -37,6 +38,7 @@ public:
     bool hasWind() const { return has("wind_u"); }
     bool hasOcean() const { return has("ocean_u"); }
     bool hasSlabTargets() const { return has("sst"); } //!< the pair sst, sss
+    bool hasSsh() const { return has("ssh"); } //!< the sea-surface height of dynamics.tilt = ssh
     std::vector<std::string> variables() const; //!< present variables, in the order of knownVariables()
 
     //! The records around model time t: k0 = the last record with time[k0] <= t, k1 = k0 + 1, w = (t - time[k0]) / (time[k1] - time[k0]);

@@ -109,7 +109,7 @@ void DynamicsBlock::createContext(bool phaseTiming)
         check(nsdg_phase_timing_set(c, 1), "nsdg_phase_timing_set");
 }
 
-void DynamicsBlock::allocate(bool brittle, bool advectColumn, int ntracers_)
+void DynamicsBlock::allocate(bool brittle, bool advectColumn, int ntracers_, bool tiltSsh)
 {
     ntracers = ntracers_;
     const long TS = nsdg_tiled_len(nx, ny, 8), TP = nsdg_tiled_len(nx, ny, 9);
@@ -137,6 +137,7 @@ void DynamicsBlock::allocate(bool brittle, bool advectColumn, int ntracers_)
     for (int a : { HG, EG, PM })
         sizes[a] = brittle ? TP : 0;
     sizes[ZERO] = brittle ? NN : 0;
+    sizes[SSH] = tiltSsh ? NN : 0;
     long total = 0;
     for (long s : sizes)
         total += (s + 1) & ~1L; // keep every sub-array 16-byte aligned

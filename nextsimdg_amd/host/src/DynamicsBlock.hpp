@@ -63,8 +63,9 @@ static_assert(fieldsOfARun(AdvectedField::BRITTLE) <= NSDG_RB_MAX_FIELDS && fiel
 
 // further device arrays of a block; the stress (its components in the order of DynamicsBlock.cpp's STRESS) and the velocity exist twice
 // (ping-pong)
-// (HG, EG, PM, ZERO: the Gauss arrays of nsdg_bbm_prepare and the zero nodal array its packing takes as u0, v0 -- empty under mEVP)
-enum Arr { S11a, S12a, S22a, S11b, S12b, S22b, PG, VXDG, VYDG, UNX, UNY, Ua, Va, Ub, Vb, UA, VA, UO, VO, PACKED, COL, HG, EG, PM, ZERO, NARR };
+// (HG, EG, PM, ZERO: the Gauss arrays of nsdg_bbm_prepare and the zero nodal array its packing takes as u0, v0 -- empty under mEVP;
+// SSH: the sea-surface height at the nodes of dynamics.tilt = ssh -- empty without it)
+enum Arr { S11a, S12a, S22a, S11b, S12b, S22b, PG, VXDG, VYDG, UNX, UNY, Ua, Va, Ub, Vb, UA, VA, UO, VO, PACKED, COL, HG, EG, PM, ZERO, SSH, NARR };
 // column planes inside COL
 enum Col { C_HSNOW, C_TICE, C_SST, C_SSS, C_TAIR, C_TDEW, C_SLP, C_QSW, C_QLW, C_MLD, C_SNOWFALL, C_WIND, C_NEWICE, NCOL };
 
@@ -134,7 +135,7 @@ public:
     void createContext(bool phaseTiming);
     //! which rows of ADVECTED this run advects; the arrays of Arr and the advected fields: one allocation, zeroed, every array 16-byte aligned
     //! ntracers: the planes and buffers of dynamics.tracers as well
-    void allocate(bool brittle, bool advectColumn, int ntracers = 0);
+    void allocate(bool brittle, bool advectColumn, int ntracers = 0, bool tiltSsh = false);
     //! the block's rows of the mask, ghost rows included, on the device and on the context: the mask is static, nothing is ever exchanged
     void setLandMask(const LandMaskFile& mask);
     //! the block's rows of the water depth, ghost rows included, and the grounding scheme's parameters, on the device and on the context

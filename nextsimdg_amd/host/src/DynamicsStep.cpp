@@ -39,7 +39,8 @@ const std::map<int, std::string> Configured<DynamicsStep>::keyMap = { { 0, "dyna
     { 18, "dynamics.substep_courant" }, { 19, "dynamics.max_substeps" }, { 20, "dynamics.forcing_file" },
     { 21, "dynamics.advect_column_state" }, { 22, "dynamics.land_mask_file" }, { 23, "dynamics.rheology" },
     { 24, "dynamics.bbm_courant" }, { 25, "dynamics.tracers" }, { 26, "dynamics.tracer_init" },
-    { 27, "dynamics.bathymetry_file" }, { 28, "dynamics.slab_ocean" }, { 29, "dynamics.snow_load" }, { 30, "dynamics.rho_snow" } };
+    { 27, "dynamics.bathymetry_file" }, { 28, "dynamics.slab_ocean" }, { 29, "dynamics.snow_load" }, { 30, "dynamics.rho_snow" },
+    { 31, "dynamics.tilt" }, { 32, "dynamics.gravity" } };
 
 // dynamics.rheology = bbm
 struct DynamicsStep::Brittle {
@@ -117,6 +118,12 @@ std::vector<std::string> DynamicsStep::tracerNames(const std::string& value)
     if (names.size() > NSDG_TRACERS_MAX)
         throw std::invalid_argument(key + ": " + std::to_string(names.size()) + " names; the tracer group carries at most " + std::to_string(NSDG_TRACERS_MAX));
     return names;
+}
+
+const std::vector<std::string>& DynamicsStep::tiltKeys()
+{
+    static const std::vector<std::string> keys = { keyMap.at(31), keyMap.at(32) };
+    return keys;
 }
 
 const std::vector<std::string>& DynamicsStep::brittleKeys()
@@ -289,6 +296,25 @@ void DynamicsStep::configure()
         rhoSnow = getConfiguration(keyMap.at(30), (double)NSDG_SNOW_DENSITY);
         if (!std::isfinite(rhoSnow) || rhoSnow < 0.)
             throw std::invalid_argument("dynamics.rho_snow = " + std::to_string(rhoSnow) + ": need a finite density >= 0");
+    }
+    // sea-surface tilt (include/nsdg_tilt.h): from the geostrophic current, as ever, or from a sea-surface height -- the rule of
+    // nsdg_tilt_set and what the forcing file must hold, applied here, before any device is touched
+    {
+        const std::string tilt = getConfiguration(keyMap.at(31), std::string("geostrophic"));
+        if (tilt != "geostrophic" && tilt != "ssh")
+            throw std::invalid_argument("dynamics.tilt must be geostrophic or ssh, got \"" + tilt + "\"");
+        tiltSsh = tilt == "ssh";
+        std::string raw;
+        if (Configurator::lookup(keyMap.at(32), raw) && !tiltSsh)
+            throw std::invalid_argument("dynamics.gravity needs dynamics.tilt = ssh");
+        gravity = getConfiguration(keyMap.at(32), (double)NSDG_GRAVITY);
+        if (!std::isfinite(gravity) || !(gravity > 0.))
+            throw std::invalid_argument("dynamics.gravity = " + std::to_string(gravity) + ": need a finite gravity > 0");
+        if (m_forcingFile && m_forcingFile->hasSsh() && !tiltSsh)
+            throw std::invalid_argument("dynamics.forcing_file " + m_forcingFile->path() + " holds ssh: it needs dynamics.tilt = ssh");
+        if (m_forcingFile && tiltSsh && m_forcingFile->hasOcean() && !m_forcingFile->hasSsh())
+            throw std::invalid_argument("dynamics.tilt = ssh: dynamics.forcing_file " + m_forcingFile->path() + " holds ocean_u / ocean_v but no ssh -- "
+                                        "the current is then the drag velocity alone and the tilt needs the height");
     }
     if (loopbackWorld != 0 && loopbackWorld < 3)
         throw std::invalid_argument("dynamics.loopback_world needs an interior block: at least 3");
@@ -503,7 +529,7 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
             check(nsdg_column_params_set(ctx, &p), "nsdg_column_params_set");
         }
         // ---- arrays
-        b.allocate(m_brittle != nullptr, advectColumn, (int)m_tracers.size());
+        b.allocate(m_brittle != nullptr, advectColumn, (int)m_tracers.size(), tiltSsh);
         check(nsdg_grid_set(ctx, b.nx, b.ny, L / nxf, L / nyf), "nsdg_grid_set");
         check(nsdg_block_set(ctx, b.lo, b.nyGlobal), "nsdg_block_set");
         // ---- land mask, upload
@@ -518,6 +544,11 @@ void DynamicsStep::start(const Iterator::TimePoint& startTime)
         // ---- forcing: the analytic box test, evaluated on the device (ocean once, wind at the current model time every step); a forcing
         // file's wind and ocean pairs replace it at every step
         check(nsdg_boxtest_forcing(ctx, L, m_time, b.d[UA], b.d[VA], b.d[UO], b.d[VO]), "nsdg_boxtest_forcing");
+        if (tiltSsh) { // the height whose geostrophic current is that gyre; a forcing file's ssh replaces it at every step
+            nsdg_mevp_params p;
+            nsdg_mevp_default_params(&p);
+            check(nsdg_boxtest_ssh(ctx, L, p.fc, gravity, b.d[SSH]), "nsdg_boxtest_ssh");
+        }
         if (m_forcingFile) // two records of every variable
             b.allocateRecords(2 * m_forcingFile->variables().size() * (std::size_t)m_forcingFile->nxr() * m_forcingFile->nyr());
         if (m_landMask)
@@ -663,6 +694,8 @@ void DynamicsStep::subStep(double dt, bool last)
         check(nsdg_phase_mark(ctx, NSDG_PHASE_PREPARE), "nsdg_phase_mark");
         if (snowLoad) // the snow as it stands after this step's column step; the transport's ping-pong moves S: set before every packing
             check(nsdg_snow_load_set(ctx, advectColumn ? b.cur(FS) : b.col(C_HSNOW), advectColumn ? 6 : 1, rhoSnow), "nsdg_snow_load_set");
+        if (tiltSsh) // the block's sea-surface height: the packing below reads it
+            check(nsdg_tilt_set(ctx, b.d[SSH], gravity), "nsdg_tilt_set");
         int32_t out = 0;
         if (m_brittle) {
             // the Gauss arrays of the brittle sub-cycle and the mEVP packing for the sub-iteration's dt with u0 = v0 = 0: no ice strength
@@ -774,7 +807,8 @@ void DynamicsStep::sampleForcingFile(DynamicsBlock& b, std::size_t k0, std::size
     // one launch per lattice: the wind and ocean pairs at the CG2 nodes, the column planes at the element centres
     std::vector<const double*> r0, r1;
     std::vector<double*> out;
-    for (const auto& pr : { std::make_pair("wind_u", UA), std::make_pair("wind_v", VA), std::make_pair("ocean_u", UO), std::make_pair("ocean_v", VO) })
+    for (const auto& pr : { std::make_pair("wind_u", UA), std::make_pair("wind_v", VA), std::make_pair("ocean_u", UO), std::make_pair("ocean_v", VO),
+             std::make_pair("ssh", SSH) })
         if (ff.has(pr.first)) {
             r0.push_back(rec(0, pr.first)), r1.push_back(rec(1, pr.first)), out.push_back(b.d[pr.second]);
         }

@@ -26,7 +26,7 @@ const std::vector<std::string>& ForcingFile::columnVariables()
 const std::vector<std::string>& ForcingFile::knownVariables()
 {
     static const std::vector<std::string> v = { "tair", "tdew", "slp", "qsw", "qlw", "mld", "snowfall", "wind_u", "wind_v", "ocean_u",
-        "ocean_v", "sst", "sss" };
+        "ocean_v", "sst", "sss", "ssh" };
     return v;
 }
 
@@ -91,7 +91,7 @@ ForcingFile::ForcingFile(const std::string& path, bool needColumn)
         fail(e.what());
     }
     if (m_vars.empty())
-        fail("no forcing variable (known: tair tdew slp qsw qlw mld snowfall wind_u wind_v ocean_u ocean_v sst sss)");
+        fail("no forcing variable (known: tair tdew slp qsw qlw mld snowfall wind_u wind_v ocean_u ocean_v sst sss ssh)");
     for (const auto& pair : { std::make_pair("wind_u", "wind_v"), std::make_pair("ocean_u", "ocean_v"), std::make_pair("sst", "sss") })
         if (has(pair.first) != has(pair.second))
             fail(std::string("variable ") + (has(pair.first) ? pair.first : pair.second) + " without " + (has(pair.first) ? pair.second : pair.first)

@@ -60,6 +60,9 @@ void HipStep::init()
         for (const std::string& key : DynamicsStep::brittleKeys())
             if (Configurator::lookup(key, raw))
                 throw std::invalid_argument(key + " is set, but Nextsim::HipStep runs the column step alone: select Nextsim::DynamicsStep");
+        for (const std::string& key : DynamicsStep::tiltKeys()) // ... and no momentum equation to tilt
+            if (Configurator::lookup(key, raw))
+                throw std::invalid_argument(key + " is set, but Nextsim::HipStep runs the column step alone: select Nextsim::DynamicsStep");
     }
     if (!ctx)
         check(nsdg_ctx_create(0, nullptr, &ctx), "HipStep::init");

@@ -1,7 +1,7 @@
 // make_forcing.cpp -- writes the forcing file of dynamics.forcing = file (host/include/ForcingFile.hpp) from .npy arrays, and
 // describes one.
 //
-//     make_forcing --out f.nc --time t.npy tair=tair.npy tdew=tdew.npy ... [wind_u=u.npy wind_v=v.npy] [ocean_u=... ocean_v=...]
+//     make_forcing --out f.nc --time t.npy tair=tair.npy tdew=tdew.npy ... [wind_u=u.npy wind_v=v.npy] [ocean_u=... ocean_v=...] [ssh=ssh.npy]
 //     make_forcing --check f.nc
 //
 // The arrays are float64 .npy files (little-endian, C order): time of shape (nt), every variable of shape (nt, nyr, nxr).  The
@@ -29,7 +29,7 @@ void usage()
 {
     std::cerr << "usage: make_forcing --out FILE --time TIME.npy NAME=ARRAY.npy ...\n"
                  "       make_forcing --check FILE\n"
-                 "NAME: tair tdew slp qsw qlw mld snowfall wind_u wind_v ocean_u ocean_v sst sss; TIME (nt) in model seconds, every ARRAY\n"
+                 "NAME: tair tdew slp qsw qlw mld snowfall wind_u wind_v ocean_u ocean_v sst sss ssh; TIME (nt) in model seconds, every ARRAY\n"
                  "(nt, nyr, nxr) float64 on one cell-centred lattice over the model's square domain\n";
 }
 

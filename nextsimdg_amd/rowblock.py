@@ -287,7 +287,13 @@ class DynamicsCore:
     tracers=("age", "origin"): named intensive planes that ride on the ice (include/nsdg.h "ice tracers") as
     Q = H T in a transport group of their own after the run of H and A; "age" grows by dt where there is ice, every other name is
     passive; tracers_read() / load_tracers() and the key "tracers" of state_dict() hold them.  None or (): no tracers, the same calls as
-    ever."""
+    ever.
+
+    tilt="ssh" (include/nsdg_tilt.h): the sea-surface tilt is -m g grad(eta) of a sea-surface height, the nodal
+    buffer self.ssh [m] -- filled by set_ssh() from a global array, by device_ssh() with the box test's, or by a ForcingSeries that holds
+    "ssh" (CoupledCore) -- and (uo, vo) is the drag velocity alone.  prepare() sets the field on the ops object before the coefficient
+    packing and clears it after it.  gravity: g [m s^-2], None = abi.GRAVITY.  tilt="geostrophic", the default: the tilt of the geostrophic
+    current, -m f_c k x u_o, the same calls as ever.  The height is forcing: the state dict does not hold it."""
 
     ORDER = 2
     # closure of the transported fields (include/nsdg.h "INPUT DOMAIN AND CLOSURE"): mean thickness H >= 0; concentration
@@ -306,6 +312,7 @@ class DynamicsCore:
     # tracers= (include/nsdg.h "ice tracers"): the calls it needs, the name that ages, and the names a tracer may not take -- the keys of
     # state_dict() and of the column state
     TRACER_OPS = ("tracers_weight", "tracers_recover", "tracers_dilute")
+    TILT_OPS = ("set_tilt", "tilt_nodal", "boxtest_ssh")
     AGE_TRACER = "age"
     STATE_KEYS = ("rows", "ny_global", "nx", "H", "A", "S", "Q", "D", "u", "v", "s11", "s12", "s22", "drifters", "tracers", "hsnow", "tice0")
     HISTORY_COLUMN_FIELDS = outputs.History.COLUMN_FIELDS
@@ -316,7 +323,8 @@ class DynamicsCore:
     def __init__(self, ops, blk, hx, hy, dt, nsub, device, exchanger=None, overlap=True, native=False, use_graph=False, closure=True,
                  phase_timing=False, land=None, rheology="mevp", bbm=None, history=None, series=None, series_capacity=1024, extent_conc=0.15,
                  drifters=None, drifter_min_conc=0.15, drifter_fields=None, stations=None, station_fields=None, station_capacity=256,
-                 tracers=None, min_conc=1e-12, min_thick=0.01, bathymetry=None, basal=None, snow_load=False, rho_snow=None):
+                 tracers=None, min_conc=1e-12, min_thick=0.01, bathymetry=None, basal=None, snow_load=False, rho_snow=None,
+                 tilt="geostrophic", gravity=None):
         if snow_load or rho_snow is not None:  # (CoupledCore takes the two itself and does not pass them on)
             raise ValueError("snow_load= needs the column state of a CoupledCore: a DynamicsCore carries no snow")
         self.ops, self.blk, self.hx, self.hy, self.dt, self.nsub, self.overlap = ops, blk, hx, hy, dt, nsub, overlap
@@ -331,6 +339,7 @@ class DynamicsCore:
         self.halo = exchanger if exchanger is not None else HaloExchanger(blk)
         # Everything that can refuse comes first: a constructor that raises has changed nothing on `ops`
         self._check_rheology(rheology, bbm)
+        self._check_tilt(tilt, gravity)
         self.TRANSPORTED, self.BOUNDS = self._transported()
         # tracers: names of intensive quantities that ride on the ice (include/nsdg.h "ice tracers"), "age" the one
         # that ages; min_conc / min_thick: the ice test of their recovery (the ice-free-node rule's defaults; 0 and 0 with closure = False)
@@ -339,13 +348,15 @@ class DynamicsCore:
         # land: bool array [ny_global, nx] of the WHOLE domain (True = land; include/nsdg.h "land mask"): the nodes of
         # land elements hold u = v = 0 like the array edge.  This rank keeps its rows, ghost rows included -- the mask is static, nothing
         # is exchanged -- and sets them on the ops object whenever it sets the grid
-        self.land, self._land_on_ops = None, False
+        self.land, self._land_on_ops, self._land_global = None, False, None
         if land is not None:
             outputs.require_ops(ops, self.LAND_OPS, "land=", "land-mask calls")
             land = np.asarray(land)
             if land.shape != (blk.ny_glob, blk.nx):
                 raise ValueError("land must be a [ny_global, nx] = [%d, %d] array, got shape %s" % (blk.ny_glob, blk.nx, land.shape))
             self.land = torch.from_numpy(np.ascontiguousarray(land[blk.elem_slice()] != 0).astype(np.uint8)).to(device)
+            if self.tilt == "ssh":
+                self._land_global = land != 0  # set_ssh() asks where the height must be finite
         # bathymetry: float64 [ny_global, nx] water depth in metres of the WHOLE domain (include/nsdg_basal.h): ice
         # whose keels reach the seabed feels a basal stress and can stay fast over a shoal.  Like the mask: this rank keeps its rows, ghost
         # rows included, nothing is exchanged, and they go to the ops object with the grid.  basal: an abi.BasalParams (None: whatever
@@ -426,6 +437,8 @@ class DynamicsCore:
         self.u, self.v, self.ub, self.vb = z(*nodal), z(*nodal), z(*nodal), z(*nodal)
         self.ua, self.va = z(*nodal), z(*nodal)
         self.uo, self.vo = z(*nodal), z(*nodal)
+        if self.tilt == "ssh":
+            self.ssh = z(*nodal)  # the sea-surface height [m] at the nodes, ghost rows included: forcing, like uo and vo
         self.packed = z(nodal[0] * nodal[1] * 8)  # per-step momentum coefficients, 8 per node
         self.adv = (z(6, ny, nx), z(6, ny, nx), z(3, ny, nx + 1), z(3, ny + 1, nx))
         self.t1 = [z(6, ny, nx) for _ in range(nf)]
@@ -463,6 +476,60 @@ class DynamicsCore:
             outputs.require_ops(self.ops, self.BBM_OPS, "rheology='bbm'", "BBM calls")
         elif bbm is not None:
             raise ValueError("bbm= parameters need rheology='bbm'")
+
+    def _check_tilt(self, tilt, gravity):
+        """tilt= and gravity=, refused before anything is asked of `ops` but the presence of the calls"""
+        if tilt not in ("geostrophic", "ssh"):
+            raise ValueError("tilt must be 'geostrophic' or 'ssh', got %r" % (tilt,))
+        if gravity is not None and tilt != "ssh":
+            raise ValueError("gravity= needs tilt='ssh'")
+        self.tilt = tilt
+        self.gravity = abi.GRAVITY if gravity is None else float(gravity)
+        if tilt == "ssh":
+            outputs.require_ops(self.ops, self.TILT_OPS, "tilt='ssh'", "sea-surface tilt calls")
+            if not (np.isfinite(self.gravity) and self.gravity > 0.0):
+                raise ValueError("gravity must be finite and > 0, got %r" % (self.gravity,))
+
+    def _need_tilt(self, what):
+        if self.tilt != "ssh":
+            raise ValueError("%s needs a core constructed with tilt='ssh'" % what)
+
+    def set_ssh(self, eta):
+        """the sea-surface height [m] from a global [2 ny_global + 1, 2 nx + 1] array of the WHOLE domain's nodes: this rank keeps its
+        rows, ghost rows included.  It must be finite at every node of every ocean element; strictly inside land it may be anything"""
+        self._need_tilt("set_ssh()")
+        b = self.blk
+        eta = np.asarray(eta, dtype=np.float64)
+        if eta.shape != (2 * b.ny_glob + 1, 2 * b.nx + 1):
+            raise ValueError("ssh must be a [2 ny_global + 1, 2 nx + 1] = [%d, %d] array, got shape %s" % (2 * b.ny_glob + 1, 2 * b.nx + 1, eta.shape))
+        needed = np.zeros(eta.shape, dtype=bool)  # the nodes of ocean elements
+        ocean = np.ones((b.ny_glob, b.nx), dtype=bool) if self._land_global is None else ~self._land_global
+        for dy in range(3):
+            for dx in range(3):
+                needed[dy:dy + 2 * b.ny_glob:2, dx:dx + 2 * b.nx:2] |= ocean
+        bad = needed & ~np.isfinite(eta)
+        if bad.any():
+            gy, gx = (int(k) for k in np.argwhere(bad)[0])
+            raise ValueError("ssh must be finite at the nodes of ocean elements: %r at node (row %d, column %d)" % (float(eta[gy, gx]), gy, gx))
+        _put(self.ssh, eta[b.node_slice()])
+
+    def device_ssh(self, domain_size, fc):
+        """the sea-surface height whose geostrophic current is the box test's gyre (Coriolis parameter fc), evaluated on the device for
+        this rank's rows"""
+        self._need_tilt("device_ssh()")
+        self._set_grid()
+        self.ops.boxtest_ssh(domain_size, fc, self.gravity, self.ssh)
+
+    def tilt_read(self):
+        """(sx, sy): the gradient of the sea-surface height at the node rows this rank owns, what the next coefficient packing uses
+        (nsdg_tilt_nodal)"""
+        self._need_tilt("tilt_read()")
+        self._set_grid()
+        sx, sy = torch.zeros_like(self.ssh), torch.zeros_like(self.ssh)
+        self.ops.set_tilt(self.ssh, self.gravity)
+        self.ops.tilt_nodal(sx, sy)
+        self.ops.set_tilt(None)
+        return self.owned(sx), self.owned(sy)
 
     def _check_tracers(self, tracers):
         """tracers= as a tuple of names (None and () alike: none), refused before anything is asked of `ops` but the presence of the calls"""
@@ -675,6 +742,15 @@ class DynamicsCore:
         """once per model step: ice strength at the Gauss points, nodal means of H and A, wind stress and the packed
         momentum coefficients (one launch); the velocity at the start of the step is read from the current iterate
         (it is only needed inside the packing)"""
+        if self.tilt == "ssh":
+            # on the ops object for the packing alone: another core on the same context packs with its own tilt
+            self.ops.set_tilt(self.ssh, self.gravity)
+            self._pack()
+            self.ops.set_tilt(None)
+        else:
+            self._pack()
+
+    def _pack(self):
         ops, b = self.ops, self.blk
         if self.rheology == "bbm":
             # the Gauss arrays of the brittle sub-cycle, and the mEVP packing for the sub-step dt / nsub with u0 = v0 = 0
@@ -1062,13 +1138,15 @@ class ForcingSeries:
     """Forcing records on one lattice at model times (include/nsdg.h "forcing from a file"; the C++ host reads the same records from a
     file, host/include/ForcingFile.hpp).  times: strictly increasing model times [s] (the clock of CoupledCore.time); fields: name ->
     float64 array [nt, nyr, nxr] on a cell-centred lattice over the square domain.  Names: the column planes tair tdew slp qsw qlw mld
-    snowfall, and the pairs wind_u / wind_v and ocean_u / ocean_v (each pair complete or absent).  A time outside [times[0], times[-1]]
+    snowfall, the pairs wind_u / wind_v and ocean_u / ocean_v (each pair complete or absent), and the sea-surface height ssh [m] of a core
+    with tilt="ssh" (sampled at the nodes with the pairs).  A time outside [times[0], times[-1]]
     is an error: there is no extrapolation."""
 
     COLUMN = ("tair", "tdew", "slp", "qsw", "qlw", "mld", "snowfall")
     WIND = ("wind_u", "wind_v")
     OCEAN = ("ocean_u", "ocean_v")
     SLAB = ("sst", "sss")  # the relaxation targets of a slab ocean (CoupledCore(slab_ocean=True)), a pair
+    SSH = ("ssh",)  # the sea-surface height of tilt="ssh" (include/nsdg_tilt.h), a nodal variable like the pairs
 
     def __init__(self, times, fields):
         t = np.array(times, dtype=np.float64)
@@ -1078,7 +1156,7 @@ class ForcingSeries:
             raise ValueError("times must be finite and strictly increasing")
         if not fields:
             raise ValueError("a forcing series needs at least one field")
-        known = self.COLUMN + self.WIND + self.OCEAN + self.SLAB
+        known = self.COLUMN + self.WIND + self.OCEAN + self.SLAB + self.SSH
         out = {}
         for name, a in fields.items():
             if name not in known:
@@ -1171,6 +1249,14 @@ class CoupledCore(DynamicsCore):
             if not (np.isfinite(self.rho_snow) and self.rho_snow >= 0.0):
                 raise ValueError("rho_snow must be finite and >= 0, got %r" % (self.rho_snow,))
         self._snow_on_ops = False
+        if isinstance(forcing, ForcingSeries):
+            # the tilt and the series agree on who states it (refused before the base class changes anything on `ops`)
+            ssh_tilt, has_ssh = kw.get("tilt", "geostrophic") == "ssh", "ssh" in forcing.fields
+            if has_ssh and not ssh_tilt:
+                raise ValueError("the forcing series holds ssh: it needs tilt='ssh'")
+            if ssh_tilt and "ocean_u" in forcing.fields and not has_ssh:
+                raise ValueError("tilt='ssh' with ocean_u / ocean_v from the forcing series needs the series to hold ssh as well: "
+                                 "the current is then the drag velocity alone")
         self.slab_ocean = bool(slab_ocean)
         if slab is not None and not self.slab_ocean:
             raise ValueError("slab= needs slab_ocean=True")
@@ -1205,7 +1291,8 @@ class CoupledCore(DynamicsCore):
                 raise ValueError("the column step needs the forcing series to hold %s" % ", ".join(missing))
             # one launch per lattice and step: the column planes at the element centres, the wind and ocean pairs at the nodes
             self._series_groups = [("elements", ForcingSeries.COLUMN, [self.col[k] for k in ForcingSeries.COLUMN])]
-            nodal = [(names, outs) for names, outs in ((ForcingSeries.WIND, (self.ua, self.va)), (ForcingSeries.OCEAN, (self.uo, self.vo)))
+            nodal = [(names, outs) for names, outs in ((ForcingSeries.WIND, (self.ua, self.va)), (ForcingSeries.OCEAN, (self.uo, self.vo)),
+                                                        (ForcingSeries.SSH, (getattr(self, "ssh", None),)))
                      if names[0] in forcing.fields]
             if nodal:
                 self._series_groups.append(("nodes", sum((n for n, _ in nodal), ()), [o for _, outs in nodal for o in outs]))

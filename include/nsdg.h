@@ -607,6 +607,13 @@ int nsdg_land_clear_nodes(nsdg_ctx* ctx, double* u, double* v);
  * test's height and their checks are declared in nsdg_tilt.h, which this header includes. */
 #include "nsdg_tilt.h"
 
+/* ---- momentum balance diagnostics: nodal forces and their power (csrc/budget.hip) ------------------------------
+ * One launch after the sub-cycle evaluates every term of the nodal momentum balance -- wind, water drag, Coriolis, sea-surface tilt,
+ * internal stress divergence, seabed stress, inertia -- and the residual of the implicit step, at the state the sub-cycle left and with the
+ * coefficients of its packing; per element row, the power of every term and the kinetic energy in a fixed order of summation.  The
+ * arithmetic, the outputs and their checks are declared in nsdg_budget.h, which this header includes. */
+#include "nsdg_budget.h"
+
 /* ---- brittle rheology: the brittle Bingham-Maxwell (BBM) sub-cycle (csrc/bbm.hip, csrc/bbm_common.h) ------------
  * A second rheology beside mEVP: damage, a Mohr-Coulomb envelope, Maxwell relaxation.  No counterpart in the reference snapshot; built from
  * the published formulation (Olason et al. 2022, "A new brittle rheology and numerical framework for large-scale sea-ice models", JAMES;

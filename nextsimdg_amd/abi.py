@@ -287,6 +287,21 @@ TILT_SYMBOLS = {
 }
 GRAVITY = 9.81  # NSDG_GRAVITY
 
+
+class BudgetOut(C.Structure):
+    """nsdg_budget_out: the sixteen nodal planes (NULL: not stored) and the row totals of nsdg_momentum_budget (include/nsdg_budget.h)"""
+    _fields_ = [(t + "_" + c, C.c_void_p) for t in ("wind", "water", "coriolis", "tilt", "internal", "basal", "inertia", "residual") for c in "xy"] + [
+        ("power", C.c_void_p), ("power_stride", C.c_int64), ("row0", C.c_int32)]
+
+
+# the functions of include/nsdg_budget.h (the "momentum budget" section, a header of its own that nsdg.h includes), bound like SYMBOLS
+BUDGET_SYMBOLS = {
+    "nsdg_momentum_budget": (C.c_int, [VP, I32, I32] + [VP] * 10 + [C.POINTER(BudgetOut)]),
+    "nsdg_budget_term_id": (C.c_int, [C.c_char_p]),
+}
+BUDGET_TERMS = ("wind", "water", "coriolis", "tilt", "internal", "basal", "inertia", "residual")  # in id order: nsdg_budget_term_id
+BUDGET_KE, BUDGET_QUANTITIES = 8, 9  # NSDG_BUDGET_KE, NSDG_BUDGET_QUANTITIES
+
 _lib = None
 
 
@@ -304,7 +319,7 @@ def load_library(path=LIB_PATH):
         raise NsdgError("HIP library %s is missing: build it with `python -m nextsimdg_amd.build` "
                         "(there is no CPU fallback)" % path)
     lib = C.CDLL(path)
-    for name, (res, args) in list(SYMBOLS.items()) + list(TRACER_SYMBOLS.items()) + list(BASAL_SYMBOLS.items()) + list(OCEAN_SYMBOLS.items()) + list(SNOW_SYMBOLS.items()) + list(TILT_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(TRACER_SYMBOLS.items()) + list(BASAL_SYMBOLS.items()) + list(OCEAN_SYMBOLS.items()) + list(SNOW_SYMBOLS.items()) + list(TILT_SYMBOLS.items()) + list(BUDGET_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -944,6 +959,30 @@ class Context:
         if ssh.numel() != (2 * self.nx + 1) * (2 * self.ny + 1):
             raise NsdgError("boxtest_ssh: the nodal arrays of the grid hold %d values" % ((2 * self.nx + 1) * (2 * self.ny + 1)))
         self._call(self.lib.nsdg_boxtest_ssh(self.h, float(domain_size), float(fc), float(gravity), _ptr(ssh)))
+
+    # ---- momentum balance diagnostics (include/nsdg_budget.h): the nodal forces of the momentum equation and their power
+    def momentum_budget(self, j0, j1, H, A, wind, s, uv, packed, planes=None, power=None, row0=0):
+        """nsdg_momentum_budget on the element rows [j0, j1): `planes` = {"<term>_x" / "<term>_y": a float64 CUDA tensor of the local CG2
+        lattice} -- only these are written --, `power` = a [9, rows] tensor of the row totals (term ids 0..7, then the kinetic energy), row
+        iy at column iy - row0; the state (uv, s) and `packed` are those the sub-cycle left"""
+        planes = dict(planes or {})
+        ts = [H, A, wind[0], wind[1], s[0], s[1], s[2], uv[0], uv[1], packed] + list(planes.values())
+        _check_f64(*ts)
+        n = (2 * self.nx + 1) * (2 * self.ny + 1)
+        out = BudgetOut()
+        names = [f[0] for f in BudgetOut._fields_[:16]]
+        for k, t in planes.items():
+            if k not in names:
+                raise NsdgError("momentum_budget: unknown plane %r" % (k,))
+            if t.numel() != n:
+                raise NsdgError("momentum_budget: plane %s holds %d values, the nodal arrays of the grid hold %d" % (k, t.numel(), n))
+            setattr(out, k, t.data_ptr())
+        if power is not None:
+            _check_f64(power)
+            if power.dim() != 2 or power.shape[0] != BUDGET_QUANTITIES:
+                raise NsdgError("momentum_budget: power must be [%d, rows]" % BUDGET_QUANTITIES)
+            out.power, out.power_stride, out.row0 = power.data_ptr(), power.shape[1], row0
+        self._call(self.lib.nsdg_momentum_budget(self.h, j0, j1, *[_ptr(t) for t in ts[:10]], C.byref(out)))
 
     def set_mevp_variant(self, variant):
         self._call(self.lib.nsdg_mevp_variant_set(self.h, variant))

@@ -11,10 +11,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libnsdg.so")
-SOURCES = ["nsdg_ctx.hip", "column_step.hip", "transport.hip", "mevp.hip", "mevp_fused.hip", "mevp_fused4.hip", "mevp_fused4_basal.hip", "halo.hip", "rowblock.hip", "forcing.hip", "substep.hip", "forcing_file.hip", "tracer.hip", "tracers.hip", "phase_timer.hip", "landmask.hip", "basal.hip", "snowload.hip", "tilt.hip", "bbm.hip", "history.hip", "drifters.hip", "points.hip"]
+SOURCES = ["nsdg_ctx.hip", "column_step.hip", "transport.hip", "mevp.hip", "mevp_fused.hip", "mevp_fused4.hip", "mevp_fused4_basal.hip", "halo.hip", "rowblock.hip", "forcing.hip", "substep.hip", "forcing_file.hip", "tracer.hip", "tracers.hip", "phase_timer.hip", "landmask.hip", "basal.hip", "snowload.hip", "tilt.hip", "budget.hip", "bbm.hip", "history.hip", "drifters.hip", "points.hip"]
 HEADERS = ["nsdg_internal.h", "dg_tables.h", "mevp_common.h", "mevp_pipeline.h", "mevp_p2p.h", "bbm_common.h", os.path.join("..", "..", "include", "nsdg.h"), os.path.join("..", "..", "include", "nsdg_tracers.h"), os.path.join("..", "..", "include", "nsdg_basal.h"),
            os.path.join("..", "..", "include", "nsdg_ocean.h"), os.path.join("..", "..", "include", "nsdg_snow.h"),
-           os.path.join("..", "..", "include", "nsdg_tilt.h")]
+           os.path.join("..", "..", "include", "nsdg_tilt.h"), os.path.join("..", "..", "include", "nsdg_budget.h")]
 # -ffp-contract=on: fuse a*b+c only where it is written as one expression (decided in the front end), so
 # that the same inlined device function rounds identically in every kernel it is inlined into -- the
 # mEVP kernel variants agree bit for bit; the default (fast) let the back end fuse differently per kernel

@@ -212,13 +212,7 @@ __device__ __forceinline__ void pack_node(const nsdg_mevp_params& P, double dt, 
     store_nodal(packed, plane, n, c);
 }
 
-__device__ __forceinline__ void wind_tau(double f_atm, double ua, double va, double& tax, double& tay)
-{
-    const double m = sqrt(ua * ua + va * va);
-    tax = f_atm * m * ua;
-    tay = f_atm * m * va;
-}
-
+// wind_tau: mevp_common.h
 // LAND: with the element land mask of the local array (nx x ny elements), land nodes are packed with the flag
 // BASAL: with the water depth of the same elements, pair 3 of a node is (T_b, 0)
 // SNOW: with the ncs coefficient planes of the snow on the same elements, the mass of a node carries its nodal mean

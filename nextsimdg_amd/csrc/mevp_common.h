@@ -579,6 +579,15 @@ __device__ __forceinline__ void node_update(const NodalConsts& K, const double (
     }
 }
 
+// the wind stress tau_a = f_atm |u_a| u_a, f_atm = c_atm rho_atm -- the ONE statement of it, shared by the packing (mevp.hip), nsdg_wind_stress
+// and the momentum budget (budget.hip)
+__device__ __forceinline__ void wind_tau(double f_atm, double ua, double va, double& tax, double& tay)
+{
+    const double m = sqrt(ua * ua + va * va);
+    tax = f_atm * m * ua;
+    tay = f_atm * m * va;
+}
+
 // The ice-free-node rule (the packing, mevp.hip: pack_node, states what it does to the coefficients and tests it
 // with this expression, written out there): a node whose mean concentration is below min_conc, whose true thickness cgH / cgA is below
 // min_thick or whose mean thickness is at the mass floor h_min.  Both thresholds 0: rule off.

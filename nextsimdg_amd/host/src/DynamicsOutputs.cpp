@@ -125,6 +125,90 @@ void SeriesChannel::atStop(const DynamicsBlocks& blocks)
     m_host.flushed();
 }
 
+// ------------------------------------------------------------------------------------------------ momentum budget
+void BudgetChannel::allocate(DynamicsBlock& b)
+{ // the launch writes the owned node rows and only they are read: no memset
+    Part& p = m_parts[b.index];
+    const BudgetOutput::Config& c = m_host.config();
+    if (!c.file.empty())
+        p.planes = b.outputBuffer(2 * c.ids.size() * (std::size_t)b.NN, "DynamicsStep: hipMalloc (budget planes)");
+    if (!c.seriesFile.empty())
+        p.power = b.outputBuffer((std::size_t)NSDG_BUDGET_QUANTITIES * b.ownedRows(), "DynamicsStep: hipMalloc (budget row totals)");
+}
+
+void BudgetChannel::launch(DynamicsBlock& b)
+{
+    const Part& p = m_parts[b.index];
+    const std::vector<int>& ids = m_host.config().ids;
+    nsdg_budget_out out = {};
+    double** plane[NSDG_BUDGET_TERMS][2] = { { &out.wind_x, &out.wind_y }, { &out.water_x, &out.water_y }, { &out.coriolis_x, &out.coriolis_y },
+        { &out.tilt_x, &out.tilt_y }, { &out.internal_x, &out.internal_y }, { &out.basal_x, &out.basal_y }, { &out.inertia_x, &out.inertia_y },
+        { &out.residual_x, &out.residual_y } };
+    if (p.planes)
+        for (std::size_t k = 0; k < ids.size(); ++k)
+            for (int c = 0; c < 2; ++c)
+                *plane[ids[k]][c] = p.planes + (2 * k + c) * (std::size_t)b.NN;
+    out.power = p.power, out.power_stride = b.ownedRows(), out.row0 = b.j0;
+    // the current side of the ping-pongs: the stress and the velocity the sub-cycle left, H and A the transport has not moved yet
+    const bool a = b.par == 0;
+    check(nsdg_momentum_budget(b.ctx.get(), b.j0, b.j1, b.cur(FH), b.cur(FA), b.d[UA], b.d[VA], b.d[a ? S11a : S11b], b.d[a ? S12a : S12b],
+              b.d[a ? S22a : S22b], b.curU(), b.curV(), b.d[PACKED], &out),
+        "nsdg_momentum_budget");
+}
+
+void BudgetChannel::afterStep(long dt, const DynamicsBlocks& blocks)
+{
+    const bool record = m_host.step(dt);
+    if (!m_host.config().seriesFile.empty()) {
+        const RowRange range(blocks);
+        const std::size_t nrows = range.rows();
+        std::vector<double> rows(NSDG_BUDGET_QUANTITIES * nrows), part;
+        forEachBlockInTurn(blocks, [&](DynamicsBlock& b) { // the blocks fill disjoint row ranges
+            check(nsdg_ctx_synchronize(b.ctx.get()), "DynamicsStep: budget series");
+            const std::size_t own = (std::size_t)b.ownedRows();
+            part.resize(NSDG_BUDGET_QUANTITIES * own);
+            toHost(part, m_parts[b.index].power, "download budget row totals");
+            for (std::size_t q = 0; q < NSDG_BUDGET_QUANTITIES; ++q)
+                std::copy(part.begin() + q * own, part.begin() + (q + 1) * own, rows.begin() + q * nrows + (b.r0 - range.row0));
+        });
+        m_host.appendLine(BudgetOutput::formatLine(m_host.clock(), BudgetOutput::totals(rows.data(), nrows)));
+    }
+    if (record)
+        write(blocks);
+}
+
+void BudgetChannel::atStop(const DynamicsBlocks& blocks)
+{
+    if (m_host.dueAtStop()) // (stop() comes twice: nothing is written twice)
+        write(blocks);
+}
+
+void BudgetChannel::write(const DynamicsBlocks& blocks)
+{
+    // a snapshot of the last (sub-)step: the owned node rows of every block into ONE host array per plane, with the history's record writer
+    ScopedTimer timer("budget record");
+    const BudgetOutput::Config& c = m_host.config();
+    const RowRange range(blocks);
+    const long nn = 2L * blocks[0]->nx + 1, nyg = blocks[0]->nyGlobal;
+    const long rows = 2L * (long)range.rows() + (range.row1 == nyg ? 1 : 0);
+    HistoryOutput::Record r;
+    r.timeStart = r.timeEnd = m_host.clock(), r.samples = 1, r.kind = "snapshot";
+    for (const std::string& t : c.terms)
+        r.fields.push_back(t + "_x"), r.fields.push_back(t + "_y");
+    r.x = 2 * nyg + 1, r.y = nn, r.row0 = 2L * range.row0, r.rows = rows;
+    const std::size_t global = (std::size_t)(rows * nn);
+    r.data.assign(r.fields.size() * global, 0.);
+    forEachBlockInTurn(blocks, [&](DynamicsBlock& b) { // the blocks fill disjoint node rows
+        check(nsdg_ctx_synchronize(b.ctx.get()), "DynamicsStep: budget record");
+        const long own = 2L * b.ownedRows() + (b.r1 == nyg ? 1 : 0);
+        for (std::size_t k = 0; k < r.fields.size(); ++k)
+            checkHip(hipMemcpy(r.data.data() + k * global + 2L * (b.r0 - range.row0) * nn, m_parts[b.index].planes + k * (std::size_t)b.NN + 2L * b.j0 * nn,
+                         (std::size_t)(own * nn) * sizeof(double), hipMemcpyDeviceToHost),
+                "download budget planes");
+    });
+    HistoryOutput::write(HistoryOutput::recordPath(c.file, r.timeEnd), c.file, r);
+}
+
 // ------------------------------------------------------------------------------------------------ drifters
 void DriftersChannel::allocate(DynamicsBlock& b)
 { // every block holds the whole list; the partner is written before it is read

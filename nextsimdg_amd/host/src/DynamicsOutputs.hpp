@@ -8,6 +8,7 @@
 // NSDG_PHASE_END mark of every model step -- the sample belongs to no phase and is never part of a captured graph --; atStop(blocks) from
 // stop(), which comes twice and writes nothing twice; for the drifters also advance(block, dt) inside every (sub-)step.
 #pragma once
+#include "BudgetOutput.hpp"
 #include "Drifters.hpp"
 #include "DynamicsBlock.hpp"
 #include "HistoryOutput.hpp"
@@ -104,6 +105,28 @@ private:
     StationsOutput m_host;
     SampledState m_state;
     std::vector<double> m_xy; // what the input file held, [2][n]
+    std::vector<Part> m_parts;
+};
+
+//! model.budget_file / model.budget_series_file: two planes of the LOCAL lattice per term asked for and, with the series, the row totals
+//! [NSDG_BUDGET_QUANTITIES][owned rows] on every block.  Unlike the other outputs it launches INSIDE every (sub-)step, right after the
+//! sub-cycle and before the transport moves H and A (launch(), from the block's own thread, in the sub-cycle's phase); afterStep()
+//! downloads the totals of the step's last launch, adds them in global row order and writes the planes when a record is due
+class BudgetChannel {
+public:
+    explicit BudgetChannel(const BudgetOutput::Config& c) : m_host(c) { }
+    void start(long time, std::size_t blocks) { m_host.start(time), m_parts.assign(blocks, Part()); }
+    void allocate(DynamicsBlock& b);
+    void launch(DynamicsBlock& b); //!< nsdg_momentum_budget on the owned rows, at the state the sub-cycle has just left
+    void afterStep(long dt, const DynamicsBlocks& blocks);
+    void atStop(const DynamicsBlocks& blocks); //!< model.budget_period = 0: the one record, once
+
+private:
+    struct Part {
+        double *planes = nullptr, *power = nullptr;
+    };
+    void write(const DynamicsBlocks& blocks);
+    BudgetOutput m_host;
     std::vector<Part> m_parts;
 };
 

@@ -54,6 +54,7 @@ struct DynamicsStep::Outputs {
     std::unique_ptr<SeriesChannel> series;
     std::unique_ptr<DriftersChannel> drifters;
     std::unique_ptr<StationsChannel> stations;
+    std::unique_ptr<BudgetChannel> budget; // (it also launches inside every sub-step: DynamicsOutputs.hpp)
     //! f(output) for every output that is on: history, series, drifters, stations
     template <class F> void each(F&& f)
     {
@@ -65,6 +66,8 @@ struct DynamicsStep::Outputs {
             f(*drifters);
         if (stations)
             f(*stations);
+        if (budget)
+            f(*budget);
     }
 };
 namespace {
@@ -401,6 +404,10 @@ void DynamicsStep::configureOutputs()
     const StationsOutput::Config stc = StationsOutput::fromConfiguration(RankEnvironment::fromEnv().world, loopbackWorld != 0, thermo, m_brittle != nullptr);
     if (stc.on())
         m_out->stations = std::make_unique<StationsChannel>(stc, sampled, StationsOutput::read(stc.file, L, L));
+    // the momentum budget (include/BudgetOutput.hpp): the same; a multi-process run and the brittle rheology are refused here
+    const BudgetOutput::Config bc = BudgetOutput::fromConfiguration(RankEnvironment::fromEnv().world, m_brittle != nullptr);
+    if (bc.on())
+        m_out->budget = std::make_unique<BudgetChannel>(bc);
 }
 
 void DynamicsStep::init()
@@ -610,6 +617,8 @@ void DynamicsStep::iterate(const Iterator::Duration& dtSeconds)
         m_out->stations->afterStep((long)dtSeconds, m_blocks);
     if (m_out->drifters)
         m_out->drifters->afterStep((long)dtSeconds, m_blocks);
+    if (m_out->budget)
+        m_out->budget->afterStep((long)dtSeconds, m_blocks);
 }
 
 int DynamicsStep::brittleSubIterations(double dt, double rhoIce)
@@ -713,6 +722,8 @@ void DynamicsStep::subStep(double dt, bool last)
             check(nsdg_rb_mevp_run(ctx, b.mevp.get(), b.par, &out), "nsdg_rb_mevp_run");
         }
         b.par = out;
+        if (m_out->budget) // still the sub-cycle's phase: H, A and the packing are the sub-cycle's
+            m_out->budget->launch(b);
         check(nsdg_phase_mark(ctx, NSDG_PHASE_TRANSPORT), "nsdg_phase_mark");
         check(nsdg_prepare_advection(ctx, 2, b.curU(), b.curV(), b.d[VXDG], b.d[VYDG], b.d[UNX], b.d[UNY]), "nsdg_prepare_advection");
         // the surface temperature travels as Q = H tice0 (every local row: element-local, the ghost rows stay equal to their owners)
@@ -850,6 +861,8 @@ void DynamicsStep::stop(const Iterator::TimePoint&)
         m_out->stations->atStop(m_blocks);
     if (m_out->drifters)
         m_out->drifters->atStop(m_blocks);
+    if (m_out->budget)
+        m_out->budget->atStop(m_blocks);
     FieldStore& f = pStructure->fields();
     std::vector<double> umax(m_blocks.size(), 0.);
     bool finite = true;

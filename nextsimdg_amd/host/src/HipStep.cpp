@@ -9,6 +9,7 @@
 #include <string>
 
 #include "../../../include/nsdg.h"
+#include "BudgetOutput.hpp"
 #include "Drifters.hpp"
 #include "HistoryOutput.hpp"
 #include "Stations.hpp"
@@ -55,6 +56,7 @@ void HipStep::init()
     SeriesOutput::refuseFor("Nextsim::HipStep"); // ... and no time series
     DriftersOutput::refuseFor("Nextsim::HipStep"); // ... and has no velocity to move drifters with
     StationsOutput::refuseFor("Nextsim::HipStep"); // ... and no dynamics state to sample at a station
+    BudgetOutput::refuseFor("Nextsim::HipStep"); // ... and no momentum balance
     {
         std::string raw; // ... and no rheology: the keys of the brittle one are the dynamics step's
         for (const std::string& key : DynamicsStep::brittleKeys())

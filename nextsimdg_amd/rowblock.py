@@ -293,7 +293,14 @@ class DynamicsCore:
     buffer self.ssh [m] -- filled by set_ssh() from a global array, by device_ssh() with the box test's, or by a ForcingSeries that holds
     "ssh" (CoupledCore) -- and (uo, vo) is the drag velocity alone.  prepare() sets the field on the ops object before the coefficient
     packing and clears it after it.  gravity: g [m s^-2], None = abi.GRAVITY.  tilt="geostrophic", the default: the tilt of the geostrophic
-    current, -m f_c k x u_o, the same calls as ever.  The height is forcing: the state dict does not hold it."""
+    current, -m f_c k x u_o, the same calls as ever.  The height is forcing: the state dict does not hold it.
+
+    budget=("wind", "water", ...), budget_power=True (include/nsdg_budget.h): right after the sub-cycle of every
+    step and sub-step -- H, A and the packed coefficients are still the sub-cycle's -- one launch on the owned rows writes the nodal forces
+    of the named terms of the momentum balance (abi.BUDGET_TERMS) and, with budget_power, the power of all eight terms and the kinetic
+    energy per element row.  budget_read() returns the last step's; merge_budget() joins the ranks.  The launch belongs to the sub-cycle
+    phase of the phase table.  None / False: nothing is allocated, nothing is launched, the same calls as ever.  The state dict does not
+    hold the forces: they are a diagnostic of the step that was run."""
 
     ORDER = 2
     # closure of the transported fields (include/nsdg.h "INPUT DOMAIN AND CLOSURE"): mean thickness H >= 0; concentration
@@ -313,6 +320,7 @@ class DynamicsCore:
     # state_dict() and of the column state
     TRACER_OPS = ("tracers_weight", "tracers_recover", "tracers_dilute")
     TILT_OPS = ("set_tilt", "tilt_nodal", "boxtest_ssh")
+    BUDGET_OPS = ("momentum_budget",)
     AGE_TRACER = "age"
     STATE_KEYS = ("rows", "ny_global", "nx", "H", "A", "S", "Q", "D", "u", "v", "s11", "s12", "s22", "drifters", "tracers", "hsnow", "tice0")
     HISTORY_COLUMN_FIELDS = outputs.History.COLUMN_FIELDS
@@ -324,7 +332,7 @@ class DynamicsCore:
                  phase_timing=False, land=None, rheology="mevp", bbm=None, history=None, series=None, series_capacity=1024, extent_conc=0.15,
                  drifters=None, drifter_min_conc=0.15, drifter_fields=None, stations=None, station_fields=None, station_capacity=256,
                  tracers=None, min_conc=1e-12, min_thick=0.01, bathymetry=None, basal=None, snow_load=False, rho_snow=None,
-                 tilt="geostrophic", gravity=None):
+                 tilt="geostrophic", gravity=None, budget=None, budget_power=False):
         if snow_load or rho_snow is not None:  # (CoupledCore takes the two itself and does not pass them on)
             raise ValueError("snow_load= needs the column state of a CoupledCore: a DynamicsCore carries no snow")
         self.ops, self.blk, self.hx, self.hy, self.dt, self.nsub, self.overlap = ops, blk, hx, hy, dt, nsub, overlap
@@ -340,6 +348,7 @@ class DynamicsCore:
         # Everything that can refuse comes first: a constructor that raises has changed nothing on `ops`
         self._check_rheology(rheology, bbm)
         self._check_tilt(tilt, gravity)
+        self._check_budget(budget, budget_power)
         self.TRANSPORTED, self.BOUNDS = self._transported()
         # tracers: names of intensive quantities that ride on the ice (include/nsdg.h "ice tracers"), "age" the one
         # that ages; min_conc / min_thick: the ice test of their recovery (the ice-free-node rule's defaults; 0 and 0 with closure = False)
@@ -440,6 +449,10 @@ class DynamicsCore:
         if self.tilt == "ssh":
             self.ssh = z(*nodal)  # the sea-surface height [m] at the nodes, ghost rows included: forcing, like uo and vo
         self.packed = z(nodal[0] * nodal[1] * 8)  # per-step momentum coefficients, 8 per node
+        if self.budget is not None:
+            # the planes of the terms asked for, on the local lattice (the launch writes the owned node rows), and the row totals
+            self._budget_planes = {t + "_" + c: z(*nodal) for t in self.budget for c in "xy"}
+            self._budget_power = z(abi.BUDGET_QUANTITIES, ny) if self.budget_power else None
         self.adv = (z(6, ny, nx), z(6, ny, nx), z(3, ny, nx + 1), z(3, ny + 1, nx))
         self.t1 = [z(6, ny, nx) for _ in range(nf)]
         self.t2 = [z(6, ny, nx) for _ in range(nf)]
@@ -489,6 +502,73 @@ class DynamicsCore:
             outputs.require_ops(self.ops, self.TILT_OPS, "tilt='ssh'", "sea-surface tilt calls")
             if not (np.isfinite(self.gravity) and self.gravity > 0.0):
                 raise ValueError("gravity must be finite and > 0, got %r" % (self.gravity,))
+
+    def _check_budget(self, budget, budget_power):
+        """budget= as a tuple of term names (None: off; () with budget_power: the totals alone), refused before anything is asked of `ops`
+        but the presence of the call"""
+        self.budget, self.budget_power = None, bool(budget_power)
+        if budget is None and not budget_power:
+            return
+        names = () if budget is None else ((budget,) if isinstance(budget, str) else tuple(budget))
+        unknown = [n for n in names if n not in abi.BUDGET_TERMS]
+        if unknown:
+            raise ValueError("unknown budget term %s (known: %s)" % (", ".join(repr(n) for n in unknown), " ".join(abi.BUDGET_TERMS)))
+        dup = sorted({n for n in names if names.count(n) > 1})
+        if dup:
+            raise ValueError("budget= names %s more than once" % ", ".join(dup))
+        if not names and not budget_power:
+            raise ValueError("budget= needs at least one term (None turns it off)")
+        if self.rheology == "bbm":
+            raise ValueError("budget= needs rheology='mevp': the brittle sub-cycle packs per sub-step with u0 = 0, and this balance -- the "
+                             "implicit step of the mEVP sub-cycle -- does not describe it")
+        outputs.require_ops(self.ops, self.BUDGET_OPS, "budget=", "momentum budget call")
+        self.budget = names
+
+    def _budget_launch(self):
+        """nsdg_momentum_budget on the owned rows, at the state the sub-cycle has just left"""
+        b = self.blk
+        if self.tilt == "ssh":  # on the ops object for this launch alone, as for the packing
+            self.ops.set_tilt(self.ssh, self.gravity)
+        self.ops.momentum_budget(b.j0, b.j1, self.H, self.A, (self.ua, self.va), self.s, (self.u, self.v), self.packed, self._budget_planes,
+                                 self._budget_power, 0)
+        if self.tilt == "ssh":
+            self.ops.set_tilt(None)
+
+    def budget_read(self):
+        """{"rows": (r0, r1), "<term>_x", "<term>_y": the owned node rows [N m^-2], "power": {term: [rows] W}, "ke": [rows] J} of the last
+        step (its last sub-step); "power" and "ke" with budget_power only"""
+        if self.budget is None:
+            raise ValueError("budget_read() needs a core constructed with budget= or budget_power=True")
+        b = self.blk
+        out = {"rows": (b.r0, b.r1)}
+        for k, t in self._budget_planes.items():
+            out[k] = self.owned(t).detach().cpu().numpy().copy()
+        if self._budget_power is not None:
+            p = self._budget_power[:, b.j0:b.j1].detach().cpu().numpy()
+            out["power"] = {t: p[i].copy() for i, t in enumerate(abi.BUDGET_TERMS)}
+            out["ke"] = p[abi.BUDGET_KE].copy()
+        return out
+
+    @staticmethod
+    def merge_budget(parts):
+        """the ranks' budget_read()s (any order) -> the budget of the whole domain: the planes and the row totals joined in row order, and
+        "power_total" {term: W}, "ke_total" J: the rows added one after the other in global row order, whatever the decomposition, so one
+        block and N blocks give the same bits"""
+        parts = sorted(parts, key=lambda p: p["rows"][0])
+        for a, b in zip(parts, parts[1:]):
+            if a["rows"][1] != b["rows"][0]:
+                raise ValueError("merge_budget: the parts' rows %s and %s do not join" % (a["rows"], b["rows"]))
+        out = {"rows": (parts[0]["rows"][0], parts[-1]["rows"][1])}
+        for k in parts[0]:
+            if k not in ("rows", "power", "ke"):
+                out[k] = np.concatenate([p[k] for p in parts], axis=0)
+        if "power" in parts[0]:
+            out["power"] = {t: np.concatenate([p["power"][t] for p in parts]) for t in parts[0]["power"]}
+            out["ke"] = np.concatenate([p["ke"] for p in parts])
+            total = lambda rows: float(np.add.accumulate(rows)[-1])  # sequential in row order: np.sum would add pairwise
+            out["power_total"] = {t: total(rows) for t, rows in out["power"].items()}
+            out["ke_total"] = total(out["ke"])
+        return out
 
     def _need_tilt(self, what):
         if self.tilt != "ssh":
@@ -737,6 +817,8 @@ class DynamicsCore:
         self.prepare()
         self._mark(PHASE_SUBCYCLE)
         self.subcycle()
+        if self.budget is not None:  # in the sub-cycle's phase: H, A and the packing are still the sub-cycle's
+            self._budget_launch()
 
     def prepare(self):
         """once per model step: ice strength at the Gauss points, nodal means of H and A, wind stress and the packed
